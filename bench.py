@@ -56,7 +56,28 @@ def parse_args(argv=None):
                          "aggregation path over gloo on a machine without a GPU; the line says so in `data`")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the sub-results (host_rows, config_2b, sharded_proof) and print the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the proofs of the last timed step (one per context, bincode bytes "
+                         "as float32) to DIR/proof_<context>.npy (rank r of N > 1: DIR/rank<r>_proof_<context>.npy)")
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write `arrays` (name -> array) as out_dir/<name>.npy in float32, DUMP_LIMIT_BYTES at most in all: an array larger
+    than its share is replaced by a fixed, seeded sample of its elements, whose positions go to <name>.index.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // (12 * max(1, len(arrays)))   # sampled elements: 4 + 8 bytes each
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))
+            np.save(os.path.join(out_dir, name + ".index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32))
 
 
 from luminair_amd.hostinfo import (cpu_budget, cpu_model, gpu_local_cpus, physical_cores, pin_rank_to_gpu_numa_node,  # noqa: E402,F401
@@ -220,7 +241,7 @@ def shard_proof_main(args, rank, local_rank, world):
     os.environ.setdefault("RANK", str(rank))
     os.environ.setdefault("WORLD_SIZE", str(world))
     emu = args.emu_library is not None
-    has_cuda = torch.cuda.is_available() and not emu
+    has_cuda = not emu and torch.cuda.is_available()   # the emulation ranks never initialise the GPU runtime
     if has_cuda:
         torch.cuda.set_device(local_rank)
     dist.init_process_group("nccl" if has_cuda else "gloo", rank=rank, world_size=world)
@@ -241,11 +262,14 @@ def shard_proof_main(args, rank, local_rank, world):
         if has_cuda:
             dist.barrier(device_ids=[local_rank])
         else:
-            dist.barrier()
+            dist.all_reduce(torch.zeros(1))   # dist.barrier() would probe for an accelerator, initialising the GPU runtime
 
     steps = 2 if emu else min(args.steps, 32)
     warm = 1 if emu else min(args.warmup, 4)
     elapsed = timed_region(step, steps, warm, barrier, torch.cuda.synchronize if has_cuda else (lambda: None))
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        dump_outputs(args.dump_outputs, {"sharded_proof": np.frombuffer(out["proof"], np.uint8)})
     t = torch.tensor([elapsed], dtype=torch.float64, device=tdev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     tmax = float(t.item())
@@ -338,6 +362,8 @@ def main(argv=None):
             os.environ["LMN_BENCH_RCCL_LOG_DIR"] = run_dir
             atexit.register(shutil.rmtree, run_dir, True)
     args = parse_args(argv)
+    if args.dump_outputs and args.steps < 1:
+        raise SystemExit("bench.py: --dump-outputs needs at least one timed step (--steps >= 1)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args, argv)
     rank, local_rank, world = dist_env()
@@ -363,7 +389,7 @@ def main(argv=None):
 
     emu = args.emu_library is not None            # test of the launch path only (no GPU, gloo, emulation build)
     library = _bk.Library(args.emu_library) if emu else None
-    has_cuda = torch.cuda.is_available() and not emu
+    has_cuda = not emu and torch.cuda.is_available()   # the emulation ranks never initialise the GPU runtime
     tdev = "cuda" if has_cuda else "cpu"
     use_dist = world > 1 or args.force_dist   # --force-dist: the N > 1 code path on one rank (self-test)
     ranks_seen = 1
@@ -398,12 +424,13 @@ def main(argv=None):
     else:
         bufs = [[(k, p.ctx.upload(r), len(r)) for k, r in tabs] for p in provers]   # trace rows resident in HBM
     out = {}
+    last = [None] * inflight      # the latest proof of every context: after the timed region, the last step's
     # one worker thread per context (a worker pool shared by the contexts could put two threads into one context)
     pools = [ThreadPoolExecutor(max_workers=1) for _ in range(inflight)]
     pending = []
 
     def one(i):
-        out["proof"] = provers[i].ctx.prove_tables(bufs[i])
+        out["proof"] = last[i] = provers[i].ctx.prove_tables(bufs[i])
 
     counter = {"n": 0}
 
@@ -436,7 +463,7 @@ def main(argv=None):
             if has_cuda:
                 dist.barrier(device_ids=[local_rank])
             else:
-                dist.barrier()
+                dist.all_reduce(torch.zeros(1))   # dist.barrier() would probe for an accelerator, initialising the GPU runtime
 
     def device_sync():
         drain()
@@ -454,6 +481,9 @@ def main(argv=None):
     ru0 = resource.getrusage(resource.RUSAGE_SELF)
     elapsed = timed_region(step, args.steps, args.warmup, barrier, device_sync)
     ru1 = resource.getrusage(resource.RUSAGE_SELF)
+    if args.dump_outputs:
+        prefix = "rank%d_" % rank if world > 1 else ""
+        dump_outputs(args.dump_outputs, {"%sproof_%02d" % (prefix, i): np.frombuffer(p, np.uint8) for i, p in enumerate(last)})
     # host CPU this rank spent in the warm-up + timed steps (user + system, all threads): what N ranks need from a
     # CPU-limited container (tools/host_cpu_per_proof.py; the library's waits back off to sleeps under load)
     host_cpu_s = (ru1.ru_utime - ru0.ru_utime) + (ru1.ru_stime - ru0.ru_stime)

@@ -229,20 +229,130 @@ def _gpu_worker(rank, world, port, fri_min_log, lib_path, q, a2a=True):
         dist.destroy_process_group()
 
 
+class _ThreadGroup:
+    """`world` ranks as threads of one process: every exchange is a rendezvous of all ranks over host memory."""
+
+    def __init__(self, world, timeout=600):
+        import threading
+        self.world, self.slots = world, [None] * world
+        self.barrier = threading.Barrier(world, timeout=timeout)
+
+    def exchange(self, rank, item):
+        """every rank's `item`, in rank order"""
+        self.slots[rank] = item
+        self.barrier.wait()
+        got = list(self.slots)
+        self.barrier.wait()         # nobody overwrites a slot before every rank has read them all
+        return got
+
+
+def _thread_shard(ctx, group, rank, fri_min_log, a2a=True):
+    """The host-staged collective of `shard_context`'s gloo form, with `_ThreadGroup` as the transport."""
+    from luminair_amd.backend import DeviceBuffer
+    world = group.world
+
+    def read(ptr, nbytes):
+        return ctx.download(DeviceBuffer(ctx, ptr, nbytes, owned=False), np.uint8) if nbytes else np.empty(0, np.uint8)
+
+    def write(ptr, data):
+        if len(data):
+            ctx.upload_to(DeviceBuffer(ctx, ptr, len(data), owned=False), data)
+
+    def all_gather(buf, nbytes, _stream):
+        write(buf, np.concatenate(group.exchange(rank, read(buf + rank * nbytes, nbytes))))
+
+    def all_to_all(send, send_off, send_bytes, recv, recv_off, recv_bytes, _stream):
+        sent = group.exchange(rank, [read(send + send_off[p], send_bytes[p]) for p in range(world)])
+        for p in range(world):
+            assert len(sent[p][rank]) == recv_bytes[p]
+            write(recv + recv_off[p], sent[p][rank])
+    ctx.set_shard(rank, world, all_gather, fri_min_log, all_to_all if a2a else None)
+
+
+def _run_thread_ranks(world, q, rank_fn):
+    """`rank_fn(rank, group)` for all `world` ranks as threads of this process; every rank's result goes to `q`."""
+    import threading
+    group, res = _ThreadGroup(world), {}
+
+    def rank_main(rank):
+        try:
+            res[rank] = rank_fn(rank, group)
+        except BaseException as e:  # noqa: BLE001 - reported through the queue; the other ranks must not wait for it
+            res[rank] = repr(e)
+            group.barrier.abort()
+    threads = [threading.Thread(target=rank_main, args=(r,)) for r in range(world)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    for r in range(world):
+        q.put((r, res.get(r)))
+
+
+def _emu_thread_ranks(world, fri_min_log, q):
+    os.environ["LMN_SHARD_A2A_MIN_LOG"] = "4"
+    os.environ["LMN_SHARD_ROWS_MIN_LOG"] = "4"
+    sys.path.insert(0, ROOT)
+
+    def rank_fn(rank, group):
+        def make(pinned, pcs=None):
+            ctx = _make_ctx(pinned, pcs)
+            _thread_shard(ctx, group, rank, fri_min_log)
+            return ctx
+        stats = []
+        proofs = _prove_all(make, stats)
+        blowup2 = [len(c) <= 4 or len(c[4]) <= 3 or c[4][3] == 1 for c in _cases()]
+        assert all((c > 0) == b2 and g > 0 for (c, _, g), b2 in zip(stats, blowup2)), stats
+        return proofs
+    _run_thread_ranks(world, q, rank_fn)
+
+
+def test_sharded_prove_thread_ranks_is_byte_identical(single_rank_proofs):
+    """The transport of the GPU test's largest world (_ThreadGroup / _thread_shard: 8 ranks as threads of one process,
+    host-staged all-gathers and all-to-alls) on the emulation build: every rank returns the unsharded bytes."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    p = ctx.Process(target=_emu_thread_ranks, args=(8, 5, q))
+    p.start()
+    res = sorted(q.get(timeout=900) for _ in range(8))
+    p.join(timeout=60)
+    assert p.exitcode == 0
+    assert [r for r, _ in res] == list(range(8))
+    for _, out in res:
+        assert out == single_rank_proofs
+
+
+def _gpu_thread_ranks(world, fri_min_log, lib_path, q, a2a=True):
+    """All `world` ranks in this one process, a thread and a context each on GPU 0."""
+    os.environ["LMN_SHARD_ROWS_MIN_LOG"] = "13" if (world == 4 and a2a) else "99"
+    sys.path.insert(0, ROOT)
+    from luminair_amd import backend
+    lib = backend.Library(lib_path)
+    _run_thread_ranks(world, q, lambda rank, group: _gpu_prove_all(lib, lambda c: _thread_shard(c, group, rank, fri_min_log, a2a)))
+
+
+# Ranks per process: a shared GPU node admits only a few processes on a device at once, so worlds above 4 run their
+# ranks as threads of ONE process (_gpu_thread_ranks) instead of a process each (_gpu_worker over gloo).
+MAX_RANK_PROCESSES = 4
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("world,fri_min_log,a2a", [(2, 6, True), (4, 0, True), (8, 7, True), (4, 6, False)])
 def test_gpu_sharded_prove_multi_rank_on_one_gpu(world, fri_min_log, a2a, hip_lib_path):
     """The world > 1 code paths of the REAL library (row-block LDEs from `k_fft_top_block`, halo blocks of the last
     logup group, row-offset constraint / quotient / fold kernels, owner-aware decommitment; with a2a the
     column-parallel interpolate + extend, the block packing and the all-to-all for columns of 2^13 rows and more) on hardware: `world`
-    processes share GPU 0, the collective is the gloo-staged callback, and every rank must return the unsharded
-    proof's bytes."""
+    ranks share GPU 0 - up to MAX_RANK_PROCESSES as processes over the gloo-staged callback, larger worlds as threads
+    of one process over the same host-staged callback - and every rank must return the unsharded proof's bytes."""
     from luminair_amd import backend
     want = _gpu_prove_all(backend.Library(hip_lib_path))
     port = _free_port()
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=_gpu_worker, args=(r, world, port, fri_min_log, hip_lib_path, q, a2a)) for r in range(world)]
+    if world > MAX_RANK_PROCESSES:
+        procs = [ctx.Process(target=_gpu_thread_ranks, args=(world, fri_min_log, hip_lib_path, q, a2a))]
+    else:
+        procs = [ctx.Process(target=_gpu_worker, args=(r, world, port, fri_min_log, hip_lib_path, q, a2a)) for r in range(world)]
     for p in procs:
         p.start()
     res = sorted(q.get(timeout=600) for _ in range(world))
