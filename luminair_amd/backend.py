@@ -139,7 +139,7 @@ EXPORTS = ["lmn_abi_version", "lmn_kind_padding_row", "lmn_strerror", "lmn_last_
            "lmn_host_alloc", "lmn_host_free", "lmn_host_register", "lmn_host_unregister",
            "lmn_op_interpolate", "lmn_op_evaluate", "lmn_op_merkle_root", "lmn_op_eval_at_point",
            "lmn_op_fft_selftest", "lmn_op_accumulate_quotients", "lmn_op_fold_line", "lmn_op_fold_circle_into_line",
-           "lmn_op_grind", "lmn_device_alloc", "lmn_download", "lmn_trace_elementwise", "lmn_trace_sum_reduce",
+           "lmn_op_grind", "lmn_ctx_grind", "lmn_device_alloc", "lmn_download", "lmn_trace_elementwise", "lmn_trace_sum_reduce",
            "lmn_trace_elementwise_v", "lmn_trace_contiguous", "lmn_trace_lut", "lmn_trace_lut_ranges", "lmn_trace_less_than", "lmn_trace_max_reduce", "lmn_upload_to", "lmn_device_copy", "lmn_op_evaluate_block",
            "lmn_verify_with_config", "lmn_verify_diagnose", "lmn_kind_constraint_layout", "lmn_lut_log_size", "lmn_lut_from_ranges", "lmn_lut_from_ranges_r", "lmn_col_alloc", "lmn_col_from_cpu", "lmn_col_to_cpu", "lmn_col_free", "lmn_col_ncols",
            "lmn_col_log_size", "lmn_col_device_ptr", "lmn_col_view", "lmn_col_bit_reverse", "lmn_col_precompute_twiddles",
@@ -215,6 +215,7 @@ class Library:
         lib.lmn_op_fold_line.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.lmn_op_fold_circle_into_line.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.lmn_op_grind.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+        lib.lmn_ctx_grind.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
         lib.lmn_device_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
         lib.lmn_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         lib.lmn_upload_to.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -963,6 +964,15 @@ class Context:
         self._check(self.lib.lib.lmn_op_fold_circle_into_line(self.handle, d.ctypes.data, a.ctypes.data,
                                                               a.shape[1].bit_length() - 1, al))
         return d
+
+    def grind(self, digest: bytes, pow_bits: int, variant: int = VARIANT_KAT) -> int:
+        """GrindOps::grind on the context's GPU (lmn_ctx_grind): the nonce Library.grind finds on the host."""
+        digest = bytes(digest)
+        if len(digest) != 32:
+            raise ValueError("digest must be 32 bytes")
+        out = C.c_uint64()
+        self._check(self.lib.lib.lmn_ctx_grind(self.handle, digest, pow_bits, variant, C.byref(out)))
+        return int(out.value)
 
     def fft_selftest(self, log_size: int, ncols: int = 2):
         self._check(self.lib.lib.lmn_op_fft_selftest(self.handle, log_size, ncols))

@@ -339,6 +339,41 @@ LMN_HD void b2_compress_fresh_nz(uint32_t out[8], const uint32_t m[16], uint32_t
 #endif
 }
 
+// h <- F(h, m, t0, f0) as b2_compress for a block whose message words m[NZ..15] are zero by construction: the
+// chaining-value form of b2_compress_fresh_nz (the proof-of-work grind of the KAT transcript form: h = the channel digest,
+// m = the nonce's two words).  On the device every half round goes through b2_half_z; elsewhere it is b2_compress.
+template <int NZ, int LO = 0, int HI = LMN_B2_PRIO_HI>
+LMN_HD void b2_compress_cv_nz(uint32_t h[8], const uint32_t m[16], uint32_t t0, uint32_t f0) {
+  static_assert(NZ >= 1 && NZ <= 16, "number of leading message words that may be non-zero");
+#ifdef LMN_B2_HAVE_FRESH
+  uint32_t v0 = h[0], v1 = h[1], v2 = h[2], v3 = h[3], v4 = h[4], v5 = h[5], v6 = h[6], v7 = h[7];
+  uint32_t v8 = 0x6A09E667u, v9 = 0xBB67AE85u, v10 = 0x3C6EF372u, v11 = 0xA54FF53Au;
+  uint32_t v12 = 0x510E527Fu ^ t0, v13 = 0x9B05688Cu, v14 = 0x1F83D9ABu ^ f0, v15 = 0x5BE0CD19u;
+  LMN_B2_ENTER
+  LMN_B2_ROUND_Z(0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15)
+  LMN_B2_ROUND_Z(14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3)
+  LMN_B2_ROUND_Z(11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4)
+  LMN_B2_ROUND_Z(7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8)
+  LMN_B2_ROUND_Z(9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13)
+  LMN_B2_ROUND_Z(2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9)
+  LMN_B2_ROUND_Z(12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11)
+  LMN_B2_ROUND_Z(13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10)
+  LMN_B2_ROUND_Z(6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5)
+  LMN_B2_ROUND_Z(10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0)
+  LMN_B2_LEAVE
+  h[0] ^= v0 ^ v8;
+  h[1] ^= v1 ^ v9;
+  h[2] ^= v2 ^ v10;
+  h[3] ^= v3 ^ v11;
+  h[4] ^= v4 ^ v12;
+  h[5] ^= v5 ^ v13;
+  h[6] ^= v6 ^ v14;
+  h[7] ^= v7 ^ v15;
+#else
+  b2_compress<LO, HI>(h, m, t0, f0);   // (host / emulation: the caller's zero words are read)
+#endif
+}
+
 // Two independent compressions interleaved statement by statement: 8 independent dependency chains per
 // half-round instead of 4, which keeps the VALU issuing when only ~2 waves share a SIMD.
 #define LMN_B2_G2(a, b, c, d, x, y, A, B, C, D, X, Y) \

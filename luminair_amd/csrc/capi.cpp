@@ -352,6 +352,15 @@ int lmn_op_grind(const uint8_t digest[32], uint32_t pow_bits, uint32_t protocol_
   return LMN_OK;
 }
 
+int lmn_ctx_grind(lmn_ctx* ctx, const uint8_t digest[32], uint32_t pow_bits, uint32_t protocol_variant, uint64_t* nonce_out) {
+  if (!ctx || !digest || !nonce_out || pow_bits > 40 || (protocol_variant & ~LMN_PV_ALL)) return LMN_ERR_INVALID_ARGUMENT;
+  return guard(ctx, [&] {
+    lmn::Hash32 d;
+    memcpy(d.w, digest, 32);
+    *nonce_out = ctx->impl->op_grind(d, pow_bits, protocol_variant);
+  });
+}
+
 int lmn_device_alloc(lmn_ctx* ctx, size_t bytes, void** device_out) {
   if (!ctx || !device_out) return LMN_ERR_INVALID_ARGUMENT;
   return guard(ctx, [&] { *device_out = ctx->impl->device_alloc(bytes); });

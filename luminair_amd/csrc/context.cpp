@@ -90,6 +90,12 @@ Context::Context(int device, const lmn_config& c) : cfg(c), device_(device) {
 #else
   stream_ = 0;
 #endif
+  // Proof of work on the device from this many bits on (below: the host loop, ~8 M tries/s on one core, against a launch
+  // and a wait of some tens of us); LMN_POW_DEVICE_MIN_BITS overrides it (41: never), LMN_POW_WINDOW_LOG caps the nonces
+  // of one grind launch ("Proof of work").  Read per context, like the switches above.
+  pow_device_min_bits_ = getenv("LMN_POW_DEVICE_MIN_BITS") ? std::max(0, atoi(getenv("LMN_POW_DEVICE_MIN_BITS"))) : POW_DEVICE_MIN_BITS;
+  pow_window_log_ = getenv("LMN_POW_WINDOW_LOG") ? std::max(POW_MIN_WINDOW_LOG, std::min(30, atoi(getenv("LMN_POW_WINDOW_LOG"))))
+                                                 : POW_WINDOW_LOG;
   event_log = new EventLog();
   pin_cap_ = 32u << 20;
   pin_base_ = (char*)lmn_host_alloc_pinned(pin_cap_);
@@ -135,6 +141,7 @@ Context::~Context() {
   shard_.rccl = nullptr;
   for (void* p : tw_allocs_) lmn_dev_free(p);
   if (bad_flag_) lmn_dev_free(bad_flag_);
+  if (pow_best_) lmn_dev_free(pow_best_);
   if (pin_base_) lmn_host_free_pinned(pin_base_);
 #ifndef LMN_EMU
   if (have_stream2_) {

@@ -268,6 +268,22 @@ struct MerkleRecompute {
 void launch_gather(const uint32_t* arena, const GatherEntry* entries, uint32_t n_entries, const MerkleRecompute* jobs,
                    uint32_t n_jobs, uint32_t* out, lmn_stream_t s);
 
+// ---- proof-of-work grind (GrindOps on the device): one launch examines the nonces [base, base + 2^window_log) and
+// lowers *best (device, u64) to the smallest of them that passes, if it is below what *best holds.  A block whose nonces
+// all lie above *best at its start returns at once, so launches queued behind the one that found a nonce cost nothing
+// and the first window with a hit yields the global minimum.  kat: the KAT form (bare compression, h = w, m0/m1 = nonce,
+// t = 0, no final flag); otherwise blake2s(w || nonce LE), i.e. the hashed mix (w = digest) or the prefixed form (w = pre).
+constexpr uint32_t POW_TPB = 256;       // lanes per block
+constexpr uint32_t POW_NPT = 8;         // nonces per lane and launch
+constexpr int POW_MIN_WINDOW_LOG = 11;  // one block: POW_TPB * POW_NPT nonces
+constexpr int POW_WINDOW_LOG = 24;      // default cap of one launch's window (Context: LMN_POW_WINDOW_LOG)
+constexpr int POW_DEVICE_MIN_BITS = 11; // prove() grinds on the device from this pow_bits on (LMN_POW_DEVICE_MIN_BITS; measured crossover)
+struct PowWords {
+  uint32_t w[8];
+};
+void launch_pow_grind(const PowWords& w, bool kat, uint64_t base, int window_log, uint32_t pow_bits,
+                      unsigned long long* best, lmn_stream_t s);
+
 // ---- trace generation for the elementwise primitives (the producer of the hot path's input)
 struct TraceNode {
   uint32_t node_id, lhs_id, rhs_id;

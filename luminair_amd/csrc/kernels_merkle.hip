@@ -1162,4 +1162,61 @@ void launch_gather(const uint32_t* arena, const GatherEntry* entries, uint32_t n
   LMN_LAUNCH(k_gather, dim3(n_entries + n_jobs), dim3(64), 0, s, arena, entries, n_entries, jobs, n_jobs, out);
 }
 
+// =============================================================================================
+// Proof-of-work grind (kernels.h launch_pow_grind): one compression per nonce, the smallest passing nonce of the
+// window by a 64-bit atomicMin.  Block b examines [lo, lo + POW_TPB * POW_NPT) with lo = base + b * POW_TPB * POW_NPT,
+// lane t the nonces lo + k * POW_TPB + t in ascending k, and stops at its first hit: the minimum of the window is exact
+// (a block skips only when a smaller nonce has already been found, and a lane's first hit is its smallest).
+// =============================================================================================
+LMN_D unsigned long long pow_best_now(const unsigned long long* best) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(LMN_EMU)
+  return __hip_atomic_load(best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // past the (non-coherent) vector L1
+#else
+  return *best;
+#endif
+}
+
+template <bool KAT>
+LMN_KERNEL k_pow_grind(PowWords pw, uint64_t base, uint64_t mask, unsigned long long* best) {
+  const uint64_t lo = base + (uint64_t)blockIdx.x * (POW_TPB * POW_NPT);
+  if (pow_best_now(best) < lo) return;
+  uint64_t found = ~0ull;
+  for (uint32_t k = 0; k < POW_NPT; ++k) {
+    const uint64_t nonce = lo + k * POW_TPB + threadIdx.x;
+    uint32_t m[16], h[8];
+    if constexpr (KAT) {
+      for (int i = 0; i < 8; ++i) h[i] = pw.w[i];
+      m[0] = (uint32_t)nonce;
+      m[1] = (uint32_t)(nonce >> 32);
+      for (int i = 2; i < 16; ++i) m[i] = 0u;
+      b2_compress_cv_nz<2>(h, m, 0u, 0u);
+    } else {
+      for (int i = 0; i < 8; ++i) m[i] = pw.w[i];
+      m[8] = (uint32_t)nonce;
+      m[9] = (uint32_t)(nonce >> 32);
+      for (int i = 10; i < 16; ++i) m[i] = 0u;
+      b2_compress_fresh_nz<10>(h, m, 40u);
+    }
+    // trailing zeros of words 0..3 (little-endian) >= pow_bits <=> the low pow_bits bits of words 0..1 are zero (pow_bits <= 40)
+    if ((((uint64_t)h[1] << 32 | h[0]) & mask) == 0u) {
+      found = nonce;
+      break;
+    }
+  }
+  if (found != ~0ull) atomicMin(best, (unsigned long long)found);
+}
+
+void launch_pow_grind(const PowWords& w, bool kat, uint64_t base, int window_log, uint32_t pow_bits,
+                      unsigned long long* best, lmn_stream_t s) {
+  static_assert(POW_TPB * POW_NPT == 1u << POW_MIN_WINDOW_LOG, "one block = the smallest window");
+  if (window_log < POW_MIN_WINDOW_LOG || window_log > 32 || pow_bits > 40) throw LmnError(-100, "pow_grind: bad window");
+  const uint64_t mask = (1ull << pow_bits) - 1u;
+  const dim3 grid(1u << (window_log - POW_MIN_WINDOW_LOG));
+  if (kat) {
+    LMN_LAUNCH(k_pow_grind<true>, grid, dim3(POW_TPB), 0, s, w, base, mask, best);
+  } else {
+    LMN_LAUNCH(k_pow_grind<false>, grid, dim3(POW_TPB), 0, s, w, base, mask, best);
+  }
+}
+
 }  // namespace lmn

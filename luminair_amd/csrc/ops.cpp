@@ -170,6 +170,15 @@ void Context::op_fold(int circle, uint32_t* dst, const uint32_t* src, uint32_t l
   lmn_sync(stream_);
 }
 
+// always on the device, whatever pow_device_min_bits_ says: the entry point of a GrindOps implementation
+uint64_t Context::op_grind(const Hash32& digest, uint32_t pow_bits, uint32_t variant) {
+  if (pow_bits > 40 || (variant & ~LMN_PV_ALL)) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "grind: bad pow_bits / variant");
+  begin_op();
+  Channel ch(variant);
+  ch.set_digest(digest);
+  return device_grind(ch, pow_bits);
+}
+
 // tiled FFT vs one-layer-per-launch kernels on pseudo-random data (device-side differential check)
 void Context::op_fft_selftest(uint32_t log_size, uint32_t ncols) {
   check_op_log(log_size, "fft_selftest");

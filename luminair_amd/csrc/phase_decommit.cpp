@@ -4,10 +4,49 @@
 
 namespace lmn {
 
+// Proof of work on the device (k_pow_grind): windows of 2^wlog nonces in ascending order, POW_WINDOWS_PER_WAIT per wait,
+// until one holds a passing nonce; its minimum is the host loop's answer (Channel::grind).  The window grows with
+// pow_bits (about two expected hits per window) up to pow_window_log_, the cap that keeps one launch well under a
+// millisecond (2^24 nonces: 0.24 ms measured), so that other contexts' launches interleave.
+uint64_t Context::device_grind(const Channel& ch, uint32_t pow_bits) {
+#ifdef LMN_BATCH
+  (void)ch;
+  (void)pow_bits;
+  throw LmnError(LMN_ERR_INVALID_ARGUMENT, "the lock-step batch library grinds on the host only (no device grind)");
+#else
+  // launches queued per host wait: one behind the launch that found a nonce returns at once (every block sees the smaller
+  // nonce at its start), so the queue costs a few us of launches and saves waits while nothing has been found
+  constexpr int POW_WINDOWS_PER_WAIT = 8;
+  const bool prefixed = (ch.flags() & LMN_PV_POW_PREFIXED) != 0;
+  const bool kat = !prefixed && !(ch.flags() & LMN_PV_MIX_U64_HASHED);
+  PowWords w;
+  const Hash32 src = prefixed ? ch.pow_prefixed_digest(pow_bits) : ch.digest();
+  memcpy(w.w, src.w, sizeof w.w);
+  if (!pow_best_) pow_best_ = (unsigned long long*)lmn_dev_malloc(sizeof(unsigned long long));
+  unsigned long long* found = (unsigned long long*)pin_alloc(sizeof(unsigned long long));
+  const int wlog = std::min(pow_window_log_, std::max(POW_MIN_WINDOW_LOG, (int)pow_bits + 1));
+  lmn_memset(pow_best_, 0xff, sizeof(unsigned long long), stream_);
+  for (uint64_t base = 0;;) {
+    for (int k = 0; k < POW_WINDOWS_PER_WAIT; ++k, base += 1ull << wlog)
+      launch_pow_grind(w, kat, base, wlog, pow_bits, pow_best_, stream_);
+    lmn_d2h(found, pow_best_, sizeof(unsigned long long), stream_);
+    lmn_sync(stream_);
+    if (*found != ~0ull) return *found;
+  }
+#endif
+}
+
+uint64_t Context::grind(const Channel& ch, uint32_t pow_bits) {
+#ifndef LMN_BATCH
+  if ((int)pow_bits >= pow_device_min_bits_) return device_grind(ch, pow_bits);
+#endif
+  return ch.grind(pow_bits);
+}
+
 void Context::run_queries(ProofRun& r) {
   LMN_RUN_ALIASES(r);
   // ---- proof of work + queries
-  proof.proof_of_work = channel.grind(cfg.pow_bits);
+  proof.proof_of_work = grind(channel, cfg.pow_bits);
   channel.mix_u64(proof.proof_of_work);
   const int ls0 = quots[0].log;
   queries.clear();

@@ -250,6 +250,11 @@ inline unsigned atomicAdd(unsigned* p, unsigned v) {  // fibers are cooperative:
   *p += v;
   return o;
 }
+inline unsigned long long atomicMin(unsigned long long* p, unsigned long long v) {
+  unsigned long long o = *p;
+  if (v < o) *p = v;
+  return o;
+}
 inline unsigned lmn_quad_perm(unsigned v, int ctrl) {  // all lanes of the block must call it together
   lmn_emu_shfl_scratch[threadIdx.x] = v;
   lmn_emu_syncthreads();

@@ -183,6 +183,8 @@ class Context {
                                const uint32_t* sample_point, const uint32_t* sample_values, uint32_t nsamples,
                                const uint32_t* points_xy, uint32_t npoints, const uint32_t alpha[4], uint32_t* out);
   void op_fold(int circle, uint32_t* dst, const uint32_t* src, uint32_t log_src, const uint32_t alpha[4]);
+  // GrindOps::grind on the device (lmn_ctx_grind): the smallest nonce the proof-of-work check of `variant` accepts
+  uint64_t op_grind(const Hash32& digest, uint32_t pow_bits, uint32_t variant);
 
   // single-proof sharding (lmn_ctx_set_shard / lmn_ctx_set_shard_rccl)
   static void check_shard_args(uint32_t rank, uint32_t world, uint32_t fri_min_log, const lmn_collective* coll);
@@ -375,6 +377,12 @@ class Context {
   lmn_event_t ev_fork_{}, ev_join_{};
   bool have_stream2_ = false;
   int fri_overlap_mode_ = 0;          // 0 never, 1 always, 2 while this is the process's only proof in flight
+  // proof of work: prove() grinds on the device from pow_bits >= pow_device_min_bits_ on (LMN_POW_DEVICE_MIN_BITS), on the
+  // host below; one launch examines at most 2^pow_window_log_ nonces (LMN_POW_WINDOW_LOG)
+  int pow_device_min_bits_ = 0, pow_window_log_ = 0;
+  unsigned long long* pow_best_ = nullptr;   // device: the smallest passing nonce found so far (allocated on first use)
+  uint64_t grind(const Channel& ch, uint32_t pow_bits);          // the proof's path: device or host by pow_device_min_bits_
+  uint64_t device_grind(const Channel& ch, uint32_t pow_bits);
   bool second_stream_wanted();
   lmn_event_t wait_before_level_ev_{};
   int wait_before_level_ = -1;    // build_merkle_levels: make stream_ wait for wait_before_level_ev_ before this level
