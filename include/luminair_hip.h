@@ -342,11 +342,27 @@ typedef struct lmn_node_info {
   uint32_t is_final_output;
   int32_t input_mults[2];
 } lmn_node_info;
-/* kind: LMN_KIND_ADD | LMN_KIND_MUL | LMN_KIND_REM (prim.rs:1323-1421, operands > 0) | unary (rhs_dev ignored):
+/* kind: LMN_KIND_ADD | LMN_KIND_MUL | LMN_KIND_REM (prim.rs:1323-1421, lhs >= 0, rhs > 0) | unary (rhs_dev ignored):
  * LMN_KIND_RECIP | LMN_KIND_SQRT (prim.rs:573-660) | LMN_KIND_CONTIGUOUS (prim.rs:229-301) | LMN_KIND_INPUTS
  * (`CopyToStwo`, prim.rs:52-88: rows of a graph input, multiplicity = num_consumers).  rows_dev receives
  * n * lmn_kind_columns(kind) words starting at row `row_offset` of the node's table (several nodes of one
- * kind share a table: prim.rs appends); out_dev (may be NULL) receives the n output values. */
+ * kind share a table: prim.rs appends); out_dev (may be NULL) receives the n output values.
+ *
+ * The producers' contract (every lmn_trace_* call; the rows go to lmn_prove unchecked otherwise):
+ *  - Value range: a Fixed<12> tensor value lies in [-(2^30-1), 2^30-1], the signed M31 range (the one
+ *    lmn_trace_lut_ranges enforces for LUT ranges).  It holds for every operand a producer reads and every output
+ *    value it writes; only the running sums inside SumReduce may leave it.
+ *  - Row words: every row word is the exact integer value reduced mod P, canonical, equal to Python's `v % P` for the
+ *    exact int64 intermediate - running sums, rem, quo and diff included.
+ *  - Preconditions: Recip needs input > 0, Sqrt input >= 0, Rem lhs >= 0 and rhs > 0.
+ *  - An element outside the contract gets the non-canonical word P in its row's output-value column (Add / Mul / Rem /
+ *    LessThan out or rem, Recip / Sqrt / Contiguous out, Inputs val, SumReduce / MaxReduce out - the group result on
+ *    its last step, or the row of an input outside the range - and Sin / Exp2 / Log2 out), the other derived words of
+ *    that row (Mul / Recip / Sqrt rem, Rem quo, LessThan diff, borrow and limbs) are 0, its operand words stay exact,
+ *    and 0 goes to the output tensor; LessThan adds nothing to the range-check multiplicities for it.  lmn_prove of a
+ *    table holding such a row fails with LMN_ERR_INVALID_ARGUMENT (non-canonical word).  The other elements of the
+ *    launch keep their exact rows, no call waits for the device to find out, and no lane does value-dependent work
+ *    for a refused element (no division by zero, no square root of a negative number). */
 int lmn_trace_elementwise(lmn_ctx* ctx, uint32_t kind, const int32_t* lhs_dev, const int32_t* rhs_dev, uint64_t n,
                           const lmn_node_info* info, uint32_t* rows_dev, uint64_t row_offset, int32_t* out_dev);
 

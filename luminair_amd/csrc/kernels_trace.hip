@@ -80,8 +80,23 @@ void launch_transpose_pad(const uint32_t* rows, uint64_t n_rows, int ncols, int 
 // gen_trace for Add / Mul / Recip nodes (crates/graph/src/op/prim.rs:967-1013, :1090-1139, :388-431):
 // one lane per tensor element computes the fixed-point op and its row; the block stages its rows in LDS
 // and writes them out as one contiguous, coalesced run of words.
+// The producers' contract (include/luminair_hip.h, lmn_trace_elementwise): every value read or written lies in
+// [-FIXED_MAX, FIXED_MAX], every row word is the exact value mod P, and an element outside the contract (range or an
+// op's precondition) gets the non-canonical word P in its row's output-value column and 0 in the output tensor, so that
+// lmn_prove refuses the table.  No lane does value-dependent work for such an element (no division by zero, no isqrt
+// of a negative number).
 // =============================================================================================
-LMN_HD uint32_t fixed_to_m31(int64_t v) { return v >= 0 ? (uint32_t)v : (uint32_t)((int64_t)P31 + v); }
+constexpr int64_t FIXED_MAX = (1ll << 30) - 1;
+LMN_HD bool fixed_ok(int64_t v) { return v >= -FIXED_MAX && v <= FIXED_MAX; }
+// v mod P for any int64 (Python's v % P): |v| folded twice on 2^31 = 1 (mod P), then negated
+LMN_HD uint32_t fixed_to_m31(int64_t v) {
+  const uint64_t m = v < 0 ? 0ull - (uint64_t)v : (uint64_t)v;
+  uint64_t x = (m & P31) + (m >> 31);  // < 2^34
+  x = (x & P31) + (x >> 31);           // < 2^31 + 8
+  uint32_t w = (uint32_t)x;
+  if (w >= P31) w -= P31;
+  return v < 0 && w ? P31 - w : w;
+}
 
 LMN_D uint64_t view_offset(const TraceView& v, uint64_t r) {
   if (v.ndim == 0) return r;
@@ -98,7 +113,7 @@ LMN_HD constexpr int trace_ncols(int kind) {
   return kind == 0 ? 15 : kind == 1 ? 16 : kind == 2 ? 13 : kind == 7 ? 13 : kind == 8 ? 16 : kind == 13 ? 22
                                                                                        : kind == 16 ? 11 : 7;
 }
-// floor(sqrt(v)) for v < 2^44, exact (double sqrt + one correction step each way)
+// floor(sqrt(v)) for 0 <= v < 2^44, exact (double sqrt + one correction step each way)
 LMN_D int64_t isqrt_u64(int64_t v) {
   int64_t r = (int64_t)sqrt((double)v);
   while (r * r > v) --r;
@@ -125,11 +140,13 @@ LMN_KERNEL k_trace_elementwise(const int32_t* __restrict__ lhs, TraceView lv, co
       // element of the input BUFFER (zero past its end) with the idx-th element of the OUTPUT (the view; past the
       // output's end the index expression wraps), is_last_idx marks the buffer's last element.  Every buffer
       // element is consumed exactly once, so slices and permutations of the input balance.
+      const int64_t in = r < nd.phys_n ? (int64_t)lhs[r] : 0;
+      const bool ok = fixed_ok(in) && fixed_ok(a);
       t[0] = nd.node_id; t[1] = nd.lhs_id; t[2] = idx; t[3] = last;
       t[4] = nd.node_id; t[5] = nd.lhs_id; t[6] = idx + 1u;
-      t[7] = r < nd.phys_n ? fixed_to_m31((int64_t)lhs[r]) : 0u;
-      t[8] = fixed_to_m31(a); t[9] = nd.lhs_mult; t[10] = nd.out_mult;
-      if (out && r < nd.out_n) out[r] = (int32_t)a;
+      t[7] = fixed_to_m31(in);
+      t[8] = ok ? fixed_to_m31(a) : P31; t[9] = nd.lhs_mult; t[10] = nd.out_mult;
+      if (out && r < nd.out_n) out[r] = ok ? (int32_t)a : 0;
     } else if (KIND == 16 || KIND == 7) {
       // Contiguous (prim.rs:229-301): out = input.  Sqrt (prim.rs:573-660): out = floor(sqrt(input * scale)),
       // rem = input * scale - out^2 (natural identity; numerair's form is unpinned)
@@ -137,13 +154,16 @@ LMN_KERNEL k_trace_elementwise(const int32_t* __restrict__ lhs, TraceView lv, co
       t[4] = nd.node_id; t[5] = nd.lhs_id; t[6] = idx + 1u;
       t[7] = fixed_to_m31(a);
       if (KIND == 16) {
-        t[8] = fixed_to_m31(a); t[9] = nd.lhs_mult; t[10] = nd.out_mult;
-        if (out) out[r] = (int32_t)a;
+        const bool ok = fixed_ok(a);
+        t[8] = ok ? fixed_to_m31(a) : P31; t[9] = nd.lhs_mult; t[10] = nd.out_mult;
+        if (out) out[r] = ok ? (int32_t)a : 0;
       } else {
-        const int64_t o = isqrt_u64(a * 4096ll);
-        t[8] = fixed_to_m31(o); t[9] = fixed_to_m31(a * 4096ll - o * o); t[10] = 4096u;
+        // input >= 0: a refused element takes the square root of 0
+        const bool ok = a >= 0 && a <= FIXED_MAX;
+        const int64_t x = ok ? a * 4096ll : 0, o = isqrt_u64(x);
+        t[8] = ok ? fixed_to_m31(o) : P31; t[9] = fixed_to_m31(x - o * o); t[10] = 4096u;
         t[11] = nd.lhs_mult; t[12] = nd.out_mult;
-        if (out) out[r] = (int32_t)o;
+        if (out) out[r] = ok ? (int32_t)o : 0;
       }
     } else if (KIND == 8 || KIND == 13) {
       const int64_t b = rhs[view_offset(rv, r)];
@@ -151,60 +171,64 @@ LMN_KERNEL k_trace_elementwise(const int32_t* __restrict__ lhs, TraceView lv, co
       t[5] = nd.node_id; t[6] = nd.lhs_id; t[7] = nd.rhs_id; t[8] = idx + 1u;
       t[9] = fixed_to_m31(a); t[10] = fixed_to_m31(b);
       if (KIND == 8) {
-        // Rem (prim.rs:1323-1421), operands > 0: lhs = rhs * quotient + rem; the out relation carries rem
-        const int64_t quo = a / b, rem = a % b;
-        t[11] = fixed_to_m31(rem); t[12] = fixed_to_m31(quo);
+        // Rem (prim.rs:1323-1421), lhs >= 0, rhs > 0: lhs = rhs * quotient + rem; the out relation carries rem.
+        // A refused element divides 0 by 1.
+        const bool ok = a >= 0 && a <= FIXED_MAX && b > 0 && b <= FIXED_MAX;
+        const uint32_t num = ok ? (uint32_t)a : 0u, den = ok ? (uint32_t)b : 1u;
+        const uint32_t quo = num / den, rem = num - quo * den;
+        t[11] = ok ? rem : P31; t[12] = quo;
         t[13] = nd.lhs_mult; t[14] = nd.rhs_mult; t[15] = nd.out_mult;
         if (out) out[r] = (int32_t)rem;
       } else {
         // LessThan (prim.rs:1203-1295): out = 1.0 iff lhs < rhs; diff = rhs - lhs (+ P with borrow) in four
         // range-checked 8-bit limbs; aux = the RangeCheckLookup multiplicity column (256 entries)
-        const bool lt = a < b;
-        const int64_t diff = b - a + (lt ? 0 : (int64_t)P31);
-        t[11] = lt ? 4096u : 0u;
-        t[12] = (uint32_t)(diff % (int64_t)P31);
-        t[13] = lt ? 0u : 1u;
+        // (a refused element has zero diff, borrow and limbs and adds nothing to the multiplicities)
+        const bool ok = fixed_ok(a) && fixed_ok(b), lt = ok && a < b;
+        const int64_t diff = ok ? b - a + (lt ? 0 : (int64_t)P31) : 0;  // 1 .. 2^31 - 2, or P for equal operands
+        t[11] = ok ? (lt ? 4096u : 0u) : P31;
+        t[12] = fixed_to_m31(diff);
+        t[13] = ok && !lt ? 1u : 0u;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const uint32_t limb = (uint32_t)(diff >> (8 * k)) & 0xFFu;
           t[14 + k] = limb;
-          atomicAdd(&aux[limb], 1u);
+          if (ok) atomicAdd(&aux[limb], 1u);
         }
         t[18] = nd.lhs_mult; t[19] = nd.rhs_mult; t[20] = nd.out_mult; t[21] = 1u;
         if (out) out[r] = lt ? 4096 : 0;
       }
     } else if (KIND == 15) {
       // CopyToStwo / Inputs (prim.rs:52-88): node, idx, is_last, next_node, next_idx, val, multiplicity
+      const bool ok = fixed_ok(a);
       t[0] = nd.node_id; t[1] = idx; t[2] = last; t[3] = nd.node_id; t[4] = idx + 1u;
-      t[5] = fixed_to_m31(a); t[6] = nd.out_mult;
-      if (out) out[r] = (int32_t)a;
+      t[5] = ok ? fixed_to_m31(a) : P31; t[6] = nd.out_mult;
+      if (out) out[r] = ok ? (int32_t)a : 0;
     } else if (KIND == 2) {
       // node, input, idx, is_last, next_node, next_input, next_idx, input, out, rem, scale, in_mult, out_mult
-      const int64_t sc2 = 4096ll * 4096ll;
-      const int64_t o = sc2 / a, rem = sc2 - a * o;
+      // input > 0 (4096^2 / input and its remainder fit 32 bits): a refused element divides by 1
+      const bool ok = a > 0 && a <= FIXED_MAX;
+      const uint32_t sc2 = 4096u * 4096u, den = ok ? (uint32_t)a : 1u;
+      const uint32_t o = sc2 / den, rem = sc2 - den * o;
       t[0] = nd.node_id; t[1] = nd.lhs_id; t[2] = idx; t[3] = last;
       t[4] = nd.node_id; t[5] = nd.lhs_id; t[6] = idx + 1u;
-      t[7] = fixed_to_m31(a); t[8] = fixed_to_m31(o); t[9] = fixed_to_m31(rem); t[10] = 4096u;
+      t[7] = fixed_to_m31(a); t[8] = ok ? o : P31; t[9] = ok ? rem : 0u; t[10] = 4096u;
       t[11] = nd.lhs_mult; t[12] = nd.out_mult;
-      if (out) out[r] = (int32_t)o;
+      if (out) out[r] = ok ? (int32_t)o : 0;
     } else {
       const int64_t b = rhs[view_offset(rv, r)];
       t[0] = nd.node_id; t[1] = nd.lhs_id; t[2] = nd.rhs_id; t[3] = idx; t[4] = last;
       t[5] = nd.node_id; t[6] = nd.lhs_id; t[7] = nd.rhs_id; t[8] = idx + 1u;
       t[9] = fixed_to_m31(a); t[10] = fixed_to_m31(b);
-      int64_t o;
+      const int64_t prod = a * b, o = KIND == 0 ? a + b : prod >> 12;  // Mul: floor
+      const bool ok = fixed_ok(a) && fixed_ok(b) && fixed_ok(o);
+      t[11] = ok ? fixed_to_m31(o) : P31;
       if (KIND == 0) {
-        o = a + b;
-        t[11] = fixed_to_m31(o);
         t[12] = nd.lhs_mult; t[13] = nd.rhs_mult; t[14] = nd.out_mult;
       } else {
-        const int64_t prod = a * b;
-        o = prod >> 12;  // floor
-        t[11] = fixed_to_m31(o);
-        t[12] = (uint32_t)(prod & 4095);
+        t[12] = ok ? (uint32_t)(prod & 4095) : 0u;
         t[13] = nd.lhs_mult; t[14] = nd.rhs_mult; t[15] = nd.out_mult;
       }
-      if (out) out[r] = (int32_t)o;
+      if (out) out[r] = ok ? (int32_t)o : 0;
     }
   }
   __syncthreads();
@@ -279,17 +303,20 @@ LMN_KERNEL k_trace_reduce(const int32_t* __restrict__ input, uint64_t dim, uint6
     }
     const int64_t next = op(acc, v);
     const bool last_step = k + 1 == dim;
+    // running values may leave the value range (exact words mod P); an input outside it, or a group result outside it
+    // on the last step, marks the row's output-value column
+    const bool ok = fixed_ok(v) && (!last_step || fixed_ok(next));
     uint32_t* t = tile + threadIdx.x * ST;
     t[0] = nd.node_id; t[1] = nd.lhs_id; t[2] = (uint32_t)g; t[3] = g + 1 == n_out ? 1u : 0u;
     t[4] = nd.node_id; t[5] = nd.lhs_id; t[6] = (uint32_t)g + 1u;
-    t[7] = fixed_to_m31(v); t[8] = last_step ? fixed_to_m31(next) : 0u;
+    t[7] = fixed_to_m31(v); t[8] = !ok ? P31 : last_step ? fixed_to_m31(next) : 0u;
     t[9] = fixed_to_m31(acc); t[10] = fixed_to_m31(next); t[11] = last_step ? 1u : 0u;
     if (MAX) {
       t[12] = v > acc ? 1u : 0u; t[13] = nd.lhs_mult; t[14] = last_step ? nd.out_mult : 0u;
     } else {
       t[12] = nd.lhs_mult; t[13] = last_step ? nd.out_mult : 0u;
     }
-    if (last_step && out) out[g] = (int32_t)next;
+    if (last_step && out) out[g] = ok ? (int32_t)next : 0;
   }
   __syncthreads();
   const uint64_t rows_here = n_rows - row0 < (uint64_t)TPB ? n_rows - row0 : (uint64_t)TPB;
@@ -339,7 +366,7 @@ LMN_KERNEL k_trace_lut(const int32_t* __restrict__ input, TraceView view, uint64
     int64_t li = -1;
     for (int k = 0; k < rg.n; ++k)
       if (a >= (int64_t)rg.lo[k] && a <= (int64_t)rg.hi[k]) li = (int64_t)rg.base[k] + (a - (int64_t)rg.lo[k]);
-    uint32_t ow = 0u;
+    uint32_t ow = P31;  // an input outside every range: the call fails, and its row is marked as well
     if (li < 0) {
       *err_flag = 1u;
     } else {

@@ -21,9 +21,8 @@ KIND_SQRT, KIND_REM = 7, 8
 
 
 def to_m31(v: np.ndarray) -> np.ndarray:
-    """Fixed<12>::to_m31: negatives map to P - |v|."""
-    v = np.asarray(v, dtype=np.int64)
-    return np.where(v >= 0, v, P + v).astype(np.uint32)
+    """Fixed<12>::to_m31, exact for any int64: v mod P (negatives map to P - |v| mod P)."""
+    return (np.asarray(v, dtype=np.int64) % P).astype(np.uint32)
 
 
 def _ids(n, node, a, b=None):
@@ -60,7 +59,10 @@ def mul_rows(lhs, rhs, node=2, lhs_id=0, rhs_id=1, mults=(0, 0, 0)) -> np.ndarra
 
 
 def recip_rows(inp, node=2, input_id=0, mults=(0, 0)) -> np.ndarray:
+    """Recip rows (`crates/graph/src/op/prim.rs:388-431`), input > 0: out = floor(4096^2 / input)."""
     inp = np.asarray(inp, np.int64)
+    if np.any(inp <= 0):
+        raise ValueError("Recip needs input > 0")
     n = len(inp)
     out = (SCALE * SCALE) // inp
     rem = SCALE * SCALE - inp * out
@@ -142,8 +144,10 @@ def contiguous_rows_ref(phys, out, node=2, input_id=0, input_mult=-1, out_mult=0
 
 def sqrt_rows(inp, node=2, input_id=0, mults=(0, 0)) -> np.ndarray:
     """Fixed-point sqrt rows (`crates/graph/src/op/prim.rs:573-660`): out = floor(sqrt(input*scale)),
-    rem = input*scale - out^2 (the natural identity; numerair's exact form is unpinned)."""
+    rem = input*scale - out^2 (the natural identity; numerair's exact form is unpinned), input >= 0."""
     inp = np.asarray(inp, np.int64)
+    if np.any(inp < 0):
+        raise ValueError("Sqrt needs input >= 0")
     n = len(inp)
     out = np.floor(np.sqrt((inp * SCALE).astype(np.float64))).astype(np.int64)
     out = np.where(out * out > inp * SCALE, out - 1, out)
@@ -155,9 +159,11 @@ def sqrt_rows(inp, node=2, input_id=0, mults=(0, 0)) -> np.ndarray:
 
 
 def rem_rows(lhs, rhs, node=2, lhs_id=0, rhs_id=1, mults=(0, 0, 0)) -> np.ndarray:
-    """Remainder rows (`crates/graph/src/op/prim.rs:1323-1421`): lhs = rhs*quotient + rem, operands > 0;
+    """Remainder rows (`crates/graph/src/op/prim.rs:1323-1421`): lhs = rhs*quotient + rem, lhs >= 0 and rhs > 0;
     the out relation carries `rem`."""
     lhs, rhs = np.asarray(lhs, np.int64), np.asarray(rhs, np.int64)
+    if np.any(lhs < 0) or np.any(rhs <= 0):
+        raise ValueError("Rem needs lhs >= 0 and rhs > 0")
     n = len(lhs)
     quo, rem = lhs // rhs, lhs % rhs
     cols = _ids(n, node, lhs_id, rhs_id) + [to_m31(lhs), to_m31(rhs), to_m31(rem), to_m31(quo)]

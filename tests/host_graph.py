@@ -1,13 +1,24 @@
 """numpy mirror of `DeviceGraph.gen_trace` for tests: walks the same node list on the host, evaluates every op on
 `Fixed<12>` integers and builds each kind's trace table with the row generators of luminair_amd/synthetic.py
 (themselves checked against the reference's `process_trace` layouts and, for Add / Mul, against the KAT).
-Returns what the device-side producer must emit: {kind: rows}, {node_id: values}."""
+Returns what the device-side producer must emit: {kind: rows}, {node_id: values}.  A value that leaves the
+Fixed<12> range [-(2^30-1), 2^30-1] of the producers' contract raises ValueError, as does an op's precondition
+(Recip input > 0, Sqrt input >= 0, Rem lhs >= 0 and rhs > 0): the device refuses the same graphs."""
 from __future__ import annotations
 
 import numpy as np
 
 from luminair_amd import synthetic as syn
 from luminair_amd.pie import TraceTableKind as K
+
+FIXED_MAX = (1 << 30) - 1
+
+
+def _check_range(node_id, x):
+    x = np.asarray(x, dtype=np.int64)
+    if x.size and (x.min() < -FIXED_MAX or x.max() > FIXED_MAX):
+        raise ValueError("host mirror: node %d yields a value outside [-(2^30-1), 2^30-1]" % node_id)
+
 
 _LUT_NAME = {int(K.Sin): ("sin", int(K.SinLookup)), int(K.Exp2): ("exp2", int(K.Exp2Lookup)),
              int(K.Log2): ("log2", int(K.Log2Lookup))}
@@ -42,20 +53,22 @@ def host_tables(g):
             elif kind == int(K.Mul):
                 out, rows = (a * b) >> 12, syn.mul_rows(a, b, t.node_id, ids[0], ids[1], (-1, -1, om))
             elif kind == int(K.Rem):
-                out, rows = a % b, syn.rem_rows(a, b, t.node_id, ids[0], ids[1], (-1, -1, om))
+                rows = syn.rem_rows(a, b, t.node_id, ids[0], ids[1], (-1, -1, om))
+                out = a % b
             else:
                 out = np.where(a < b, S, 0)
                 rows, c = syn.less_than_rows(a, b, t.node_id, ids[0], ids[1], (-1, -1, om))
                 rc_counts += c
         elif kind == int(K.Recip):
             a = read_view(vals, n.inputs[0])
-            out, rows = (S * S) // a, syn.recip_rows(a, t.node_id, ids[0], (-1, om))
+            rows = syn.recip_rows(a, t.node_id, ids[0], (-1, om))
+            out = (S * S) // a
         elif kind == int(K.Sqrt):
             a = read_view(vals, n.inputs[0])
+            rows = syn.sqrt_rows(a, t.node_id, ids[0], (-1, om))
             out = np.array([int(np.floor(np.sqrt(float(x * S)))) for x in a], dtype=np.int64)
             out = np.where(out * out > a * S, out - 1, out)
             out = np.where((out + 1) * (out + 1) <= a * S, out + 1, out)
-            rows = syn.sqrt_rows(a, t.node_id, ids[0], (-1, om))
         elif kind == int(K.Contiguous):
             v = n.inputs[0]
             out = read_view(vals, v)
@@ -88,6 +101,7 @@ def host_tables(g):
                 base += b - a_ + 1
         else:
             raise ValueError("host mirror: kind %d" % kind)
+        _check_range(t.node_id, out)     # every value an op reads is some earlier node's output (running sums may leave)
         vals[t.node_id] = np.asarray(out, dtype=np.int64).reshape(-1)
         tabs.setdefault(kind, []).append(rows)
     tables = {k: np.concatenate(v) for k, v in tabs.items()}
