@@ -482,7 +482,8 @@ int lmn_op_eval_at_point(lmn_ctx* ctx, const uint32_t* coeffs, uint32_t log_size
 /* QuotientOps::accumulate_quotients for the columns of ONE LDE size: `cols[c]` = 2^log_size evaluations
  * (bit-reversed canonic domain); sample i = (column sample_col[i], point sample_point[i], value
  * sample_values[4i..4i+4)), in (column, mask-position) order; points_xy = npoints x 8 words (x then y);
- * out = 4 coordinate columns x 2^log_size. */
+ * out = 4 coordinate columns x 2^log_size.  Limits of one call (also of lmn_col_accumulate_quotients): at most 4
+ * distinct sample_point indices and at most 512 samples; beyond either the call returns LMN_ERR_INVALID_ARGUMENT. */
 int lmn_op_accumulate_quotients(lmn_ctx* ctx, uint32_t log_size, const uint32_t* const* cols, uint32_t ncols,
                                 const uint32_t* sample_col, const uint32_t* sample_point, const uint32_t* sample_values,
                                 uint32_t nsamples, const uint32_t* points_xy, uint32_t npoints, const uint32_t alpha[4],
@@ -549,7 +550,8 @@ uint32_t lmn_tree_log_size(const lmn_tree* tree);
 int lmn_tree_layer_to_cpu(lmn_ctx* ctx, const lmn_tree* tree, uint32_t layer_log, uint8_t* hashes_out); /* 32 * 2^layer_log bytes */
 void lmn_tree_free(lmn_ctx* ctx, lmn_tree* tree);
 int lmn_col_accumulate(lmn_ctx* ctx, lmn_col* dst, const lmn_col* src);     /* AccumulationOps::accumulate: dst += src (same shape) */
-/* QuotientOps::accumulate_quotients (one LDE size; samples as in lmn_op_accumulate_quotients): out = 4 coordinate columns */
+/* QuotientOps::accumulate_quotients (one LDE size; samples and limits as in lmn_op_accumulate_quotients: at most 4
+ * distinct sample points and 512 samples, else LMN_ERR_INVALID_ARGUMENT): out = 4 coordinate columns */
 int lmn_col_accumulate_quotients(lmn_ctx* ctx, const lmn_col* const* cols, uint32_t n, const uint32_t* sample_col,
                                  const uint32_t* sample_point, const uint32_t* sample_values, uint32_t nsamples,
                                  const uint32_t* points_xy, uint32_t npoints, const uint32_t alpha[4], lmn_col** out);

@@ -213,7 +213,9 @@ LMN_D void fft_stage(const uint32_t* sm_in, uint32_t* sm_out, uint32_t* col, con
     uint32_t v[1 << R];
     if (from_global) {
       if (p == 0 && cb == 0 && R >= 2) {
-        if (e0 < lim) {
+        // the group is 2^R consecutive words: one vector load only when all of them are readable (a transform of
+        // 2^4 points or fewer is a single stage, and its coefficients can end inside the group)
+        if (e0 + (1u << R) <= lim) {
           const uint4* q = reinterpret_cast<const uint4*>(tsrc + e0);
 #pragma unroll
           for (int k = 0; k < (1 << R) / 4; ++k) {
@@ -225,7 +227,7 @@ LMN_D void fft_stage(const uint32_t* sm_in, uint32_t* sm_out, uint32_t* col, con
           }
         } else {
 #pragma unroll
-          for (int j = 0; j < (1 << R); ++j) v[j] = 0u;
+          for (int j = 0; j < (1 << R); ++j) v[j] = e0 + (uint32_t)j < lim ? tsrc[e0 + (uint32_t)j] : 0u;
         }
       } else if (full) {
 #pragma unroll

@@ -237,6 +237,20 @@ void Context::col_accumulate(lmn_col* dst, const lmn_col* src) {
   launch_secure_add(dst->d, src->d, dst->words(), stream_);
 }
 
+// at most QUOT_MAX_BATCH distinct sample points and QUOT_MAX_ENTRIES samples (include/luminair_hip.h): make_quotient_args
+// sizes its batch and entry tables by them
+void check_quotient_limits(const uint32_t* sample_point, uint32_t nsamples) {
+  if (nsamples > (uint32_t)QUOT_MAX_ENTRIES)
+    throw LmnError(LMN_ERR_INVALID_ARGUMENT, "accumulate_quotients: more than 512 samples");
+  uint32_t seen[QUOT_MAX_BATCH];
+  int n = 0;
+  for (uint32_t i = 0; i < nsamples; ++i) {
+    if (std::find(seen, seen + n, sample_point[i]) != seen + n) continue;
+    if (n == QUOT_MAX_BATCH) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "accumulate_quotients: more than 4 distinct sample points");
+    seen[n++] = sample_point[i];
+  }
+}
+
 lmn_col* Context::col_accumulate_quotients(const lmn_col* const* cols, uint32_t n, const uint32_t* sample_col,
                                            const uint32_t* sample_point, const uint32_t* sample_values, uint32_t nsamples,
                                            const uint32_t* points_xy, uint32_t npoints, const uint32_t alpha[4]) {
@@ -244,6 +258,7 @@ lmn_col* Context::col_accumulate_quotients(const lmn_col* const* cols, uint32_t 
   if (n == 0 || !cols[0]) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "accumulate_quotients: no columns / null column handle");
   const uint32_t log_size = cols[0]->log_size;
   if (log_size < 2) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "accumulate_quotients: domain too small");
+  check_quotient_limits(sample_point, nsamples);
   std::vector<const uint32_t*> d_cols;
   for (uint32_t k = 0; k < n; ++k) {
     if (!cols[k] || cols[k]->log_size != log_size) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "accumulate_quotients: columns of one size only");

@@ -120,6 +120,7 @@ void Context::op_accumulate_quotients(uint32_t log_size, const uint32_t* const* 
                                       uint32_t nsamples, const uint32_t* points_xy, uint32_t npoints, const uint32_t alpha[4],
                                       uint32_t* out) {
   if (log_size < 2 || log_size > 26) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "bad log_size");
+  check_quotient_limits(sample_point, nsamples);
   ensure_twiddles((int)log_size);
   const uint64_t L = 1ull << log_size;
   arena_.reserve(((uint64_t)ncols + 4) * L * 4 + (8u << 20));

@@ -154,6 +154,9 @@ struct DevTree {
   DevMerkle merkle;
 };
 
+// the caller-facing limits of one accumulate_quotients call (level2.cpp): LMN_ERR_INVALID_ARGUMENT past them
+void check_quotient_limits(const uint32_t* sample_point, uint32_t nsamples);
+
 struct StageTimer;
 
 struct ProofRun;   // state of one proof across the phases of Context::prove (prove_run.h)
