@@ -32,7 +32,7 @@ LMN_HD uint32_t b2_rotr(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); 
   LMN_B2_G(v2, v7, v8, v13, m[s12], m[s13])                                                \
   LMN_B2_G(v3, v4, v9, v14, m[s14], m[s15])
 
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(LMN_EMU) && !defined(LMN_B2_NO_PRIO)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(LMN_EMU)
 // gfx950 issue order for one half round (four independent quarter rounds), written out as instructions.
 // Measured (profiles/ceilings/valu_coissue_two_ports.txt, tools/microbench_reconcile.hip `prio`): a SIMD issues up to two VALU
 // instructions per 4-cycle slot from two different waves, but v_add3_u32 / v_alignbit_b32 (and every other three-operand
@@ -92,10 +92,7 @@ __device__ __forceinline__ void b2_half(uint32_t& a0, uint32_t& a1, uint32_t& a2
 
 // h <- F(h, m, t, f0).  The sigma schedule is unrolled so message words stay in registers.  LO / HI: wave priority
 // while issuing the any-port / first-port-only instruction runs on the device (LO == HI: constant priority).
-#ifndef LMN_B2_PRIO_HI
-#define LMN_B2_PRIO_HI 3
-#endif
-template <int LO = 0, int HI = LMN_B2_PRIO_HI>
+template <int LO = 0, int HI = 3>
 LMN_HD void b2_compress(uint32_t h[8], const uint32_t m[16], uint32_t t0, uint32_t f0) {
   uint32_t v0 = h[0], v1 = h[1], v2 = h[2], v3 = h[3], v4 = h[4], v5 = h[5], v6 = h[6], v7 = h[7];
   uint32_t v8 = 0x6A09E667u, v9 = 0xBB67AE85u, v10 = 0x3C6EF372u, v11 = 0xA54FF53Au;
@@ -127,7 +124,7 @@ LMN_HD void b2_compress(uint32_t h[8], const uint32_t m[16], uint32_t t0, uint32
 // state as LITERAL operands - a = (h_a + h_b) + x, d = K_d ^ a, c = K_c + d, b = K_b ^ c - so the 16 state registers are
 // first written by arithmetic instead of 16 constant moves in front of every compression (the asm operands of b2_half
 // are read-write); instruction classes and phases as in b2_half.
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(LMN_EMU) && !defined(LMN_B2_NO_PRIO) && !defined(LMN_B2_NO_FRESH)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(LMN_EMU)
 template <int LO, int HI>
 __device__ __forceinline__ void b2_half_first(uint32_t& a0, uint32_t& a1, uint32_t& a2, uint32_t& a3, uint32_t& b0, uint32_t& b1,
                                               uint32_t& b2, uint32_t& b3, uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3,
@@ -172,7 +169,7 @@ __device__ __forceinline__ void b2_half_first(uint32_t& a0, uint32_t& a1, uint32
 #endif
 
 LMN_HD void b2_init(uint32_t h[8]);
-template <int LO = 0, int HI = LMN_B2_PRIO_HI>
+template <int LO = 0, int HI = 3>
 LMN_HD void b2_compress_fresh(uint32_t out[8], const uint32_t m[16], uint32_t t0) {
 #ifdef LMN_B2_HAVE_FRESH
   uint32_t v0, v1, v2, v3, v4, v5, v6, v7, v8, v9, v10, v11, v12, v13, v14, v15;
@@ -291,7 +288,7 @@ __device__ __forceinline__ void b2_half_z(uint32_t& a0, uint32_t& a1, uint32_t& 
   LMN_B2_HALF_Z(v0, v1, v2, v3, v5, v6, v7, v4, v10, v11, v8, v9, v15, v12, v13, v14, s8, s9, s10, s11, s12, s13, s14, s15)
 #endif
 
-template <int NZ, int LO = 0, int HI = LMN_B2_PRIO_HI>
+template <int NZ, int LO = 0, int HI = 3>
 LMN_HD void b2_compress_fresh_nz(uint32_t out[8], const uint32_t m[16], uint32_t t0) {
   static_assert(NZ >= 1 && NZ <= 16, "number of leading message words that may be non-zero");
 #ifdef LMN_B2_HAVE_FRESH
@@ -342,7 +339,7 @@ LMN_HD void b2_compress_fresh_nz(uint32_t out[8], const uint32_t m[16], uint32_t
 // h <- F(h, m, t0, f0) as b2_compress for a block whose message words m[NZ..15] are zero by construction: the
 // chaining-value form of b2_compress_fresh_nz (the proof-of-work grind of the KAT transcript form: h = the channel digest,
 // m = the nonce's two words).  On the device every half round goes through b2_half_z; elsewhere it is b2_compress.
-template <int NZ, int LO = 0, int HI = LMN_B2_PRIO_HI>
+template <int NZ, int LO = 0, int HI = 3>
 LMN_HD void b2_compress_cv_nz(uint32_t h[8], const uint32_t m[16], uint32_t t0, uint32_t f0) {
   static_assert(NZ >= 1 && NZ <= 16, "number of leading message words that may be non-zero");
 #ifdef LMN_B2_HAVE_FRESH

@@ -23,7 +23,7 @@ void Context::build_merkle_levels(std::vector<uint32_t*>& layers, int max_log,
                                   const ChanStep* step) {
   bool chan_done = false;
   // LMN_CHAN_STEP_SEPARATE=1 (measurements, tests): a commitment phase's transcript step as a launch of its own behind the tree
-  const bool step_inside = step && getenv("LMN_CHAN_STEP_SEPARATE") == nullptr;
+  const bool step_inside = step && !env_set("LMN_CHAN_STEP_SEPARATE");
   const ChanStep* d_step = nullptr;   // the kernels read the plan from page-locked memory (one load per lane)
   if (step) {
     check_chan_step(*step);
@@ -44,8 +44,7 @@ void Context::build_merkle_levels(std::vector<uint32_t*>& layers, int max_log,
     MerkleFold below{};   // the leaf level of a tree whose next level has columns too: hashed by that level's launch
     // from 2^19 leaves on (below that the launches are latency-bound and the separate leaf launch is the cheaper form);
     // LMN_MERKLE_BELOW_MIN_LOG lowers the threshold for the emulation tests
-    const char* below_env = getenv("LMN_MERKLE_BELOW_MIN_LOG");
-    const int below_min_log = below_env ? std::max(12, atoi(below_env)) : 19;
+    const int below_min_log = std::max(12, env_int("LMN_MERKLE_BELOW_MIN_LOG", 19));
     // runs of contiguous equal-size columns of a level; false if there are more than MERKLE_MAX_SEG of them
     auto make_segs = [&](int lv, MerkleSegs& sg) {
       int nseg = 0;
@@ -64,10 +63,6 @@ void Context::build_merkle_levels(std::vector<uint32_t*>& layers, int max_log,
     };
     while (level >= 0) {
       auto& lc = per_level[level];
-      if (level == wait_before_level_) {   // this level's columns were produced on the second stream
-        lmn_stream_wait_event(stream_, wait_before_level_ev_);
-        wait_before_level_ = -1;
-      }
       if (cuts && !fold && !prev && level == max_log && level >= below_min_log && !lc.empty() && lc.size() <= 8 &&
           !per_level[level - 1].empty()) {
         MerkleSegs sl{}, snext{};
@@ -110,7 +105,7 @@ void Context::build_merkle_levels(std::vector<uint32_t*>& layers, int max_log,
         nfused = std::min(std::min(plain, MERKLE_MAX_FUSED), level - 10);
         // per-lane subtree depth: only as deep as still leaves >= 2^17 lanes (latency-bound below that)
         int sub = std::max(0, std::min(std::min(MERKLE_MAX_SUB, nfused), level - 17));
-        if (const char* e = getenv("LMN_MERKLE_SUB")) sub = std::min(std::min(atoi(e), nfused), MERKLE_MAX_SUB);
+        if (env_set("LMN_MERKLE_SUB")) sub = std::min(std::min(env_int("LMN_MERKLE_SUB", 0), nfused), MERKLE_MAX_SUB);
         nfused = std::min(nfused, sub + 8);
         // the `sub` levels a lane reduces in registers are not written when the caller can recompute what it needs of them
         const int skip = cuts ? sub : 0;
@@ -243,21 +238,21 @@ void Context::gather_columns(uint32_t* base, uint64_t col_stride, int ncols, uin
 }
 
 bool Context::shard_all_to_all() const {
-  static const bool off = getenv("LMN_SHARD_A2A") && atoi(getenv("LMN_SHARD_A2A")) == 0;   // ablation: replicated interpolation
+  static const bool off = env_int("LMN_SHARD_A2A", 1) == 0;   // ablation: replicated interpolation
   return shard_.active && shard_.world > 1 && shard_.coll.all_to_all != nullptr && !off;
 }
 
 // column-parallel interpolation pays where the transforms are throughput-bound; small columns stay replicated (two more
 // collectives would cost more than the few microseconds of butterflies).  LMN_SHARD_A2A_MIN_LOG lowers the bar (tests).
 bool Context::shard_a2a_columns(int log_size) const {
-  static const int min_log = getenv("LMN_SHARD_A2A_MIN_LOG") ? atoi(getenv("LMN_SHARD_A2A_MIN_LOG")) : 13;
+  static const int min_log = env_int("LMN_SHARD_A2A_MIN_LOG", 13);
   return shard_all_to_all() && cfg.log_blowup == 1 && log_size >= min_log && log_size >= 4;
 }
 // Row-parallel front end: every rank transposes and computes the logup fractions of its row block only; the blocks go to
 // the columns' owners by an all-to-all (the reverse of stage B).  Three more collectives per component: worth it for the
 // big tables (BASELINE config 5: 2^23 rows), not at 2^20.  LMN_SHARD_ROWS_MIN_LOG lowers the bar (tests).
 bool Context::shard_rows_front(int log_size) const {
-  static const int min_log = getenv("LMN_SHARD_ROWS_MIN_LOG") ? atoi(getenv("LMN_SHARD_ROWS_MIN_LOG")) : 22;
+  static const int min_log = env_int("LMN_SHARD_ROWS_MIN_LOG", 22);
   return shard_a2a_columns(log_size) && log_size >= min_log && ((1ull << log_size) >> shard_.g) >= 64;
 }
 

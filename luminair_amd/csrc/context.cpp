@@ -53,28 +53,9 @@ Context::Context(int device, const lmn_config& c) : cfg(c), device_(device) {
     // pipeline instead - measured on 20-proof regions with 4 contexts: {488, 471, 432, 429, 386, 485} proofs/s
     // without, {466, 485, 486, 461, 486, 489} with; long runs and solo latency unchanged.
     // LMN_STREAM_PRIO_CYCLE=0 switches it off.
-    static const bool cycle = !(getenv("LMN_STREAM_PRIO_CYCLE") && atoi(getenv("LMN_STREAM_PRIO_CYCLE")) == 0);
+    static const bool cycle = env_int("LMN_STREAM_PRIO_CYCLE", 1) != 0;
     static std::atomic<int> counter{0};
     int lo = 0, hi = 0;
-    // LMN_CU_SPLIT=P[:1] (experiment of round 6, docs/SWITCHES.md): context k's stream runs on partition k mod P of the CUs
-    // only (P = 2, 4, 8; contiguous mask bits, or ":1" = bit i belongs to partition (i mod 8) * P / 8) - do launches of
-    // different proofs overlap better side by side on parts of the chip than queued behind each other on all of it?
-    static const char* split_env = getenv("LMN_CU_SPLIT");
-    const int parts = split_env ? atoi(split_env) : 0;
-    if (parts == 2 || parts == 4 || parts == 8) {
-      static std::atomic<int> split_counter{0};
-      const int part = split_counter.fetch_add(1) % parts;
-      const bool by_xcd = strstr(split_env, ":1") != nullptr;
-      hipDeviceProp_t prop;
-      LMN_HIP_CHECK(hipGetDeviceProperties(&prop, device));
-      const int n_cu = prop.multiProcessorCount;
-      std::vector<uint32_t> mask((size_t)(n_cu + 31) / 32, 0u);
-      for (int i = 0; i < n_cu; ++i) {
-        const int owner = by_xcd ? (i % 8) * parts / 8 : (int)((int64_t)i * parts / n_cu);
-        if (owner == part) mask[(size_t)i / 32] |= 1u << (i % 32);
-      }
-      LMN_HIP_CHECK(hipExtStreamCreateWithCUMask(&stream_, (uint32_t)mask.size(), mask.data()));
-    } else
     if (cycle && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi) {
       const int span = lo - hi + 1;                     // lo = least priority (numerically greatest)
       const int prio = hi + (counter.fetch_add(1) % span);
@@ -83,19 +64,14 @@ Context::Context(int device, const lmn_config& c) : cfg(c), device_(device) {
       LMN_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
     }
   }
-#ifndef LMN_BATCH
-  // LMN_FRI_OVERLAP (experiment; default off): 1 = always, 2 = while this is the process's only proof in flight
-  fri_overlap_mode_ = getenv("LMN_FRI_OVERLAP") ? std::max(0, std::min(2, atoi(getenv("LMN_FRI_OVERLAP")))) : 0;
-#endif
 #else
   stream_ = 0;
 #endif
   // Proof of work on the device from this many bits on (below: the host loop, ~8 M tries/s on one core, against a launch
   // and a wait of some tens of us); LMN_POW_DEVICE_MIN_BITS overrides it (41: never), LMN_POW_WINDOW_LOG caps the nonces
   // of one grind launch ("Proof of work").  Read per context, like the switches above.
-  pow_device_min_bits_ = getenv("LMN_POW_DEVICE_MIN_BITS") ? std::max(0, atoi(getenv("LMN_POW_DEVICE_MIN_BITS"))) : POW_DEVICE_MIN_BITS;
-  pow_window_log_ = getenv("LMN_POW_WINDOW_LOG") ? std::max(POW_MIN_WINDOW_LOG, std::min(30, atoi(getenv("LMN_POW_WINDOW_LOG"))))
-                                                 : POW_WINDOW_LOG;
+  pow_device_min_bits_ = std::max(0, env_int("LMN_POW_DEVICE_MIN_BITS", POW_DEVICE_MIN_BITS));
+  pow_window_log_ = std::max(POW_MIN_WINDOW_LOG, std::min(30, env_int("LMN_POW_WINDOW_LOG", POW_WINDOW_LOG)));
   event_log = new EventLog();
   pin_cap_ = 32u << 20;
   pin_base_ = (char*)lmn_host_alloc_pinned(pin_cap_);
@@ -108,25 +84,6 @@ Context::Context(int device, const lmn_config& c) : cfg(c), device_(device) {
 }
 
 std::atomic<int> g_proofs_in_flight{0};
-
-// Experiment switch: the smaller FRI quotient column on a second stream next to the leaf hashing of the larger one's.  It
-// helped a solo proof in round 3 (-50 us) and cost 7 % of throughput; with round 4's fused first layer it costs a solo
-// proof 60 - 100 us as well (round 5, gpu_session_r8k: 2.37 - 2.46 vs 2.33 - 2.37 ms), also in the "only while no other proof
-// of the process is in flight" form (mode 2).  Off by default; the stream is created on first use.
-bool Context::second_stream_wanted() {
-#if defined(LMN_EMU) || defined(LMN_BATCH)
-  return false;
-#else
-  if (fri_overlap_mode_ == 0 || (fri_overlap_mode_ == 2 && g_proofs_in_flight.load(std::memory_order_relaxed) != 1)) return false;
-  if (!have_stream2_) {
-    LMN_HIP_CHECK(hipStreamCreateWithFlags(&stream2_, hipStreamNonBlocking));
-    ev_fork_ = lmn_event_create_sync();
-    ev_join_ = lmn_event_create_sync();
-    have_stream2_ = true;
-  }
-  return true;
-#endif
-}
 
 Context::~Context() {
 #ifndef LMN_EMU
@@ -144,12 +101,6 @@ Context::~Context() {
   if (pow_best_) lmn_dev_free(pow_best_);
   if (pin_base_) lmn_host_free_pinned(pin_base_);
 #ifndef LMN_EMU
-  if (have_stream2_) {
-    (void)hipStreamSynchronize(stream2_);
-    (void)hipStreamDestroy(stream2_);
-    lmn_event_destroy(ev_fork_);
-    lmn_event_destroy(ev_join_);
-  }
   if (owns_stream_) (void)hipStreamDestroy(stream_);
 #endif
 }

@@ -465,9 +465,9 @@ static void launch_rows_fx(uint32_t* coeffs, uint64_t col_stride, const uint32_t
 
 bool launch_fft_rows_fixed(uint32_t* coeffs, uint64_t col_stride, const uint32_t* rows, uint64_t n_rows, int ncols, int log_n,
                            const PadRow& pad, uint32_t* bad_flag, uint32_t bad_value, const TwPtrs& itw, lmn_stream_t s) {
-  static const bool off = getenv("LMN_NO_FFT_FIXED") != nullptr;
+  static const bool off = env_set("LMN_NO_FFT_FIXED");
   if (off || !itw.d[0] || log_n < 13 || ncols < 1 || ncols > 32) return false;
-  const int cols = getenv("LMN_ROWS_FX_COLS") ? atoi(getenv("LMN_ROWS_FX_COLS")) : 8;
+  const int cols = env_int("LMN_ROWS_FX_COLS", 8);
   if (cols == 4)
     launch_rows_fx<4>(coeffs, col_stride, rows, n_rows, ncols, log_n, pad, bad_flag, bad_value, itw, s);
   else
@@ -475,18 +475,12 @@ bool launch_fft_rows_fixed(uint32_t* coeffs, uint64_t col_stride, const uint32_t
   return true;
 }
 
-// experiment knob (docs/SWITCHES.md): bytes of unused dynamic LDS per transform workgroup - caps how many of them a CU holds
-static size_t fx_lds_pad() {
-  static const size_t pad = getenv("LMN_FFT_LDS_PAD") ? (size_t)atol(getenv("LMN_FFT_LDS_PAD")) : 0;
-  return pad;
-}
-
 template <bool INV, int RBITS, int CB, bool LO0, bool ZX = false>
 static void launch_fx(uint32_t* data, uint64_t col_stride, const uint32_t* src, uint64_t src_stride, int lo, int log_n,
                       const TwPtrs& tw, uint32_t scale_log, int ncols, int cpb, uint32_t h_off, int xcd, lmn_stream_t s) {
   using S = FxShape<RBITS, CB, LO0>;
   const unsigned tiles = 1u << (log_n - S::TB);
-  const size_t smem = (size_t)4 * S::LDS_WORDS + fx_lds_pad();
+  const size_t smem = (size_t)4 * S::LDS_WORDS;
 #if !defined(LMN_EMU) && !defined(LMN_BATCH)
   if (smem > 64 * 1024) allow_big_lds((const void*)k_fft_fx<INV, RBITS, CB, LO0, ZX>, 160 * 1024);
 #endif
@@ -538,7 +532,7 @@ static bool dispatch_fx(uint32_t* data, uint64_t col_stride, const uint32_t* src
 bool launch_fft_fixed_pass(bool inverse, uint32_t* data, uint64_t col_stride, const uint32_t* src, uint64_t src_stride, int lo,
                            int rbits, int cb, int log_n, const TwPtrs& tw, uint32_t scale_log, int ncols, int cpb,
                            uint32_t h_off, int xcd_swizzle, bool zero_extended_top, lmn_stream_t s) {
-  static const bool off = getenv("LMN_NO_FFT_FIXED") != nullptr;
+  static const bool off = env_set("LMN_NO_FFT_FIXED");
   if (off || !tw.d[0]) return false;
   if (zero_extended_top && (inverse || lo + rbits != log_n)) return false;
   return inverse ? dispatch_fx<true>(data, col_stride, src, src_stride, lo, rbits, cb, log_n, tw, scale_log, ncols, cpb, h_off,
@@ -551,7 +545,7 @@ template <int RBITS>
 static void launch_ie(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, uint64_t lde_stride, const TwPtrs& itw,
                       const TwPtrs& tw_ext, uint32_t scale_log, int ncols, lmn_stream_t s) {
   using S = FxShape<RBITS, 4, false>;
-  const size_t smem = (size_t)8 * S::LDS_WORDS + fx_lds_pad();
+  const size_t smem = (size_t)8 * S::LDS_WORDS;
 #if !defined(LMN_EMU) && !defined(LMN_BATCH)
   if (smem > 64 * 1024) allow_big_lds((const void*)k_fft_interp_extend_fx<RBITS>, 160 * 1024);
 #endif
@@ -561,7 +555,7 @@ static void launch_ie(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, ui
 
 bool launch_interp_extend_fixed(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, uint64_t lde_stride, int log_n,
                                 const TwPtrs& itw, const TwPtrs& tw_ext, int ncols, lmn_stream_t s) {
-  static const bool off = getenv("LMN_NO_FFT_FIXED") != nullptr;
+  static const bool off = env_set("LMN_NO_FFT_FIXED");
   if (off || !itw.d[0] || !tw_ext.d[0]) return false;
   const uint32_t scale_log = (uint32_t)((31 - (log_n % 31)) % 31);   // 2^-log_n = 2^(31 - log_n mod 31)
   switch (log_n - 12) {

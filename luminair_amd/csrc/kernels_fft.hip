@@ -6,65 +6,14 @@ namespace lmn {
 
 // =============================================================================================
 // a4  Circle FFT.  Layer i pairs indices differing in bit i; twiddle index = idx >> (i+1).
-//     A pass runs layers [lo, hi) on LDS tiles of 2^(hi-lo) rows x 2^cb contiguous words.
+//     A pass runs layers [lo, hi) on LDS tiles of 2^(hi-lo) rows x 2^cb contiguous words: tile t has
+//     q = t mod 2^(lo-cb), H = t >> (lo-cb), starts at word (H << hi) + (q << cb), and its rows are 2^lo words apart.
+//     src may differ from data (out-of-place first pass); words at index >= src_len read as zero
+//     (zero-extension of a coefficient vector onto a larger domain, i.e. the LDE).
 // =============================================================================================
-// src may differ from data (out-of-place first pass); words at index >= src_len read as zero
-// (zero-extension of a coefficient vector onto a larger domain, i.e. the LDE).
-template <bool INV>
-LMN_KERNEL k_fft_pass(uint32_t* data, uint64_t col_stride, const uint32_t* src,
-                      uint64_t src_stride, uint64_t src_len, int lo, int hi, int cb, TwPtrs tw, uint32_t scale) {
-  LMN_DYN_SMEM(uint32_t, sm);
-  const int rbits = hi - lo;
-  const int C = 1 << cb;
-  const int tile_elems = 1 << (rbits + cb);
-  uint32_t* col = data + (uint64_t)blockIdx.y * col_stride;
-  const uint32_t* scol = src + (uint64_t)blockIdx.y * src_stride;
-  const uint32_t tile = blockIdx.x;
-  const uint32_t q = tile & ((1u << (lo - cb)) - 1u);
-  const uint32_t H = tile >> (lo - cb);
-  const uint64_t base = ((uint64_t)H << hi) + ((uint64_t)q << cb);
-  for (int e = threadIdx.x; e < tile_elems; e += blockDim.x) {
-    int m = e >> cb, c = e & (C - 1);
-    uint64_t gi = base + ((uint64_t)m << lo) + c;
-    sm[e] = gi < src_len ? scol[gi] : 0u;
-  }
-  __syncthreads();
-  for (int step = 0; step < rbits; ++step) {
-    const int i = INV ? lo + step : hi - 1 - step;
-    const int bit = i - lo;
-    const uint32_t* __restrict__ t = tw.l[i];
-    const uint32_t hbase = H << (hi - i - 1);
-    for (int b = threadIdx.x; b < tile_elems / 2; b += blockDim.x) {
-      int c = b & (C - 1);
-      int p = b >> cb;
-      int m0 = ((p >> bit) << (bit + 1)) | (p & ((1 << bit) - 1));
-      int m1 = m0 | (1 << bit);
-      uint32_t w = t[hbase + (uint32_t)(m0 >> (bit + 1))];
-      int i0 = (m0 << cb) | c, i1 = (m1 << cb) | c;
-      uint32_t v0 = sm[i0], v1 = sm[i1];
-      if (INV) {
-        sm[i0] = m_add(v0, v1);
-        sm[i1] = m_mul(m_sub(v0, v1), w);
-      } else {
-        uint32_t x = m_mul(v1, w);
-        sm[i0] = m_add(v0, x);
-        sm[i1] = m_sub(v0, x);
-      }
-    }
-    __syncthreads();
-  }
-  for (int e = threadIdx.x; e < tile_elems; e += blockDim.x) {
-    int m = e >> cb, c = e & (C - 1);
-    uint32_t v = sm[e];
-    if (INV && scale != 1u) v = m_mul(v, scale);
-    col[base + ((uint64_t)m << lo) + c] = v;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Staged variant: each lane keeps 2^R points (R <= 4) in registers and runs R butterfly layers
-// on them before exchanging through LDS, so a 12-layer tile needs 2 LDS exchanges instead of 12
-// and the per-layer index arithmetic disappears.  Tile geometry as in k_fft_pass.
+// Each lane keeps 2^R points (R <= 4) in registers and runs R butterfly layers on them before
+// exchanging through LDS, so a 12-layer tile needs 2 LDS exchanges instead of 12 and the
+// per-layer index arithmetic disappears.
 // ---------------------------------------------------------------------------------------------
 constexpr int FFT_MAX_STAGES = 4;
 struct FftStagePlan {
@@ -373,9 +322,6 @@ constexpr int FFT_HIGH_BITS = 10;   // strided high passes: 2^10 rows x 16 words
 constexpr int FFT_HIGH_CB = 4;
 
 static int plan_passes(int log_n, FftPass* out) {
-  // LMN_FFT_SPLIT (experiment): 0 = strided passes of equal depth (default), 1 = deepest first (10, then the rest),
-  // 2 = deepest last
-  static const int split = getenv("LMN_FFT_SPLIT") ? atoi(getenv("LMN_FFT_SPLIT")) : 0;
   int n = 0;
   int lo = 0;
   int hi = log_n < FFT_LOW_BITS ? log_n : FFT_LOW_BITS;
@@ -384,13 +330,10 @@ static int plan_passes(int log_n, FftPass* out) {
   while (lo < log_n) {
     int rem = log_n - lo;
     int npass = (rem + FFT_HIGH_BITS - 1) / FFT_HIGH_BITS;
-    int take = (rem + npass - 1) / npass;
-    if (split == 1 && npass > 1) take = FFT_HIGH_BITS;
-    if (split == 2 && npass > 1) take = rem - (npass - 1) * FFT_HIGH_BITS;
+    int take = (rem + npass - 1) / npass;   // strided passes of equal depth
     // three-pass sizes (2^23 points and more) have strided passes of 5 - 7 layers: 32-word runs (whole 128-byte lines)
     // keep their tiles at 4 - 16 KiB; the single strided pass of the smaller sizes keeps 16-word runs (up to 2^10 rows)
-    static const int cb3 = getenv("LMN_FFT_CB3") ? atoi(getenv("LMN_FFT_CB3")) : 5;
-    out[n++] = {lo, lo + take, take == 5 ? 5 : (npass > 1 && take <= 7 ? cb3 : FFT_HIGH_CB)};
+    out[n++] = {lo, lo + take, (take == 5 || (npass > 1 && take <= 7)) ? 5 : FFT_HIGH_CB};
     lo += take;
   }
   return n;
@@ -427,15 +370,11 @@ static void launch_staged_pass(uint32_t* data, uint64_t col_stride, const uint32
   pl.hi = p.hi;
   pl.cb = p.cb;
   split_stages(pl);
-  static const int env_xcd = getenv("LMN_FFT_XCD") ? atoi(getenv("LMN_FFT_XCD")) : 1;
-  pl.xcd_swizzle = (env_xcd && p.cb > 0) ? 1 : 0;
+  pl.xcd_swizzle = p.cb > 0 ? 1 : 0;
   uint32_t tile_elems = 1u << (rbits + p.cb);
   size_t smem = (size_t)4 * (tile_elems + (tile_elems >> 5) + 1);
   // several columns per block when there are plenty of tiles: twiddles stay hot in L1/L2
   int cpb = tiles >= 2048 ? 3 : (tiles >= 512 ? 2 : 1);
-  static const int env_cpb = getenv("LMN_FFT_CPB") ? atoi(getenv("LMN_FFT_CPB")) : 0;
-  static const int env_thr = getenv("LMN_FFT_THREADS") ? atoi(getenv("LMN_FFT_THREADS")) : 0;
-  if (env_cpb > 0) cpb = env_cpb;
   if (cpb > ncols) cpb = ncols;
   // the shapes of the prover's committed columns have compile-time-specialised kernels (fft_fixed.hip)
   const bool full = plen >= (1ull << log_n);
@@ -447,8 +386,7 @@ static void launch_staged_pass(uint32_t* data, uint64_t col_stride, const uint32
       return;
   }
   unsigned gy = (unsigned)((ncols + cpb - 1) / cpb);
-  int threads = (int)std::min<uint32_t>(TPB, std::max<uint32_t>(64u, tile_elems >> 4));
-  if (env_thr > 0) threads = env_thr;
+  const int threads = (int)std::min<uint32_t>(TPB, std::max<uint32_t>(64u, tile_elems >> 4));
   LMN_LAUNCH(k_fft_staged<INV>, dim3(tiles, gy), dim3(threads), smem, s, data, col_stride, psrc, pstride, plen, pl, tw,
              scale, ncols, cpb, block_index << (log_n - p.hi));
 }
@@ -457,24 +395,15 @@ template <bool INV>
 static int run_fft(uint32_t* data, uint64_t col_stride, const uint32_t* src, uint64_t src_stride, int log_src,
                     int ncols, int log_n, const TwPtrs& tw, lmn_stream_t s, uint32_t block_index = 0) {
   if (log_n < 1) throw LmnError(-100, "fft: log_n < 1");
-  static const bool use_v1 = getenv("LMN_FFT_V1") != nullptr;
   FftPass passes[8];
   int np = plan_passes(log_n, passes);
   for (int k = 0; k < np; ++k) {
     const FftPass& p = INV ? passes[k] : passes[np - 1 - k];
-    int rbits = p.hi - p.lo;
-    unsigned tiles = 1u << (log_n - rbits - p.cb);
     bool last = INV && k == np - 1;
     uint32_t scale = last ? inv_pow2(log_n) : 1u;
     const uint32_t* psrc = k == 0 ? src : data;
     uint64_t pstride = k == 0 ? src_stride : col_stride;
     uint64_t plen = k == 0 ? (1ull << log_src) : (1ull << log_n);
-    if (use_v1) {
-      size_t smem = (size_t)4 << (rbits + p.cb);
-      LMN_LAUNCH(k_fft_pass<INV>, dim3(tiles, ncols), dim3(TPB), smem, s, data, col_stride, psrc, pstride, plen,
-                 p.lo, p.hi, p.cb, tw, scale);
-      continue;
-    }
     launch_staged_pass<INV>(data, col_stride, psrc, pstride, plen, p, log_n, tw, scale, ncols, s, block_index);
   }
   return np;
@@ -484,7 +413,7 @@ static int run_fft(uint32_t* data, uint64_t col_stride, const uint32_t* src, uin
 // inverse low pass, the fused strided pass (k_fft_interp_extend), forward low pass.  Applies when both transforms
 // have exactly one strided pass of at most FFT_HIGH_BITS layers.
 bool fft_interp_extend_supported(int log_n) {
-  static const bool off = getenv("LMN_NO_FFT_FUSION") != nullptr;
+  static const bool off = env_set("LMN_NO_FFT_FUSION");
   return !off && log_n > FFT_LOW_BITS && log_n - FFT_LOW_BITS <= FFT_HIGH_BITS - 1;
 }
 // the fused strided pass on coefficients that have been through the inverse low pass, then the forward low pass
@@ -513,7 +442,6 @@ static void interp_extend_tail(uint32_t* coeffs, uint64_t coeff_stride, uint32_t
 
 int launch_interp_extend(uint32_t* coeffs, uint64_t coeff_stride, const uint32_t* evals, uint64_t evals_stride, uint32_t* lde,
                          uint64_t lde_stride, int ncols, int log_n, const TwPtrs& itw, const TwPtrs& tw_ext, lmn_stream_t s) {
-  if (LMN_ABLATED(2u)) return 3;
   if (!fft_interp_extend_supported(log_n)) throw LmnError(-100, "interp_extend: unsupported size");
   const FftPass low{0, FFT_LOW_BITS, 0};
   launch_staged_pass<true>(coeffs, coeff_stride, evals, evals_stride, 1ull << log_n, low, log_n, itw, 1u, ncols, s);
@@ -528,7 +456,6 @@ bool launch_interp_extend_rows(uint32_t* coeffs, uint64_t coeff_stride, const ui
                                const TwPtrs& itw, const TwPtrs& tw_ext, lmn_stream_t s) {
   static_assert(FFT_LOW_BITS == 12, "k_fft_rows_fx is the 12-layer contiguous pass");
   if (!fft_interp_extend_supported(log_n)) return false;
-  if (LMN_ABLATED(2u)) return true;
   if (!launch_fft_rows_fixed(coeffs, coeff_stride, rows, n_rows, ncols, log_n, pad, bad_flag, bad_value, itw, s)) return false;
   interp_extend_tail(coeffs, coeff_stride, lde, lde_stride, ncols, log_n, itw, tw_ext, s);
   return true;
@@ -536,12 +463,10 @@ bool launch_interp_extend_rows(uint32_t* coeffs, uint64_t coeff_stride, const ui
 
 int launch_ifft(uint32_t* dst, uint64_t dst_stride, const uint32_t* src, uint64_t src_stride, int ncols, int log_n,
                 const TwPtrs& itw, lmn_stream_t s) {
-  if (LMN_ABLATED(2u)) return 1;
   return run_fft<true>(dst, dst_stride, src, src_stride, log_n, ncols, log_n, itw, s);
 }
 int launch_fft(uint32_t* dst, uint64_t dst_stride, const uint32_t* src, uint64_t src_stride, int log_src, int ncols,
                int log_n, const TwPtrs& tw, lmn_stream_t s) {
-  if (LMN_ABLATED(2u)) return 1;
   return run_fft<false>(dst, dst_stride, src, src_stride, log_src, ncols, log_n, tw, s);
 }
 

@@ -76,7 +76,6 @@ LMN_KERNEL k_logup_fracs(LogupArgs a) {
 }
 
 void launch_logup_fracs(const LogupArgs& a, lmn_stream_t s) {
-  if (LMN_ABLATED(32u)) return;
   dim3 g(logup_num_blocks(a.n)), b(TPB);
   switch (a.k) {
     case 1: LMN_LAUNCH(k_logup_fracs<1>, g, b, 0, s, a); break;
@@ -88,7 +87,6 @@ void launch_logup_fracs(const LogupArgs& a, lmn_stream_t s) {
 }
 
 LMN_KERNEL k_logup_reduce(const uint32_t* __restrict__ partials, int nblocks, uint32_t n_inv, QM31* out) {
-  LMN_SERIAL_KERNEL();
   LMN_SHARED uint64_t red[TPB * 4];
   uint64_t acc[4] = {0, 0, 0, 0};
   for (int b = threadIdx.x; b < nblocks; b += blockDim.x)
@@ -181,7 +179,6 @@ constexpr int SCAN_SUMS_THREADS = 1024;
 // is that of the shifted values: prefix(b) - (values up to and including block b) * shift.  One launch instead of a
 // reduction over the fraction kernel's partial sums in front of the totals.
 LMN_KERNEL k_scan_blocksums(QM31* blocksums, int nblocks, QM31* claim_out, uint32_t n_inv, uint32_t per_block, uint32_t n) {
-  LMN_SERIAL_KERNEL();
   LMN_SHARED QM31 sh[SCAN_SUMS_THREADS / 64];
   const int T = (int)blockDim.x;
   const int per = (nblocks + T - 1) / T;
@@ -261,7 +258,6 @@ static_assert(SCAN2_ELEMS == TPB * 16 && (1 << (SCAN2_C + 1)) * 8 == TPB, "one 8
 template <int MODE>
 LMN_KERNEL k_logup_scan2(const QM31* __restrict__ last_tmp, const QM31* __restrict__ claimed_shift, int log_size,
                          uint32_t* __restrict__ out_cols, QM31* __restrict__ blocksums) {
-  LMN_SERIAL_KERNEL();
   LMN_DYN_SMEM(QM31, T);
   constexpr int A = SCAN2_A, C = SCAN2_C;
   const int gbits = log_size - 1 - A - C;                 // bits of the region index G
@@ -339,12 +335,11 @@ int logup_scan_num_blocks(int log_size) {
 
 void launch_logup_scan(const QM31* last_tmp, QM31* claimed_shift, int log_size, uint32_t* out_cols, QM31* blocksums,
                        lmn_stream_t s, bool derive_claim, uint32_t n_inv) {
-  static const bool scattered = getenv("LMN_LOGUP_SCAN_V1") != nullptr;   // ablation: the round-1 kernel
-  int nb = logup_scan_num_blocks(log_size);
+  const int nb = logup_scan_num_blocks(log_size);
   const uint32_t n = 1u << log_size;
   QM31* claim_out = derive_claim ? claimed_shift : nullptr;
   const dim3 sums_block(nb > 2048 ? SCAN_SUMS_THREADS : TPB);
-  if (log_size >= SCAN2_MIN_LOG && !scattered) {
+  if (log_size >= SCAN2_MIN_LOG) {
     const dim3 grid(1u << (log_size - 2 - SCAN2_A - SCAN2_C));
     const size_t smem = (size_t)SCAN2_ELEMS * sizeof(QM31);
 #if !defined(LMN_EMU) && !defined(LMN_BATCH)
@@ -360,7 +355,6 @@ void launch_logup_scan(const QM31* last_tmp, QM31* claimed_shift, int log_size, 
     LMN_LAUNCH(k_logup_scan2<1>, grid, dim3(TPB), smem, s, last_tmp, (const QM31*)claimed_shift, log_size, out_cols, blocksums);
     return;
   }
-  if (scattered) nb = (int)cdiv(1ull << log_size, SCAN_PER_BLOCK);
   LMN_LAUNCH(k_logup_scan, dim3(nb), dim3(TPB), 0, s, last_tmp, (const QM31*)claimed_shift, log_size, out_cols, blocksums,
              derive_claim ? 2 : 0);
   LMN_LAUNCH(k_scan_blocksums, dim3(1), dim3(nb > 2048 ? SCAN_SUMS_THREADS : TPB), 0, s, blocksums, nb, claim_out, n_inv,

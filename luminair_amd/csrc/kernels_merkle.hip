@@ -338,11 +338,6 @@ LMN_D void merkle_load_mode(const uint32_t* __restrict__ prev, const MerkleSegs&
     }
   } else if (MODE == 1) {
     const uint32_t* __restrict__ base = sg.base[0];   // block-uniform column bases + the leaf as a 32-bit lane offset
-#ifdef LMN_ABLATE
-    // experiment build, mask 128: the 4-column leaves of the composition tree read a 16 KB stand-in that stays in L2 (garbage
-    // hashes): the upper bound of what feeding those leaves from the last forward pass's LDS tile could save
-    if (fold.below_ncols == -128) i &= 4095u;
-#endif
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
       if (k < ncols)
@@ -571,7 +566,6 @@ template <int MODE>
 LMN_KERNEL k_merkle_small(const uint32_t* __restrict__ prev, MerkleSegs sg, int ncols, uint32_t size,
                           MerkleLevels outs, int nfused, DevChannel* ch, QM31* alpha_out, uint32_t* root_copy,
                           const ChanStep* __restrict__ step, int step_kind) {
-  LMN_SERIAL_KERNEL();
   LMN_SHARED uint32_t sh[MERKLE_SMALL_BLOCK * 8];
   LMN_SHARED alignas(16) uint32_t sh_step[CHAN_STEP_WORDS];
   const uint32_t i = threadIdx.x;
@@ -597,7 +591,6 @@ LMN_KERNEL k_merkle_small(const uint32_t* __restrict__ prev, MerkleSegs sg, int 
     for (int k = 0; k < 8; ++k) sh[k * MERKLE_SMALL_BLOCK + i] = cur[k];   // word-major (merkle_lds_level)
   }
   if (step_lane) sh_step[i] = step_word;
-  LMN_SERIAL_KERNEL();  // the leaf compression left the wave at its low phase priority
   merkle_lds_climb<MERKLE_SMALL_BLOCK>(sh, outs, 1, nfused, size);
   if (fs && step_kind == 0) chan_mix_root_draw_block(ch, dg, variant, sh, MERKLE_SMALL_BLOCK, sh + 16, alpha_out, root_copy);
   if (fs && step_kind != 0) {
@@ -610,15 +603,11 @@ LMN_KERNEL k_merkle_small(const uint32_t* __restrict__ prev, MerkleSegs sg, int 
 
 void launch_merkle_fused(const uint32_t* prev, const MerkleSegs& sg, int ncols, uint32_t size,
                          const MerkleLevels& outs, int sub, int nfused, lmn_stream_t s, const MerkleFold* fold) {
-  if (LMN_ABLATED(1u)) return;
   if (!prev && ncols == 0) throw LmnError(-100, "merkle level with no input");
   if (nfused > MERKLE_MAX_FUSED || sub > MERKLE_MAX_SUB || sub > nfused || nfused - sub > 8 ||
       size % ((uint32_t)TPB << sub) != 0)
     throw LmnError(-100, "merkle_fused: bad arguments");
   const dim3 g(cdiv(size >> sub, TPB)), b(TPB);
-  // experiment knob (docs/SWITCHES.md): bytes of unused dynamic LDS per workgroup - caps the workgroups of these issue-bound
-  // launches per CU (24 KB static + pad; 5 fit by registers) so that HBM-bound launches of other proofs find room next to them
-  static const size_t lds_pad = getenv("LMN_MERKLE_LDS_PAD") ? (size_t)atol(getenv("LMN_MERKLE_LDS_PAD")) : 0;
   const MerkleFold none{};
   // a null p[l] (l < sub only: the levels a lane keeps in registers) is a level the caller does not want written
   for (int l = sub; l <= nfused; ++l)
@@ -626,29 +615,26 @@ void launch_merkle_fused(const uint32_t* prev, const MerkleSegs& sg, int ncols, 
   if (fold && fold->below) {
     if (prev || fold->src || ncols < 1 || fold->below_ncols < 1 || fold->below_ncols > 8)
       throw LmnError(-100, "merkle_fused: a start level over its own leaf level has columns, no stored children and <= 8 leaf columns");
-    LMN_LAUNCH(k_merkle_fused<4>, g, b, lds_pad, s, prev, sg, ncols, size, outs, sub, nfused, *fold);
+    LMN_LAUNCH(k_merkle_fused<4>, g, b, 0, s, prev, sg, ncols, size, outs, sub, nfused, *fold);
   } else if (fold) {
     if (prev || ncols != 4) throw LmnError(-100, "merkle_fused: a folded level is a leaf level of 4 coordinate columns");
-    LMN_LAUNCH(k_merkle_fused<3>, g, b, lds_pad, s, prev, sg, ncols, size, outs, sub, nfused, *fold);
+    LMN_LAUNCH(k_merkle_fused<3>, g, b, 0, s, prev, sg, ncols, size, outs, sub, nfused, *fold);
   } else if (!prev && ncols <= 16 && sg.n[0] == ncols) {
     // the leaf's zero message words are compile-time zeros of the instantiation (blake2s.h b2_compress_fresh_nz)
-    if (ncols <= 4) {
-      MerkleFold leaf4 = none;
-      if (LMN_ABLATED(128u)) leaf4.below_ncols = -128;
-      LMN_LAUNCH((k_merkle_fused<1, 4>), g, b, lds_pad, s, prev, sg, ncols, size, outs, sub, nfused, leaf4);
-    }
+    if (ncols <= 4)
+      LMN_LAUNCH((k_merkle_fused<1, 4>), g, b, 0, s, prev, sg, ncols, size, outs, sub, nfused, none);
     else if (ncols <= 8)
-      LMN_LAUNCH((k_merkle_fused<1, 8>), g, b, lds_pad, s, prev, sg, ncols, size, outs, sub, nfused, none);
+      LMN_LAUNCH((k_merkle_fused<1, 8>), g, b, 0, s, prev, sg, ncols, size, outs, sub, nfused, none);
     else if (ncols <= 12)
-      LMN_LAUNCH((k_merkle_fused<1, 12>), g, b, lds_pad, s, prev, sg, ncols, size, outs, sub, nfused, none);
+      LMN_LAUNCH((k_merkle_fused<1, 12>), g, b, 0, s, prev, sg, ncols, size, outs, sub, nfused, none);
     else if (ncols <= 15)
-      LMN_LAUNCH((k_merkle_fused<1, 15>), g, b, lds_pad, s, prev, sg, ncols, size, outs, sub, nfused, none);
+      LMN_LAUNCH((k_merkle_fused<1, 15>), g, b, 0, s, prev, sg, ncols, size, outs, sub, nfused, none);
     else
-      LMN_LAUNCH((k_merkle_fused<1, 16>), g, b, lds_pad, s, prev, sg, ncols, size, outs, sub, nfused, none);
+      LMN_LAUNCH((k_merkle_fused<1, 16>), g, b, 0, s, prev, sg, ncols, size, outs, sub, nfused, none);
   } else if (prev && ncols == 0)
-    LMN_LAUNCH(k_merkle_fused<2>, g, b, lds_pad, s, prev, sg, ncols, size, outs, sub, nfused, none);
+    LMN_LAUNCH(k_merkle_fused<2>, g, b, 0, s, prev, sg, ncols, size, outs, sub, nfused, none);
   else
-    LMN_LAUNCH(k_merkle_fused<0>, g, b, lds_pad, s, prev, sg, ncols, size, outs, sub, nfused, none);
+    LMN_LAUNCH(k_merkle_fused<0>, g, b, 0, s, prev, sg, ncols, size, outs, sub, nfused, none);
 }
 
 void launch_merkle_small(const uint32_t* prev, const MerkleSegs& sg, int ncols, uint32_t size,
@@ -674,7 +660,6 @@ void launch_merkle_small(const uint32_t* prev, const MerkleSegs& sg, int ncols, 
 // =============================================================================================
 LMN_KERNEL k_chan_mix_root_draw(DevChannel* ch, const uint32_t* __restrict__ root, QM31* out_alpha,
                                 uint32_t* root_copy) {
-  LMN_SERIAL_KERNEL();
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   chan_mix_root_draw(ch, root, out_alpha, root_copy);
 }
@@ -880,7 +865,6 @@ LMN_D void chan_step_root_oods(uint32_t* scr, DevChannel* ch, uint32_t dg, uint3
 constexpr int QUOT_PREP_PLAN_WORDS = (int)(sizeof(QuotPrepPlan) / 4);
 static_assert(sizeof(QuotPrepPlan) % 8 == 0, "the plan is fetched word by word");
 LMN_KERNEL k_quot_prepare(DevChannel* ch, const QuotPrepPlan* __restrict__ plan_g) {
-  LMN_SERIAL_KERNEL();
   LMN_SHARED alignas(16) uint32_t sh_plan[QUOT_PREP_PLAN_WORDS];
   LMN_SHARED uint32_t W[8 + 4 * QUOT_PREP_MAX_SAMPLES + 16];   // digest || values, zero-padded to whole blocks
   LMN_SHARED uint32_t scr[32];                                   // msg 16 | drawn words 8 | alpha 4
@@ -996,7 +980,6 @@ LMN_D void chan_step_run(uint32_t* scr, DevChannel* ch, uint32_t dg, uint32_t va
 
 // a step as a launch of its own (trees whose root is not produced by k_merkle_small)
 LMN_KERNEL k_chan_step(DevChannel* ch, const ChanStep* __restrict__ step, int step_kind, const uint32_t* __restrict__ root) {
-  LMN_SERIAL_KERNEL();
   LMN_SHARED uint32_t scr[CHAN_STEP_SCRATCH];
   LMN_SHARED alignas(16) uint32_t sh_step[CHAN_STEP_WORDS];
   for (uint32_t k = threadIdx.x; k < (uint32_t)CHAN_STEP_WORDS; k += blockDim.x) sh_step[k] = reinterpret_cast<const uint32_t*>(step)[k];
@@ -1029,7 +1012,6 @@ void launch_chan_step(DevChannel* ch, const ChanStep* step, int step_kind, const
 // =============================================================================================
 LMN_KERNEL k_fri_tail(DevChannel* ch, const FriTailLayer* __restrict__ layers, int n_layers, int first_log,
                       QM31* alphas_out, uint32_t* roots_out, FriTailIo pre) {
-  LMN_SERIAL_KERNEL();
   LMN_SHARED uint32_t sh[MERKLE_SMALL_BLOCK * 8];
   LMN_SHARED uint32_t shv[MERKLE_SMALL_BLOCK * 4];   // the layer's values, coordinate-major: the fold reads its pair here
   const uint32_t i = threadIdx.x;
@@ -1117,7 +1099,6 @@ void launch_fri_tail(DevChannel* ch, const FriTailLayer* layers, int n_layers, i
 // =============================================================================================
 LMN_KERNEL k_gather(const uint32_t* __restrict__ arena, const GatherEntry* __restrict__ entries, uint32_t n,
                     const MerkleRecompute* __restrict__ jobs, uint32_t n_jobs, uint32_t* __restrict__ out) {
-  LMN_SERIAL_KERNEL();
   uint32_t e = blockIdx.x;
   if (e < n) {
     GatherEntry g = entries[e];

@@ -259,7 +259,6 @@ LMN_KERNEL k_composition(CompositionArgs a) {
 }
 
 void launch_composition(const CompositionArgs& a, lmn_stream_t s) {
-  if (LMN_ABLATED(8u)) return;
   if (a.eval_log != a.log_size + 1) throw LmnError(-100, "composition: eval domain must be log_size+1");
   if (a.n_rows == 0 || (uint64_t)a.row0 + a.n_rows > (1ull << a.eval_log) || a.stride < a.n_rows || !a.prev_last)
     throw LmnError(-100, "composition: bad row block");
@@ -362,12 +361,10 @@ LMN_KERNEL k_eval_at_point(const EvalJob* __restrict__ jobs, const QM31* __restr
 #pragma unroll
   for (uint32_t hh = 0; hh < (uint32_t)EVAL_HI_PER_CHUNK; ++hh) {
     if (hh >= hpc) break;
-    LMN_QPHASE_PORT0();
     qacc_mad(in0, Hv[hh], cv[hh][0]);
     qacc_mad(in1, Hv[hh], cv[hh][1]);
     qacc_mad(in2, Hv[hh], cv[hh][2]);
     qacc_mad(in3, Hv[hh], cv[hh][3]);
-    LMN_QPHASE_ANY();
     if (++pending == 3) {
       pending = 0;
       qacc_fold(in0);
@@ -393,7 +390,6 @@ void launch_eval_at_point(const EvalJob* jobs, int njobs, const QM31* lo_tab, co
                           int max_log, QM31* partial_out, int max_chunks, lmn_stream_t s, uint32_t shard_rank,
                           uint32_t shard_world) {
   (void)max_log;
-  if (LMN_ABLATED(16u)) return;
   LMN_LAUNCH(k_eval_at_point, dim3(max_chunks, njobs), dim3(TPB), 0, s, jobs, lo_tab, hi_tab, hi_stride, partial_out,
              max_chunks, shard_rank, shard_world);
 }
@@ -402,7 +398,6 @@ void launch_eval_at_point(const EvalJob* jobs, int njobs, const QM31* lo_tab, co
 // with maps[p][EVAL_LB + k].  maps = [y, x, pi(x), pi^2(x), ...] per sample point.
 LMN_KERNEL k_eval_tables(const QM31* __restrict__ maps, int maps_stride, QM31* __restrict__ lo_tab,
                          QM31* __restrict__ hi_tab, uint32_t hi_n, int hi_bits) {
-  LMN_SERIAL_KERNEL();
   const int p = blockIdx.y;
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   const QM31* mp = maps + (uint64_t)p * maps_stride;
@@ -431,7 +426,6 @@ void launch_eval_tables(const QM31* maps, int maps_stride, int npoints, QM31* lo
 // out[job] = sum over that job's chunks of partial[job][chunk]
 LMN_KERNEL k_eval_reduce(const EvalJob* __restrict__ jobs, const QM31* __restrict__ partial, int max_chunks,
                          QM31* __restrict__ out) {
-  LMN_SERIAL_KERNEL();
   LMN_SHARED QM31 red[TPB];
   const int job = blockIdx.x;
   const int nc = eval_num_chunks_hd(jobs[job].log_n);
@@ -470,14 +464,8 @@ LMN_HD uint32_t domain_y(const uint32_t* tw_y, uint32_t s) {
 // (64 VGPRs, no spills) those two launches fill the chip in whole rounds (16 waves per SIMD in two rounds of 8; at 87
 // VGPRs the 8 waves per SIMD of the two-batch launch ran as 5 + 3): 0.167 -> 0.150 ms per proof, + 2 % proofs/s.
 // Three and four batches keep 4 rows at the compiler's own budget (they would spill at 64).
-#ifndef LMN_QUOT_ROWS1
-#define LMN_QUOT_ROWS1 4
-#endif
-#ifndef LMN_QUOT_ROWS2
-#define LMN_QUOT_ROWS2 2
-#endif
 template <int NB>
-constexpr int quot_rows() { return NB == 1 ? LMN_QUOT_ROWS1 : (NB == 2 ? LMN_QUOT_ROWS2 : 4); }   // rows per lane
+constexpr int quot_rows() { return NB == 2 ? 2 : 4; }   // rows per lane
 template <int NB>
 LMN_D void quotients_body(const QuotientArgs& a);
 template <int NB>
@@ -492,7 +480,7 @@ LMN_KERNEL k_quotients_occ(QuotientArgs a) { quotients_body<NB>(a); }
 template <int NB>
 LMN_D void quotients_body(const QuotientArgs& a) {
   constexpr int QUOT_ROWS = quot_rows<NB>();
-#if defined(LMN_QUOT_TAB_LDS) || defined(LMN_EMU) || !defined(__HIP_DEVICE_COMPILE__)
+#if defined(LMN_EMU) || !defined(__HIP_DEVICE_COMPILE__)
   // (column pointer, alpha^k * c) table staged once per block in LDS: the per-column loop then
   // reads wave-uniform LDS words instead of chasing pointers through global memory
   LMN_SHARED QuotEntry tab[QUOT_MAX_ENTRIES];
@@ -559,17 +547,13 @@ LMN_D void quotients_body(const QuotientArgs& a) {
       for (; kk + 6 <= k1; kk += 6) {
         uint32_t f0 = LMN_QCOL(kk, s), f1 = LMN_QCOL(kk + 1, s), f2 = LMN_QCOL(kk + 2, s);
         uint32_t f3 = LMN_QCOL(kk + 3, s), f4 = LMN_QCOL(kk + 4, s), f5 = LMN_QCOL(kk + 5, s);
-        LMN_QPHASE_PORT0();
         qacc_mad(acc, tab[kk].c, f0);
         qacc_mad(acc, tab[kk + 1].c, f1);
         qacc_mad(acc, tab[kk + 2].c, f2);
-        LMN_QPHASE_ANY();
         qacc_fold(acc);
-        LMN_QPHASE_PORT0();
         qacc_mad(acc, tab[kk + 3].c, f3);
         qacc_mad(acc, tab[kk + 4].c, f4);
         qacc_mad(acc, tab[kk + 5].c, f5);
-        LMN_QPHASE_ANY();
         qacc_fold(acc);
       }
       for (; kk < k1; ++kk) {
@@ -593,7 +577,6 @@ LMN_D void quotients_body(const QuotientArgs& a) {
 }
 
 void launch_quotients(const QuotientArgs& a, lmn_stream_t s) {
-  if (LMN_ABLATED(4u)) return;
   if (a.nbatch < 1 || a.nbatch > QUOT_MAX_BATCH) throw LmnError(-100, "quotients: bad batch count");
   if (a.batch_start[a.nbatch] > QUOT_MAX_ENTRIES) throw LmnError(-100, "quotients: too many column samples");
   if (!a.dev || !a.entries) throw LmnError(-100, "quotients: no batch table");
@@ -617,7 +600,6 @@ void launch_quotients(const QuotientArgs& a, lmn_stream_t s) {
 LMN_KERNEL k_fold(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, uint32_t src_len,
                   const uint32_t* __restrict__ itw, const QM31* __restrict__ alpha_ptr, int accumulate,
                   uint64_t dst_stride) {
-  LMN_SERIAL_KERNEL();
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (src_len >> 1)) return;
   const uint64_t n = dst_stride;

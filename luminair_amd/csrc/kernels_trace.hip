@@ -54,7 +54,6 @@ LMN_KERNEL k_transpose_pad(const uint32_t* __restrict__ rows, uint64_t n_rows, i
 void launch_transpose_pad_rows(const uint32_t* rows, uint64_t n_rows, int ncols, int log_size, uint32_t* cols,
                                uint64_t out_stride, uint64_t blk_row0, uint64_t blk_rows, const PadRow& pad, uint32_t* bad_flag,
                                lmn_stream_t s, uint32_t bad_value) {
-  if (LMN_ABLATED(64u)) return;   // (experiment build: the whole cost of the transpose launch = the upper bound of fusing it away)
   uint64_t size = 1ull << log_size;
   const bool big = blk_row0 % 256 == 0 && blk_rows % 256 == 0;
   const unsigned tr_rows = big ? 256u : 64u;

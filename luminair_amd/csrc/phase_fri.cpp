@@ -134,7 +134,7 @@ void Context::run_fri_commit(ProofRun& r) {
       if (pend.join) fold(true, dst, false, pend.join, pend.src_log, false, pend.alpha, 1);
       pend.on = false;
     };
-    const bool fuse_folds = getenv("LMN_NO_FOLD_FUSION") == nullptr;   // (read per proof: the tests toggle it)
+    const bool fuse_folds = !env_set("LMN_NO_FOLD_FUSION");   // (read per proof: the tests toggle it)
     if (!sh && fuse_folds) {
       pend = {true, true, quots[0].vals, ls0, d_alphas + (n_roots - 1)};
     } else {
@@ -218,7 +218,7 @@ void Context::run_fri_commit(ProofRun& r) {
       const bool next_sh = sharded_log(next_log);
       uint32_t* next = layer_alloc(next_log, next_sh);
       const bool joins = qi < quots.size() && quots[qi].log - 1 == next_log;
-      const bool fuse_joins = getenv("LMN_NO_JOIN_FUSION") == nullptr;   // (read per proof: the tests toggle it)
+      const bool fuse_joins = !env_set("LMN_NO_JOIN_FUSION");   // (read per proof: the tests toggle it)
       if (!sh && fuse_folds && next_log > 10 && (!joins || (fuse_joins && !quots[qi].sharded))) {
         pend = {true, false, layer, layer_log, d_alpha, joins ? quots[qi].vals : nullptr};
         if (joins) ++qi;   // (quotient sizes are distinct: at most one column joins a layer)
@@ -314,7 +314,7 @@ void Context::run_fri_commit(ProofRun& r) {
     }
     uint32_t bound = 1u << cfg.log_last_layer;
     for (uint32_t j = bound; j < n; ++j)
-      if (!q_is_zero(coeffs[j]) && !LMN_ABLATED(~0u)) throw LmnError(LMN_ERR_INTERNAL, "FRI: invalid last-layer degree");
+      if (!q_is_zero(coeffs[j])) throw LmnError(LMN_ERR_INTERNAL, "FRI: invalid last-layer degree");
     coeffs.resize(bound);
     proof.last_layer_coeffs = coeffs;
     proof.last_layer_log_size = cfg.log_last_layer;

@@ -122,7 +122,7 @@ void Context::check_composition_identity(ProofRun& r) {
   LMN_RUN_ALIASES(r);
   QM31 lhs = q_from_partial_evals(sampled[3][0][0], sampled[3][1][0], sampled[3][2][0], sampled[3][3][0]);
   QM31 rhs = eval_composition_at_point(inst, sampled, oods, elems, comp_alpha, cfg.protocol_variant);
-  if (!q_eq(lhs, rhs) && !LMN_ABLATED(~0u)) throw LmnError(LMN_ERR_CONSTRAINTS, "ProverError(ConstraintsNotSatisfied)");
+  if (!q_eq(lhs, rhs)) throw LmnError(LMN_ERR_CONSTRAINTS, "ProverError(ConstraintsNotSatisfied)");
 }
 
 // The quotient kernels' tables without the host (kernels.h QuotPrepPlan): the sample batches of every LDE size are a
@@ -274,7 +274,7 @@ void Context::run_oods(ProofRun& r) {
   }
   // unsharded proofs with the device-resident transcript do not wait here: the sampled values stay on the device, where
   // k_quot_prepare makes the transcript step and the quotient kernels' tables (LMN_HOST_QUOT=1: the wait of round 5)
-  r.quot_dev = r.dev_fs && !shard_.active && getenv("LMN_HOST_QUOT") == nullptr && r.eval_jobs.size() <= (size_t)QUOT_PREP_MAX_SAMPLES &&
+  r.quot_dev = r.dev_fs && !shard_.active && !env_set("LMN_HOST_QUOT") && r.eval_jobs.size() <= (size_t)QUOT_PREP_MAX_SAMPLES &&
                r.eval_jobs.size() <= (size_t)QUOT_MAX_ENTRIES && !r.eval_jobs.empty();
   if (r.quot_dev) {
     std::set<int> lde_sizes;
@@ -400,19 +400,7 @@ void Context::run_quotients(ProofRun& r) {
     for (size_t k = 0; k < sizes.size(); ++k) {
       const int ls = sizes[k];
       const QuotientArgs& a = qargs[k];
-      // LMN_FRI_OVERLAP (experiment): unsharded proofs with two LDE sizes compute the second (smaller) size on the second
-      // stream, next to the leaf hashing of the first size's quotient columns; build_merkle_levels waits for it before level `ls`
-      const bool overlap = !sh && sizes.size() == 2 && ls == sizes[1] && second_stream_wanted();
-      if (overlap) {
-        lmn_event_record(ev_fork_, stream_);            // everything enqueued so far (incl. the table upload)
-        lmn_stream_wait_event(stream2_, ev_fork_);
-        launch_quotients(a, stream2_);
-        lmn_event_record(ev_join_, stream2_);
-        wait_before_level_ev_ = ev_join_;
-        wait_before_level_ = ls;
-      } else {
-        launch_quotients(a, stream_);
-      }
+      launch_quotients(a, stream_);
       if (sh && !quots[k].sharded) gather_columns(quots[k].vals, 1ull << ls, 4, (1ull << ls) >> g);
     }
   }

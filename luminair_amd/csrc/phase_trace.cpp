@@ -119,11 +119,9 @@ void Context::run_main_trace(ProofRun& r) {
       // worth 5 % proofs/s, but the pass that absorbs it costs what the two launches cost (54 us against 27 + 27 solo;
       // +0.4 % under load: inside the noise) - byte-identical proofs, kept for the next idea.  Components with
       // preprocessed (LUT) columns keep the plain path; LMN_ROWS_FUSION_MIN_LOG (default 18) lowers the size threshold.
-      const char* fmin = getenv("LMN_ROWS_FUSION_MIN_LOG");
-      const char* fon = getenv("LMN_ROWS_FUSION");
-      const bool try_fused = fon && atoi(fon) != 0 && !shard_.active && lb == 1 && ti.spec->n_pre == 0 &&
-                             fft_interp_extend_supported(ti.log_size) && ti.log_size >= (fmin ? std::max(13, atoi(fmin)) : 18) &&
-                             getenv("LMN_NO_FFT_FIXED") == nullptr;
+      const bool try_fused = env_int("LMN_ROWS_FUSION", 0) != 0 && !shard_.active && lb == 1 && ti.spec->n_pre == 0 &&
+                             fft_interp_extend_supported(ti.log_size) &&
+                             ti.log_size >= std::max(13, env_int("LMN_ROWS_FUSION_MIN_LOG", 18)) && !env_set("LMN_NO_FFT_FIXED");
       if (try_fused) {
         inst[t].trace_evals = nullptr;
       } else {

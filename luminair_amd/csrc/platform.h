@@ -13,6 +13,14 @@
 #include <stdexcept>
 #include <string>
 
+// The LMN_* environment switches (docs/SWITCHES.md): an integer with a default, or set / unset.  When a switch is read -
+// once per process (a static const at the call site), per context or per proof - is the call site's business.
+inline int env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
+inline bool env_set(const char* name) { return getenv(name) != nullptr; }
+
 #ifndef LMN_EMU
 #include <hip/hip_runtime.h>
 #include <time.h>
@@ -92,7 +100,7 @@ inline void lmn_sync(lmn_stream_t s) {
   ::lmn::batch_sync(s);   // a rendezvous of the lock-step group: one stream wait for all members
   return;
 #endif
-  static const int mode = getenv("LMN_SYNC_MODE") ? atoi(getenv("LMN_SYNC_MODE")) : 0;  // 0 spin, 1 hipStreamSynchronize, 2 hybrid, 3 blocking event
+  static const int mode = env_int("LMN_SYNC_MODE", 0);  // 0 spin, 1 hipStreamSynchronize, 2 hybrid, 3 blocking event
   if (mode == 1) {
     LMN_HIP_CHECK(hipStreamSynchronize(s));
     return;
@@ -117,16 +125,12 @@ inline void lmn_sync(lmn_stream_t s) {
   // waits did so starts sleeping after 100 us already; a few short waits bring it back to polling.  Default 3000 us since
   // round 6 (1200 before): with the quotient step on the device a solo 2^20-row proof has ONE wait of 2 ms in front of its
   // decommitment instead of three below a millisecond - at 1200 us it went to sleep in it and woke up 50 - 100 us late.
-  static const long spin_us = getenv("LMN_SPIN_US") ? atol(getenv("LMN_SPIN_US")) : 3000;
+  static const long spin_us = env_int("LMN_SPIN_US", 3000);
   static thread_local int long_waits = 0;   // 0 .. 8: how many of the recent waits on this thread outlasted spin_us
   // (end of round 6) the direct signal: while this process proves several proofs at once the GPU is shared whatever this
   // thread's own history says - with the limit at 3000 us a wait of 1 - 3 ms under load (the gather launch queued behind other
   // proofs' work) kept a thread polling and reset its history: 3.2 instead of 1.9 ms of host CPU per proof at 24 in flight
-#ifdef LMN_NO_SHARED_SIGNAL   // (experiment build: the policy before this signal)
-  const bool shared = false;
-#else
   const bool shared = ::lmn::g_proofs_in_flight.load(std::memory_order_relaxed) > 1;
-#endif
   const long limit_us = (shared || long_waits >= 2) ? 100 : spin_us;
   const auto t_start = std::chrono::steady_clock::now();
   auto waited_us = [&] {
@@ -198,12 +202,6 @@ inline float lmn_event_elapsed_ms(lmn_event_t a, lmn_event_t b) {
   LMN_HIP_CHECK(hipEventElapsedTime(&ms, a, b));
   return ms;
 }
-inline lmn_event_t lmn_event_create_sync() {   // ordering only (no timestamps)
-  hipEvent_t e;
-  LMN_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  return e;
-}
-inline void lmn_stream_wait_event(lmn_stream_t s, lmn_event_t e) { LMN_HIP_CHECK(hipStreamWaitEvent(s, e, 0)); }
 
 #else  // ------------------------------------------------------------------ LMN_EMU (tests only)
 #include <barrier>
@@ -372,6 +370,4 @@ inline void lmn_event_record(lmn_event_t e, lmn_stream_t) {
   *e = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 inline float lmn_event_elapsed_ms(lmn_event_t a, lmn_event_t b) { return (float)(*b - *a); }
-inline lmn_event_t lmn_event_create_sync() { return new double(0.0); }
-inline void lmn_stream_wait_event(lmn_stream_t, lmn_event_t) {}
 #endif

@@ -64,24 +64,18 @@ std::vector<uint8_t> Context::prove(const lmn_table* tables, size_t n_tables, co
   r.log = g_log(this);
   r.log->reset();
   memset(&timings, 0, sizeof timings);
-#ifndef LMN_EMU
-  // LMN_FRI_OVERLAP: a previous proof that failed between the fork and the join may have left a kernel of the second
-  // stream writing the arena this proof is about to reset
-  if (have_stream2_) lmn_sync(stream2_);
-#endif
-  wait_before_level_ = -1;
   // big trees are stored without the levels their fused launches keep in registers (MerkleCut); sharded proofs and the
   // level-2 ops (whose handles expose every layer) keep whole trees
   struct CutScope {
     bool& flag;
     ~CutScope() { flag = false; }
   } cut_scope{merkle_cut_};
-  merkle_cut_ = !shard_.active && getenv("LMN_MERKLE_FULL") == nullptr;
+  merkle_cut_ = !shard_.active && !env_set("LMN_MERKLE_FULL");
 
   // Device-resident Fiat-Shamir of the commitment phases - sharded proofs included since round 6 (every rank runs the same
   // steps behind the all-gather of the subtree roots); LMN_HOST_FS=1 keeps the transcript on the host (round 1-4
   // behaviour, for A/B measurements)
-  r.dev_fs = getenv("LMN_HOST_FS") == nullptr;
+  r.dev_fs = !env_set("LMN_HOST_FS");
   run_setup(r);               // prove.cpp: validate the tables, size the arena, twiddles, transcript
   run_preprocessed(r);        // phase_trace.cpp: tree 0 (LUT columns)                      prover.rs:54-59
   run_main_trace(r);          // phase_trace.cpp: transpose + commit, claim mixed           prover.rs:70-179

@@ -374,21 +374,12 @@ class Context {
   int device_;
   lmn_stream_t stream_{};
   bool owns_stream_ = true;
-  // second stream + ordering events: the quotient kernel of the smaller LDE size runs next to the leaf hashing of
-  // the larger one in the first FRI layer (LMN_FRI_OVERLAP=1, experiment)
-  lmn_stream_t stream2_{};
-  lmn_event_t ev_fork_{}, ev_join_{};
-  bool have_stream2_ = false;
-  int fri_overlap_mode_ = 0;          // 0 never, 1 always, 2 while this is the process's only proof in flight
   // proof of work: prove() grinds on the device from pow_bits >= pow_device_min_bits_ on (LMN_POW_DEVICE_MIN_BITS), on the
   // host below; one launch examines at most 2^pow_window_log_ nonces (LMN_POW_WINDOW_LOG)
   int pow_device_min_bits_ = 0, pow_window_log_ = 0;
   unsigned long long* pow_best_ = nullptr;   // device: the smallest passing nonce found so far (allocated on first use)
   uint64_t grind(const Channel& ch, uint32_t pow_bits);          // the proof's path: device or host by pow_device_min_bits_
   uint64_t device_grind(const Channel& ch, uint32_t pow_bits);
-  bool second_stream_wanted();
-  lmn_event_t wait_before_level_ev_{};
-  int wait_before_level_ = -1;    // build_merkle_levels: make stream_ wait for wait_before_level_ev_ before this level
   bool merkle_cut_ = false;       // inside prove() of an unsharded proof: trees are stored without their register levels
   Arena arena_;
   int tw_max_log_ = 0;

@@ -114,7 +114,7 @@ void plan_fri_witness(const ColRef (&cols)[4], int g, const std::vector<uint32_t
 
 // optional host-side wall-clock marks (LMN_HOST_PROFILE=1), printed to stderr
 struct HostMarks {
-  bool on = getenv("LMN_HOST_PROFILE") != nullptr;
+  bool on = env_set("LMN_HOST_PROFILE");
   std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(), last = t0;
   void mark(const char* what) {
     if (!on) return;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Solo latency of BASELINE config 4 (many small components) - used with the ablation switches
-LMN_LOGUP_SCAN_V1 / LMN_NO_FFT_FUSION / LMN_NO_FOLD_FUSION to see what each round-3 kernel costs at small sizes."""
+LMN_NO_FFT_FUSION / LMN_NO_FOLD_FUSION to see what each round-3 kernel costs at small sizes."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import luminair_amd
