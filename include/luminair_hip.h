@@ -121,7 +121,8 @@ typedef struct lmn_config {
  * component's `Column::index()` order (e.g. crates/air/src/components/add/table.rs:191-211). */
 typedef struct lmn_table {
   uint32_t kind;        /* LMN_KIND_* */
-  uint32_t flags;       /* LMN_TABLE_ROWS_ON_DEVICE: `rows` is a device pointer (lmn_upload) */
+  uint32_t flags;       /* LMN_TABLE_ROWS_ON_DEVICE: `rows` is a device pointer (lmn_upload);
+                           LMN_TABLE_COLS_ON_DEVICE: a finished row sink's columns (lmn_rows_finish, below) */
   uint64_t n_rows;
   const uint32_t* rows; /* n_rows * n_columns(kind) words */
 } lmn_table;
@@ -425,6 +426,55 @@ int lmn_trace_max_reduce(lmn_ctx* ctx, const int32_t* input_dev, uint64_t front,
  * acc / next_acc; out_dev (may be NULL) receives the front*back sums. */
 int lmn_trace_sum_reduce(lmn_ctx* ctx, const int32_t* input_dev, uint64_t front, uint64_t dim, uint64_t back,
                          const lmn_node_info* info, uint32_t* rows_dev, uint64_t row_offset, int32_t* out_dev);
+
+/* ---- Row sinks: host trace rows streamed to the GPU while they are produced.  The reference builds its pie on the
+ * host node by node - every operator's `process_trace` appends with `table.add_row(...)`
+ * (crates/graph/src/op/prim.rs:75, 412, 992, 1117) - and hands `prove` the finished pie (crates/prover/src/prover.rs:28-31,
+ * 70).  A caller that keeps `process_trace` on the CPU opens one sink per table and pushes each node's rows when the node
+ * is done: transfer and AoS -> SoA transpose then run under its own CPU work, and what is left in front of the proof is
+ * the last chunk, the padding rows and one wait.  lmn_prove on plain host rows is unchanged.
+ *
+ * The contract:
+ *  - Rows: lmn_kind_columns(kind) words each, in `Column::index()` order, as in lmn_table.  A chunk has ANY length >= 1
+ *    (one node's rows), chunks arrive in table order.  More than `capacity_rows` (1 .. 2^26) in total is
+ *    LMN_ERR_INVALID_ARGUMENT and the sink keeps what it had.  A sink never grows and never reallocates: its columns
+ *    (capacity rounded up to a power of two, at least 16 rows) are allocated by lmn_rows_open, outside the context's
+ *    per-proof arena.
+ *  - lmn_rows_push returns when the library no longer needs `host_rows`: they went through the sink's own page-locked
+ *    staging ring (4 slots of 4 MiB, allocated by the first such push; a push waits only when every slot is still in
+ *    flight).  lmn_rows_push_pinned makes no CPU copy - the GPU reads the rows where they lie, once - and the buffer must
+ *    stay untouched until lmn_rows_sync or lmn_rows_finish returns; memory the runtime does not know as page-locked
+ *    (lmn_host_alloc / lmn_host_register) is refused with LMN_ERR_INVALID_ARGUMENT, never copied slowly instead.
+ *  - Neither push waits for the device.  All device work of a sink runs on a stream of its own, not on the context's
+ *    proof stream, and no lmn_rows_* call takes the context's lock: a proof of the previous pie on the same context
+ *    (lmn_prove_submit, or lmn_prove on another thread) overlaps with the filling of the next sink.  Calls on ONE sink
+ *    are serialised by the sink.
+ *  - lmn_rows_finish writes the padding rows (lmn_kind_padding_row; rows [count, 2^log_size), log_size as lmn_prove
+ *    derives it from n_rows: the next power of two, at least 16 rows), waits ONCE, and returns LMN_ERR_INVALID_ARGUMENT
+ *    if any pushed word was >= 2^31 - 1, LMN_ERR_EMPTY_TRACE if no row was pushed.  If 2^log_size is smaller than the
+ *    column stride chosen at open, the columns are compacted so that table_out->rows has stride 2^log_size.  After an
+ *    error the sink can be reset and the context is usable.  Pushing or finishing again without lmn_rows_reset is
+ *    LMN_ERR_INVALID_ARGUMENT.
+ *  - table_out = {kind, LMN_TABLE_COLS_ON_DEVICE, count, device pointer}.  lmn_prove / lmn_prove_submit accept such tables
+ *    mixed freely with the two other kinds in one pie, on any context of the sink's device, with log_blowup 1, 2 or 3.
+ *    The proof only READS the columns: proving the same finished sink twice gives the same bytes.  The sink must outlive
+ *    the proof (lmn_prove_wait for submitted ones) and must not be reset or closed before; a table whose `rows` is not
+ *    the columns of a live finished sink is LMN_ERR_INVALID_ARGUMENT.
+ *  - Refused with LMN_ERR_INVALID_ARGUMENT and a text that says so: a LMN_TABLE_COLS_ON_DEVICE table on a sharded context
+ *    (lmn_ctx_set_shard), and everything of this block in libluminair_hip_batch.so - lmn_rows_open there, and such a
+ *    table in its lmn_batch_* AND in its solo lmn_prove.
+ *  - The text of a failed lmn_rows_* call is available through lmn_last_error(NULL) on the calling thread. */
+typedef struct lmn_rows lmn_rows;          /* a table being filled: column-major, in HBM, owned by the sink */
+#define LMN_TABLE_COLS_ON_DEVICE 2u        /* `rows` = device pointer to n_columns(kind) columns of 2^log_size words each,
+                                              padded, canonical: what lmn_rows_finish writes into table_out */
+int lmn_rows_open(lmn_ctx* ctx, uint32_t kind, uint64_t capacity_rows, lmn_rows** out);
+int lmn_rows_push(lmn_rows* rows, const uint32_t* host_rows, uint64_t n);         /* any host memory */
+int lmn_rows_push_pinned(lmn_rows* rows, const uint32_t* host_rows, uint64_t n);  /* lmn_host_alloc / lmn_host_register memory */
+int lmn_rows_sync(lmn_rows* rows);                         /* everything pushed so far has left the caller's buffers */
+int lmn_rows_finish(lmn_rows* rows, lmn_table* table_out); /* pad, verdict on non-canonical words, fill table_out */
+uint64_t lmn_rows_count(const lmn_rows* rows);
+int lmn_rows_reset(lmn_rows* rows);                        /* same capacity, zero rows: the next proof's table */
+void lmn_rows_close(lmn_rows* rows);
 
 /* ---- Single-proof sharding over the GPUs of one node (BASELINE.json configs 4 and 5).
  * One context per GPU, world = 1, 2, 4 or 8 ranks.  Every rank calls lmn_prove with the SAME tables and gets the

@@ -43,6 +43,7 @@ STEP_NAMES = ["root_preprocessed", "claim", "root_main", "interaction_claim", "r
 ROUND_HALF_AWAY, ROUND_HALF_EVEN, ROUND_TRUNC, ROUND_FLOOR = 0, 1, 2, 3
 MAX_TRANSCRIPT_STEPS = 48
 TABLE_ROWS_ON_DEVICE = 1
+TABLE_COLS_ON_DEVICE = 2
 
 
 class LmnConfig(C.Structure):
@@ -146,7 +147,9 @@ EXPORTS = ["lmn_abi_version", "lmn_kind_padding_row", "lmn_strerror", "lmn_last_
            "lmn_col_interpolate", "lmn_col_evaluate", "lmn_col_evaluate_block", "lmn_col_extend", "lmn_col_eval_at_point",
            "lmn_col_commit", "lmn_tree_root", "lmn_tree_log_size", "lmn_tree_layer_to_cpu", "lmn_tree_free",
            "lmn_col_accumulate", "lmn_col_accumulate_quotients", "lmn_col_fold_line", "lmn_col_fold_circle_into_line",
-           "lmn_col_decompose", "lmn_col_logup", "lmn_col_composition", "lmn_kind_constraints", "lmn_kind_relations", "lmn_ctx_set_shard", "lmn_rccl_unique_id", "lmn_ctx_set_shard_rccl", "lmn_ctx_clear_shard"]
+           "lmn_col_decompose", "lmn_col_logup", "lmn_col_composition", "lmn_kind_constraints", "lmn_kind_relations", "lmn_ctx_set_shard", "lmn_rccl_unique_id", "lmn_ctx_set_shard_rccl", "lmn_ctx_clear_shard",
+           "lmn_rows_open", "lmn_rows_push", "lmn_rows_push_pinned", "lmn_rows_sync", "lmn_rows_finish", "lmn_rows_count",
+           "lmn_rows_reset", "lmn_rows_close"]
 
 
 class LuminairBackendError(RuntimeError):
@@ -270,6 +273,16 @@ class Library:
         lib.lmn_rccl_unique_id.argtypes = [C.c_void_p]
         lib.lmn_ctx_set_shard_rccl.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         lib.lmn_ctx_clear_shard.argtypes = [C.c_void_p]
+        lib.lmn_rows_open.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_void_p)]
+        lib.lmn_rows_push.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        lib.lmn_rows_push_pinned.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        lib.lmn_rows_sync.argtypes = [C.c_void_p]
+        lib.lmn_rows_finish.argtypes = [C.c_void_p, C.POINTER(LmnTable)]
+        lib.lmn_rows_count.argtypes = [C.c_void_p]
+        lib.lmn_rows_count.restype = C.c_uint64
+        lib.lmn_rows_reset.argtypes = [C.c_void_p]
+        lib.lmn_rows_close.argtypes = [C.c_void_p]
+        lib.lmn_rows_close.restype = None
         lib.lmn_trace_elementwise_v.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(LmnView), C.c_void_p,
                                                 C.POINTER(LmnView), C.c_uint64, C.POINTER(LmnNodeInfo), C.c_void_p,
                                                 C.c_uint64, C.c_void_p]
@@ -433,6 +446,103 @@ class DeviceBuffer:
         if self.ptr and self.owned:
             self.ctx.lib.lib.lmn_device_free(self.ctx.handle, self.ptr)
         self.ptr = 0
+
+
+class RowSink:
+    """`lmn_rows`: one trace table of a pie, filled chunk by chunk while the host produces its rows (the reference's
+    `table.add_row` loop, one `push` at the end of every node) and kept column-major in HBM.  After `finish()` it stands
+    where a `TraceTable` stands: in `LuminairPie.from_tables`, `Prover.prove`, `ProverPool.prove_many`, and as the rows of
+    a `Context.prove_tables` entry.  It must stay open (and not be reset) until the proof that reads it has returned."""
+
+    def __init__(self, ctx: "Context", kind: int, capacity_rows: int):
+        self.ctx, self.kind, self.capacity = ctx, int(kind), int(capacity_rows)
+        self.ncols = ctx.lib.kind_columns(self.kind)
+        self.table: Optional[LmnTable] = None       # filled in by finish()
+        self._keep = []                              # page-locked chunks the GPU may still be reading
+        h = C.c_void_p()
+        self._check(ctx.lib.lib.lmn_rows_open(ctx.handle, self.kind, self.capacity, C.byref(h)))
+        self.handle = h
+
+    @staticmethod
+    def open(ctx: "Context", kind: int, capacity_rows: int) -> "RowSink":
+        return RowSink(ctx, kind, capacity_rows)
+
+    def _check(self, rc: int):
+        if rc != LMN_OK:
+            lib = self.ctx.lib.lib
+            raise LuminairBackendError(rc, lib.lmn_last_error(None).decode() or lib.lmn_strerror(rc).decode())
+
+    def _chunk(self, rows) -> np.ndarray:
+        a = np.asarray(rows)
+        if a.dtype != np.uint32 or not a.flags["C_CONTIGUOUS"] or a.size % max(self.ncols, 1):
+            raise ValueError("a chunk is a C-contiguous uint32 array of whole rows (%d words each)" % self.ncols)
+        return a
+
+    def push(self, rows) -> "RowSink":
+        """Rows in any host memory; they are free again when the call returns."""
+        a = self._chunk(np.ascontiguousarray(rows, dtype=np.uint32))
+        self._check(self.ctx.lib.lib.lmn_rows_push(self.handle, a.ctypes.data, a.size // self.ncols))
+        return self
+
+    def push_pinned(self, rows) -> "RowSink":
+        """Rows in page-locked memory (a `PinnedArray`'s `.array` or a slice of it, or a `host_register`ed array): no CPU
+        copy; the memory must stay untouched until `sync()` or `finish()` returns."""
+        a = self._chunk(rows)
+        self._check(self.ctx.lib.lib.lmn_rows_push_pinned(self.handle, a.ctypes.data, a.size // self.ncols))
+        self._keep.append(a)
+        return self
+
+    def sync(self):
+        self._check(self.ctx.lib.lib.lmn_rows_sync(self.handle))
+        self._keep = []
+
+    def finish(self) -> "RowSink":
+        t = LmnTable()
+        try:
+            self._check(self.ctx.lib.lib.lmn_rows_finish(self.handle, C.byref(t)))
+        finally:
+            self._keep = []
+        self.table = t
+        return self
+
+    def reset(self) -> "RowSink":
+        self._check(self.ctx.lib.lib.lmn_rows_reset(self.handle))
+        self.table = None
+        return self
+
+    @property
+    def n_rows(self) -> int:
+        return int(self.ctx.lib.lib.lmn_rows_count(self.handle))
+
+    @property
+    def rows(self) -> "RowSink":          # what a TraceTable's `rows` is to the prover wrappers
+        return self
+
+    def columns(self) -> np.ndarray:
+        """The finished table as data: (ncols, 2^log_size) words, padding rows included."""
+        if self.table is None:
+            raise ValueError("the sink is not finished")
+        size = max(16, 1 << max(int(self.table.n_rows) - 1, 0).bit_length())
+        nbytes = self.ncols * size * 4
+        return self.ctx.download(DeviceBuffer(self.ctx, self.table.rows, nbytes, owned=False)).reshape(self.ncols, size)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.ctx.lib.lib.lmn_rows_close(self.handle)
+            self.handle = None
+            self.table = None
+
+    def __enter__(self) -> "RowSink":
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Col:
@@ -831,7 +941,14 @@ class Context:
         for i, (kind, rows, n_rows) in enumerate(tables):
             arr[i].kind = kind
             arr[i].n_rows = n_rows
-            if isinstance(rows, DeviceBuffer):
+            if isinstance(rows, RowSink):
+                if rows.table is None:
+                    raise LuminairBackendError(ERR_INVALID_ARGUMENT, "a RowSink must be finished before it is proved")
+                arr[i].flags = TABLE_COLS_ON_DEVICE
+                arr[i].n_rows = rows.table.n_rows
+                arr[i].rows = rows.table.rows
+                keep.append(rows)
+            elif isinstance(rows, DeviceBuffer):
                 arr[i].flags = TABLE_ROWS_ON_DEVICE
                 arr[i].rows = rows.ptr
             else:
@@ -852,8 +969,12 @@ class Context:
         keep += [arr, lut_arr, settings]
         return arr, n, settings, keep
 
+    def row_sink(self, kind: int, capacity_rows: int) -> RowSink:
+        """`lmn_rows_open`: a table of `kind` to be filled with up to `capacity_rows` host rows while they are produced."""
+        return RowSink(self, kind, capacity_rows)
+
     def prove_tables(self, tables: Sequence[Tuple[int, object, int]], luts=None) -> bytes:
-        """tables: [(kind, rows, n_rows)] where rows is a uint32 ndarray (host) or a DeviceBuffer;
+        """tables: [(kind, rows, n_rows)] where rows is a uint32 ndarray (host), a DeviceBuffer or a finished RowSink;
         luts: {"sin" | "exp2" | "log2": (col0, col1)} preprocessed LUT columns (uint32, 2^k words each)."""
         arr, n, settings, _keep = self._marshal_tables(tables, luts)
         out = C.POINTER(C.c_uint8)()

@@ -281,6 +281,56 @@ int lmn_host_unregister(void* host) {
   return host_guard([&] { lmn_host_unregister_range(host); });
 }
 
+// ---- row sinks (trace_gen.cpp RowSink).  No call here takes the context's lock: a sink fills while its context proves.
+}  // extern "C"
+struct lmn_rows {
+  lmn::RowSink sink;
+  lmn_rows(int device, uint32_t kind, uint64_t capacity) : sink(device, kind, capacity) {}
+};
+namespace {
+template <class F>
+int rows_guard(F&& f) {
+  lmn_ctx tmp{nullptr, {}};
+  const int rc = guard(&tmp, std::forward<F>(f));
+  if (rc != LMN_OK) g_create_error = tmp.last_error;
+  return rc;
+}
+}  // namespace
+extern "C" {
+int lmn_rows_open(lmn_ctx* ctx, uint32_t kind, uint64_t capacity_rows, lmn_rows** out) {
+  if (!ctx || !out) return LMN_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+#ifdef LMN_BATCH
+  g_create_error = "row sinks are not part of the batch library (use libluminair_hip.so)";
+  return LMN_ERR_INVALID_ARGUMENT;
+#else
+  const int device = ctx->impl->device();
+  return rows_guard([&] { *out = new lmn_rows(device, kind, capacity_rows); });
+#endif
+}
+int lmn_rows_push(lmn_rows* rows, const uint32_t* host_rows, uint64_t n) {
+  if (!rows || !host_rows) return LMN_ERR_INVALID_ARGUMENT;
+  return rows_guard([&] { rows->sink.push(host_rows, n, false); });
+}
+int lmn_rows_push_pinned(lmn_rows* rows, const uint32_t* host_rows, uint64_t n) {
+  if (!rows || !host_rows) return LMN_ERR_INVALID_ARGUMENT;
+  return rows_guard([&] { rows->sink.push(host_rows, n, true); });
+}
+int lmn_rows_sync(lmn_rows* rows) {
+  if (!rows) return LMN_ERR_INVALID_ARGUMENT;
+  return rows_guard([&] { rows->sink.sync(); });
+}
+int lmn_rows_finish(lmn_rows* rows, lmn_table* table_out) {
+  if (!rows || !table_out) return LMN_ERR_INVALID_ARGUMENT;
+  return rows_guard([&] { rows->sink.finish(table_out); });
+}
+uint64_t lmn_rows_count(const lmn_rows* rows) { return rows ? rows->sink.count() : 0; }
+int lmn_rows_reset(lmn_rows* rows) {
+  if (!rows) return LMN_ERR_INVALID_ARGUMENT;
+  return rows_guard([&] { rows->sink.reset(); });
+}
+void lmn_rows_close(lmn_rows* rows) { delete rows; }
+
 int lmn_upload(lmn_ctx* ctx, const void* host, size_t bytes, void** device_out) {
   if (!ctx || !host || !device_out) return LMN_ERR_INVALID_ARGUMENT;
   return guard(ctx, [&] { *device_out = ctx->impl->upload(host, bytes); });

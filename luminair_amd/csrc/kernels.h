@@ -27,6 +27,13 @@ void launch_transpose_pad_rows(const uint32_t* rows, uint64_t n_rows, int ncols,
                                uint64_t out_stride, uint64_t blk_row0, uint64_t blk_rows, const PadRow& pad, uint32_t* bad_flag,
                                lmn_stream_t s,
                                uint32_t bad_value = 1u /* what a non-canonical word writes to *bad_flag */);
+// Row sinks (lmn_rows_*): one CHUNK of rows - its row 0 is table row r0, any r0, any length n >= 1 - transposed into
+// columns `stride` words apart.  `chunk` may be page-locked HOST memory in its device view (read over the link, once).
+// chunk == nullptr: rows [r0, r0 + n) receive the padding row instead.  A non-canonical word sets *bad_word to 1.
+constexpr int CHUNK_ROWS = 256;      // table rows per workgroup, aligned in the DESTINATION: every full tile stores 1 KB runs
+constexpr int CHUNK_MAX_COLS = 30;   // CHUNK_ROWS * (ncols | 1) * 4 B of LDS <= 31 744 B: two workgroups per CU and more
+void launch_rows_chunk(const uint32_t* chunk, uint64_t r0, uint64_t n, int ncols, uint32_t* cols, uint64_t stride,
+                       const PadRow& pad, uint32_t* bad_word, lmn_stream_t s);
 
 // ---- a4: circle FFT passes.  data = ncols columns of 2^log_n words at stride col_stride.
 // dst may equal src (in place).  launch_fft zero-extends src (2^log_src words) to 2^log_n (LDE).

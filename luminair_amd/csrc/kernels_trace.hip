@@ -75,6 +75,59 @@ void launch_transpose_pad(const uint32_t* rows, uint64_t n_rows, int ncols, int 
   launch_transpose_pad_rows(rows, n_rows, ncols, log_size, cols, 1ull << log_size, 0, 1ull << log_size, pad, bad_flag, s);
 }
 
+// a3 for a row sink: the rows arrive in chunks while the caller produces them.  Against k_transpose_pad: the chunk starts at
+// an arbitrary table row r0, so the tiles are cut in the DESTINATION - workgroup b owns table rows [t0, t0 + CHUNK_ROWS)
+// with t0 = (r0 rounded down to CHUNK_ROWS) + b * CHUNK_ROWS, of which the first and the last workgroup hold only the
+// chunk's head and tail - and every full tile stores aligned 1 KB runs per column whatever r0 is.  The tile's words are
+// one contiguous run of the chunk (rows are AoS), read with consecutive lanes on consecutive words, 8 loads in flight per
+// lane before the first is used; the run may lie in page-locked host memory (one pass over the link, no staging copy on
+// the device).  chunk == nullptr (launch-uniform): the padding row is written instead.
+LMN_KERNEL k_rows_chunk(const uint32_t* __restrict__ chunk, uint64_t r0, uint64_t n, int ncols, uint32_t magic,
+                        uint32_t* __restrict__ cols, uint64_t col_stride, PadRow pad, uint32_t* __restrict__ bad_word) {
+  LMN_DYN_SMEM(uint32_t, tile);  // CHUNK_ROWS x stride, indexed by (table row - t0)
+  const int stride = ncols | 1;  // odd: the column-major read below walks rows at that stride (k_transpose_pad)
+  const uint64_t t0 = (r0 & ~(uint64_t)(CHUNK_ROWS - 1)) + (uint64_t)blockIdx.x * CHUNK_ROWS;
+  const uint64_t lo = t0 > r0 ? t0 : r0, hi = t0 + CHUNK_ROWS < r0 + n ? t0 + CHUNK_ROWS : r0 + n;
+  const int first = (int)(lo - t0), total = (int)(hi - lo) * ncols;   // rows [lo, hi) of the table: total <= 7 680 words
+  const uint32_t* __restrict__ src = chunk ? chunk + (lo - r0) * (uint64_t)ncols : nullptr;
+  constexpr int BATCH = 8;   // loads issued before the first of them is used
+  for (int k0 = threadIdx.x; k0 < total; k0 += BATCH * TPB) {
+    uint32_t v[BATCH];
+#pragma unroll
+    for (int j = 0; j < BATCH; ++j) {
+      const int k = k0 + j * TPB;
+      v[j] = 0u;
+      if (src && k < total) v[j] = src[k];
+    }
+#pragma unroll
+    for (int j = 0; j < BATCH; ++j) {
+      const int k = k0 + j * TPB;
+      if (k >= total) break;
+      // k / ncols by the precomputed reciprocal (exact for k < 2^16); magic 0: one column
+      const int r = magic ? (int)(((uint64_t)(uint32_t)k * magic) >> 32) : k, c = k - r * ncols;
+      const uint32_t w = src ? v[j] : pad.v[c];
+      if (w >= P31) *bad_word = 1u;  // the boundary takes raw u32 words: reject non-canonical M31 values
+      tile[(first + r) * stride + c] = w;
+    }
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < CHUNK_ROWS * ncols; k += TPB) {
+    const int c = k / CHUNK_ROWS, r = k - c * CHUNK_ROWS;
+    if (t0 + r >= lo && t0 + r < hi) cols[(uint64_t)c * col_stride + t0 + r] = tile[r * stride + c];
+  }
+}
+
+void launch_rows_chunk(const uint32_t* chunk, uint64_t r0, uint64_t n, int ncols, uint32_t* cols, uint64_t stride,
+                       const PadRow& pad, uint32_t* bad_word, lmn_stream_t s) {
+  if (ncols > CHUNK_MAX_COLS || ncols < 1) throw LmnError(-100, "row chunk: bad column count");
+  if (n == 0 || r0 + n > stride) throw LmnError(-100, "row chunk: rows outside the columns");
+  const uint64_t t0 = r0 & ~(uint64_t)(CHUNK_ROWS - 1);
+  const unsigned grid = cdiv(r0 + n - t0, CHUNK_ROWS);
+  const size_t smem = (size_t)CHUNK_ROWS * (ncols | 1) * 4;
+  const uint32_t magic = ncols == 1 ? 0u : (uint32_t)((0x100000000ull + (uint64_t)ncols - 1) / (uint64_t)ncols);  // ceil(2^32 / ncols)
+  LMN_LAUNCH(k_rows_chunk, dim3(grid), dim3(TPB), smem, s, chunk, r0, n, ncols, magic, cols, stride, pad, bad_word);
+}
+
 // =============================================================================================
 // gen_trace for Add / Mul / Recip nodes (crates/graph/src/op/prim.rs:967-1013, :1090-1139, :388-431):
 // one lane per tensor element computes the fixed-point op and its row; the block stages its rows in LDS

@@ -101,6 +101,14 @@ void Context::run_main_trace(ProofRun& r) {
       // host tables, uploaded
       const uint64_t nb = rows_front ? n >> shard_.g : n, blk0 = rows_front ? (uint64_t)shard_.rank * nb : 0;
       const uint64_t up0 = std::min<uint64_t>(blk0, ti.n_rows), up1 = std::min<uint64_t>(blk0 + nb, ti.n_rows);
+      if (ti.cols_on_device) {
+        // a finished row sink (lmn_rows_finish): padded, checked and column-major already, and only read from here on -
+        // no upload, no transpose launch, no copy into the arena
+        inst[t].trace_evals = const_cast<uint32_t*>(ti.rows);
+        inst[t].rows_n = ti.n_rows;
+        proof.claim[ti.spec->kind] = ti.log_size;
+        continue;
+      }
       const uint32_t* d_rows = ti.rows;
       if (!ti.on_device) {
         uint32_t* stg = arena_.alloc_words(std::max<uint64_t>(up1 - up0, 1) * ti.spec->n_cols);

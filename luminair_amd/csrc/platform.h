@@ -203,6 +203,52 @@ inline float lmn_event_elapsed_ms(lmn_event_t a, lmn_event_t b) {
   return ms;
 }
 
+// ---- what a row sink needs besides the context's proof stream (trace_gen.cpp): a stream of its own, events that only
+// order work (no timing), and the device's address of page-locked host memory that its chunk kernel reads over the link
+inline void lmn_set_device(int device) { LMN_HIP_CHECK(hipSetDevice(device)); }
+inline lmn_stream_t lmn_stream_create() {
+  hipStream_t s;
+  LMN_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  return s;
+}
+inline void lmn_stream_destroy(lmn_stream_t s) { (void)hipStreamDestroy(s); }
+inline lmn_event_t lmn_event_create_untimed() {
+  hipEvent_t e;
+  LMN_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  return e;
+}
+inline void lmn_stream_wait_event(lmn_stream_t s, lmn_event_t e) { LMN_HIP_CHECK(hipStreamWaitEvent(s, e, 0)); }
+// the host waits until the work recorded in `e` is done (an event never recorded is done): polls first, as lmn_sync does
+inline void lmn_event_wait(lmn_event_t e) {
+  for (int it = 0; it < 4096; ++it) {
+    hipError_t q = hipEventQuery(e);
+    if (q == hipSuccess) return;
+    if (q != hipErrorNotReady) LMN_HIP_CHECK(q);
+#if defined(__x86_64__)
+    for (int k = 0; k < 32; ++k) __builtin_ia32_pause();
+#endif
+  }
+  LMN_HIP_CHECK(hipEventSynchronize(e));
+}
+// Device address of [host, host + bytes) if the runtime knows both ends as page-locked host memory (hipHostMalloc,
+// hipHostRegister), else nullptr.  A failed query leaves no sticky error behind for the next launch to trip over.
+inline const void* lmn_host_device_view(const void* host, size_t bytes) {
+  const char* ends[2] = {(const char*)host, (const char*)host + (bytes ? bytes - 1 : 0)};
+  for (const char* p : ends) {
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess || a.type != hipMemoryTypeHost) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+  }
+  void* d = nullptr;
+  if (hipHostGetDevicePointer(&d, const_cast<void*>(host), 0) != hipSuccess) {
+    (void)hipGetLastError();
+    return nullptr;
+  }
+  return d;
+}
+
 #else  // ------------------------------------------------------------------ LMN_EMU (tests only)
 #include <barrier>
 #include <functional>
@@ -370,4 +416,13 @@ inline void lmn_event_record(lmn_event_t e, lmn_stream_t) {
   *e = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 inline float lmn_event_elapsed_ms(lmn_event_t a, lmn_event_t b) { return (float)(*b - *a); }
+// row sinks (trace_gen.cpp): the emulation runs every launch to its end inside the call, so a second stream is the same
+// stream, an event is always done, and host memory is its own device view (page-locked or not: nothing here can tell)
+inline void lmn_set_device(int) {}
+inline lmn_stream_t lmn_stream_create() { return 0; }
+inline void lmn_stream_destroy(lmn_stream_t) {}
+inline lmn_event_t lmn_event_create_untimed() { return new double(0.0); }
+inline void lmn_stream_wait_event(lmn_stream_t, lmn_event_t) {}
+inline void lmn_event_wait(lmn_event_t) {}
+inline const void* lmn_host_device_view(const void* host, size_t) { return host; }
 #endif

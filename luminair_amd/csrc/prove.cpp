@@ -123,10 +123,22 @@ void Context::run_setup(ProofRun& r) {
     if (ls <= (int)cfg.log_last_layer)
       throw LmnError(LMN_ERR_INVALID_ARGUMENT, "a table needs more than 2^log_last_layer rows (after padding)");
     infos.push_back({sp, tb.n_rows, ls, tb.rows, (tb.flags & LMN_TABLE_ROWS_ON_DEVICE) != 0});
+    if (tb.flags & LMN_TABLE_COLS_ON_DEVICE) {
+      if (tb.flags & LMN_TABLE_ROWS_ON_DEVICE)
+        throw LmnError(LMN_ERR_INVALID_ARGUMENT, "a table is LMN_TABLE_ROWS_ON_DEVICE or LMN_TABLE_COLS_ON_DEVICE, not both");
+#ifdef LMN_BATCH
+      throw LmnError(LMN_ERR_INVALID_ARGUMENT, "LMN_TABLE_COLS_ON_DEVICE (row sinks) is not supported by the batch library");
+#else
+      if (shard_.active)
+        throw LmnError(LMN_ERR_INVALID_ARGUMENT, "LMN_TABLE_COLS_ON_DEVICE (row sinks) is not supported on a sharded context");
+      rows_sink_attach(tb, device_, stream_);   // the proof's stream waits for the sink's finish event; the host does not
+      infos.back().cols_on_device = true;
+#endif
+    }
     max_log = std::max(max_log, ls);
     uint64_t cells = (uint64_t)(sp->n_cols + 4 * sp->n_rel) << ls;
     words += cells * 2 + row_split(cells << lb);               // evals + coeffs + lde (this rank's row block)
-    if (!infos.back().on_device) words += tb.n_rows * sp->n_cols;  // staging
+    if (!infos.back().on_device && !infos.back().cols_on_device) words += tb.n_rows * sp->n_cols;  // staging
     words += (uint64_t)sp->n_pre * ((2ull << ls) + row_split(2ull << ls));  // preprocessed columns: evals + coeffs + lde
     words += (4ull << ls) * 2;                                 // logup temps
     words += (4ull << (ls + 1)) * 3;                           // per-size composition scratch

@@ -12,6 +12,7 @@ struct TableInfo {
   int log_size;
   const uint32_t* rows;
   bool on_device;
+  bool cols_on_device = false;   // LMN_TABLE_COLS_ON_DEVICE: `rows` = a finished row sink's padded columns, 2^log_size apart
 };
 // one FRI quotient column (the columns of one LDE size accumulated)
 struct Quot {

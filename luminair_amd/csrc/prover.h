@@ -3,6 +3,7 @@
 #pragma once
 #include <functional>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -157,6 +158,52 @@ struct DevTree {
 // the caller-facing limits of one accumulate_quotients call (level2.cpp): LMN_ERR_INVALID_ARGUMENT past them
 void check_quotient_limits(const uint32_t* sample_point, uint32_t nsamples);
 
+// A trace table that a HOST producer fills chunk by chunk while it works (lmn_rows_*, trace_gen.cpp): column-major in
+// HBM from the first push on, so that what is left between the last row and the proof is one chunk's transfer, the padding
+// rows and one wait.  The columns come from lmn_dev_malloc, outside every context's per-proof arena; all device work runs
+// on the sink's own stream, so a proof on the context it was opened on overlaps with its filling.  Calls on one sink are
+// serialised by its own lock and never take the context's.
+class RowSink {
+ public:
+  RowSink(int device, uint32_t kind, uint64_t capacity_rows);
+  ~RowSink();
+  RowSink(const RowSink&) = delete;
+  RowSink& operator=(const RowSink&) = delete;
+  // pinned: `host_rows` is page-locked and read by the GPU where it lies; otherwise it is copied through the staging ring
+  void push(const uint32_t* host_rows, uint64_t n, bool pinned);
+  void sync();
+  void finish(lmn_table* table_out);
+  void reset();
+  uint64_t count() const;
+
+ private:
+  friend void rows_sink_attach(const lmn_table& tb, int device, lmn_stream_t proof_stream);
+  void forget();   // no longer a finished table prove() accepts
+  int device_;
+  const ComponentSpec* spec_;
+  uint64_t cap_, stride_, count_ = 0;
+  enum { FILLING, FINISHED, FAILED } state_ = FILLING;
+  PadRow pad_{};
+  uint32_t* cols_ = nullptr;     // n_cols x stride_ words (n_cols x 2^log_size after a finish that compacted them)
+  uint32_t* bad_ = nullptr;      // the sink's own device word: set by a chunk that held a non-canonical word
+  uint32_t* h_bad_ = nullptr;    // page-locked: its copy, read after finish's one wait
+  lmn_stream_t stream_{};
+  lmn_event_t done_{};           // recorded behind finish's last launch: what a proof's stream waits for
+  // Staging ring of lmn_rows_push (pageable rows), allocated by the first such push: SLOTS page-locked slots of SLOT_BYTES.
+  // 4 MiB holds one of the 16 chunks of BASELINE config 2a (2^16 rows x 15 columns = 3.75 MiB) in ONE launch, and
+  // is ~75 us of link time against ~400 us of the CPU copy that fills it: with 4 slots the copy never waits for the link.
+  static constexpr int SLOTS = 4;
+  static constexpr size_t SLOT_BYTES = 4u << 20;
+  char* ring_ = nullptr;
+  const char* ring_dev_ = nullptr;   // the ring as the chunk kernel addresses it
+  lmn_event_t slot_done_[SLOTS] = {};
+  int next_slot_ = 0;
+  mutable std::mutex mu_;
+};
+// prove(): a LMN_TABLE_COLS_ON_DEVICE table must be the finished columns of a sink on this device (LMN_ERR_INVALID_ARGUMENT
+// otherwise); the proof stream is made to wait for the sink's finish event - the host does not wait
+void rows_sink_attach(const lmn_table& tb, int device, lmn_stream_t proof_stream);
+
 struct StageTimer;
 
 struct ProofRun;   // state of one proof across the phases of Context::prove (prove_run.h)
@@ -240,6 +287,7 @@ class Context {
                  uint64_t row_offset, int32_t* out);
   void device_free(void* p);
 
+  int device() const { return device_; }
   lmn_config cfg;
   lmn_timings timings{};
   bool profiling = false;  // record HIP events around stages/kernels (lmn_set_profiling)

@@ -136,4 +136,158 @@ void Context::trace_contiguous(const int32_t* input, uint64_t in_size, const lmn
                            stream_);
 }
 
+// ------------------------------------------------------------------------------------ row sinks (lmn_rows_*)
+// The reference builds its pie on the host, node by node (`table.add_row` in every operator's process_trace,
+// crates/graph/src/op/prim.rs:75, 412, 992, 1117; prove takes it at crates/prover/src/prover.rs:28-31,70).  A sink takes
+// each node's rows when the node is done and keeps the table column-major in HBM: transfer and transpose run under the
+// producer's CPU work instead of in front of the proof.
+namespace {
+std::mutex g_sinks_mu;
+std::map<const uint32_t*, RowSink*> g_sinks;   // finished sinks by the column block they handed out
+}  // namespace
+
+RowSink::RowSink(int device, uint32_t kind, uint64_t capacity_rows)
+    : device_(device), spec_(component_spec((int)kind)), cap_(capacity_rows) {
+  if (!spec_) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "row sink: unsupported component kind " + std::to_string(kind));
+  if (spec_->n_cols > CHUNK_MAX_COLS) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "row sink: component has too many columns");
+  if (cap_ == 0 || cap_ > (1ull << 26)) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "row sink: capacity must be 1 .. 2^26 rows");
+  stride_ = 16;
+  while (stride_ < cap_) stride_ <<= 1;
+  if (spec_->is_last_col >= 0) pad_.v[spec_->is_last_col] = 1u;
+  for (int k = 0; k < spec_->n_pad; ++k) pad_.v[spec_->pad_col[k]] = spec_->pad_val[k];
+  lmn_set_device(device_);
+  try {
+    cols_ = (uint32_t*)lmn_dev_malloc((size_t)spec_->n_cols * stride_ * 4);
+    bad_ = (uint32_t*)lmn_dev_malloc(4);
+  } catch (const LmnError& e) {
+    if (cols_) lmn_dev_free(cols_);
+    throw LmnError(LMN_ERR_OUT_OF_MEMORY, std::string("row sink: device allocation failed: ") + e.what());
+  }
+  h_bad_ = (uint32_t*)lmn_host_alloc_pinned(64);
+  stream_ = lmn_stream_create();
+  done_ = lmn_event_create_untimed();
+  for (auto& e : slot_done_) e = lmn_event_create_untimed();
+  lmn_memset(bad_, 0, 4, stream_);
+}
+
+RowSink::~RowSink() {
+  forget();
+  try {
+    lmn_set_device(device_);
+    lmn_sync(stream_);
+  } catch (...) {
+  }
+  lmn_event_destroy(done_);
+  for (auto e : slot_done_) lmn_event_destroy(e);
+  lmn_stream_destroy(stream_);
+  if (ring_) lmn_host_free_pinned(ring_);
+  lmn_host_free_pinned(h_bad_);
+  lmn_dev_free(bad_);
+  lmn_dev_free(cols_);
+}
+
+void RowSink::forget() {
+  std::lock_guard<std::mutex> lk(g_sinks_mu);
+  auto it = g_sinks.find(cols_);
+  if (it != g_sinks.end() && it->second == this) g_sinks.erase(it);
+}
+
+uint64_t RowSink::count() const {
+  std::lock_guard<std::mutex> lk(mu_);
+  return count_;
+}
+
+void RowSink::push(const uint32_t* host_rows, uint64_t n, bool pinned) {
+  std::lock_guard<std::mutex> lk(mu_);
+  if (state_ != FILLING)
+    throw LmnError(LMN_ERR_INVALID_ARGUMENT, "row sink: push after finish (lmn_rows_reset starts the next table)");
+  if (!host_rows || n == 0) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "row sink: a chunk has at least one row");
+  if (n > cap_ - count_) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "row sink: more rows than the capacity it was opened with");
+  const uint64_t row_bytes = (uint64_t)spec_->n_cols * 4;
+  lmn_set_device(device_);
+  if (pinned) {
+    const uint32_t* view = (const uint32_t*)lmn_host_device_view(host_rows, n * row_bytes);
+    if (!view)
+      throw LmnError(LMN_ERR_INVALID_ARGUMENT,
+                     "lmn_rows_push_pinned: the rows are not in page-locked memory (lmn_host_alloc / lmn_host_register)");
+    launch_rows_chunk(view, count_, n, spec_->n_cols, cols_, stride_, pad_, bad_, stream_);
+    count_ += n;
+    return;
+  }
+  if (!ring_) {
+    ring_ = (char*)lmn_host_alloc_pinned(SLOTS * SLOT_BYTES);
+    ring_dev_ = (const char*)lmn_host_device_view(ring_, SLOTS * SLOT_BYTES);
+    if (!ring_dev_) throw LmnError(LMN_ERR_INTERNAL, "row sink: the staging ring has no device address");
+  }
+  const uint64_t slot_rows = SLOT_BYTES / row_bytes;
+  for (uint64_t done = 0; done < n;) {
+    const uint64_t m = std::min(slot_rows, n - done);
+    const size_t at = (size_t)next_slot_ * SLOT_BYTES;
+    lmn_event_wait(slot_done_[next_slot_]);   // waits only when every slot of the ring is still in flight
+    memcpy(ring_ + at, host_rows + done * spec_->n_cols, m * row_bytes);
+    launch_rows_chunk((const uint32_t*)(ring_dev_ + at), count_, m, spec_->n_cols, cols_, stride_, pad_, bad_, stream_);
+    lmn_event_record(slot_done_[next_slot_], stream_);
+    next_slot_ = (next_slot_ + 1) % SLOTS;
+    count_ += m;
+    done += m;
+  }
+}
+
+void RowSink::sync() {
+  std::lock_guard<std::mutex> lk(mu_);
+  lmn_set_device(device_);
+  lmn_sync(stream_);
+}
+
+void RowSink::finish(lmn_table* table_out) {
+  std::lock_guard<std::mutex> lk(mu_);
+  if (state_ != FILLING)
+    throw LmnError(LMN_ERR_INVALID_ARGUMENT, "row sink: finished already (lmn_rows_reset starts the next table)");
+  if (count_ == 0) throw LmnError(LMN_ERR_EMPTY_TRACE, "TraceError::EmptyTrace");
+  uint64_t size = 16;   // as lmn_prove derives log_size from n_rows
+  while (size < count_) size <<= 1;
+  lmn_set_device(device_);
+  if (size > count_) launch_rows_chunk(nullptr, count_, size - count_, spec_->n_cols, cols_, stride_, pad_, bad_, stream_);
+  // a sink opened for more rows than came: columns `size` apart, as the proof's phases index them.  stride_ >= 2 * size,
+  // so column c's new place ends before its old one - and every later column's - begins
+  if (size < stride_)
+    for (int c = 1; c < spec_->n_cols; ++c)
+      lmn_d2d(cols_ + (uint64_t)c * size, cols_ + (uint64_t)c * stride_, size * 4, stream_);
+  lmn_d2h(h_bad_, bad_, 4, stream_);
+  lmn_event_record(done_, stream_);
+  lmn_sync(stream_);   // the one wait: every pushed buffer is free, and the verdict is here
+  if (*h_bad_) {
+    state_ = FAILED;
+    throw LmnError(LMN_ERR_INVALID_ARGUMENT, "row sink: a pushed word is not a canonical M31 (>= 2^31-1)");
+  }
+  state_ = FINISHED;
+  {
+    std::lock_guard<std::mutex> g(g_sinks_mu);
+    g_sinks[cols_] = this;
+  }
+  table_out->kind = (uint32_t)spec_->kind;
+  table_out->flags = LMN_TABLE_COLS_ON_DEVICE;
+  table_out->n_rows = count_;
+  table_out->rows = cols_;
+}
+
+void RowSink::reset() {
+  std::lock_guard<std::mutex> lk(mu_);
+  forget();
+  lmn_set_device(device_);
+  lmn_memset(bad_, 0, 4, stream_);   // ordered in front of the next table's chunks
+  count_ = 0;
+  state_ = FILLING;
+}
+
+void rows_sink_attach(const lmn_table& tb, int device, lmn_stream_t proof_stream) {
+  std::lock_guard<std::mutex> lk(g_sinks_mu);
+  auto it = g_sinks.find(tb.rows);
+  if (it == g_sinks.end() || (uint32_t)it->second->spec_->kind != tb.kind || it->second->count_ != tb.n_rows ||
+      it->second->device_ != device)
+    throw LmnError(LMN_ERR_INVALID_ARGUMENT,
+                   "LMN_TABLE_COLS_ON_DEVICE: the table is not what lmn_rows_finish of a live sink on this device filled in");
+  lmn_stream_wait_event(proof_stream, it->second->done_);
+}
+
 }  // namespace lmn

@@ -84,7 +84,9 @@ class LuminairPie:
 
     @staticmethod
     def from_tables(tables) -> "LuminairPie":
-        tts = [t if isinstance(t, TraceTable) else TraceTable.from_rows(t[0], t[1]) for t in tables]
+        # a finished backend.RowSink stands for its table as it is (kind / rows / n_rows): its rows are already in HBM
+        tts = [t if isinstance(t, TraceTable) or hasattr(t, "push_pinned") else TraceTable.from_rows(t[0], t[1])
+               for t in tables]
         mx = 0
         for t in tts:
             size = max(16, 1 << max(t.n_rows - 1, 0).bit_length())
