@@ -598,6 +598,29 @@ int lmn_col_commit(lmn_ctx* ctx, const lmn_col* const* cols, uint32_t n, lmn_tre
 int lmn_tree_root(lmn_ctx* ctx, const lmn_tree* tree, uint8_t root_out[32]);
 uint32_t lmn_tree_log_size(const lmn_tree* tree);
 int lmn_tree_layer_to_cpu(lmn_ctx* ctx, const lmn_tree* tree, uint32_t layer_log, uint8_t* hashes_out); /* 32 * 2^layer_log bytes */
+/* MerkleProver::decommit on a device tree: the walk that decides which nodes an opening needs runs on the host, ONE launch
+ * fetches them from the tree's layers and the column handles, ONE transfer brings them back - the columns and the layers
+ * themselves never leave HBM.  `cols`: the handles the tree was committed from, same order (views are fine).
+ * Queries: n_groups groups; group g holds query_counts[g] positions for columns of size 2^query_logs[g], flat in
+ * `queries`, each group strictly ascending, every position < 2^query_logs[g], query_logs distinct and <= the tree's
+ * log size (a log size at which the tree has no columns is allowed).  Outputs are allocated by the library and released
+ * with lmn_free (an empty one is NULL with count 0): queried values and column witness as words, hash witness as 32-byte
+ * hashes.  Order of all three = MerkleProver::decommit's: layer by layer from the leaves up, node-ascending, a layer's
+ * columns in size-sorted tree order.  Zero groups give the root-only walk's result: three empty outputs.
+ * LMN_ERR_INVALID_ARGUMENT, with a text that names the argument, and all six outputs NULL / 0: columns whose sizes differ
+ * from what the tree was committed from, unsorted or repeated positions, a position out of range, a repeated or too large
+ * query log size, a null pointer where a count is non-zero, an opening of more than 12 MiB.  Context and tree stay usable. */
+int lmn_tree_decommit(lmn_ctx* ctx, const lmn_tree* tree, const lmn_col* const* cols, uint32_t n_cols,
+                      const uint32_t* query_logs, const uint32_t* query_counts, uint32_t n_groups,
+                      const uint32_t* queries,
+                      uint32_t** queried_values, size_t* n_values,
+                      uint8_t** hash_witness, size_t* n_hashes,
+                      uint32_t** column_witness, size_t* n_column_words);
+/* host_out[j * n + i] = column j of `col` at positions[i]; any order, repeats allowed, every position < 2^log_size
+ * (else LMN_ERR_INVALID_ARGUMENT before anything is launched).  One launch, one transfer back, one wait; works on views;
+ * n = 0 returns LMN_OK and writes nothing; at most 12 MiB of positions and of values per call.  What FriProver::decommit
+ * needs for its witness evaluations, and the queried values of a secure column. */
+int lmn_col_gather(lmn_ctx* ctx, const lmn_col* col, const uint32_t* positions, uint32_t n, uint32_t* host_out);
 void lmn_tree_free(lmn_ctx* ctx, lmn_tree* tree);
 int lmn_col_accumulate(lmn_ctx* ctx, lmn_col* dst, const lmn_col* src);     /* AccumulationOps::accumulate: dst += src (same shape) */
 /* QuotientOps::accumulate_quotients (one LDE size; samples and limits as in lmn_op_accumulate_quotients: at most 4

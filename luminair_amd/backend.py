@@ -146,6 +146,7 @@ EXPORTS = ["lmn_abi_version", "lmn_kind_padding_row", "lmn_strerror", "lmn_last_
            "lmn_col_log_size", "lmn_col_device_ptr", "lmn_col_view", "lmn_col_bit_reverse", "lmn_col_precompute_twiddles",
            "lmn_col_interpolate", "lmn_col_evaluate", "lmn_col_evaluate_block", "lmn_col_extend", "lmn_col_eval_at_point",
            "lmn_col_commit", "lmn_tree_root", "lmn_tree_log_size", "lmn_tree_layer_to_cpu", "lmn_tree_free",
+           "lmn_tree_decommit", "lmn_col_gather",
            "lmn_col_accumulate", "lmn_col_accumulate_quotients", "lmn_col_fold_line", "lmn_col_fold_circle_into_line",
            "lmn_col_decompose", "lmn_col_logup", "lmn_col_composition", "lmn_kind_constraints", "lmn_kind_relations", "lmn_ctx_set_shard", "lmn_rccl_unique_id", "lmn_ctx_set_shard_rccl", "lmn_ctx_clear_shard",
            "lmn_rows_open", "lmn_rows_push", "lmn_rows_push_pinned", "lmn_rows_sync", "lmn_rows_finish", "lmn_rows_count",
@@ -256,6 +257,9 @@ class Library:
         lib.lmn_tree_log_size.argtypes = [VP]
         lib.lmn_tree_log_size.restype = U32
         lib.lmn_tree_layer_to_cpu.argtypes = [VP, VP, U32, VP]
+        lib.lmn_tree_decommit.argtypes = [VP, VP, C.POINTER(VP), U32, VP, VP, U32, VP, C.POINTER(VP), C.POINTER(C.c_size_t),
+                                          C.POINTER(VP), C.POINTER(C.c_size_t), C.POINTER(VP), C.POINTER(C.c_size_t)]
+        lib.lmn_col_gather.argtypes = [VP, VP, VP, U32, VP]
         lib.lmn_tree_free.argtypes = [VP, VP]
         lib.lmn_tree_free.restype = None
         lib.lmn_col_accumulate.argtypes = [VP, VP, VP]
@@ -622,6 +626,15 @@ class Col:
         self.ctx._check(self.ctx.lib.lib.lmn_col_fold_circle_into_line(self.ctx.handle, self.handle, src.handle, al))
         return self
 
+    def gather(self, positions) -> np.ndarray:
+        """-> (ncols, n) array: every column at `positions` (any order, repeats allowed).  One launch, one transfer of
+        the gathered words; the columns stay in HBM."""
+        pos = np.ascontiguousarray(positions, dtype=np.uint32).reshape(-1)
+        out = np.empty((self.ncols, len(pos)), dtype=np.uint32)
+        self.ctx._check(self.ctx.lib.lib.lmn_col_gather(self.ctx.handle, self.handle, pos.ctypes.data, len(pos),
+                                                        out.ctypes.data))
+        return out
+
     def decompose(self):
         """FriOps::decompose -> (g, lambda)"""
         out = C.c_void_p()
@@ -650,6 +663,32 @@ class Tree:
         self.ctx._check(self.ctx.lib.lib.lmn_tree_layer_to_cpu(self.ctx.handle, self.handle, layer_log, buf))
         raw = bytes(buf)
         return [raw[32 * i:32 * i + 32] for i in range(1 << layer_log)]
+
+    def decommit(self, cols: Sequence[Col], queries_by_log) -> Tuple[np.ndarray, List[bytes], np.ndarray]:
+        """MerkleProver::decommit on the device tree -> (queried values, hash witness, column witness).  `cols`: the
+        handles the tree was committed from, same order; `queries_by_log`: {log_size: sorted positions}.  Only the
+        opened words and hashes cross the link."""
+        L = self.ctx.lib.lib
+        groups = [(int(lg), np.ascontiguousarray(q, dtype=np.uint32).reshape(-1)) for lg, q in queries_by_log.items()]
+        logs = np.array([lg for lg, _ in groups], dtype=np.uint32)
+        counts = np.array([len(q) for _, q in groups], dtype=np.uint32)
+        flat = np.concatenate([q for _, q in groups]) if groups else np.zeros(0, dtype=np.uint32)
+        arr = (C.c_void_p * max(len(cols), 1))(*[c.handle for c in cols])
+        vals, hashes, wit = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        nv, nh, nw = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        try:
+            self.ctx._check(L.lmn_tree_decommit(self.ctx.handle, self.handle, arr, len(cols), logs.ctypes.data,
+                                                counts.ctypes.data, len(groups), flat.ctypes.data, C.byref(vals),
+                                                C.byref(nv), C.byref(hashes), C.byref(nh), C.byref(wit), C.byref(nw)))
+
+            def words(p, n):
+                return np.frombuffer(C.string_at(p, 4 * n), dtype=np.uint32).copy() if n else np.zeros(0, dtype=np.uint32)
+            raw = C.string_at(hashes, 32 * nh.value) if nh.value else b""
+            return (words(vals, nv.value), [raw[32 * i:32 * i + 32] for i in range(nh.value)], words(wit, nw.value))
+        finally:
+            for p in (vals, hashes, wit):
+                if p.value:
+                    L.lmn_free(p)
 
     def free(self):
         if self.handle:

@@ -261,6 +261,21 @@ struct MerkleRecompute {
 void launch_gather(const uint32_t* arena, const GatherEntry* entries, uint32_t n_entries, const MerkleRecompute* jobs,
                    uint32_t n_jobs, uint32_t* out, lmn_stream_t s);
 
+// ---- decommitment of a level-2 tree (lmn_tree_decommit): the tree's slab and the column handles are separate
+// allocations, so an entry names its source through a table of base pointers instead of an arena offset.  The plan holds
+// n_hashes hash entries, then n_words word entries; out = n_hashes x 8 words, then n_words words:
+//   hash entry t:  out[8t .. 8t+8)        = src[plan[t].src][8 * idx .. 8 * idx + 8)   (src[..] and out 32-byte aligned)
+//   word entry t:  out[8 * n_hashes + t'] = src[plan[t].src][idx],  t' = t - n_hashes
+struct DecommitEntry {
+  uint32_t src;  // index into the pointer table: a tree layer (hash entries) or a column in tree order (word entries)
+  uint32_t idx;  // node
+};
+void launch_tree_decommit(const uint32_t* const* src, const DecommitEntry* plan, uint32_t n_hashes, uint32_t n_words,
+                          uint32_t* out, lmn_stream_t s);
+// out[j * n + i] = cols[j * 2^log_size + positions[i]], j < ncols (lmn_col_gather)
+void launch_col_gather(const uint32_t* cols, uint32_t log_size, uint32_t ncols, const uint32_t* positions, uint32_t n,
+                       uint32_t* out, lmn_stream_t s);
+
 // ---- proof-of-work grind (GrindOps on the device): one launch examines the nonces [base, base + 2^window_log) and
 // lowers *best (device, u64) to the smallest of them that passes, if it is below what *best holds.  A block whose nonces
 // all lie above *best at its start returns at once, so launches queued behind the one that found a nonce cost nothing

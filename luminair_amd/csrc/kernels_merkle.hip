@@ -1144,6 +1144,53 @@ void launch_gather(const uint32_t* arena, const GatherEntry* entries, uint32_t n
 }
 
 // =============================================================================================
+// Decommitment on device handles (kernels.h launch_tree_decommit, launch_col_gather): one lane per plan entry.  A hash is
+// two 16-byte loads and stores by one lane; a column word is read at base[column] + node.  The reads are a few kilobytes
+// scattered over gigabytes, so there is nothing to coalesce: what counts is that the whole plan is ONE launch.
+// =============================================================================================
+constexpr uint32_t DECOMMIT_TPB = 256;
+
+LMN_KERNEL k_tree_decommit(const uint32_t* const* __restrict__ src, const DecommitEntry* __restrict__ plan,
+                           uint32_t n_hashes, uint32_t n_words, uint32_t* __restrict__ out) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_hashes + n_words) return;
+  const DecommitEntry e = plan[t];
+  const uint32_t* p = src[e.src];
+  if (t < n_hashes) {
+    const uint4* h = reinterpret_cast<const uint4*>(p) + (uint64_t)e.idx * 2;
+    uint4* o = reinterpret_cast<uint4*>(out) + (uint64_t)t * 2;
+    const uint4 a = h[0], b = h[1];
+    o[0] = a;
+    o[1] = b;
+  } else {
+    out[(uint64_t)n_hashes * 8 + (t - n_hashes)] = p[e.idx];
+  }
+}
+
+void launch_tree_decommit(const uint32_t* const* src, const DecommitEntry* plan, uint32_t n_hashes, uint32_t n_words,
+                          uint32_t* out, lmn_stream_t s) {
+  const uint32_t n = n_hashes + n_words;
+  if (n == 0) return;
+  LMN_LAUNCH(k_tree_decommit, dim3((n + DECOMMIT_TPB - 1) / DECOMMIT_TPB), dim3(DECOMMIT_TPB), 0, s, src, plan, n_hashes,
+             n_words, out);
+}
+
+LMN_KERNEL k_col_gather(const uint32_t* __restrict__ cols, uint32_t log_size, uint32_t ncols,
+                        const uint32_t* __restrict__ positions, uint32_t n, uint32_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t pos = positions[i];
+  for (uint32_t j = 0; j < ncols; ++j) out[(uint64_t)j * n + i] = cols[((uint64_t)j << log_size) + pos];
+}
+
+void launch_col_gather(const uint32_t* cols, uint32_t log_size, uint32_t ncols, const uint32_t* positions, uint32_t n,
+                       uint32_t* out, lmn_stream_t s) {
+  if (n == 0) return;
+  LMN_LAUNCH(k_col_gather, dim3((n + DECOMMIT_TPB - 1) / DECOMMIT_TPB), dim3(DECOMMIT_TPB), 0, s, cols, log_size, ncols,
+             positions, n, out);
+}
+
+// =============================================================================================
 // Proof-of-work grind (kernels.h launch_pow_grind): one compression per nonce, the smallest passing nonce of the
 // window by a 64-bit atomicMin.  Block b examines [lo, lo + POW_TPB * POW_NPT) with lo = base + b * POW_TPB * POW_NPT,
 // lane t the nonces lo + k * POW_TPB + t in ascending k, and stops at its first hit: the minimum of the window is exact

@@ -17,6 +17,7 @@ struct lmn_tree {
   std::vector<uint32_t*> layers;  // layers[k]: 2^k hashes
   int max_log;
   lmn::Hash32 root;
+  std::vector<uint32_t> ncols_of_log;  // [log]: how many columns of 2^log rows it was committed from (lmn_tree_decommit)
 };
 
 namespace lmn {
@@ -210,6 +211,8 @@ lmn_tree* Context::col_commit(const lmn_col* const* cols, uint32_t n) {
     lmn_d2d(t->layers[l], m.layers[l], (32ull << l), stream_);
     off += 8ull << l;
   }
+  t->ncols_of_log.assign(m.max_log + 1, 0u);
+  for (const ColRef& c : sorted) t->ncols_of_log[c.log]++;
   fetch_root_async(m);
   lmn_sync(stream_);
   m.finish_root();
@@ -228,6 +231,177 @@ void Context::tree_free(lmn_tree* t) {
   lmn_sync(stream_);
   lmn_dev_free(t->slab);
   delete t;
+}
+
+// ---- decommitment on the device (lmn_tree_decommit, lmn_col_gather): the host decides WHICH nodes an opening needs, one
+// launch fetches them from the tree's slab and the column handles, one transfer brings them back.
+constexpr size_t OPENING_MAX_BYTES = 12u << 20;   // of the plan and of the result, each: what the context's staging carries
+
+static std::string u32s(uint64_t v) { return std::to_string(v); }
+
+// MerkleProver::decommit's walk (stwo prover/vcs/prover.rs; the rule oracle/merkle.py restates): layer by layer from the
+// leaves up, the nodes to open are the parents of the layer below's nodes merged with this layer's own queries; a child
+// that is not itself opened goes to the hash witness, the layer's column values at a node to the queried values if the
+// node is a query and to the column witness otherwise.
+struct OpeningPlan {
+  std::vector<DecommitEntry> hashes, values, witness;
+};
+static OpeningPlan plan_opening(int max_log, const std::vector<uint32_t>& ncols_of_log,
+                                const std::vector<const uint32_t*>& queries_of_log, const std::vector<uint32_t>& count_of_log) {
+  OpeningPlan pl;
+  const uint32_t col_src0 = (uint32_t)max_log + 1;   // the pointer table: layers 0 .. max_log, then the columns in tree order
+  uint32_t first_col = 0;                            // tree order = size descending: the columns of a layer are a run
+  std::vector<uint32_t> prev, cur;
+  for (int log = max_log; log >= 0; --log) {
+    const uint32_t ncols = ncols_of_log[log];
+    const uint32_t* q = queries_of_log[log];
+    const size_t nq = count_of_log[log];
+    const bool have_prev = log < max_log;
+    size_t pi = 0, ci = 0;
+    cur.clear();
+    while (pi < prev.size() || ci < nq) {
+      uint32_t node = 0xFFFFFFFFu;
+      if (pi < prev.size()) node = prev[pi] >> 1;
+      if (ci < nq) node = std::min(node, q[ci]);
+      if (have_prev) {
+        for (uint32_t child = 2 * node; child <= 2 * node + 1; ++child) {
+          if (pi < prev.size() && prev[pi] == child)
+            ++pi;
+          else
+            pl.hashes.push_back({(uint32_t)log + 1, child});
+        }
+      }
+      const bool queried = ci < nq && q[ci] == node;
+      if (queried) ++ci;
+      std::vector<DecommitEntry>& dst = queried ? pl.values : pl.witness;
+      for (uint32_t c = 0; c < ncols; ++c) dst.push_back({col_src0 + first_col + c, node});
+      cur.push_back(node);
+    }
+    first_col += ncols;
+    prev.swap(cur);
+  }
+  return pl;
+}
+
+static uint32_t* malloc_words(size_t n) {
+  if (n == 0) return nullptr;
+  uint32_t* p = (uint32_t*)malloc(n * 4);
+  if (!p) throw std::bad_alloc();
+  return p;
+}
+
+void Context::tree_decommit(const lmn_tree* t, const lmn_col* const* cols, uint32_t n_cols, const uint32_t* query_logs,
+                            const uint32_t* query_counts, uint32_t n_groups, const uint32_t* queries, TreeOpening& out) {
+  const char* F = "tree_decommit: ";
+  auto refuse = [&](const std::string& what) { throw LmnError(LMN_ERR_INVALID_ARGUMENT, F + what); };
+  if (n_cols && !cols) refuse("cols is null with n_cols = " + u32s(n_cols));
+  if (n_groups && !query_logs) refuse("query_logs is null with n_groups = " + u32s(n_groups));
+  if (n_groups && !query_counts) refuse("query_counts is null with n_groups = " + u32s(n_groups));
+  // the columns: same sizes, in tree order, as at commit time
+  const int max_log = t->max_log;
+  std::vector<ColRef> sorted;
+  std::vector<uint32_t> have(max_log + 1, 0u);
+  for (uint32_t k = 0; k < n_cols; ++k) {
+    const lmn_col* c = cols[k];
+    if (!c) refuse("cols[" + u32s(k) + "] is null");
+    if ((int)c->log_size > max_log)
+      refuse("cols[" + u32s(k) + "] has log size " + u32s(c->log_size) + ", the tree's is " + u32s(max_log));
+    for (uint32_t j = 0; j < c->ncols; ++j) sorted.push_back({c->d + ((uint64_t)j << c->log_size), (int)c->log_size, false});
+    have[c->log_size] += c->ncols;
+  }
+  for (int log = max_log; log >= 0; --log)
+    if (have[log] != t->ncols_of_log[log])
+      refuse("cols holds " + u32s(have[log]) + " columns of log size " + u32s(log) + ", the tree was committed from " +
+             u32s(t->ncols_of_log[log]));
+  std::stable_sort(sorted.begin(), sorted.end(), [](auto& a, auto& b) { return a.log > b.log; });
+  // the queries
+  std::vector<const uint32_t*> queries_of_log(max_log + 1, nullptr);
+  std::vector<uint32_t> count_of_log(max_log + 1, 0u);
+  std::vector<bool> seen(max_log + 1, false);
+  uint64_t at = 0;
+  for (uint32_t g = 0; g < n_groups; ++g) {
+    const uint32_t log = query_logs[g], n = query_counts[g];
+    if ((int)log > max_log) refuse("query_logs[" + u32s(g) + "] = " + u32s(log) + " exceeds the tree's log size " + u32s(max_log));
+    if (seen[log]) refuse("query_logs[" + u32s(g) + "] repeats log size " + u32s(log));
+    seen[log] = true;
+    if (n && !queries) refuse("queries is null with query_counts[" + u32s(g) + "] = " + u32s(n));
+    const uint32_t* q = queries + at;
+    for (uint32_t i = 0; i < n; ++i) {
+      if (q[i] >> log)
+        refuse("queries: position " + u32s(q[i]) + " of group " + u32s(g) + " is out of range for log size " + u32s(log));
+      if (i && q[i] <= q[i - 1])
+        refuse("queries: group " + u32s(g) + " is not strictly ascending at index " + u32s(i) + " (" + u32s(q[i - 1]) +
+               " then " + u32s(q[i]) + ")");
+    }
+    queries_of_log[log] = q;
+    count_of_log[log] = n;
+    at += n;
+  }
+  const OpeningPlan pl = plan_opening(max_log, t->ncols_of_log, queries_of_log, count_of_log);
+  const size_t nh = pl.hashes.size(), nv = pl.values.size(), nw = pl.witness.size();
+  if (nh + nv + nw == 0) return;
+  const size_t n_ptrs = (size_t)max_log + 1 + sorted.size();
+  const size_t plan_bytes = n_ptrs * sizeof(void*) + (nh + nv + nw) * sizeof(DecommitEntry);
+  const size_t out_bytes = nh * 32 + (nv + nw) * 4;
+  if (plan_bytes > OPENING_MAX_BYTES || out_bytes > OPENING_MAX_BYTES)
+    refuse("queries: the opening (" + u32s(out_bytes) + " bytes, a plan of " + u32s(plan_bytes) + ") exceeds the " +
+           u32s(OPENING_MAX_BYTES) + " bytes one call carries");
+  arena_.reserve(std::max<size_t>(8u << 20, plan_bytes + out_bytes + (1u << 20)));
+  begin_op();
+  // pointer table and plan: built in page-locked staging, ONE transfer
+  char* h_plan = (char*)pin_alloc(plan_bytes);
+  const uint32_t** h_ptrs = (const uint32_t**)h_plan;
+  for (int l = 0; l <= max_log; ++l) h_ptrs[l] = t->layers[l];
+  for (size_t c = 0; c < sorted.size(); ++c) h_ptrs[max_log + 1 + c] = sorted[c].ptr;
+  DecommitEntry* h_e = (DecommitEntry*)(h_plan + n_ptrs * sizeof(void*));
+  if (nh) memcpy(h_e, pl.hashes.data(), nh * sizeof(DecommitEntry));
+  if (nv) memcpy(h_e + nh, pl.values.data(), nv * sizeof(DecommitEntry));
+  if (nw) memcpy(h_e + nh + nv, pl.witness.data(), nw * sizeof(DecommitEntry));
+  char* d_plan = (char*)arena_.alloc_bytes(plan_bytes);
+  uint32_t* d_out = (uint32_t*)arena_.alloc_bytes(out_bytes);
+  lmn_h2d(d_plan, h_plan, plan_bytes, stream_);
+  launch_tree_decommit((const uint32_t* const*)d_plan, (const DecommitEntry*)(d_plan + n_ptrs * sizeof(void*)), (uint32_t)nh,
+                       (uint32_t)(nv + nw), d_out, stream_);
+  const uint32_t* got = (const uint32_t*)stage_download(d_out, out_bytes);
+  // the caller's buffers are allocated under the transfer
+  TreeOpening o;
+  try {
+    o.hash_witness = (uint8_t*)malloc_words(nh * 8);
+    o.queried_values = malloc_words(nv);
+    o.column_witness = malloc_words(nw);
+  } catch (...) {
+    lmn_sync(stream_);
+    free(o.hash_witness);
+    free(o.queried_values);
+    throw;
+  }
+  lmn_sync(stream_);
+  if (nh) memcpy(o.hash_witness, got, nh * 32);
+  if (nv) memcpy(o.queried_values, got + nh * 8, nv * 4);
+  if (nw) memcpy(o.column_witness, got + nh * 8 + nv, nw * 4);
+  o.n_hashes = nh;
+  o.n_values = nv;
+  o.n_column_words = nw;
+  out = o;
+}
+
+void Context::col_gather(const lmn_col* c, const uint32_t* positions, uint32_t n, uint32_t* host_out) {
+  for (uint32_t i = 0; i < n; ++i)
+    if (positions[i] >> c->log_size)
+      throw LmnError(LMN_ERR_INVALID_ARGUMENT, "col_gather: positions[" + u32s(i) + "] = " + u32s(positions[i]) +
+                                                   " is out of range for columns of log size " + u32s(c->log_size));
+  const size_t in_bytes = (size_t)n * 4, out_bytes = (size_t)n * c->ncols * 4;
+  if (in_bytes > OPENING_MAX_BYTES || out_bytes > OPENING_MAX_BYTES)
+    throw LmnError(LMN_ERR_INVALID_ARGUMENT, "col_gather: n = " + u32s(n) + " positions of " + u32s(c->ncols) +
+                                                 " columns exceed the " + u32s(OPENING_MAX_BYTES) + " bytes one call carries");
+  arena_.reserve(std::max<size_t>(8u << 20, in_bytes + out_bytes + (1u << 20)));
+  begin_op();
+  const uint32_t* d_pos = (const uint32_t*)stage_upload(positions, in_bytes);
+  uint32_t* d_out = (uint32_t*)arena_.alloc_bytes(out_bytes);
+  launch_col_gather(c->d, c->log_size, c->ncols, d_pos, n, d_out, stream_);
+  const void* got = stage_download(d_out, out_bytes);
+  lmn_sync(stream_);
+  memcpy(host_out, got, out_bytes);
 }
 
 void Context::col_accumulate(lmn_col* dst, const lmn_col* src) {
@@ -529,6 +703,41 @@ uint32_t lmn_tree_log_size(const lmn_tree* tree) { return tree ? (uint32_t)tree-
 int lmn_tree_layer_to_cpu(lmn_ctx* ctx, const lmn_tree* tree, uint32_t layer_log, uint8_t* hashes_out) {
   if (!ctx || !tree || !hashes_out) return LMN_ERR_INVALID_ARGUMENT;
   return guard2(ctx, [&] { ctx->impl->tree_layer_to_cpu(tree, layer_log, hashes_out); });
+}
+int lmn_tree_decommit(lmn_ctx* ctx, const lmn_tree* tree, const lmn_col* const* cols, uint32_t n_cols,
+                      const uint32_t* query_logs, const uint32_t* query_counts, uint32_t n_groups, const uint32_t* queries,
+                      uint32_t** queried_values, size_t* n_values, uint8_t** hash_witness, size_t* n_hashes,
+                      uint32_t** column_witness, size_t* n_column_words) {
+  if (queried_values) *queried_values = nullptr;
+  if (hash_witness) *hash_witness = nullptr;
+  if (column_witness) *column_witness = nullptr;
+  if (n_values) *n_values = 0;
+  if (n_hashes) *n_hashes = 0;
+  if (n_column_words) *n_column_words = 0;
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  return guard2(ctx, [&] {
+    if (!tree) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "tree_decommit: tree is null");
+    if (!queried_values || !n_values || !hash_witness || !n_hashes || !column_witness || !n_column_words)
+      throw LmnError(LMN_ERR_INVALID_ARGUMENT, "tree_decommit: an output pointer is null");
+    lmn::TreeOpening o;
+    ctx->impl->tree_decommit(tree, cols, n_cols, query_logs, query_counts, n_groups, queries, o);
+    *queried_values = o.queried_values;
+    *n_values = o.n_values;
+    *hash_witness = o.hash_witness;
+    *n_hashes = o.n_hashes;
+    *column_witness = o.column_witness;
+    *n_column_words = o.n_column_words;
+  });
+}
+int lmn_col_gather(lmn_ctx* ctx, const lmn_col* col, const uint32_t* positions, uint32_t n, uint32_t* host_out) {
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  return guard2(ctx, [&] {
+    if (!col) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "col_gather: col is null");
+    if (n == 0) return;
+    if (!positions) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "col_gather: positions is null with n = " + std::to_string(n));
+    if (!host_out) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "col_gather: host_out is null with n = " + std::to_string(n));
+    ctx->impl->col_gather(col, positions, n, host_out);
+  });
 }
 void lmn_tree_free(lmn_ctx* ctx, lmn_tree* tree) {
   if (ctx && tree) guard2(ctx, [&] { ctx->impl->tree_free(tree); });

@@ -155,6 +155,16 @@ struct DevTree {
   DevMerkle merkle;
 };
 
+// what lmn_tree_decommit hands to its caller: three buffers from malloc (released with lmn_free), null where empty
+struct TreeOpening {
+  uint32_t* queried_values = nullptr;
+  size_t n_values = 0;
+  uint8_t* hash_witness = nullptr;   // n_hashes x 32 bytes
+  size_t n_hashes = 0;
+  uint32_t* column_witness = nullptr;
+  size_t n_column_words = 0;
+};
+
 // the caller-facing limits of one accumulate_quotients call (level2.cpp): LMN_ERR_INVALID_ARGUMENT past them
 void check_quotient_limits(const uint32_t* sample_point, uint32_t nsamples);
 
@@ -258,6 +268,9 @@ class Context {
   lmn_tree* col_commit(const lmn_col* const* cols, uint32_t n);
   void tree_layer_to_cpu(const lmn_tree* t, uint32_t layer_log, uint8_t* out);
   void tree_free(lmn_tree* t);
+  void tree_decommit(const lmn_tree* t, const lmn_col* const* cols, uint32_t n_cols, const uint32_t* query_logs,
+                     const uint32_t* query_counts, uint32_t n_groups, const uint32_t* queries, TreeOpening& out);
+  void col_gather(const lmn_col* c, const uint32_t* positions, uint32_t n, uint32_t* host_out);
   void col_accumulate(lmn_col* dst, const lmn_col* src);
   lmn_col* col_accumulate_quotients(const lmn_col* const* cols, uint32_t n, const uint32_t* sample_col,
                                     const uint32_t* sample_point, const uint32_t* sample_values, uint32_t nsamples,
