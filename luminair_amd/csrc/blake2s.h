@@ -332,7 +332,11 @@ LMN_HD void b2_compress_fresh_nz(uint32_t out[8], const uint32_t m[16], uint32_t
     out[7] = 0x5BE0CD19u ^ v7 ^ v15;
   }
 #else
-  b2_compress_fresh<LO, HI>(out, m, t0);   // (host / emulation: the caller's zero words are read)
+  // host / emulation: the device form's contract - words NZ..15 count as zero whatever the caller left there - so that a
+  // wrong NZ shows on the emulation build as it would on the GPU
+  uint32_t mz[16];
+  for (int k = 0; k < 16; ++k) mz[k] = k < NZ ? m[k] : 0u;
+  b2_compress_fresh<LO, HI>(out, mz, t0);
 #endif
 }
 

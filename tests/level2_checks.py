@@ -430,8 +430,8 @@ def check_device_handle_ops(ctx, log=7):
     cols_host = [c for c in small.to_cpu()] + [c for c in lde.to_cpu()]
     ref = MerkleTree(cols_host)
     assert tree.root() == ref.root() and tree.log_size == log + 1
-    for lg in (0, 1, log + 1):
-        assert tree.layer(lg) == [bytes(x) for x in ref.layers[lg]]
+    for lg in range(log + 2):
+        assert tree.layer(lg) == [bytes(x) for x in ref.layers[lg]], lg
     tree.free()
     small.free()
 
