@@ -476,6 +476,78 @@ uint64_t lmn_rows_count(const lmn_rows* rows);
 int lmn_rows_reset(lmn_rows* rows);                        /* same capacity, zero rows: the next proof's table */
 void lmn_rows_close(lmn_rows* rows);
 
+/* ---- lmn_trace_check: which rows and which logup tuples break a trace.  lmn_prove answers a bad trace once, at the end of
+ * a whole proof, with LMN_ERR_CONSTRAINTS - no table, no row, no constraint - and a trace whose logup relations do not
+ * balance is proved all the same (only lmn_verify says LMN_ERR_INVALID_LOGUP).  This call is the prover-side counterpart of
+ * lmn_verify_diagnose: it commits, transforms and draws nothing; it reads the tables where they lie and reports.
+ *
+ * The contract (exact and deterministic; tests compare for equality with the oracle):
+ *  - Input: `tables` in exactly the forms lmn_prove takes (host rows, LMN_TABLE_ROWS_ON_DEVICE, LMN_TABLE_COLS_ON_DEVICE of
+ *    a finished sink), validated by lmn_prove's own setup rules (supported kind with a claim slot, ascending kinds, at most
+ *    2^26 rows, a LUT for each lookup table, a lookup table whose padded size is the LUT's).  What lmn_prove's setup refuses
+ *    is refused here with the same code, and the text (lmn_last_error) names the table: "table 2 (kind 4): ...".
+ *  - Scope: only the n_rows real rows.  The padding rows are the library's own and carry multiplicity 0.
+ *  - Non-canonical words: a word >= 2^31 - 1.  `n_noncanonical` counts them all; nc_table / nc_row / nc_column name the
+ *    smallest (table, row, column).  A row that holds one is left out of the two checks below.
+ *  - Local constraints: for every table and every local kernel slot - the component's local constraints in `evaluate`
+ *    order, the first lmn_kind_constraints(kind) - lmn_kind_relations(kind) slots in lmn_kind_constraint_layout's indexing;
+ *    Mul's slot 2 is identically zero - the number of real rows on which the slot is non-zero and the smallest such row.
+ *    The constraint-form bits (LMN_PV_*_NEG, LMN_PV_*_SLOT(S)) do not change which rows violate: no flags.  Evaluated in
+ *    M31 on the row's own words (every constraint is row-local: the next_* values are columns of the row).
+ *    `n_constraint_slots` (table, slot) pairs are violated; the first LMN_TRACE_REPORT_MAX of them, sorted by (table, slot),
+ *    are listed, `constraints_truncated` says whether that was all.
+ *  - Relation balance: every relation entry of every row whose multiplicity word is non-zero contributes +mult (-mult where
+ *    the component's relation is subtracted: the lookup tables) to the tuple (element set, val, id) - element sets as in
+ *    LMN_N_ELEMS below (0 NodeElements, 1 RangeCheck, 2 Sin, 3 Exp2, 4 Log2), id = 0 for width-1 relations, lookup tables
+ *    take val and id from the LUT columns of `settings`, the range check takes val from the row index.  A tuple is
+ *    unbalanced when its net sum is non-zero mod P.  `n_unbalanced` is their exact number; up to LMN_TRACE_REPORT_MAX are
+ *    listed with the net as an M31 word and the smallest (table, slot, row) that mentions the tuple (slot = the relation's
+ *    kernel slot, local slots first).  With at most LMN_TRACE_REPORT_MAX unbalanced tuples all are listed, sorted by (set, id,
+ *    val); with more, `tuples_truncated` is set and every listed entry is still a true one.  An exact multiset check - no
+ *    randomness, no soundness parameter.
+ *  - Returns LMN_OK when the check ran, whatever it found (as lmn_verify_diagnose does); report->ok = 1 iff all three findings
+ *    are empty; report->summary is one line of text.  LMN_ERR_OUT_OF_MEMORY when a tuple table cannot be allocated.
+ *  - Takes the context's lock, runs on its stream, frees all its scratch before it returns and leaves the context usable
+ *    after any outcome.  No collective: works on a sharded context (for the table forms lmn_prove accepts there) and in
+ *    libluminair_hip_batch.so's solo path. */
+#define LMN_TRACE_REPORT_MAX 64
+struct lmn_trace_constraint {
+  uint32_t table;      /* index into `tables` */
+  uint32_t kind;       /* LMN_KIND_* of that table */
+  uint32_t slot;       /* local kernel slot */
+  uint32_t reserved;
+  uint64_t count;      /* real rows on which the slot is non-zero */
+  uint64_t first_row;  /* the smallest of them */
+};
+typedef struct lmn_trace_constraint lmn_trace_constraint;
+struct lmn_trace_tuple {
+  uint32_t set;          /* element set 0..4 */
+  uint32_t val, id;      /* the tuple; id = 0 for width-1 relations */
+  uint32_t net;          /* net multiplicity, an M31 word != 0 */
+  uint32_t first_table;  /* smallest (table, slot, row) that mentions the tuple */
+  uint32_t first_slot;
+  uint64_t first_row;
+};
+typedef struct lmn_trace_tuple lmn_trace_tuple;
+struct lmn_trace_report {
+  uint32_t ok;                     /* 1 iff no non-canonical word, no violated slot, no unbalanced tuple */
+  uint32_t n_constraints;          /* entries of `constraints` */
+  uint32_t n_constraint_slots;     /* violated (table, slot) pairs in all */
+  uint32_t constraints_truncated;
+  uint32_t n_tuples;               /* entries of `tuples` */
+  uint32_t tuples_truncated;
+  uint64_t n_unbalanced;           /* unbalanced tuples in all */
+  uint64_t n_noncanonical;         /* words >= 2^31 - 1 in all */
+  uint32_t nc_table, nc_column;    /* the smallest (table, row, column) holding one (n_noncanonical != 0) */
+  uint64_t nc_row;
+  lmn_trace_constraint constraints[LMN_TRACE_REPORT_MAX];
+  lmn_trace_tuple tuples[LMN_TRACE_REPORT_MAX];
+  char summary[256];
+};
+typedef struct lmn_trace_report lmn_trace_report;
+int lmn_trace_check(lmn_ctx* ctx, const lmn_table* tables, size_t n_tables, const lmn_settings* settings,
+                    lmn_trace_report* report);
+
 /* ---- Single-proof sharding over the GPUs of one node (BASELINE.json configs 4 and 5).
  * One context per GPU, world = 1, 2, 4 or 8 ranks.  Every rank calls lmn_prove with the SAME tables and gets the
  * SAME proof bytes as an unsharded context would produce.  What is split: every rank evaluates only its aligned

@@ -7,9 +7,9 @@ gfx950 behind the C ABI of `include/luminair_hip.h`; there is no CPU fallback.
 """
 from .pie import (CircuitSettings, ExecutionResources, Lookup, LookupLayout, LuminairError, LuminairPie, LuminairProof,
                   Metadata, RangeCheckLookup, TraceTable, TraceTableKind)
-from .backend import RowSink
+from .backend import RowSink, TraceReport
 from .graph import DeviceGraph
-from .prover import Prover, ProverPool, prove, verify
+from .prover import Prover, ProverPool, check_trace, prove, verify
 
 __all__ = ["Lookup", "LookupLayout", "RangeCheckLookup", "CircuitSettings", "ExecutionResources", "LuminairError", "LuminairPie", "LuminairProof", "Metadata",
-           "TraceTable", "TraceTableKind", "Prover", "ProverPool", "prove", "verify", "DeviceGraph", "RowSink"]
+           "TraceTable", "TraceTableKind", "Prover", "ProverPool", "prove", "verify", "DeviceGraph", "RowSink", "TraceReport", "check_trace"]

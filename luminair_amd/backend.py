@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -133,6 +134,57 @@ class LmnVerifyReport(C.Structure):
                 ("first_failure", C.c_char * 128)]
 
 
+TRACE_REPORT_MAX = 64   # LMN_TRACE_REPORT_MAX
+ELEM_SET_NAMES = ["NodeElements", "RangeCheck", "Sin", "Exp2", "Log2"]
+
+
+class LmnTraceConstraint(C.Structure):
+    _fields_ = [("table", C.c_uint32), ("kind", C.c_uint32), ("slot", C.c_uint32), ("reserved", C.c_uint32),
+                ("count", C.c_uint64), ("first_row", C.c_uint64)]
+
+
+class LmnTraceTuple(C.Structure):
+    _fields_ = [("set", C.c_uint32), ("val", C.c_uint32), ("id", C.c_uint32), ("net", C.c_uint32),
+                ("first_table", C.c_uint32), ("first_slot", C.c_uint32), ("first_row", C.c_uint64)]
+
+
+class LmnTraceReport(C.Structure):
+    """`lmn_trace_report`: what lmn_trace_check found in a trace."""
+    _fields_ = [("ok", C.c_uint32), ("n_constraints", C.c_uint32), ("n_constraint_slots", C.c_uint32),
+                ("constraints_truncated", C.c_uint32), ("n_tuples", C.c_uint32), ("tuples_truncated", C.c_uint32),
+                ("n_unbalanced", C.c_uint64), ("n_noncanonical", C.c_uint64), ("nc_table", C.c_uint32),
+                ("nc_column", C.c_uint32), ("nc_row", C.c_uint64), ("constraints", LmnTraceConstraint * TRACE_REPORT_MAX),
+                ("tuples", LmnTraceTuple * TRACE_REPORT_MAX), ("summary", C.c_char * 256)]
+
+
+@dataclass
+class TraceReport:
+    """`Context.check_trace`'s answer.  constraints: [(table, kind, slot, count, first_row)] sorted by (table, slot) -
+    local kernel slots on which real rows are non-zero; tuples: [(set, val, id, net, first_table, first_slot, first_row)]
+    sorted by (set, id, val) - logup tuples whose net multiplicity (an M31 word) is not zero, with the smallest
+    (table, slot, row) that mentions each; first_noncanonical: (table, row, column) or None."""
+    ok: bool
+    summary: str
+    n_noncanonical: int
+    first_noncanonical: Optional[Tuple[int, int, int]]
+    n_constraint_slots: int
+    constraints: List[Tuple[int, int, int, int, int]]
+    constraints_truncated: bool
+    n_unbalanced: int
+    tuples: List[Tuple[int, int, int, int, int, int, int]]
+    tuples_truncated: bool
+
+    @staticmethod
+    def from_c(r: "LmnTraceReport") -> "TraceReport":
+        cons = [(int(c.table), int(c.kind), int(c.slot), int(c.count), int(c.first_row))
+                for c in r.constraints[:r.n_constraints]]
+        tup = [(int(t.set), int(t.val), int(t.id), int(t.net), int(t.first_table), int(t.first_slot), int(t.first_row))
+               for t in r.tuples[:r.n_tuples]]
+        nc = (int(r.nc_table), int(r.nc_row), int(r.nc_column)) if r.n_noncanonical else None
+        return TraceReport(bool(r.ok), r.summary.decode(), int(r.n_noncanonical), nc, int(r.n_constraint_slots), cons,
+                           bool(r.constraints_truncated), int(r.n_unbalanced), tup, bool(r.tuples_truncated))
+
+
 API_VERSION = 6   # LMN_API_VERSION of include/luminair_hip.h
 
 EXPORTS = ["lmn_abi_version", "lmn_kind_padding_row", "lmn_strerror", "lmn_last_error", "lmn_default_config", "lmn_kind_columns", "lmn_ctx_create",
@@ -150,7 +202,7 @@ EXPORTS = ["lmn_abi_version", "lmn_kind_padding_row", "lmn_strerror", "lmn_last_
            "lmn_col_accumulate", "lmn_col_accumulate_quotients", "lmn_col_fold_line", "lmn_col_fold_circle_into_line",
            "lmn_col_decompose", "lmn_col_logup", "lmn_col_composition", "lmn_kind_constraints", "lmn_kind_relations", "lmn_ctx_set_shard", "lmn_rccl_unique_id", "lmn_ctx_set_shard_rccl", "lmn_ctx_clear_shard",
            "lmn_rows_open", "lmn_rows_push", "lmn_rows_push_pinned", "lmn_rows_sync", "lmn_rows_finish", "lmn_rows_count",
-           "lmn_rows_reset", "lmn_rows_close"]
+           "lmn_rows_reset", "lmn_rows_close", "lmn_trace_check"]
 
 
 class LuminairBackendError(RuntimeError):
@@ -287,6 +339,8 @@ class Library:
         lib.lmn_rows_reset.argtypes = [C.c_void_p]
         lib.lmn_rows_close.argtypes = [C.c_void_p]
         lib.lmn_rows_close.restype = None
+        lib.lmn_trace_check.argtypes = [C.c_void_p, C.POINTER(LmnTable), C.c_size_t, C.POINTER(LmnSettings),
+                                        C.POINTER(LmnTraceReport)]
         lib.lmn_trace_elementwise_v.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(LmnView), C.c_void_p,
                                                 C.POINTER(LmnView), C.c_uint64, C.POINTER(LmnNodeInfo), C.c_void_p,
                                                 C.c_uint64, C.c_void_p]
@@ -1022,6 +1076,15 @@ class Context:
         data = C.string_at(out, out_len.value)
         self.lib.lib.lmn_free(out)
         return data
+
+    def check_trace(self, tables: Sequence[Tuple[int, object, int]], luts=None) -> TraceReport:
+        """`lmn_trace_check` on what `prove_tables` takes: which rows break a local constraint, which logup tuples do not
+        balance, which words are no canonical M31.  Nothing is committed or drawn; raises only for what `prove_tables`
+        itself refuses before it starts (the text names the table)."""
+        arr, n, settings, _keep = self._marshal_tables(tables, luts)
+        rep = LmnTraceReport()
+        self._check(self.lib.lib.lmn_trace_check(self.handle, arr, n, C.byref(settings), C.byref(rep)))
+        return TraceReport.from_c(rep)
 
     def prove_submit(self, tables: Sequence[Tuple[int, object, int]], luts=None):
         """`lmn_prove_submit`: start the proof on the context's own worker thread and return; collect it with

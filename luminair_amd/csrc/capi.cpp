@@ -483,6 +483,14 @@ int lmn_trace_max_reduce(lmn_ctx* ctx, const int32_t* input_dev, uint64_t front,
   return guard(ctx, [&] { ctx->impl->trace_reduce(true, input_dev, front, dim, back, *info, rows_dev, row_offset, out_dev); });
 }
 
+int lmn_trace_check(lmn_ctx* ctx, const lmn_table* tables, size_t n_tables, const lmn_settings* settings,
+                    lmn_trace_report* report) {
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  if (!report) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_check: null report");
+  memset(report, 0, sizeof *report);
+  return guard(ctx, [&] { ctx->impl->trace_check(tables, n_tables, settings, *report); });
+}
+
 namespace lmn {
 void rccl_unique_id(uint8_t* out);
 }

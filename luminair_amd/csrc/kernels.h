@@ -326,6 +326,39 @@ void launch_trace_lut(const int32_t* input, const TraceView& view, uint64_t n, c
 void launch_trace_reduce(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back,
                          const TraceNode& nd, uint32_t* rows, int32_t* out, lmn_stream_t s);
 
+// ---- lmn_trace_check (trace_gen.cpp): which rows break a local constraint, which logup tuples do not balance.
+// One open-addressing table per relation element set: entry i = {keys[i] = val | id << 31 (TC_EMPTY: free), sums[i] = the
+// sum of the signed multiplicity words (u64: below 2^26 rows x 7 relations x 2^31 it cannot overflow), firsts[i] = the
+// smallest mention, table << 40 | slot << 32 | row}.  mask + 1 = a power of two of at least twice the entries the set can get.
+constexpr unsigned long long TC_EMPTY = ~0ull;
+constexpr int TC_MAX_SLOTS = 16;   // local slots per table in the counters (at most 9 are used)
+struct TcSet {
+  unsigned long long *keys, *sums, *firsts;   // null: no table of the pie uses the set
+  uint64_t mask;
+};
+struct TcOut {
+  uint32_t* slot_count;             // [table * TC_MAX_SLOTS + slot]: real rows on which the slot is non-zero
+  unsigned long long* slot_first;   // ... and the smallest of them (TC_EMPTY: none)
+  unsigned long long* noncanon;     // [0] words >= P in all, [1] the smallest table << 40 | row << 8 | column
+  const TcSet* sets;                // device: the tuple table of each of the 5 element sets (read through the scalar cache)
+};
+struct TcTable {
+  const uint32_t* data;        // row-major: n_rows x n_cols words; column-major: n_cols columns `stride` words apart
+  uint64_t n_rows, stride;
+  uint32_t table;              // index in the caller's table list
+  const uint32_t *pre0, *pre1; // lookup tables: the LUT columns val / id come from (range check: null, val = the row index)
+  int n_rel, slot0;            // relations; kernel slot of the first (= the component's number of local slots)
+  int rel_mult[7], rel_val[7], rel_id[7], rel_set[7], rel_neg[7], rel_pre[7];   // as ComponentSpec's
+};
+struct TcFound {   // one unbalanced tuple, as k_trace_check_collect compacts it
+  uint64_t key, first;
+  uint32_t set, net;
+};
+void launch_trace_check(int kind, bool cols_layout, const TcTable& tb, const TcOut& out, lmn_stream_t s);
+// counts the entries of `set` whose sum is non-zero mod P into *n_unbalanced and writes the first `cap` of them to `found`
+void launch_trace_check_collect(const TcSet& set, uint32_t set_index, unsigned long long* n_unbalanced, TcFound* found,
+                                uint32_t cap, lmn_stream_t s);
+
 // ---- a6: logup
 constexpr int LOGUP_MAX_REL = 7;
 struct LogupArgs {

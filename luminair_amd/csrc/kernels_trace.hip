@@ -446,6 +446,242 @@ void launch_trace_lut(const int32_t* input, const TraceView& view, uint64_t n, c
 }
 
 // =============================================================================================
+// lmn_trace_check: the rows that break a local constraint, the logup tuples that do not balance
+// =============================================================================================
+LMN_HD constexpr int tc_ncols(int kind) {
+  return kind == 0 ? 15 : kind == 1 ? 16 : kind == 2 ? 13 : kind == 3 ? 12 : kind == 5 ? 14 : kind == 6 ? 15 : kind == 7 ? 13
+       : kind == 8 ? 16 : kind == 9 ? 12 : kind == 11 ? 12 : kind == 13 ? 22 : kind == 15 ? 7 : kind == 16 ? 11 : 1;
+}
+LMN_HD constexpr int tc_nlocal(int kind) {
+  return kind == 0 ? 6 : kind == 1 ? 7 : kind == 2 ? 5 : kind == 3 ? 4 : kind == 5 ? 7 : kind == 6 ? 9 : kind == 7 ? 5
+       : kind == 8 ? 6 : kind == 9 ? 4 : kind == 11 ? 4 : kind == 13 ? 9 : kind == 15 ? 3 : kind == 16 ? 4 : 0;
+}
+LMN_HD uint32_t tc_bool(uint32_t b) { return m_mul(b, m_sub(b, 1u)); }
+// not_last * (next - cur) per id column, then not_last * (next_idx - idx - 1): the transition constraints every component
+// ends its local list with.  c[first .. first + n] = the n id columns and idx, c[first + n + 2 ..] their next_* columns
+// (is_last sits between them)
+template <int N>
+LMN_D void tc_transition(const uint32_t* c, int first, uint32_t* v) {
+  const uint32_t not_last = m_sub(1u, c[first + N + 1]);
+#pragma unroll
+  for (int k = 0; k < N; ++k) v[k] = m_mul(not_last, m_sub(c[first + N + 2 + k], c[first + k]));
+  v[N] = m_mul(not_last, m_sub(m_sub(c[first + 2 * N + 2], c[first + N]), 1u));
+}
+// The component's local constraints on one row, in `evaluate` order (crates/air/src/components/*/component.rs; the host's
+// restatement at a point is components.cpp local_constraints, the composition's is k_composition): v[0 .. tc_nlocal(KIND))
+template <int KIND>
+LMN_D void tc_local(const uint32_t* c, uint32_t* v) {
+  if constexpr (KIND == 0 || KIND == 1 || KIND == 8) {   // node, lhs_id, rhs_id, idx, is_last, next_*, lhs, rhs, out, ...
+    v[0] = tc_bool(c[4]);
+    if constexpr (KIND == 0) {
+      v[1] = m_sub(c[11], m_add(c[9], c[10]));
+      tc_transition<3>(c, 0, v + 2);
+    } else if constexpr (KIND == 1) {
+      v[1] = m_sub(m_mul(c[9], c[10]), m_add(m_mul(c[11], 4096u), c[12]));
+      v[2] = 0u;   // eval_fixed_mul's second slot: identically zero
+      tc_transition<3>(c, 0, v + 3);
+    } else {       // Rem: lhs = rhs * quotient + rem (rem at 11, quotient at 12)
+      v[1] = m_sub(c[9], m_add(m_mul(c[10], c[12]), c[11]));
+      tc_transition<3>(c, 0, v + 2);
+    }
+  } else if constexpr (KIND == 2 || KIND == 7) {   // node, input_id, idx, is_last, next_*, input, out, rem, scale
+    v[0] = tc_bool(c[3]);
+    v[1] = KIND == 2 ? m_sub(m_sqr(c[10]), m_add(m_mul(c[7], c[8]), c[9]))
+                     : m_sub(m_mul(c[7], c[10]), m_add(m_sqr(c[8]), c[9]));
+    tc_transition<2>(c, 0, v + 2);
+  } else if constexpr (KIND == 15) {               // node, idx, is_last, next_node, next_idx, val, multiplicity
+    v[0] = tc_bool(c[2]);
+    tc_transition<1>(c, 0, v + 1);
+  } else if constexpr (KIND == 5) {                // ..., input, out, acc, next_acc, is_last_step
+    v[0] = tc_bool(c[3]);
+    v[1] = tc_bool(c[11]);
+    v[2] = m_sub(c[10], m_add(c[9], c[7]));
+    v[3] = m_mul(m_sub(c[8], c[10]), c[11]);
+    tc_transition<2>(c, 0, v + 4);
+  } else if constexpr (KIND == 6) {                // ..., input, out, max, next_max, is_last_step, is_max
+    v[0] = tc_bool(c[3]);
+    v[1] = tc_bool(c[11]);
+    v[2] = tc_bool(c[12]);
+    v[3] = m_mul(c[12], m_sub(c[10], c[7]));
+    v[4] = m_mul(m_sub(1u, c[12]), m_sub(c[10], c[9]));
+    v[5] = m_mul(m_sub(c[8], c[10]), c[11]);
+    tc_transition<2>(c, 0, v + 6);
+  } else if constexpr (KIND == 13) {               // less_than/component.rs:48-185
+    const uint32_t borrow = c[13];
+    v[0] = tc_bool(c[4]);
+    v[1] = tc_bool(borrow);
+    v[2] = m_sub(c[11], m_mul(m_sub(1u, borrow), 4096u));
+    v[3] = m_sub(m_add(c[9], c[12]), c[10]);       // - borrow * (2^31 - 1), which is 0 in M31
+    v[4] = m_sub(c[12], m_add(m_add(m_mul(c[17], 1u << 24), m_mul(c[16], 1u << 16)), m_add(m_mul(c[15], 1u << 8), c[14])));
+    tc_transition<3>(c, 0, v + 5);
+  } else if constexpr (tc_nlocal(KIND) == 4) {     // Contiguous, Sin, Exp2, Log2: boolean + transitions only
+    v[0] = tc_bool(c[3]);
+    tc_transition<2>(c, 0, v + 1);
+  }
+}
+
+// add `w` to the tuple `key` of one element set and lower its first mention: linear probing, the slot claimed by a 64-bit
+// compare-and-swap on the key.  The plain reads in front of the atomics can only be stale towards "free" and "larger", in
+// which case the atomic decides; the table holds at most half as many keys as slots, so the walk ends.
+LMN_D void tc_insert(const TcSet S, unsigned long long key, unsigned long long w, unsigned long long mention) {
+  unsigned long long x = (key ^ (key >> 29)) * 0x9E3779B97F4A7C15ull;
+  uint64_t h = (x >> 24) & S.mask;
+  for (;;) {
+    unsigned long long k = S.keys[h];
+    if (k == TC_EMPTY) k = atomicCAS(&S.keys[h], TC_EMPTY, key);
+    if (k == TC_EMPTY || k == key) break;
+    h = (h + 1) & S.mask;
+  }
+  atomicAdd(&S.sums[h], w);
+  if (S.firsts[h] > mention) atomicMin(&S.firsts[h], mention);
+}
+
+// One lane per real row.  COLS: the table is column-major (a finished row sink) and a lane's words are coalesced column
+// reads; otherwise the workgroup's TPB x NC words are one contiguous run of the row-major table, staged through LDS with
+// an odd row pitch (a row is 7 .. 22 words: per-lane global reads of it would be 28 .. 88-byte strides).  Per local slot: a
+// wave ballot, and only when it is non-zero one atomicAdd of its population count and one atomicMin of the wave's smallest
+// row, by the leader - a clean trace issues no atomic here.  Relation entries with a non-zero multiplicity go to their
+// element set's tuple table; LessThan's limbs (4 per row on the 256 keys of the range check) are summed per workgroup in
+// LDS, direct-indexed, and reach the table once per workgroup.
+template <int KIND, bool COLS>
+LMN_KERNEL k_trace_check(TcTable tb, TcOut out) {
+  constexpr int NC = tc_ncols(KIND), NL = tc_nlocal(KIND), ST = NC | 1;
+  LMN_SHARED uint32_t tile[COLS ? 1 : TPB * ST];
+  LMN_SHARED unsigned long long rc_sum[KIND == 13 ? 256 : 1], rc_first[KIND == 13 ? 256 : 1];
+  const uint64_t row0 = (uint64_t)blockIdx.x * TPB;
+  const uint64_t r = row0 + threadIdx.x;
+  const bool on = r < tb.n_rows;
+  uint32_t c[NC];
+  if constexpr (COLS) {
+#pragma unroll
+    for (int k = 0; k < NC; ++k) c[k] = on ? tb.data[(uint64_t)k * tb.stride + r] : 0u;
+  } else {
+    const uint64_t rows_here = tb.n_rows - row0 < (uint64_t)TPB ? tb.n_rows - row0 : (uint64_t)TPB;
+    const uint32_t words = (uint32_t)rows_here * NC;
+    const uint32_t* __restrict__ src = tb.data + row0 * NC;
+    for (uint32_t w = threadIdx.x; w < words; w += TPB) tile[(w / NC) * ST + (w % NC)] = src[w];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NC; ++k) c[k] = on ? tile[threadIdx.x * ST + k] : 0u;
+  }
+  if constexpr (KIND == 13) {
+    rc_sum[threadIdx.x] = 0ull;       // TPB == 256 keys
+    rc_first[threadIdx.x] = TC_EMPTY;
+    __syncthreads();
+  }
+  // words that are no canonical M31: counted, the smallest (table, row, column) kept, and the row is out of both checks
+  uint32_t n_bad = 0u, first_bad = 0u;
+#pragma unroll
+  for (int k = NC - 1; k >= 0; --k)
+    if (c[k] >= P31) {
+      ++n_bad;
+      first_bad = (uint32_t)k;
+    }
+  if (n_bad) {
+    atomicAdd(&out.noncanon[0], (unsigned long long)n_bad);
+    atomicMin(&out.noncanon[1], (unsigned long long)tb.table << 40 | r << 8 | first_bad);
+  }
+  const bool live = on && n_bad == 0u;
+  const unsigned lane = threadIdx.x & 63u;
+  if constexpr (NL > 0) {
+    uint32_t v[NL];
+    tc_local<KIND>(c, v);
+#pragma unroll
+    for (int sl = 0; sl < NL; ++sl) {
+      const unsigned long long bal = lmn_ballot(live && v[sl] != 0u);
+      if (bal != 0ull && lane == (unsigned)__builtin_ctzll(bal)) {   // the leader holds the wave's smallest violating row
+        atomicAdd(&out.slot_count[tb.table * TC_MAX_SLOTS + sl], (uint32_t)__builtin_popcountll(bal));
+        atomicMin(&out.slot_first[tb.table * TC_MAX_SLOTS + sl], (unsigned long long)r);
+      }
+    }
+  }
+  auto word = [&](int col) -> uint32_t {   // a relation's column is launch-uniform data, not a register index: read it again
+    if constexpr (COLS) return tb.data[(uint64_t)col * tb.stride + r];
+    else return tile[threadIdx.x * ST + col];
+  };
+  // (the relation wiring is read from the argument block at constant offsets - a loop over it would be indexed by a register
+  // and the block copied to scratch)
+  auto relation = [&](int j, int mult_col, int val_col, int id_col, int set, int neg, int pre) {
+    if (j >= tb.n_rel || !live) return;
+    const uint32_t mult = word(mult_col);
+    if (mult == 0u) return;
+    uint32_t val, id = 0u;
+    if (pre) {
+      val = tb.pre0 ? tb.pre0[r] : (uint32_t)r;
+      if (id_col >= 0) id = tb.pre1[r];
+    } else {
+      val = word(val_col);
+      if (id_col >= 0) id = word(id_col);
+    }
+    const unsigned long long w = neg ? P31 - mult : mult;
+    const unsigned long long mention = (unsigned long long)tb.table << 40 | (unsigned long long)(tb.slot0 + j) << 32 | r;
+    if (KIND == 13 && set == 1 && val < 256u) {
+      atomicAdd(&rc_sum[val], w);
+      atomicMin(&rc_first[val], mention);
+    } else {
+      tc_insert(out.sets[set], (unsigned long long)val | (unsigned long long)id << 31, w, mention);
+    }
+  };
+#define LMN_TC_REL(J) relation(J, tb.rel_mult[J], tb.rel_val[J], tb.rel_id[J], tb.rel_set[J], tb.rel_neg[J], tb.rel_pre[J])
+  LMN_TC_REL(0); LMN_TC_REL(1); LMN_TC_REL(2); LMN_TC_REL(3); LMN_TC_REL(4); LMN_TC_REL(5); LMN_TC_REL(6);
+#undef LMN_TC_REL
+  if constexpr (KIND == 13) {
+    __syncthreads();
+    if (rc_first[threadIdx.x] != TC_EMPTY) tc_insert(out.sets[1], threadIdx.x, rc_sum[threadIdx.x], rc_first[threadIdx.x]);
+  }
+}
+
+void launch_trace_check(int kind, bool cols_layout, const TcTable& tb, const TcOut& out, lmn_stream_t s) {
+  if (tb.n_rows == 0 || tb.n_rows > (1ull << 26)) throw LmnError(-100, "trace check: bad row count");
+  if (cols_layout && tb.n_rows > tb.stride) throw LmnError(-100, "trace check: rows outside the columns");
+  const dim3 g(cdiv(tb.n_rows, TPB)), b(TPB);
+#define LMN_TC_CASE(K)                                                             \
+  case K:                                                                          \
+    if (cols_layout) LMN_LAUNCH((k_trace_check<K, true>), g, b, 0, s, tb, out);    \
+    else LMN_LAUNCH((k_trace_check<K, false>), g, b, 0, s, tb, out);               \
+    break;
+  switch (kind) {
+    LMN_TC_CASE(0) LMN_TC_CASE(1) LMN_TC_CASE(2) LMN_TC_CASE(3) LMN_TC_CASE(4) LMN_TC_CASE(5) LMN_TC_CASE(6) LMN_TC_CASE(7)
+    LMN_TC_CASE(8) LMN_TC_CASE(9) LMN_TC_CASE(10) LMN_TC_CASE(11) LMN_TC_CASE(12) LMN_TC_CASE(13) LMN_TC_CASE(14)
+    LMN_TC_CASE(15) LMN_TC_CASE(16)
+    default: throw LmnError(-100, "trace check: unsupported kind");
+  }
+#undef LMN_TC_CASE
+}
+
+// One lane per slot of a tuple table: the sum reduced mod P, the non-zero ones counted (one atomicAdd per wave) and the
+// first `cap` of them compacted into `found`.
+LMN_KERNEL k_trace_check_collect(TcSet S, uint32_t set_index, unsigned long long* __restrict__ n_unbalanced,
+                                 TcFound* __restrict__ found, uint32_t cap) {
+  LMN_SHARED unsigned long long wave_base[TPB / 64];
+  const uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x;
+  unsigned long long key = TC_EMPTY;
+  if (i <= S.mask) key = S.keys[i];
+  uint32_t net = 0u;
+  if (key != TC_EMPTY) net = m_red64(S.sums[i]);
+  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const unsigned long long bal = lmn_ballot(net != 0u);
+  if (bal != 0ull && lane == (unsigned)__builtin_ctzll(bal))
+    wave_base[wave] = atomicAdd(n_unbalanced, (unsigned long long)__builtin_popcountll(bal));
+  __syncthreads();
+  if (net != 0u) {
+    const unsigned long long at = wave_base[wave] + (unsigned long long)__builtin_popcountll(bal & ((1ull << lane) - 1ull));
+    if (at < cap) {
+      TcFound f;
+      f.key = key;
+      f.first = S.firsts[i];
+      f.set = set_index;
+      f.net = net;
+      found[at] = f;
+    }
+  }
+}
+void launch_trace_check_collect(const TcSet& set, uint32_t set_index, unsigned long long* n_unbalanced, TcFound* found,
+                                uint32_t cap, lmn_stream_t s) {
+  LMN_LAUNCH(k_trace_check_collect, dim3(cdiv(set.mask + 1, TPB)), dim3(TPB), 0, s, set, set_index, n_unbalanced, found, cap);
+}
+
+// =============================================================================================
 // level-2 column ops: bit reversal, FriOps::decompose
 // =============================================================================================
 LMN_KERNEL k_bit_reverse(uint32_t* __restrict__ data, uint64_t col_stride, int log_n) {

@@ -40,6 +40,8 @@ typedef hipStream_t lmn_stream_t;
 // value of lane (quad base + ((CTRL >> 2*(lane&3)) & 3)): DPP quad_perm, no LDS round trip
 #define lmn_quad_perm(v, CTRL) ((uint32_t)__builtin_amdgcn_mov_dpp((int)(v), (CTRL), 0xf, 0xf, true))
 #define LMN_ASSUME(x) __builtin_assume(x)
+// bit l = the predicate of lane l of this wave (inactive lanes: 0)
+#define lmn_ballot(pred) ((unsigned long long)__ballot(pred))
 
 struct LmnError : std::runtime_error {
   int code;
@@ -298,6 +300,26 @@ inline unsigned long long atomicMin(unsigned long long* p, unsigned long long v)
   unsigned long long o = *p;
   if (v < o) *p = v;
   return o;
+}
+// the 64-bit atomics of k_trace_check / k_trace_check_collect (kernels_trace.hip)
+inline unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) {
+  unsigned long long o = *p;
+  *p += v;
+  return o;
+}
+inline unsigned long long atomicCAS(unsigned long long* p, unsigned long long expected, unsigned long long v) {
+  unsigned long long o = *p;
+  if (o == expected) *p = v;
+  return o;
+}
+inline unsigned long long lmn_ballot(bool pred) {  // all lanes of the block must call it together
+  lmn_emu_shfl_scratch[threadIdx.x] = pred ? 1u : 0u;
+  lmn_emu_syncthreads();
+  unsigned long long r = 0;
+  const unsigned w0 = threadIdx.x & ~63u;
+  for (unsigned l = 0; l < 64u && w0 + l < blockDim.x; ++l) r |= (unsigned long long)lmn_emu_shfl_scratch[w0 + l] << l;
+  lmn_emu_syncthreads();
+  return r;
 }
 inline unsigned lmn_quad_perm(unsigned v, int ctrl) {  // all lanes of the block must call it together
   lmn_emu_shfl_scratch[threadIdx.x] = v;

@@ -299,6 +299,8 @@ class Context {
                  const uint32_t* lut_col1, const lmn_range* ranges, uint32_t n_ranges, uint32_t* mult, uint32_t* rows,
                  uint64_t row_offset, int32_t* out);
   void device_free(void* p);
+  // lmn_trace_check (trace_gen.cpp): the rows that break a local constraint and the logup tuples that do not balance
+  void trace_check(const lmn_table* tables, size_t n_tables, const lmn_settings* settings, lmn_trace_report& report);
 
   int device() const { return device_; }
   lmn_config cfg;

@@ -2,6 +2,8 @@
 // (crates/graph/src/op/prim.rs), filling trace-table rows in HBM.  Host side of the lmn_trace_* entry points.
 #include "prover_internal.h"
 
+#include <algorithm>
+
 namespace lmn {
 
 static TraceNode trace_node(const lmn_node_info& info) {
@@ -134,6 +136,265 @@ void Context::trace_contiguous(const int32_t* input, uint64_t in_size, const lmn
   const uint64_t n = std::max(in_size, out_size);
   launch_trace_elementwise(LMN_KIND_CONTIGUOUS, input, tv, nullptr, TraceView{}, n, nd, rows + row_offset * 11ull, out, nullptr,
                            stream_);
+}
+
+// ------------------------------------------------------------------------------------ lmn_trace_check
+// lmn_prove answers a bad trace with ProverError(ConstraintsNotSatisfied) after the FRI loop (phase_oods.cpp) and proves an
+// unbalanced one all the same.  This pass names the rows and the tuples instead: one launch per table over the rows where
+// they lie (kernels_trace.hip k_trace_check), one per element set to pick the unbalanced tuples out of its table.
+namespace {
+const char* const kKindNames[17] = {"Add", "Mul", "Recip", "Sin", "SinLookup", "SumReduce", "MaxReduce", "Sqrt", "Rem", "Exp2",
+                                    "Exp2Lookup", "Log2", "Log2Lookup", "LessThan", "RangeCheckLookup", "Inputs", "Contiguous"};
+const char* const kSetNames[N_ELEMS] = {"NodeElements", "RangeCheck", "Sin", "Exp2", "Log2"};
+const char* kind_name(uint32_t kind) { return kind < 17 ? kKindNames[kind] : "?"; }
+
+// device scratch of one call: everything is released when the call returns, whatever its outcome
+struct TcScratch {
+  std::vector<void*> ptrs;
+  lmn_stream_t stream;
+  explicit TcScratch(lmn_stream_t s) : stream(s) {}
+  ~TcScratch() {
+    if (ptrs.empty()) return;
+    try {
+      lmn_sync(stream);   // a launch of a failed call may still be reading them
+    } catch (...) {
+    }
+    for (void* p : ptrs) lmn_dev_free(p);
+  }
+  void* get(size_t bytes, const char* what) {
+    try {
+      void* p = lmn_dev_malloc(bytes);
+      ptrs.push_back(p);
+      return p;
+    } catch (const LmnError&) {
+#ifndef LMN_EMU
+      (void)hipGetLastError();   // the failed allocation must not surface at the next launch
+#endif
+      throw LmnError(LMN_ERR_OUT_OF_MEMORY, std::string("trace check: cannot allocate ") + std::to_string(bytes) + " bytes for " + what);
+    }
+  }
+};
+}  // namespace
+
+void Context::trace_check(const lmn_table* tables, size_t n_tables, const lmn_settings* settings, lmn_trace_report& rep) {
+#ifndef LMN_EMU
+  LMN_HIP_CHECK(hipSetDevice(device_));
+#endif
+  if (!tables || n_tables == 0) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "no trace tables");
+  // ---- the rules of lmn_prove's setup (prove.cpp run_setup, phase_trace.cpp run_preprocessed), in its order and with its
+  // codes; the text names the table
+  struct Info {
+    const ComponentSpec* spec;
+    int log_size;
+    bool on_device, cols;
+  };
+  std::vector<Info> infos;
+  const int n_slots = claim_slots(cfg.protocol_variant), lb = (int)cfg.log_blowup;
+  int prev_kind = -1;
+  auto refuse = [&](size_t t, int code, const std::string& why) {
+    throw LmnError(code, "table " + std::to_string(t) + " (kind " + std::to_string(tables[t].kind) + "): " + why);
+  };
+  for (size_t t = 0; t < n_tables; ++t) {
+    const lmn_table& tb = tables[t];
+    const ComponentSpec* sp = component_spec((int)tb.kind);
+    if (!sp) refuse(t, LMN_ERR_INVALID_ARGUMENT, "unsupported component kind");
+    if ((int)tb.kind >= n_slots) refuse(t, LMN_ERR_INVALID_ARGUMENT, "component kind has no claim slot in this protocol variant");
+    if ((int)tb.kind <= prev_kind)
+      refuse(t, LMN_ERR_INVALID_ARGUMENT, "tables must be in gen_trace order (ascending kind, no duplicates)");
+    prev_kind = (int)tb.kind;
+    if (tb.n_rows == 0) refuse(t, LMN_ERR_EMPTY_TRACE, "TraceError::EmptyTrace");
+    if (!tb.rows) refuse(t, LMN_ERR_INVALID_ARGUMENT, "null rows pointer");
+    if (tb.n_rows > (1ull << 26)) refuse(t, LMN_ERR_INVALID_ARGUMENT, "trace table has more than 2^26 rows");
+    int ls = 4;
+    while ((1ull << ls) < tb.n_rows) ++ls;
+    if (ls + lb + 2 > MAX_LOG - 2) refuse(t, LMN_ERR_INVALID_ARGUMENT, "trace too large");
+    if (ls <= (int)cfg.log_last_layer)
+      refuse(t, LMN_ERR_INVALID_ARGUMENT, "a table needs more than 2^log_last_layer rows (after padding)");
+    const bool cols = (tb.flags & LMN_TABLE_COLS_ON_DEVICE) != 0;
+    if (cols) {
+      if (tb.flags & LMN_TABLE_ROWS_ON_DEVICE)
+        refuse(t, LMN_ERR_INVALID_ARGUMENT, "a table is LMN_TABLE_ROWS_ON_DEVICE or LMN_TABLE_COLS_ON_DEVICE, not both");
+#ifdef LMN_BATCH
+      refuse(t, LMN_ERR_INVALID_ARGUMENT, "LMN_TABLE_COLS_ON_DEVICE (row sinks) is not supported by the batch library");
+#else
+      if (shard_.active)
+        refuse(t, LMN_ERR_INVALID_ARGUMENT, "LMN_TABLE_COLS_ON_DEVICE (row sinks) is not supported on a sharded context");
+      try {
+        rows_sink_attach(tb, device_, stream_);   // this stream waits for the sink's finish event; the host does not
+      } catch (const LmnError& e) {
+        refuse(t, e.code, e.what());
+      }
+#endif
+    }
+    infos.push_back({sp, ls, (tb.flags & LMN_TABLE_ROWS_ON_DEVICE) != 0, cols});
+  }
+  const lmn_lut* lut_of[3] = {nullptr, nullptr, nullptr};
+  {
+    uint32_t present = 0;
+    for (auto& ti : infos) {
+      if (ti.spec->kind == LMN_KIND_SIN_LOOKUP) present |= LMN_LOOKUP_SIN;
+      if (ti.spec->kind == LMN_KIND_EXP2_LOOKUP) present |= LMN_LOOKUP_EXP2;
+      if (ti.spec->kind == LMN_KIND_LOG2_LOOKUP) present |= LMN_LOOKUP_LOG2;
+      if (ti.spec->kind == LMN_KIND_RANGE_CHECK_LOOKUP) present |= LMN_LOOKUP_RANGE_CHECK;
+    }
+    if (settings && (settings->has_lookups & ~present))
+      throw LmnError(LMN_ERR_INVALID_ARGUMENT, "settings announce a lookup whose table is not in the pie");
+    if (settings && settings->n_luts) {
+      if (!settings->luts) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "null luts pointer");
+      for (uint32_t i = 0; i < settings->n_luts; ++i) {
+        const lmn_lut& l = settings->luts[i];
+        if (l.kind > LMN_LUT_LOG2 || !l.col0 || !l.col1 || lut_of[l.kind])
+          throw LmnError(LMN_ERR_INVALID_ARGUMENT, "bad or duplicate LUT in settings");
+        lut_of[l.kind] = &l;
+      }
+    }
+    for (size_t t = 0; t < n_tables; ++t) {
+      const ComponentSpec* sp = infos[t].spec;
+      if (sp->n_pre == 0) continue;
+      if (sp->pre_id[0] == PRE_RANGE_CHECK) {
+        if (infos[t].log_size != 8) refuse(t, LMN_ERR_INVALID_ARGUMENT, "RangeCheckLookup table must have exactly 256 rows");
+        continue;
+      }
+      const lmn_lut* l = lut_of[sp->pre_id[0] / 2];
+      if (!l) refuse(t, LMN_ERR_INVALID_ARGUMENT, "lookup table present but settings carry no LUT columns for it");
+      if ((int)l->log_size != infos[t].log_size) refuse(t, LMN_ERR_INVALID_ARGUMENT, "lookup table rows must match the LUT column size");
+      for (uint64_t r = 0; r < (1ull << l->log_size); ++r)
+        if (l->col0[r] >= P31 || l->col1[r] >= P31) refuse(t, LMN_ERR_INVALID_ARGUMENT, "LUT value is not a canonical M31");
+    }
+  }
+
+  // ---- scratch: the counters, one tuple table per element set the pie uses, device copies of host rows and LUT columns
+  TcScratch scratch(stream_);
+  uint64_t bound[N_ELEMS] = {0, 0, 0, 0, 0};   // entries a set can get: every relation entry of every real row
+  for (size_t t = 0; t < n_tables; ++t)
+    for (int j = 0; j < infos[t].spec->n_rel; ++j) bound[infos[t].spec->rel_elems[j]] += tables[t].n_rows;
+  // counters: [n_unbalanced, noncanon count, noncanon first, slot_first x n_tables x TC_MAX_SLOTS] u64, then the found
+  // tuples, then slot_count u32; behind them the five sets' table descriptors as the kernels read them
+  const size_t n_sl = n_tables * TC_MAX_SLOTS;
+  const size_t off_found = (3 + n_sl) * 8, off_count = off_found + LMN_TRACE_REPORT_MAX * sizeof(TcFound);
+  const size_t ctrl_bytes = (off_count + n_sl * 4 + 7) / 8 * 8, off_sets = ctrl_bytes;
+  char* d_ctrl = (char*)scratch.get(ctrl_bytes + N_ELEMS * sizeof(TcSet), "the counters");
+  unsigned long long* d_u64 = (unsigned long long*)d_ctrl;
+  lmn_memset(d_ctrl, 0, ctrl_bytes, stream_);
+  lmn_memset(d_u64 + 2, 0xff, (1 + n_sl) * 8, stream_);
+  TcOut out{};
+  out.slot_count = (uint32_t*)(d_ctrl + off_count);
+  out.slot_first = d_u64 + 3;
+  out.noncanon = d_u64 + 1;
+  out.sets = (const TcSet*)(d_ctrl + off_sets);
+  TcSet sets[N_ELEMS] = {};
+  for (int e = 0; e < N_ELEMS; ++e) {
+    if (!bound[e]) continue;
+    uint64_t cap = 256;
+    while (cap < 2 * bound[e]) cap <<= 1;
+    unsigned long long* base = (unsigned long long*)scratch.get(cap * 24, "a tuple table");
+    sets[e] = {base, base + 2 * cap, base + cap, cap - 1};   // keys | firsts | sums
+    lmn_memset(base, 0xff, cap * 16, stream_);
+    lmn_memset(base + 2 * cap, 0, cap * 8, stream_);
+  }
+  lmn_h2d(d_ctrl + off_sets, sets, sizeof sets, stream_);
+  const uint32_t* d_lut[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
+  for (size_t t = 0; t < n_tables; ++t) {
+    const ComponentSpec* sp = infos[t].spec;
+    TcTable tb{};
+    tb.n_rows = tables[t].n_rows;
+    tb.stride = 1ull << infos[t].log_size;
+    tb.table = (uint32_t)t;
+    if (infos[t].on_device || infos[t].cols) {
+      tb.data = tables[t].rows;
+    } else {
+      const size_t bytes = (size_t)tb.n_rows * sp->n_cols * 4;
+      uint32_t* d = (uint32_t*)scratch.get(bytes, "a copy of host rows");
+      lmn_h2d(d, tables[t].rows, bytes, stream_);
+      tb.data = d;
+    }
+    if (sp->n_pre == 2) {
+      const int k = sp->pre_id[0] / 2;
+      for (int h = 0; h < 2; ++h) {
+        uint32_t* d = (uint32_t*)scratch.get((size_t)tb.n_rows * 4, "a LUT column");
+        lmn_h2d(d, h ? lut_of[k]->col1 : lut_of[k]->col0, (size_t)tb.n_rows * 4, stream_);
+        d_lut[k][h] = d;
+      }
+      tb.pre0 = d_lut[k][0];
+      tb.pre1 = d_lut[k][1];
+    }
+    tb.n_rel = sp->n_rel;
+    tb.slot0 = sp->n_local;
+    for (int j = 0; j < sp->n_rel; ++j) {
+      tb.rel_mult[j] = sp->rel_mult[j];
+      tb.rel_val[j] = sp->rel_val[j];
+      tb.rel_id[j] = sp->rel_id[j];
+      tb.rel_set[j] = sp->rel_elems[j];
+      tb.rel_neg[j] = sp->rel_neg[j];
+      tb.rel_pre[j] = sp->rel_pre[j];
+    }
+    launch_trace_check(sp->kind, infos[t].cols, tb, out, stream_);
+  }
+  TcFound* d_found = (TcFound*)(d_ctrl + off_found);
+  for (int e = 0; e < N_ELEMS; ++e)
+    if (sets[e].keys) launch_trace_check_collect(sets[e], (uint32_t)e, d_u64, d_found, LMN_TRACE_REPORT_MAX, stream_);
+  std::vector<char> h_ctrl(ctrl_bytes);
+  lmn_d2h(h_ctrl.data(), d_ctrl, ctrl_bytes, stream_);
+  lmn_sync(stream_);
+
+  // ---- the report
+  const unsigned long long* h_u64 = (const unsigned long long*)h_ctrl.data();
+  const uint32_t* h_count = (const uint32_t*)(h_ctrl.data() + off_count);
+  rep.n_unbalanced = h_u64[0];
+  rep.n_noncanonical = h_u64[1];
+  if (rep.n_noncanonical) {
+    rep.nc_table = (uint32_t)(h_u64[2] >> 40);
+    rep.nc_row = (h_u64[2] >> 8) & 0xffffffffull;
+    rep.nc_column = (uint32_t)(h_u64[2] & 0xffu);
+  }
+  for (size_t t = 0; t < n_tables; ++t)
+    for (int sl = 0; sl < infos[t].spec->n_local; ++sl) {
+      const uint32_t cnt = h_count[t * TC_MAX_SLOTS + sl];
+      if (!cnt) continue;
+      if (rep.n_constraints < LMN_TRACE_REPORT_MAX)
+        rep.constraints[rep.n_constraints++] = {(uint32_t)t, (uint32_t)infos[t].spec->kind, (uint32_t)sl, 0u, cnt,
+                                                h_u64[3 + t * TC_MAX_SLOTS + sl]};
+      ++rep.n_constraint_slots;
+    }
+  rep.constraints_truncated = rep.n_constraint_slots > rep.n_constraints ? 1u : 0u;
+  std::vector<TcFound> found((size_t)std::min<uint64_t>(rep.n_unbalanced, LMN_TRACE_REPORT_MAX));
+  if (!found.empty()) memcpy(found.data(), h_ctrl.data() + off_found, found.size() * sizeof(TcFound));
+  auto val_of = [](const TcFound& f) { return (uint32_t)(f.key & P31); };
+  auto id_of = [](const TcFound& f) { return (uint32_t)(f.key >> 31); };
+  std::sort(found.begin(), found.end(), [&](const TcFound& a, const TcFound& b) {
+    if (a.set != b.set) return a.set < b.set;
+    if (id_of(a) != id_of(b)) return id_of(a) < id_of(b);
+    return val_of(a) < val_of(b);
+  });
+  for (const TcFound& f : found)
+    rep.tuples[rep.n_tuples++] = {f.set, val_of(f), id_of(f), f.net, (uint32_t)(f.first >> 40), (uint32_t)((f.first >> 32) & 0xffu),
+                                  f.first & 0xffffffffull};
+  rep.tuples_truncated = rep.n_unbalanced > rep.n_tuples ? 1u : 0u;
+  rep.ok = rep.n_noncanonical == 0 && rep.n_constraint_slots == 0 && rep.n_unbalanced == 0 ? 1u : 0u;
+
+  std::string text;
+  auto part = [&](const std::string& p) { text += (text.empty() ? "" : "; ") + p; };
+  if (rep.ok) {
+    uint64_t rows = 0;
+    for (size_t t = 0; t < n_tables; ++t) rows += tables[t].n_rows;
+    part("ok: " + std::to_string(n_tables) + " tables, " + std::to_string(rows) + " rows, constraints hold and relations balance");
+  }
+  if (rep.n_noncanonical)
+    part(std::to_string(rep.n_noncanonical) + " non-canonical words, first: table " + std::to_string(rep.nc_table) + " (" +
+         kind_name(tables[rep.nc_table].kind) + ") row " + std::to_string(rep.nc_row) + " column " + std::to_string(rep.nc_column));
+  if (rep.n_constraints) {
+    const lmn_trace_constraint& c = rep.constraints[0];
+    part("table " + std::to_string(c.table) + " (" + kind_name(c.kind) + ") row " + std::to_string(c.first_row) +
+         ": constraint slot " + std::to_string(c.slot) + " non-zero" +
+         (rep.n_constraint_slots > 1 ? " (" + std::to_string(rep.n_constraint_slots) + " violated slots in all)" : ""));
+  }
+  if (rep.n_unbalanced) {
+    const lmn_trace_tuple& u = rep.tuples[0];
+    const long long net = u.net > P31 / 2 ? (long long)u.net - (long long)P31 : (long long)u.net;
+    part(std::to_string(rep.n_unbalanced) + " unbalanced tuples, first: " + kSetNames[u.set] + " id " + std::to_string(u.id) +
+         " val " + std::to_string(u.val) + " net " + std::to_string(net));
+  }
+  snprintf(rep.summary, sizeof rep.summary, "%s", text.c_str());
 }
 
 // ------------------------------------------------------------------------------------ row sinks (lmn_rows_*)

@@ -45,6 +45,16 @@ class Prover:
         except backend.LuminairBackendError as e:
             raise LuminairError(_ERR_VARIANT.get(e.code, "Internal"), str(e), e.code) from e
 
+    def check(self, pie: LuminairPie, settings: Optional[CircuitSettings] = None) -> backend.TraceReport:
+        """`lmn_trace_check`: the rows and logup tuples that would make `prove(pie, settings)` fail (or prove a statement
+        its verifier rejects), named - for the pies `prove` accepts, `RowSink` and `DeviceGraph` tables included."""
+        tables = [(int(t.kind), t.rows, t.n_rows) for t in pie.trace_tables]
+        luts = settings.lut_columns(self.ctx.lib) if settings is not None else None
+        try:
+            return self.ctx.check_trace(tables, luts)
+        except backend.LuminairBackendError as e:
+            raise LuminairError(_ERR_VARIANT.get(e.code, "Internal"), str(e), e.code) from e
+
     def timings(self) -> dict:
         return self.ctx.timings()
 
@@ -103,6 +113,14 @@ def prove(pie: LuminairPie, settings: Optional[CircuitSettings] = None) -> Lumin
     if _default is None:
         _default = Prover(0)
     return _default.prove(pie, settings)
+
+
+def check_trace(pie: LuminairPie, settings: Optional[CircuitSettings] = None) -> backend.TraceReport:
+    """`Prover.check` on GPU 0's default prover."""
+    global _default
+    if _default is None:
+        _default = Prover(0)
+    return _default.check(pie, settings)
 
 
 def verify(proof: LuminairProof, settings: Optional[CircuitSettings] = None,

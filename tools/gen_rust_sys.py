@@ -61,7 +61,7 @@ def rust_type(ctype, opaque, structs):
 
 
 def parse(headers):
-    defines, structs, opaque, funcs, fnptr_structs = [], {}, [], [], {}
+    defines, structs, opaque, funcs, tagged = [], {}, [], [], {}
     for h in headers:
         raw = open(h).read()
         for m in re.finditer(r"^#define\s+(LMN_[A-Z0-9_]+)\s+(\(?-?[0-9][0-9a-fx]*u?\)?|\([A-Z_ |()]+\)|LMN_[A-Z_]+)\s*(?:/\*.*)?$", raw, re.M):
@@ -70,8 +70,7 @@ def parse(headers):
         for m in re.finditer(r"typedef\s+struct\s+(\w+)\s+(\w+)\s*;", text):
             if m.group(2) not in opaque:
                 opaque.append(m.group(2))
-        for m in re.finditer(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", text, re.S):
-            name, body = m.group(3), m.group(2)
+        def parse_fields(name, body):
             fields = []
             for decl in [d.strip() for d in body.split(";") if d.strip()]:
                 fp = re.match(r"(.+?)\(\s*\*\s*(\w+)\s*\)\s*\((.*)\)$", decl, re.S)
@@ -82,7 +81,7 @@ def parse(headers):
                 toks = decl.replace("*", " * ").split()
                 k = 0
                 while k < len(toks) and (toks[k] in ("const", "struct", "unsigned") or toks[k] in SCALARS or toks[k] in structs
-                                         or toks[k] in opaque):
+                                         or toks[k] in tagged or toks[k] in opaque):
                     k += 1
                 ctype = " ".join(toks[:k])
                 dmap = {a: b for a, b in defines}
@@ -94,7 +93,14 @@ def parse(headers):
                         raise ValueError("cannot parse field %r of %s" % (decl, name))
                     dims = [int(d) if d.isdigit() else int(dmap[d].strip("()u")) for d in re.findall(r"\[(\w+)\]", im.group(2))]
                     fields.append((im.group(1), ("data", ctype + " *" * stars, dims)))
-            structs[name] = fields
+            return fields
+        for m in re.finditer(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*(\w+)\s*;", text, re.S):
+            structs[m.group(3)] = parse_fields(m.group(3), m.group(2))
+        # `struct name { ... }; typedef struct name name;` - the form of the structs added after ABI version 6's struct set
+        # (the report of lmn_trace_check): same repr(C) emission and layout, kept apart from the typedef'd set
+        for m in re.finditer(r"(?<![\w])struct\s+(\w+)\s*\{([^{}]*)\}\s*;", text, re.S):
+            tagged[m.group(1)] = parse_fields(m.group(1), m.group(2))
+        text = re.sub(r"(?<![\w])struct\s+\w+\s*\{[^{}]*\}\s*;", " ", text, flags=re.S)
         body = re.sub(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;", " ", text, flags=re.S)
         body = re.sub(r"#.*", " ", body)                      # preprocessor lines
         body = body.replace('extern "C" {', " ").replace("}", " ")
@@ -102,8 +108,8 @@ def parse(headers):
             m = re.match(r"\s*((?:const\s+)?\w+(?:\s*\*+)?)\s*(lmn_\w+)\s*\((.*)\)\s*$", stmt, re.S)
             if m:
                 funcs.append((m.group(2), m.group(1).strip(), m.group(3).strip()))
-    opaque = [o for o in opaque if o not in structs]
-    return defines, structs, opaque, funcs
+    opaque = [o for o in opaque if o not in structs and o not in tagged]
+    return defines, structs, opaque, funcs, tagged
 
 
 def params(text, opaque, structs):
@@ -190,7 +196,8 @@ def layout(structs, opaque):
 
 
 def generate():
-    defines, structs, opaque, funcs = parse(HEADERS)
+    defines, typedefd, opaque, funcs, tagged = parse(HEADERS)
+    structs = dict(typedefd, **tagged)
     L = ["// GENERATED by tools/gen_rust_sys.py from include/luminair_hip.h and include/luminair_hip_batch.h - do not edit.",
          "// `extern \"C\"` declarations of libluminair_hip.so / libluminair_hip_batch.so for a Rust binding of the reference",
          "// (/root/reference/crates/prover/src/prover.rs:28-31 `prove`, crates/verifiers/rust/src/verifier.rs:21 `verify`; the",
@@ -229,7 +236,7 @@ def generate():
         r = "" if ret == "void" else " -> " + rust_type(ret, opaque, structs)
         L.append("    pub fn %s(%s)%s;" % (name, ", ".join("%s: %s" % (n, t) for n, t in ps), r))
     L += ["}", ""]
-    return "\n".join(L), structs, funcs, lay
+    return "\n".join(L), typedefd, funcs, lay
 
 
 def main():
