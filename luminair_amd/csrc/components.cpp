@@ -1,5 +1,5 @@
-// The 17 AIR components as data (column layouts, relation wiring, padding rows: crates/air/src/components/**/table.rs,
-// component.rs), the constraint slots under the protocol's constraint-form bits, the relation-element draws
+// The 17 AIR components on the host (their shapes and local constraints are constraints.h): the constraint slots under the
+// protocol's constraint-form bits, the relation-element draws
 // (components/mod.rs:227-235, lookups/mod.rs:44-51) and the host-side evaluation of the composition polynomial at the OODS
 // point from sampled mask values (shared by the prover's self-check and the verifier).
 #include "prover_internal.h"
@@ -7,39 +7,7 @@
 namespace lmn {
 
 // ------------------------------------------------------------------------------------ components
-// Column layouts / relation wiring: crates/air/src/components/{add,mul,recip,inputs}/{table,component}.rs
-static const ComponentSpec kSpecs[] = {
-    // kind, n_cols, is_last, n_rel, rel_mult, rel_val, rel_id, n_local, rel_elems, rel_neg, rel_pre, n_pre, pre_id, n_pad, pad_col, pad_val
-    {LMN_KIND_ADD, 15, 4, 3, {12, 13, 14}, {9, 10, 11}, {1, 2, 0}, 6, {0}, {0}, {0}, 0, {0, 0}, 0, {0}, {0}},
-    {LMN_KIND_MUL, 16, 4, 3, {13, 14, 15}, {9, 10, 11}, {1, 2, 0}, 7, {0}, {0}, {0}, 0, {0, 0}, 0, {0}, {0}},
-    {LMN_KIND_RECIP, 13, 3, 2, {11, 12}, {7, 8}, {1, 0}, 5, {0}, {0}, {0}, 0, {0, 0}, 0, {0}, {0}},
-    {LMN_KIND_INPUTS, 7, 2, 1, {6}, {5}, {0}, 3, {0}, {0}, {0}, 0, {0, 0}, 0, {0}, {0}},
-    // constraint forms fully visible in the reference (no numerair helper):
-    {LMN_KIND_SUM_REDUCE, 14, 3, 2, {12, 13}, {7, 8}, {1, 0}, 7, {0}, {0}, {0}, 0, {0, 0}, 0, {0}, {0}},   // sum_reduce/component.rs:36-110
-    {LMN_KIND_MAX_REDUCE, 15, 3, 2, {13, 14}, {7, 8}, {1, 0}, 9, {0}, {0}, {0}, 0, {0, 0}, 0, {0}, {0}},   // max_reduce/component.rs
-    {LMN_KIND_CONTIGUOUS, 11, 3, 2, {9, 10}, {7, 8}, {1, 0}, 4, {0}, {0}, {0}, 0, {0, 0}, 0, {0}, {0}},    // contiguous/component.rs
-    // numerair's eval_fixed_sqrt / eval_fixed_rem are un-vendored: natural fixed-point identities (unpinned)
-    {LMN_KIND_SQRT, 13, 3, 2, {11, 12}, {7, 8}, {1, 0}, 5, {0}, {0}, {0}, 0, {0, 0}, 0, {0}, {0}},
-    {LMN_KIND_REM, 16, 4, 3, {13, 14, 15}, {9, 10, 11}, {1, 2, 0}, 6, {0}, {0}, {0}, 0, {0, 0}, 0, {0}, {0}},
-    // less_than/component.rs:48-185; padding row less_than/table.rs:47-72 (rhs=1, out=4096, diff=1, limb0=1)
-    {LMN_KIND_LESS_THAN, 22, 4, 7, {18, 19, 20, 21, 21, 21, 21}, {9, 10, 11, 14, 15, 16, 17}, {1, 2, 0, -1, -1, -1, -1}, 9,
-     {0, 0, 0, 1, 1, 1, 1}, {0}, {0}, 0, {0, 0}, 4, {10, 11, 12, 14}, {1u, 4096u, 1u, 1u}},
-    // lookups/range_check/component.rs: (-multiplicity, [range_check_8_column_0])
-    {LMN_KIND_RANGE_CHECK_LOOKUP, 1, -1, 1, {0}, {0}, {-1}, 0, {ELEMS_RANGE_CHECK}, {1}, {1}, 1, {PRE_RANGE_CHECK, 0}, 0, {0}, {0}},
-    // sin/component.rs:50-122 (exp2, log2 alike): node relations on input/out + LUT relation (lookup_mult, [input, out])
-    {LMN_KIND_SIN, 12, 3, 3, {9, 10, 11}, {7, 8, 7}, {1, 0, 8}, 4, {0, 0, ELEMS_SIN}, {0}, {0}, 0, {0, 0}, 0, {0}, {0}},
-    {LMN_KIND_EXP2, 12, 3, 3, {9, 10, 11}, {7, 8, 7}, {1, 0, 8}, 4, {0, 0, ELEMS_EXP2}, {0}, {0}, 0, {0, 0}, 0, {0}, {0}},
-    {LMN_KIND_LOG2, 12, 3, 3, {9, 10, 11}, {7, 8, 7}, {1, 0, 8}, 4, {0, 0, ELEMS_LOG2}, {0}, {0}, 0, {0, 0}, 0, {0}, {0}},
-    // lookups/sin/component.rs:40-59: (-multiplicity, [lut_0, lut_1]) over the two preprocessed columns
-    {LMN_KIND_SIN_LOOKUP, 1, -1, 1, {0}, {0}, {1}, 0, {ELEMS_SIN}, {1}, {1}, 2, {PRE_SIN0, PRE_SIN0 + 1}, 0, {0}, {0}},
-    {LMN_KIND_EXP2_LOOKUP, 1, -1, 1, {0}, {0}, {1}, 0, {ELEMS_EXP2}, {1}, {1}, 2, {PRE_EXP20, PRE_EXP20 + 1}, 0, {0}, {0}},
-    {LMN_KIND_LOG2_LOOKUP, 1, -1, 1, {0}, {0}, {1}, 0, {ELEMS_LOG2}, {1}, {1}, 2, {PRE_LOG20, PRE_LOG20 + 1}, 0, {0}, {0}},
-};
-const ComponentSpec* component_spec(int kind) {
-  for (auto& s : kSpecs)
-    if (s.kind == kind) return &s;
-  return nullptr;
-}
+const ComponentSpec* component_spec(int kind) { return kind >= 0 && kind < N_KINDS ? &kSpecs[kind] : nullptr; }
 
 ConstraintLayout constraint_layout(const ComponentSpec& sp, uint32_t flags) {
   ConstraintLayout L;
@@ -113,87 +81,17 @@ std::vector<int> assign_preprocessed(std::vector<Instance>& inst) {
 }
 
 // ------------------------------------------------------------------------------------ host-side AIR at a point
-static QM31 qsub1(QM31 a) { return q_sub_m(a, 1u); }
-static QM31 one_minus(QM31 a) { return q_sub(q_one(), a); }
-
-// local constraints at a point, in `evaluate` order (crates/air/src/components/*/component.rs)
-static std::vector<QM31> local_constraints(int kind, const std::vector<QM31>& c) {
+// local constraints at a point: constraints.h local_constraints<kind> on QM31 values
+static std::vector<QM31> local_constraints_at(int kind, const std::vector<QM31>& c) {
   std::vector<QM31> out;
-  if (kind == LMN_KIND_ADD || kind == LMN_KIND_MUL) {
-    QM31 is_last = c[4], not_last = one_minus(is_last);
-    out.push_back(q_mul(is_last, qsub1(is_last)));
-    if (kind == LMN_KIND_ADD) {
-      out.push_back(q_sub(c[11], q_add(c[9], c[10])));
-    } else {
-      out.push_back(q_sub(q_mul(c[9], c[10]), q_add(q_mul_m(c[11], 4096u), c[12])));
-      out.push_back(q_zero());
-    }
-    out.push_back(q_mul(not_last, q_sub(c[5], c[0])));
-    out.push_back(q_mul(not_last, q_sub(c[6], c[1])));
-    out.push_back(q_mul(not_last, q_sub(c[7], c[2])));
-    out.push_back(q_mul(not_last, qsub1(q_sub(c[8], c[3]))));
-  } else if (kind == LMN_KIND_RECIP) {
-    QM31 is_last = c[3], not_last = one_minus(is_last);
-    out.push_back(q_mul(is_last, qsub1(is_last)));
-    out.push_back(q_sub(q_sqr(c[10]), q_add(q_mul(c[7], c[8]), c[9])));
-    out.push_back(q_mul(not_last, q_sub(c[4], c[0])));
-    out.push_back(q_mul(not_last, q_sub(c[5], c[1])));
-    out.push_back(q_mul(not_last, qsub1(q_sub(c[6], c[2]))));
-  } else if (kind == LMN_KIND_SQRT) {
-    QM31 is_last = c[3], not_last = one_minus(is_last);
-    out.push_back(q_mul(is_last, qsub1(is_last)));
-    out.push_back(q_sub(q_mul(c[7], c[10]), q_add(q_sqr(c[8]), c[9])));
-    out.push_back(q_mul(not_last, q_sub(c[4], c[0])));
-    out.push_back(q_mul(not_last, q_sub(c[5], c[1])));
-    out.push_back(q_mul(not_last, qsub1(q_sub(c[6], c[2]))));
-  } else if (kind == LMN_KIND_REM) {
-    QM31 is_last = c[4], not_last = one_minus(is_last);
-    out.push_back(q_mul(is_last, qsub1(is_last)));
-    out.push_back(q_sub(c[9], q_add(q_mul(c[10], c[12]), c[11])));
-    out.push_back(q_mul(not_last, q_sub(c[5], c[0])));
-    out.push_back(q_mul(not_last, q_sub(c[6], c[1])));
-    out.push_back(q_mul(not_last, q_sub(c[7], c[2])));
-    out.push_back(q_mul(not_last, qsub1(q_sub(c[8], c[3]))));
-  } else if (kind == LMN_KIND_RANGE_CHECK_LOOKUP || kind == LMN_KIND_SIN_LOOKUP || kind == LMN_KIND_EXP2_LOOKUP ||
-             kind == LMN_KIND_LOG2_LOOKUP) {
-    // no local constraints
-  } else if (kind == LMN_KIND_LESS_THAN) {
-    QM31 is_last = c[4], not_last = one_minus(is_last), borrow = c[13];
-    out.push_back(q_mul(is_last, qsub1(is_last)));
-    out.push_back(q_mul(borrow, qsub1(borrow)));
-    out.push_back(q_sub(c[11], q_mul_m(one_minus(borrow), 4096u)));
-    out.push_back(q_sub(q_add(c[9], c[12]), c[10]));  // - borrow * (2^31 - 1) == 0 in M31
-    out.push_back(q_sub(c[12], q_add(q_add(q_mul_m(c[17], 1u << 24), q_mul_m(c[16], 1u << 16)),
-                                     q_add(q_mul_m(c[15], 1u << 8), c[14]))));
-    out.push_back(q_mul(not_last, q_sub(c[5], c[0])));
-    out.push_back(q_mul(not_last, q_sub(c[6], c[1])));
-    out.push_back(q_mul(not_last, q_sub(c[7], c[2])));
-    out.push_back(q_mul(not_last, qsub1(q_sub(c[8], c[3]))));
-  } else if (kind == LMN_KIND_INPUTS) {
-    QM31 is_last = c[2], not_last = one_minus(is_last);
-    out.push_back(q_mul(is_last, qsub1(is_last)));
-    out.push_back(q_mul(not_last, q_sub(c[3], c[0])));
-    out.push_back(q_mul(not_last, qsub1(q_sub(c[4], c[1]))));
-  } else {  // SumReduce / MaxReduce / Contiguous / Sin / Exp2 / Log2 share the id/idx prefix (columns 0..6)
-    QM31 is_last = c[3], not_last = one_minus(is_last);
-    out.push_back(q_mul(is_last, qsub1(is_last)));
-    if (kind == LMN_KIND_SUM_REDUCE) {
-      QM31 ils = c[11];
-      out.push_back(q_mul(ils, qsub1(ils)));
-      out.push_back(q_sub(c[10], q_add(c[9], c[7])));
-      out.push_back(q_mul(q_sub(c[8], c[10]), ils));
-    } else if (kind == LMN_KIND_MAX_REDUCE) {
-      QM31 ils = c[11], im = c[12];
-      out.push_back(q_mul(ils, qsub1(ils)));
-      out.push_back(q_mul(im, qsub1(im)));
-      out.push_back(q_mul(im, q_sub(c[10], c[7])));
-      out.push_back(q_mul(one_minus(im), q_sub(c[10], c[9])));
-      out.push_back(q_mul(q_sub(c[8], c[10]), ils));
-    }
-    out.push_back(q_mul(not_last, q_sub(c[4], c[0])));
-    out.push_back(q_mul(not_last, q_sub(c[5], c[1])));
-    out.push_back(q_mul(not_last, qsub1(q_sub(c[6], c[2]))));
+  auto emit = [&](QM31 v) { out.push_back(v); };
+#define LMN_LC_CASE(K) case K: local_constraints<K>(c.data(), emit); break;
+  switch (kind) {
+    LMN_LC_CASE(0) LMN_LC_CASE(1) LMN_LC_CASE(2) LMN_LC_CASE(3) LMN_LC_CASE(4) LMN_LC_CASE(5) LMN_LC_CASE(6) LMN_LC_CASE(7)
+    LMN_LC_CASE(8) LMN_LC_CASE(9) LMN_LC_CASE(10) LMN_LC_CASE(11) LMN_LC_CASE(12) LMN_LC_CASE(13) LMN_LC_CASE(14)
+    LMN_LC_CASE(15) LMN_LC_CASE(16)
   }
+#undef LMN_LC_CASE
   return out;
 }
 
@@ -205,7 +103,7 @@ QM31 eval_composition_at_point(const std::vector<Instance>& inst,
     const ComponentSpec* sp = ci.spec;
     std::vector<QM31> main(sp->n_cols);
     for (int c = 0; c < sp->n_cols; ++c) main[c] = sv[1][ci.main_start + c][0];
-    std::vector<QM31> cons = local_constraints(sp->kind, main);
+    std::vector<QM31> cons = local_constraints_at(sp->kind, main);
     QM31 prev = q_zero();
     QM31 shift = q_mul_m(ci.claimed, m_inv((uint32_t)((1ull << ci.log_size) % P31)));
     for (int j = 0; j < sp->n_rel; ++j) {

@@ -9,22 +9,22 @@ namespace lmn {
 
 constexpr uint32_t P31 = 0x7fffffffu;
 
-LMN_HD uint32_t m_add(uint32_t a, uint32_t b) {
+LMN_HD constexpr uint32_t m_add(uint32_t a, uint32_t b) {
   uint32_t s = a + b;
   return s >= P31 ? s - P31 : s;
 }
-LMN_HD uint32_t m_sub(uint32_t a, uint32_t b) {
+LMN_HD constexpr uint32_t m_sub(uint32_t a, uint32_t b) {
   // a >= b: d = a-b < P <= d+P; a < b: d wrapped (> 2^32-P), d+P wraps to a-b+P < P.  sub, add, min.
   uint32_t d = a - b, e = d + P31;
   return d < e ? d : e;
 }
 LMN_HD uint32_t m_neg(uint32_t a) { return a ? P31 - a : 0u; }
-LMN_HD uint32_t m_mul(uint32_t a, uint32_t b) {
+LMN_HD constexpr uint32_t m_mul(uint32_t a, uint32_t b) {
   uint64_t p = (uint64_t)a * (uint64_t)b;
   uint32_t s = (uint32_t)(p & P31) + (uint32_t)(p >> 31);
   return s >= P31 ? s - P31 : s;
 }
-LMN_HD uint32_t m_sqr(uint32_t a) { return m_mul(a, a); }
+LMN_HD constexpr uint32_t m_sqr(uint32_t a) { return m_mul(a, a); }
 LMN_HD uint32_t m_dbl(uint32_t a) { return m_add(a, a); }
 // reduce any 64-bit value to canonical M31
 LMN_HD uint32_t m_red64(uint64_t p) {

@@ -1,6 +1,7 @@
 // gfx950 kernels, part 5: constraint quotients of all 17 components, point evaluation, FRI quotients and folds
 // (SURVEY.md section 8a rows a7, a9).
 #include "kernels_common.h"
+#include "constraints.h"
 
 namespace lmn {
 
@@ -45,16 +46,6 @@ struct ConsAcc {
   }
 };
 
-template <int NCOLS>
-LMN_D void load_row(const uint32_t* __restrict__ base, uint64_t stride, uint32_t s, uint32_t* c) {
-#pragma unroll
-  for (int k = 0; k < NCOLS; ++k) c[k] = base[(uint64_t)k * stride + s];
-}
-
-LMN_D QM31 load_secure(const uint32_t* __restrict__ base, uint64_t stride, uint32_t s) {
-  return QM31{base[s], base[stride + s], base[2 * stride + s], base[3 * stride + s]};
-}
-
 // logup constraints for NREL relations; values are passed by value (no indexed private arrays:
 // those get promoted to LDS and cost occupancy).  rc[j]: 0 = NodeElements (z, alpha); 1 = width-1
 // LUT relation val - z2 (range check); 2 = width-2 LUT relation val + alpha2*id - z2 (sin/exp2/log2).
@@ -98,153 +89,29 @@ LMN_KERNEL k_composition(CompositionArgs a) {
                                  : CompElems{a.z, a.alpha, a.z2, a.alpha2};
   const uint32_t* __restrict__ mn = a.main;   // wave-uniform column bases, the row as a 32-bit lane offset (ld_ub)
   const uint64_t cstride = a.stride;
-#define LMN_COL(k) ld_col(mn, (k), cstride, t)
-  if (KIND == 0 || KIND == 1) {
-    // Add (15 cols) / Mul (16 cols: rem inserted at 12)
-    constexpr bool mul = KIND == 1;
-    constexpr int mo = mul ? 13 : 12;
-    const uint32_t node = LMN_COL(0), lhs_id = LMN_COL(1), rhs_id = LMN_COL(2), idx = LMN_COL(3), is_last = LMN_COL(4);
-    const uint32_t n_node = LMN_COL(5), n_lhs = LMN_COL(6), n_rhs = LMN_COL(7), n_idx = LMN_COL(8);
-    const uint32_t lhs = LMN_COL(9), rhs = LMN_COL(10), out = LMN_COL(11);
-    const uint32_t m0 = LMN_COL(mo), m1 = LMN_COL(mo + 1), m2 = LMN_COL(mo + 2);
-    ca.add_m(m_mul(is_last, m_sub(is_last, 1u)));
-    if (mul) {
-      const uint32_t rem = LMN_COL(12);
-      ca.add_m(m_sub(m_mul(lhs, rhs), m_add(m_mul(out, 4096u), rem)));
-      ca.add_m(0u);  // second eval_fixed_mul slot: zero on rem == 0 (KAT-pinned form)
+  // the row in registers (compile-time indices only), its local constraints (constraints.h), then the relations as the
+  // component's table entry wires them: main columns, or the preprocessed LUT columns of a lookup component
+  constexpr ComponentSpec sp = kSpecs[KIND];
+  constexpr int NC = sp.n_cols, NR = sp.n_rel;
+  uint32_t c[NC];
+#pragma unroll
+  for (int k = 0; k < NC; ++k) c[k] = ld_col(mn, k, cstride, t);
+  local_constraints<KIND>(c, [&](uint32_t v) { ca.add_m(v); });
+  uint32_t rm[NR], rv[NR], ri[NR];
+  int rc[NR];
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    rm[j] = c[sp.rel_mult[j]];
+    if (sp.rel_pre[j]) {
+      rv[j] = ld_ub(sp.rel_val[j] ? a.pre2 : a.pre, t);
+      ri[j] = sp.rel_id[j] < 0 ? 0u : ld_ub(sp.rel_id[j] ? a.pre2 : a.pre, t);
     } else {
-      ca.add_m(m_sub(out, m_add(lhs, rhs)));
+      rv[j] = c[sp.rel_val[j]];
+      ri[j] = sp.rel_id[j] < 0 ? 0u : c[sp.rel_id[j]];
     }
-    const uint32_t not_last = m_sub(1u, is_last);
-    ca.add_m(m_mul(not_last, m_sub(n_node, node)));
-    ca.add_m(m_mul(not_last, m_sub(n_lhs, lhs_id)));
-    ca.add_m(m_mul(not_last, m_sub(n_rhs, rhs_id)));
-    ca.add_m(m_mul(not_last, m_sub(m_sub(n_idx, idx), 1u)));
-    const uint32_t rm[3] = {m0, m1, m2}, rv[3] = {lhs, rhs, out}, ri[3] = {lhs_id, rhs_id, node};
-    const int rc[3] = {0, 0, 0};
-    logup_constraints<3>(ca, a, ce, rm, rv, ri, rc, false, s, t, E);
-  } else if (KIND == 2 || KIND == 7) {
-    // Recip / Sqrt (13 cols; the eval_fixed_* forms are unpinned natural identities)
-    const uint32_t node = LMN_COL(0), in_id = LMN_COL(1), idx = LMN_COL(2), is_last = LMN_COL(3);
-    const uint32_t n_node = LMN_COL(4), n_in = LMN_COL(5), n_idx = LMN_COL(6);
-    const uint32_t inp = LMN_COL(7), out = LMN_COL(8), rem = LMN_COL(9), scale = LMN_COL(10);
-    const uint32_t m0 = LMN_COL(11), m1 = LMN_COL(12);
-    ca.add_m(m_mul(is_last, m_sub(is_last, 1u)));
-    if (KIND == 2)
-      ca.add_m(m_sub(m_sqr(scale), m_add(m_mul(inp, out), rem)));
-    else
-      ca.add_m(m_sub(m_mul(inp, scale), m_add(m_sqr(out), rem)));
-    const uint32_t not_last = m_sub(1u, is_last);
-    ca.add_m(m_mul(not_last, m_sub(n_node, node)));
-    ca.add_m(m_mul(not_last, m_sub(n_in, in_id)));
-    ca.add_m(m_mul(not_last, m_sub(m_sub(n_idx, idx), 1u)));
-    const uint32_t rm[2] = {m0, m1}, rv[2] = {inp, out}, ri[2] = {in_id, node};
-    const int rc[2] = {0, 0};
-    logup_constraints<2>(ca, a, ce, rm, rv, ri, rc, false, s, t, E);
-  } else if (KIND == 8) {
-    // Rem (16 cols): lhs = rhs*quotient + rem (unpinned form); the out relation carries `rem`
-    const uint32_t node = LMN_COL(0), lhs_id = LMN_COL(1), rhs_id = LMN_COL(2), idx = LMN_COL(3), is_last = LMN_COL(4);
-    const uint32_t n_node = LMN_COL(5), n_lhs = LMN_COL(6), n_rhs = LMN_COL(7), n_idx = LMN_COL(8);
-    const uint32_t lhs = LMN_COL(9), rhs = LMN_COL(10), rem = LMN_COL(11), quo = LMN_COL(12);
-    const uint32_t m0 = LMN_COL(13), m1 = LMN_COL(14), m2 = LMN_COL(15);
-    ca.add_m(m_mul(is_last, m_sub(is_last, 1u)));
-    ca.add_m(m_sub(lhs, m_add(m_mul(rhs, quo), rem)));
-    const uint32_t not_last = m_sub(1u, is_last);
-    ca.add_m(m_mul(not_last, m_sub(n_node, node)));
-    ca.add_m(m_mul(not_last, m_sub(n_lhs, lhs_id)));
-    ca.add_m(m_mul(not_last, m_sub(n_rhs, rhs_id)));
-    ca.add_m(m_mul(not_last, m_sub(m_sub(n_idx, idx), 1u)));
-    const uint32_t rm[3] = {m0, m1, m2}, rv[3] = {lhs, rhs, rem}, ri[3] = {lhs_id, rhs_id, node};
-    const int rc[3] = {0, 0, 0};
-    logup_constraints<3>(ca, a, ce, rm, rv, ri, rc, false, s, t, E);
-  } else if (KIND == 13) {
-    // LessThan (22 cols; less_than/component.rs:48-185): 9 local constraints, 3 node relations +
-    // 4 range-check relations on the 8-bit limbs of diff
-    const uint32_t node = LMN_COL(0), lhs_id = LMN_COL(1), rhs_id = LMN_COL(2), idx = LMN_COL(3), is_last = LMN_COL(4);
-    const uint32_t n_node = LMN_COL(5), n_lhs = LMN_COL(6), n_rhs = LMN_COL(7), n_idx = LMN_COL(8);
-    const uint32_t lhs = LMN_COL(9), rhs = LMN_COL(10), out = LMN_COL(11), diff = LMN_COL(12), borrow = LMN_COL(13);
-    const uint32_t l0 = LMN_COL(14), l1 = LMN_COL(15), l2 = LMN_COL(16), l3 = LMN_COL(17);
-    const uint32_t m0 = LMN_COL(18), m1 = LMN_COL(19), m2 = LMN_COL(20), md = LMN_COL(21);
-    ca.add_m(m_mul(is_last, m_sub(is_last, 1u)));
-    ca.add_m(m_mul(borrow, m_sub(borrow, 1u)));
-    ca.add_m(m_sub(out, m_mul(m_sub(1u, borrow), 4096u)));
-    ca.add_m(m_sub(m_add(lhs, diff), rhs));  // - borrow * (2^31 - 1), which is 0 in M31
-    ca.add_m(m_sub(diff, m_add(m_add(m_mul(l3, 1u << 24), m_mul(l2, 1u << 16)), m_add(m_mul(l1, 1u << 8), l0))));
-    const uint32_t not_last = m_sub(1u, is_last);
-    ca.add_m(m_mul(not_last, m_sub(n_node, node)));
-    ca.add_m(m_mul(not_last, m_sub(n_lhs, lhs_id)));
-    ca.add_m(m_mul(not_last, m_sub(n_rhs, rhs_id)));
-    ca.add_m(m_mul(not_last, m_sub(m_sub(n_idx, idx), 1u)));
-    const uint32_t rm[7] = {m0, m1, m2, md, md, md, md}, rv[7] = {lhs, rhs, out, l0, l1, l2, l3};
-    const uint32_t ri[7] = {lhs_id, rhs_id, node, 0u, 0u, 0u, 0u};
-    const int rc[7] = {0, 0, 0, 1, 1, 1, 1};
-    logup_constraints<7>(ca, a, ce, rm, rv, ri, rc, false, s, t, E);
-  } else if (KIND == 14) {
-    // RangeCheckLookup: multiplicity column + preprocessed LUT column, relation (-multiplicity, [lut])
-    const uint32_t rm[1] = {LMN_COL(0)}, rv[1] = {ld_ub(a.pre, t)}, ri[1] = {0u};
-    const int rc[1] = {1};
-    logup_constraints<1>(ca, a, ce, rm, rv, ri, rc, true, s, t, E);
-  } else if (KIND == 4) {
-    // SinLookup / Exp2Lookup / Log2Lookup (lookups/sin/component.rs:40-59): multiplicity column + the two
-    // preprocessed LUT columns, relation (-multiplicity, [lut_0, lut_1])
-    const uint32_t rm[1] = {LMN_COL(0)}, rv[1] = {ld_ub(a.pre, t)}, ri[1] = {ld_ub(a.pre2, t)};
-    const int rc[1] = {2};
-    logup_constraints<1>(ca, a, ce, rm, rv, ri, rc, true, s, t, E);
-  } else if (KIND == 3) {
-    // Sin / Exp2 / Log2 (12 cols; sin/component.rs:50-122): the function value is enforced by the LUT
-    // relation (lookup_mult, [input, out]) only
-    const uint32_t node = LMN_COL(0), in_id = LMN_COL(1), idx = LMN_COL(2), is_last = LMN_COL(3);
-    const uint32_t n_node = LMN_COL(4), n_in = LMN_COL(5), n_idx = LMN_COL(6);
-    const uint32_t inp = LMN_COL(7), out = LMN_COL(8);
-    const uint32_t m0 = LMN_COL(9), m1 = LMN_COL(10), m2 = LMN_COL(11);
-    ca.add_m(m_mul(is_last, m_sub(is_last, 1u)));
-    const uint32_t not_last = m_sub(1u, is_last);
-    ca.add_m(m_mul(not_last, m_sub(n_node, node)));
-    ca.add_m(m_mul(not_last, m_sub(n_in, in_id)));
-    ca.add_m(m_mul(not_last, m_sub(m_sub(n_idx, idx), 1u)));
-    const uint32_t rm[3] = {m0, m1, m2}, rv[3] = {inp, out, inp}, ri[3] = {in_id, node, out};
-    const int rc[3] = {0, 0, 2};
-    logup_constraints<3>(ca, a, ce, rm, rv, ri, rc, false, s, t, E);
-  } else if (KIND == 5 || KIND == 6 || KIND == 16) {
-    // SumReduce (14 cols) / MaxReduce (15) / Contiguous (11): shared id/idx prefix, 2 relations
-    const uint32_t node = LMN_COL(0), in_id = LMN_COL(1), idx = LMN_COL(2), is_last = LMN_COL(3);
-    const uint32_t n_node = LMN_COL(4), n_in = LMN_COL(5), n_idx = LMN_COL(6);
-    const uint32_t inp = LMN_COL(7), out = LMN_COL(8);
-    constexpr int mo = KIND == 5 ? 12 : (KIND == 6 ? 13 : 9);
-    const uint32_t m0 = LMN_COL(mo), m1 = LMN_COL(mo + 1);
-    ca.add_m(m_mul(is_last, m_sub(is_last, 1u)));
-    if (KIND == 5) {
-      const uint32_t acc = LMN_COL(9), next_acc = LMN_COL(10), ils = LMN_COL(11);
-      ca.add_m(m_mul(ils, m_sub(ils, 1u)));
-      ca.add_m(m_sub(next_acc, m_add(acc, inp)));
-      ca.add_m(m_mul(m_sub(out, next_acc), ils));
-    } else if (KIND == 6) {
-      const uint32_t mx = LMN_COL(9), next_mx = LMN_COL(10), ils = LMN_COL(11), im = LMN_COL(12);
-      ca.add_m(m_mul(ils, m_sub(ils, 1u)));
-      ca.add_m(m_mul(im, m_sub(im, 1u)));
-      ca.add_m(m_mul(im, m_sub(next_mx, inp)));
-      ca.add_m(m_mul(m_sub(1u, im), m_sub(next_mx, mx)));
-      ca.add_m(m_mul(m_sub(out, next_mx), ils));
-    }
-    const uint32_t not_last = m_sub(1u, is_last);
-    ca.add_m(m_mul(not_last, m_sub(n_node, node)));
-    ca.add_m(m_mul(not_last, m_sub(n_in, in_id)));
-    ca.add_m(m_mul(not_last, m_sub(m_sub(n_idx, idx), 1u)));
-    const uint32_t rm[2] = {m0, m1}, rv[2] = {inp, out}, ri[2] = {in_id, node};
-    const int rc[2] = {0, 0};
-    logup_constraints<2>(ca, a, ce, rm, rv, ri, rc, false, s, t, E);
-  } else {
-    const uint32_t node = LMN_COL(0), idx = LMN_COL(1), is_last = LMN_COL(2), n_node = LMN_COL(3), n_idx = LMN_COL(4);
-    const uint32_t val = LMN_COL(5), mult = LMN_COL(6);
-    ca.add_m(m_mul(is_last, m_sub(is_last, 1u)));
-    const uint32_t not_last = m_sub(1u, is_last);
-    ca.add_m(m_mul(not_last, m_sub(n_node, node)));
-    ca.add_m(m_mul(not_last, m_sub(m_sub(n_idx, idx), 1u)));
-    const uint32_t rm[1] = {mult}, rv[1] = {val}, ri[1] = {node};
-    const int rc[1] = {0};
-    logup_constraints<1>(ca, a, ce, rm, rv, ri, rc, false, s, t, E);
+    rc[j] = sp.rel_elems[j] == ELEMS_NODE ? 0 : sp.rel_id[j] < 0 ? 1 : 2;   // NodeElements / width-1 LUT / width-2 LUT
   }
-#undef LMN_COL
+  logup_constraints<NR>(ca, a, ce, rm, rv, ri, rc, sp.rel_neg[0] != 0, s, t, E);
   QM31 r = q_mul_m(qacc_reduce(ca.acc), a.zinv[(s >> a.log_size) & 1u]);
   if (a.accumulate) {
     r.a = m_add(r.a, ld_ub(a.out, s));
@@ -263,26 +130,13 @@ void launch_composition(const CompositionArgs& a, lmn_stream_t s) {
   if (a.n_rows == 0 || (uint64_t)a.row0 + a.n_rows > (1ull << a.eval_log) || a.stride < a.n_rows || !a.prev_last)
     throw LmnError(-100, "composition: bad row block");
   dim3 g(cdiv(a.n_rows, TPB)), b(TPB);
-  switch (a.kind) {
-    case 0: LMN_LAUNCH(k_composition<0>, g, b, 0, s, a); break;
-    case 1: LMN_LAUNCH(k_composition<1>, g, b, 0, s, a); break;
-    case 2: LMN_LAUNCH(k_composition<2>, g, b, 0, s, a); break;
-    case 3:
-    case 9:
-    case 11: LMN_LAUNCH(k_composition<3>, g, b, 0, s, a); break;
-    case 4:
-    case 10:
-    case 12: LMN_LAUNCH(k_composition<4>, g, b, 0, s, a); break;
-    case 5: LMN_LAUNCH(k_composition<5>, g, b, 0, s, a); break;
-    case 6: LMN_LAUNCH(k_composition<6>, g, b, 0, s, a); break;
-    case 7: LMN_LAUNCH(k_composition<7>, g, b, 0, s, a); break;
-    case 8: LMN_LAUNCH(k_composition<8>, g, b, 0, s, a); break;
-    case 13: LMN_LAUNCH(k_composition<13>, g, b, 0, s, a); break;
-    case 14: LMN_LAUNCH(k_composition<14>, g, b, 0, s, a); break;
-    case 15: LMN_LAUNCH(k_composition<15>, g, b, 0, s, a); break;
-    case 16: LMN_LAUNCH(k_composition<16>, g, b, 0, s, a); break;
+#define LMN_COMP_CASE(K) case K: LMN_LAUNCH(k_composition<K>, g, b, 0, s, a); break;
+  switch (composition_shape(a.kind)) {   // one instantiation per shape: Exp2 / Log2 run Sin's, their lookups SinLookup's
+    LMN_COMP_CASE(0) LMN_COMP_CASE(1) LMN_COMP_CASE(2) LMN_COMP_CASE(3) LMN_COMP_CASE(4) LMN_COMP_CASE(5) LMN_COMP_CASE(6)
+    LMN_COMP_CASE(7) LMN_COMP_CASE(8) LMN_COMP_CASE(13) LMN_COMP_CASE(14) LMN_COMP_CASE(15) LMN_COMP_CASE(16)
     default: throw LmnError(-100, "composition: unsupported component kind");
   }
+#undef LMN_COMP_CASE
 }
 
 LMN_KERNEL k_secure_add(uint32_t* __restrict__ out, const uint32_t* __restrict__ in, uint64_t n) {

@@ -2,6 +2,7 @@
 // generation (`process_trace`, section 8f-3) and the level-2 column ops (bit reversal, decompose).  One wavefront = 64 lanes;
 // global accesses are laid out so that consecutive lanes touch consecutive 4-byte words of a column.
 #include "kernels_common.h"
+#include "constraints.h"
 
 namespace lmn {
 
@@ -448,78 +449,6 @@ void launch_trace_lut(const int32_t* input, const TraceView& view, uint64_t n, c
 // =============================================================================================
 // lmn_trace_check: the rows that break a local constraint, the logup tuples that do not balance
 // =============================================================================================
-LMN_HD constexpr int tc_ncols(int kind) {
-  return kind == 0 ? 15 : kind == 1 ? 16 : kind == 2 ? 13 : kind == 3 ? 12 : kind == 5 ? 14 : kind == 6 ? 15 : kind == 7 ? 13
-       : kind == 8 ? 16 : kind == 9 ? 12 : kind == 11 ? 12 : kind == 13 ? 22 : kind == 15 ? 7 : kind == 16 ? 11 : 1;
-}
-LMN_HD constexpr int tc_nlocal(int kind) {
-  return kind == 0 ? 6 : kind == 1 ? 7 : kind == 2 ? 5 : kind == 3 ? 4 : kind == 5 ? 7 : kind == 6 ? 9 : kind == 7 ? 5
-       : kind == 8 ? 6 : kind == 9 ? 4 : kind == 11 ? 4 : kind == 13 ? 9 : kind == 15 ? 3 : kind == 16 ? 4 : 0;
-}
-LMN_HD uint32_t tc_bool(uint32_t b) { return m_mul(b, m_sub(b, 1u)); }
-// not_last * (next - cur) per id column, then not_last * (next_idx - idx - 1): the transition constraints every component
-// ends its local list with.  c[first .. first + n] = the n id columns and idx, c[first + n + 2 ..] their next_* columns
-// (is_last sits between them)
-template <int N>
-LMN_D void tc_transition(const uint32_t* c, int first, uint32_t* v) {
-  const uint32_t not_last = m_sub(1u, c[first + N + 1]);
-#pragma unroll
-  for (int k = 0; k < N; ++k) v[k] = m_mul(not_last, m_sub(c[first + N + 2 + k], c[first + k]));
-  v[N] = m_mul(not_last, m_sub(m_sub(c[first + 2 * N + 2], c[first + N]), 1u));
-}
-// The component's local constraints on one row, in `evaluate` order (crates/air/src/components/*/component.rs; the host's
-// restatement at a point is components.cpp local_constraints, the composition's is k_composition): v[0 .. tc_nlocal(KIND))
-template <int KIND>
-LMN_D void tc_local(const uint32_t* c, uint32_t* v) {
-  if constexpr (KIND == 0 || KIND == 1 || KIND == 8) {   // node, lhs_id, rhs_id, idx, is_last, next_*, lhs, rhs, out, ...
-    v[0] = tc_bool(c[4]);
-    if constexpr (KIND == 0) {
-      v[1] = m_sub(c[11], m_add(c[9], c[10]));
-      tc_transition<3>(c, 0, v + 2);
-    } else if constexpr (KIND == 1) {
-      v[1] = m_sub(m_mul(c[9], c[10]), m_add(m_mul(c[11], 4096u), c[12]));
-      v[2] = 0u;   // eval_fixed_mul's second slot: identically zero
-      tc_transition<3>(c, 0, v + 3);
-    } else {       // Rem: lhs = rhs * quotient + rem (rem at 11, quotient at 12)
-      v[1] = m_sub(c[9], m_add(m_mul(c[10], c[12]), c[11]));
-      tc_transition<3>(c, 0, v + 2);
-    }
-  } else if constexpr (KIND == 2 || KIND == 7) {   // node, input_id, idx, is_last, next_*, input, out, rem, scale
-    v[0] = tc_bool(c[3]);
-    v[1] = KIND == 2 ? m_sub(m_sqr(c[10]), m_add(m_mul(c[7], c[8]), c[9]))
-                     : m_sub(m_mul(c[7], c[10]), m_add(m_sqr(c[8]), c[9]));
-    tc_transition<2>(c, 0, v + 2);
-  } else if constexpr (KIND == 15) {               // node, idx, is_last, next_node, next_idx, val, multiplicity
-    v[0] = tc_bool(c[2]);
-    tc_transition<1>(c, 0, v + 1);
-  } else if constexpr (KIND == 5) {                // ..., input, out, acc, next_acc, is_last_step
-    v[0] = tc_bool(c[3]);
-    v[1] = tc_bool(c[11]);
-    v[2] = m_sub(c[10], m_add(c[9], c[7]));
-    v[3] = m_mul(m_sub(c[8], c[10]), c[11]);
-    tc_transition<2>(c, 0, v + 4);
-  } else if constexpr (KIND == 6) {                // ..., input, out, max, next_max, is_last_step, is_max
-    v[0] = tc_bool(c[3]);
-    v[1] = tc_bool(c[11]);
-    v[2] = tc_bool(c[12]);
-    v[3] = m_mul(c[12], m_sub(c[10], c[7]));
-    v[4] = m_mul(m_sub(1u, c[12]), m_sub(c[10], c[9]));
-    v[5] = m_mul(m_sub(c[8], c[10]), c[11]);
-    tc_transition<2>(c, 0, v + 6);
-  } else if constexpr (KIND == 13) {               // less_than/component.rs:48-185
-    const uint32_t borrow = c[13];
-    v[0] = tc_bool(c[4]);
-    v[1] = tc_bool(borrow);
-    v[2] = m_sub(c[11], m_mul(m_sub(1u, borrow), 4096u));
-    v[3] = m_sub(m_add(c[9], c[12]), c[10]);       // - borrow * (2^31 - 1), which is 0 in M31
-    v[4] = m_sub(c[12], m_add(m_add(m_mul(c[17], 1u << 24), m_mul(c[16], 1u << 16)), m_add(m_mul(c[15], 1u << 8), c[14])));
-    tc_transition<3>(c, 0, v + 5);
-  } else if constexpr (tc_nlocal(KIND) == 4) {     // Contiguous, Sin, Exp2, Log2: boolean + transitions only
-    v[0] = tc_bool(c[3]);
-    tc_transition<2>(c, 0, v + 1);
-  }
-}
-
 // add `w` to the tuple `key` of one element set and lower its first mention: linear probing, the slot claimed by a 64-bit
 // compare-and-swap on the key.  The plain reads in front of the atomics can only be stale towards "free" and "larger", in
 // which case the atomic decides; the table holds at most half as many keys as slots, so the walk ends.
@@ -545,7 +474,7 @@ LMN_D void tc_insert(const TcSet S, unsigned long long key, unsigned long long w
 // LDS, direct-indexed, and reach the table once per workgroup.
 template <int KIND, bool COLS>
 LMN_KERNEL k_trace_check(TcTable tb, TcOut out) {
-  constexpr int NC = tc_ncols(KIND), NL = tc_nlocal(KIND), ST = NC | 1;
+  constexpr int NC = kSpecs[KIND].n_cols, NL = kSpecs[KIND].n_local, ST = NC | 1;
   LMN_SHARED uint32_t tile[COLS ? 1 : TPB * ST];
   LMN_SHARED unsigned long long rc_sum[KIND == 13 ? 256 : 1], rc_first[KIND == 13 ? 256 : 1];
   const uint64_t row0 = (uint64_t)blockIdx.x * TPB;
@@ -584,8 +513,9 @@ LMN_KERNEL k_trace_check(TcTable tb, TcOut out) {
   const bool live = on && n_bad == 0u;
   const unsigned lane = threadIdx.x & 63u;
   if constexpr (NL > 0) {
-    uint32_t v[NL];
-    tc_local<KIND>(c, v);
+    uint32_t v[NL];   // the component's local constraints on this row, one per slot (constraints.h)
+    int n = 0;
+    local_constraints<KIND>(c, [&](uint32_t x) { v[n++] = x; });
 #pragma unroll
     for (int sl = 0; sl < NL; ++sl) {
       const unsigned long long bal = lmn_ballot(live && v[sl] != 0u);

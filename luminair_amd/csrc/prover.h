@@ -8,32 +8,14 @@
 #include <vector>
 
 #include "../../include/luminair_hip.h"
+#include "constraints.h"
 #include "host.h"
 #include "kernels.h"
 
 namespace lmn {
 
-constexpr int MAX_REL = 7;
-struct ComponentSpec {
-  int kind;
-  int n_cols;
-  int is_last_col;
-  int n_rel;
-  int rel_mult[MAX_REL], rel_val[MAX_REL], rel_id[MAX_REL];  // rel_id < 0: width-1 relation (value only)
-  int n_local;                // number of local constraints (including zero slots)
-  int rel_elems[MAX_REL];     // ELEMS_*: 0 NodeElements, 1 RangeCheckLookup, 2 SinLookup, 3 Exp2Lookup, 4 Log2Lookup
-  int rel_neg[MAX_REL];       // numerator is -mult
-  int rel_pre[MAX_REL];       // rel_val / rel_id index the component's preprocessed columns
-  int n_pre;                  // preprocessed (tree 0) columns read (0..2)
-  int pre_id[2];              // PRE_*: position in PreProcessedTrace order (preprocessed.rs:157-179)
-  int n_pad;                  // extra non-zero padding cells besides is_last_col = 1
-  int pad_col[4];
-  uint32_t pad_val[4];
-};
+// kSpecs[kind] (constraints.h); nullptr for an unknown kind
 const ComponentSpec* component_spec(int kind);
-enum { ELEMS_NODE = 0, ELEMS_RANGE_CHECK = 1, ELEMS_SIN = 2, ELEMS_EXP2 = 3, ELEMS_LOG2 = 4, N_ELEMS = 5 };
-// tree-0 column order before the stable size sort: sin_lut_0/1, exp2_lut_0/1, log2_lut_0/1, range_check_8
-enum { PRE_SIN0 = 0, PRE_EXP20 = 2, PRE_LOG20 = 4, PRE_RANGE_CHECK = 6, N_PRE_IDS = 7 };
 // relation element sets drawn after the main commitment (components/mod.rs:227-235, lookups/mod.rs:44-51)
 struct RelElems {
   QM31 z[N_ELEMS], alpha[N_ELEMS];
@@ -46,8 +28,9 @@ int relation_draw_sets(uint32_t protocol_flags, int sets_out[5]);
 inline int claim_slots(uint32_t protocol_flags) { return (protocol_flags & LMN_PV_CLAIM17) ? 17 : 8; }
 
 // Constraint slots of a component under the protocol's constraint-form bits (LMN_PV_*_SLOT(S) / _NEG, luminair_hip.h).
-// "Kernel slot" k = the k-th value k_composition<KIND> (and local_constraints() on the host) emits: the local constraints
-// in `evaluate` order with the KAT-era shape (eval_fixed_mul: two slots; recip / sqrt / rem: one), then one per relation.
+// "Kernel slot" k = the k-th value of the component: what local_constraints<KIND> (constraints.h: the one statement that
+// k_composition, k_trace_check and the host's evaluation at the OODS point all instantiate) emits, in `evaluate` order with
+// the KAT-era shape (eval_fixed_mul: two slots; recip / sqrt / rem: one), then one per relation.
 // The protocol may give a helper one slot more or less and the opposite sign; that only changes WHICH power of the
 // composition randomness multiplies a kernel slot, so it is decided here on the host and the kernels never see the bits.
 struct ConstraintLayout {

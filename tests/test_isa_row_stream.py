@@ -61,7 +61,7 @@ def test_two_workgroups_fit_a_cu_at_the_widest_launch(chunk_kernels):
     for name, k in chunk_kernels.items():
         assert k["lds"] + dynamic <= LDS_BUDGET, (name, k["lds"], dynamic)
     # and the widest component of the protocol is inside what the launch admits
-    spec = open(os.path.join(CSRC, "components.cpp")).read()
+    spec = open(os.path.join(CSRC, "constraints.h")).read()       # kSpecs: the table of the components' shapes
     widest = max(int(m) for m in re.findall(r"\{LMN_KIND_\w+, (\d+),", spec))
     assert widest <= max_cols, (widest, max_cols)
 

@@ -264,36 +264,61 @@ def check_slots(lib, kinds=None):
 
 # ------------------------------------------------------------------------------------------------ 3: agreement with the prover
 def prover_cases():
-    """(name, variant, tables): single-cell changes of small valid pies"""
+    """(name, variant, tables, luts): single-cell changes of small valid pies.  Between them the changes break a local
+    constraint of every component that has one, so that the host's evaluation at the OODS point (the prover's self-check and
+    lmn_verify) meets each component's constraints on a row that violates them as well as on rows that satisfy them."""
     def changed(tabs, t, r, c, delta):
         tabs = [(k, rows.copy()) for k, rows in tabs]
         tabs[t][1][r, c] = (int(tabs[t][1][r, c]) + delta) % P
         return tabs
+
+    def of_kind(tabs, kind, r, c):                   # + 1 in row r, column c of the table of that kind
+        return changed(tabs, [k for k, _ in tabs].index(kind), r, c, 1)
     se, lt = syn.simple_example(), syn.less_than_graph(19)
-    return [("simple_example unchanged", KAT, se),
-            ("Mul out + 1", KAT, changed(se, 1, 2, 11, 1)),
-            ("Add lhs + 1", KAT, changed(se, 0, 0, 9, 1)),
-            ("Add is_last of a middle row", KAT, changed(se, 0, 1, 4, 1)),
-            ("Add next_node of the last row (unconstrained)", KAT, changed(se, 0, 3, 5, 7)),
-            ("Mul out multiplicity 2 -> 3", KAT, changed(se, 1, 0, 15, 1)),
-            ("Add lhs_id of the last row", KAT, changed(se, 0, 3, 1, 1)),
-            ("LessThan limb 0 + 1", PINNED, changed(lt, 1, 5, 14, 1)),
-            ("RangeCheckLookup multiplicity + 1", PINNED, changed(lt, 2, 200, 0, 1))]
+    # the smallest tables the prover takes: everything below 16 rows is padded to 2^4
+    ch, sr, ll = syn.chain_graph(5), syn.sqrt_rem_graph(5), syn.linear_layer(2, 4, with_max=True)
+    act = {n: syn.activation_graph(5, names=(n,), ranges={n: r}) for n, r in (("sin", (-7, 7)), ("exp2", (-7, 7)), ("log2", (1, 15)))}
+    x = np.arange(5) - 2
+    co = [(air.KIND_INPUTS, syn.inputs_rows(x, 0, 1)), (air.KIND_CONTIGUOUS, syn.contiguous_rows(x, node=2, input_id=0))]
+    return [("simple_example unchanged", KAT, se, None),
+            ("Mul out + 1", KAT, changed(se, 1, 2, 11, 1), None),
+            ("Add lhs + 1", KAT, changed(se, 0, 0, 9, 1), None),
+            ("Add is_last of a middle row", KAT, changed(se, 0, 1, 4, 1), None),
+            ("Add next_node of the last row (unconstrained)", KAT, changed(se, 0, 3, 5, 7), None),
+            ("Mul out multiplicity 2 -> 3", KAT, changed(se, 1, 0, 15, 1), None),
+            ("Add lhs_id of the last row", KAT, changed(se, 0, 3, 1, 1), None),
+            ("LessThan limb 0 + 1", PINNED, changed(lt, 1, 5, 14, 1), None),
+            ("RangeCheckLookup multiplicity + 1", PINNED, changed(lt, 2, 200, 0, 1), None),
+            # columns that no relation reads: the local constraint is the only thing the change breaks
+            ("Recip rem + 1", KAT, of_kind(ch, air.KIND_RECIP, 2, 9), None),
+            ("Sqrt rem + 1", PINNED, of_kind(sr, air.KIND_SQRT, 2, 9), None),
+            ("Rem quotient + 1", PINNED, of_kind(sr, air.KIND_REM, 2, 12), None),
+            ("Inputs idx of a middle row + 1", PINNED, of_kind(sr, air.KIND_INPUTS, 3, 1), None),
+            ("SumReduce next_acc + 1", KAT, of_kind(ll, air.KIND_SUM_REDUCE, 1, 10), None),
+            ("MaxReduce next_max + 1", KAT, of_kind(ll, air.KIND_MAX_REDUCE, 0, 10), None),
+            ("Contiguous unchanged", PINNED, co, None),
+            ("Contiguous idx of a middle row + 1", PINNED, of_kind(co, air.KIND_CONTIGUOUS, 1, 2), None),
+            ("Sin idx of a middle row + 1", PINNED, of_kind(act["sin"][0], air.KIND_SIN, 1, 2), act["sin"][1]),
+            ("Exp2 idx of a middle row + 1", PINNED, of_kind(act["exp2"][0], air.KIND_EXP2, 1, 2), act["exp2"][1]),
+            ("Log2 idx of a middle row + 1", PINNED, of_kind(act["log2"][0], air.KIND_LOG2, 1, 2), act["log2"][1])]
 
 
 def check_prover_agreement(lib):
-    seen = set()
-    for name, variant, tabs in prover_cases():
+    seen, broken = set(), set()
+    for name, variant, tabs, luts in prover_cases():
         ctx = ctx_for(lib, variant)
-        ref = Ref(tabs)
-        rep = ctx.check_trace(pie(tabs))
+        ref = Ref(tabs, luts)
+        rep = ctx.check_trace(pie(tabs), luts)
         assert_equals_oracle(rep, ref, name)
-        ok, why = proves_and_verifies(ctx, tabs)
+        ok, why = proves_and_verifies(ctx, tabs, luts)
         assert rep.ok == ok, (name, rep.summary, why)
         seen.add(ok)
+        broken |= {kind for _, kind, _, _, _ in ref.constraints}
         if "multiplicity" in name:                   # invisible to lmn_prove: it returns bytes, only the verifier objects
             assert not ok and str(backend.ERR_INVALID_LOGUP) in why.split()[0], (name, why)
     assert seen == {True, False}
+    # the condition on the cases, asserted of the ORACLE's results: a local constraint of every component that has one is broken
+    assert broken == set(LOCAL_KINDS), sorted(broken)
 
 
 # ------------------------------------------------------------------------------------------------ 4: imbalances
