@@ -694,6 +694,54 @@ int lmn_tree_decommit(lmn_ctx* ctx, const lmn_tree* tree, const lmn_col* const* 
  * needs for its witness evaluations, and the queried values of a secure column. */
 int lmn_col_gather(lmn_ctx* ctx, const lmn_col* col, const uint32_t* positions, uint32_t n, uint32_t* host_out);
 void lmn_tree_free(lmn_ctx* ctx, lmn_tree* tree);
+/* FriProver::commit without the last layer's interpolation: the layer loop of lmn_prove's FRI commit phase - the same
+ * function, so the same launches - on secure-column handles, with everything it left in device memory brought to the host.
+ * `cols`: n >= 1 handles of 4 coordinate columns each (the FRI quotient columns, bit-reversed circle-domain evaluations), of
+ * strictly decreasing log sizes; they need not be low-degree.  cols[0] is folded (circle to line) with the alpha drawn after
+ * the first tree's root; cols[k] joins the line layer of half its size.  `start_digest`: the channel's 32-byte digest before
+ * the first root is mixed.  The context's log_last_layer, log_blowup and the LMN_PV_DRAW_CTR_U32 bit of protocol_variant
+ * apply: the loop ends at the layer of 2^(log_last_layer + log_blowup) values.
+ * Result (every pointer from malloc, each released with lmn_free; the struct itself is the caller's):
+ *   trees    t = 0 .. n_trees-1: the first tree (over all of `cols`), then one per inner layer.  roots[32 t], alphas[4 t] (the
+ *            alpha drawn after root t), tree_logs[t], level_masks[t] (bit l set: level l of 2^l hashes was written to device
+ *            memory; clear: a fused launch kept it in registers, or the leaf level was hashed by the launch of the level
+ *            above it), `levels`: the written levels of tree 0, then of tree 1, ..., each tree's from level 0 upwards,
+ *            8 words per hash.
+ *   layers   i = 0 .. n_trees-1: inner layer i (log size tree_logs[0] - 1 - i, committed by tree i + 1), the last one being
+ *            the last layer (no tree).  `values`: 4 x 2^log words per layer, coordinate-major, one layer after the other.
+ *   forms    n_trees + 1 words.  forms[0]: LMN_FRI_FIRST_TREE, or LMN_FRI_FIRST_TREE_BELOW when the first tree's leaf level
+ *            was hashed by the launch of the level above it.  forms[1 + i]: how layer i's values were produced
+ *            (LMN_FRI_FOLD_*) or'ed with how it was committed (LMN_FRI_TREE_*; neither for the last layer).
+ * LMN_ERR_INVALID_ARGUMENT with a text naming the argument, the result zeroed, context and handles usable: a null
+ * pointer, n = 0, a handle that is not 4 columns, sizes not strictly decreasing, a first line layer smaller than the last
+ * layer, a column that would join below the last layer, a sharded context. */
+#define LMN_FRI_FOLD_LAUNCH 1u          /* plain fold launch(es): k_fold (a joining column: one more launch each) */
+#define LMN_FRI_FOLD_IN_LEAVES 2u       /* inside the layer's own leaf hashing (k_merkle_fused<3>) */
+#define LMN_FRI_FOLD_IN_LEAVES_JOIN 3u  /* the same, with a joining quotient column */
+#define LMN_FRI_FOLD_MATERIALISED 4u    /* a fold left for the leaf hashing, made by k_fold after all (layer <= 2^10, or the last) */
+#define LMN_FRI_FOLD_TAIL_FRONT 5u      /* by the tail's launch, in front of its first layer (k_fri_tail) */
+#define LMN_FRI_FOLD_IN_TAIL 6u         /* inside the tail's launch */
+#define LMN_FRI_FOLD_MASK 0xffu
+#define LMN_FRI_TREE_OWN 0x100u         /* committed by launches of its own */
+#define LMN_FRI_TREE_IN_TAIL 0x200u     /* committed inside the tail's launch */
+#define LMN_FRI_FIRST_TREE 0x10000u
+#define LMN_FRI_FIRST_TREE_BELOW 0x10001u
+struct lmn_fri_commit_result {
+  uint32_t n_trees;
+  uint32_t reserved;
+  uint8_t* roots;          /* n_trees x 32 bytes */
+  uint32_t* alphas;        /* n_trees x 4 words */
+  uint32_t* tree_logs;     /* n_trees */
+  uint32_t* level_masks;   /* n_trees */
+  uint32_t* forms;         /* n_trees + 1 */
+  uint32_t* values;        /* n_value_words */
+  uint32_t* levels;        /* n_level_words */
+  uint64_t n_value_words;
+  uint64_t n_level_words;
+};
+typedef struct lmn_fri_commit_result lmn_fri_commit_result;
+int lmn_col_fri_commit(lmn_ctx* ctx, const lmn_col* const* cols, uint32_t n, const uint8_t start_digest[32],
+                       lmn_fri_commit_result* result);
 int lmn_col_accumulate(lmn_ctx* ctx, lmn_col* dst, const lmn_col* src);     /* AccumulationOps::accumulate: dst += src (same shape) */
 /* QuotientOps::accumulate_quotients (one LDE size; samples and limits as in lmn_op_accumulate_quotients: at most 4
  * distinct sample points and 512 samples, else LMN_ERR_INVALID_ARGUMENT): out = 4 coordinate columns */

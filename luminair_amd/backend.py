@@ -134,6 +134,33 @@ class LmnVerifyReport(C.Structure):
                 ("first_failure", C.c_char * 128)]
 
 
+# form codes of lmn_col_fri_commit (LMN_FRI_*)
+FRI_FOLD_LAUNCH, FRI_FOLD_IN_LEAVES, FRI_FOLD_IN_LEAVES_JOIN, FRI_FOLD_MATERIALISED, FRI_FOLD_TAIL_FRONT, FRI_FOLD_IN_TAIL = 1, 2, 3, 4, 5, 6
+FRI_FOLD_MASK, FRI_TREE_OWN, FRI_TREE_IN_TAIL = 0xff, 0x100, 0x200
+FRI_FIRST_TREE, FRI_FIRST_TREE_BELOW = 0x10000, 0x10001
+
+
+class LmnFriCommitResult(C.Structure):
+    """`lmn_fri_commit_result`"""
+    _fields_ = [("n_trees", C.c_uint32), ("reserved", C.c_uint32), ("roots", C.c_void_p), ("alphas", C.c_void_p),
+                ("tree_logs", C.c_void_p), ("level_masks", C.c_void_p), ("forms", C.c_void_p), ("values", C.c_void_p),
+                ("levels", C.c_void_p), ("n_value_words", C.c_uint64), ("n_level_words", C.c_uint64)]
+
+
+@dataclass
+class FriCommit:
+    """What `Context.fri_commit` returns.  Trees t = 0 .. n-1 (the first tree, then one per inner layer); layers i = 0 .. n-1
+    (inner layer i is committed by tree i + 1, the last one is the last layer)."""
+    roots: List[bytes]
+    alphas: List[Tuple[int, int, int, int]]
+    tree_logs: List[int]
+    tree_levels: List[List[Optional[np.ndarray]]]   # [tree][level] -> (2^level, 8) uint32, None: not written to device memory
+    first_tree_form: int
+    layer_logs: List[int]
+    layer_values: List[np.ndarray]                  # (4, 2^log) uint32
+    layer_forms: List[int]                          # FRI_FOLD_* | FRI_TREE_*
+
+
 TRACE_REPORT_MAX = 64   # LMN_TRACE_REPORT_MAX
 ELEM_SET_NAMES = ["NodeElements", "RangeCheck", "Sin", "Exp2", "Log2"]
 
@@ -198,7 +225,7 @@ EXPORTS = ["lmn_abi_version", "lmn_kind_padding_row", "lmn_strerror", "lmn_last_
            "lmn_col_log_size", "lmn_col_device_ptr", "lmn_col_view", "lmn_col_bit_reverse", "lmn_col_precompute_twiddles",
            "lmn_col_interpolate", "lmn_col_evaluate", "lmn_col_evaluate_block", "lmn_col_extend", "lmn_col_eval_at_point",
            "lmn_col_commit", "lmn_tree_root", "lmn_tree_log_size", "lmn_tree_layer_to_cpu", "lmn_tree_free",
-           "lmn_tree_decommit", "lmn_col_gather",
+           "lmn_tree_decommit", "lmn_col_gather", "lmn_col_fri_commit",
            "lmn_col_accumulate", "lmn_col_accumulate_quotients", "lmn_col_fold_line", "lmn_col_fold_circle_into_line",
            "lmn_col_decompose", "lmn_col_logup", "lmn_col_composition", "lmn_kind_constraints", "lmn_kind_relations", "lmn_ctx_set_shard", "lmn_rccl_unique_id", "lmn_ctx_set_shard_rccl", "lmn_ctx_clear_shard",
            "lmn_rows_open", "lmn_rows_push", "lmn_rows_push_pinned", "lmn_rows_sync", "lmn_rows_finish", "lmn_rows_count",
@@ -312,6 +339,7 @@ class Library:
         lib.lmn_tree_decommit.argtypes = [VP, VP, C.POINTER(VP), U32, VP, VP, U32, VP, C.POINTER(VP), C.POINTER(C.c_size_t),
                                           C.POINTER(VP), C.POINTER(C.c_size_t), C.POINTER(VP), C.POINTER(C.c_size_t)]
         lib.lmn_col_gather.argtypes = [VP, VP, VP, U32, VP]
+        lib.lmn_col_fri_commit.argtypes = [VP, C.POINTER(VP), U32, VP, C.POINTER(LmnFriCommitResult)]
         lib.lmn_tree_free.argtypes = [VP, VP]
         lib.lmn_tree_free.restype = None
         lib.lmn_col_accumulate.argtypes = [VP, VP, VP]
@@ -756,6 +784,7 @@ class Context:
     def __init__(self, device: int = 0, config: Optional[LmnConfig] = None, library: Optional[Library] = None):
         self.lib = library or default_library()
         self.config = config or self.lib.default_config()
+        self.device = device
         h = C.c_void_p()
         rc = self.lib.lib.lmn_ctx_create(device, C.byref(self.config), C.byref(h))
         if rc != LMN_OK:
@@ -808,6 +837,54 @@ class Context:
         out = C.c_void_p()
         self._check(self.lib.lib.lmn_col_commit(self.handle, arr, len(cols), C.byref(out)))
         return Tree(self, out)
+
+    def fri_commit(self, cols: Sequence[Col], start_digest: bytes) -> FriCommit:
+        """`lmn_col_fri_commit`: the FRI commit loop of `prove` (stwo FriProver::commit without the last layer's
+        interpolation) on secure-column handles of strictly decreasing sizes, from the channel digest `start_digest`;
+        roots, alphas, every layer's values, every tree level the loop wrote and the form each layer took."""
+        L = self.lib.lib
+        if len(start_digest) != 32:
+            raise ValueError("start_digest is 32 bytes")
+        arr = (C.c_void_p * max(len(cols), 1))(*[c.handle for c in cols])
+        dig = (C.c_uint8 * 32)(*start_digest)
+        res = LmnFriCommitResult()
+        try:
+            self._check(L.lmn_col_fri_commit(self.handle, arr, len(cols), dig, C.byref(res)))
+            n = int(res.n_trees)
+
+            def words(p, count):
+                return np.frombuffer(C.string_at(p, 4 * count), dtype=np.uint32).copy() if count else np.zeros(0, dtype=np.uint32)
+            raw = C.string_at(res.roots, 32 * n)
+            alphas = words(res.alphas, 4 * n).reshape(n, 4)
+            tree_logs = [int(v) for v in words(res.tree_logs, n)]
+            masks = words(res.level_masks, n)
+            forms = [int(v) for v in words(res.forms, n + 1)]
+            values = words(res.values, int(res.n_value_words))
+            levels = words(res.levels, int(res.n_level_words))
+            layer_logs = [tree_logs[0] - 1 - i for i in range(n)]
+            layer_values, at = [], 0
+            for lg in layer_logs:
+                layer_values.append(values[at:at + (4 << lg)].reshape(4, 1 << lg))
+                at += 4 << lg
+            assert at == len(values)
+            tree_levels, at = [], 0
+            for t in range(n):
+                lv = []
+                for l in range(tree_logs[t] + 1):
+                    if (int(masks[t]) >> l) & 1:
+                        lv.append(levels[at:at + (8 << l)].reshape(1 << l, 8))
+                        at += 8 << l
+                    else:
+                        lv.append(None)
+                tree_levels.append(lv)
+            assert at == len(levels)
+            return FriCommit([raw[32 * t:32 * t + 32] for t in range(n)], [tuple(int(v) for v in a) for a in alphas],
+                             tree_logs, tree_levels, forms[0], layer_logs, layer_values, forms[1:])
+        finally:
+            for name in ("roots", "alphas", "tree_logs", "level_masks", "forms", "values", "levels"):
+                p = getattr(res, name)
+                if p:
+                    L.lmn_free(p)
 
     def col_accumulate_quotients(self, cols: Sequence[Col], samples, points, alpha) -> Col:
         """As `accumulate_quotients`, on resident columns; returns the secure column (4 coordinate columns)."""

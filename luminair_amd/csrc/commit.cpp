@@ -69,7 +69,7 @@ void Context::build_merkle_levels(std::vector<uint32_t*>& layers, int max_log,
         if (make_segs(level, sl) && sl.n[0] == (int)lc.size() && make_segs(level - 1, snext)) {
           below.below = lc[0];
           below.below_ncols = (int)lc.size();
-          cuts->push_back({level, 1, nullptr, sl, (int)lc.size()});   // a node of this level = the hash of its leaf
+          cuts->push_back({level, 1, nullptr, sl, (int)lc.size(), nullptr, 0, true});   // a node of this level = the hash of its leaf
           timings.merkle_fused_bytes += ((uint64_t)1 << level) * (4ull * lc.size() + 32ull);
           timings.merkle_fused_compressions += (uint64_t)1 << level;
           timings.merkle_bytes += ((uint64_t)1 << level) * (4ull * lc.size() + 32ull);

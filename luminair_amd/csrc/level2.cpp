@@ -3,6 +3,7 @@
 // /root/reference/crates/air/src/utils.rs:112-128).  Columns live in HBM from lmn_col_from_cpu to lmn_col_to_cpu;
 // every op is one or a few launches of the same gfx950 kernels `lmn_prove` uses, on the context's stream.
 #include "capi_internal.h"
+#include "prove_run.h"
 
 #include <algorithm>
 
@@ -404,6 +405,128 @@ void Context::col_gather(const lmn_col* c, const uint32_t* positions, uint32_t n
   memcpy(host_out, got, out_bytes);
 }
 
+// ---- the FRI commit loop on handles (lmn_col_fri_commit): prove()'s own layer loop (phase_fri.cpp fri_commit_layers) on
+// caller-given quotient columns, then everything it left in device memory brought to the host
+FriCommitOut::~FriCommitOut() {
+  free(r.roots);
+  free(r.alphas);
+  free(r.tree_logs);
+  free(r.level_masks);
+  free(r.forms);
+  free(r.values);
+  free(r.levels);
+}
+lmn_fri_commit_result FriCommitOut::release() {
+  lmn_fri_commit_result o = r;
+  r = lmn_fri_commit_result{};
+  return o;
+}
+
+void Context::col_fri_commit(const lmn_col* const* cols, uint32_t n, const uint8_t start_digest[32], FriCommitOut& out) {
+  const char* F = "fri_commit: ";
+  auto refuse = [&](const std::string& what) { throw LmnError(LMN_ERR_INVALID_ARGUMENT, F + what); };
+  if (shard_.active) refuse("ctx is sharded (lmn_ctx_set_shard): the layer loop on handles runs on an unsharded context only");
+  if (!cols || n == 0) refuse("cols is empty");
+  if (!start_digest) refuse("start_digest is null");
+  const int lb = (int)cfg.log_blowup, last_log = (int)cfg.log_last_layer + lb;
+  for (uint32_t k = 0; k < n; ++k) {
+    const lmn_col* c = cols[k];
+    if (!c) refuse("cols[" + u32s(k) + "] is null");
+    if (c->ncols != 4) refuse("cols[" + u32s(k) + "] has " + u32s(c->ncols) + " columns, a secure column has 4 coordinate columns");
+    if (k && c->log_size >= cols[k - 1]->log_size)
+      refuse("cols[" + u32s(k) + "] has log size " + u32s(c->log_size) + " after cols[" + u32s(k - 1) + "] of log size " +
+             u32s(cols[k - 1]->log_size) + ": sizes must be strictly decreasing");
+  }
+  const int ls0 = (int)cols[0]->log_size;
+  if (ls0 - 1 < last_log)
+    refuse("cols[0] has log size " + u32s(ls0) + ": its first line layer is smaller than the last layer of log size " +
+           u32s(last_log) + " (log_last_layer + log_blowup)");
+  for (uint32_t k = 1; k < n; ++k)
+    if ((int)cols[k]->log_size - 1 < last_log)
+      refuse("cols[" + u32s(k) + "] has log size " + u32s(cols[k]->log_size) + ": it would join below the last layer of log size " +
+             u32s(last_log));
+  set_device();
+  ensure_twiddles(ls0);
+  // first tree 16 << ls0 words, line layers 4 << ls0 in all, their trees 16 << ls0 in all; tables and alignment in the slack
+  arena_.reserve(((size_t)48 << ls0) * 4 + (16u << 20));
+  begin_op();
+  reset_event_log();
+  // as in prove(): trees are stored without the levels their fused launches keep in registers
+  struct CutScope {
+    bool& flag;
+    ~CutScope() { flag = false; }
+  } cut_scope{merkle_cut_};
+  // lmn_get_timings keeps describing the last proof: the loop adds to the counters as it does inside prove()
+  struct TimingsScope {
+    lmn_timings& t;
+    lmn_timings saved;
+    ~TimingsScope() { t = saved; }
+  } timings_scope{timings, timings};
+  merkle_cut_ = !env_set("LMN_MERKLE_FULL");
+  ProofRun r(cfg.protocol_variant);
+  r.lb = lb;
+  r.log = g_log(this);
+  Hash32 d0;
+  memcpy(d0.w, start_digest, 32);
+  r.channel.set_digest(d0);
+  for (uint32_t k = 0; k < n; ++k) r.quots.push_back({(int)cols[k]->log_size, cols[k]->d, false});
+  try {
+    plan_fri_buffers(r);
+    fri_commit_layers(r);
+  } catch (...) {
+    lmn_sync(stream_);   // launches in flight read tables in the staging memory the next op reuses
+    throw;
+  }
+  const ProofRun::FriPlan& fp = r.fri;
+  const size_t n_trees = 1 + r.inner.size();
+  if (fp.forms.size() != n_trees) throw LmnError(LMN_ERR_INTERNAL, "FRI: one form per layer expected");
+  auto tree_of = [&](size_t t) -> const DevMerkle& { return t == 0 ? r.first_merkle : r.inner[t - 1].merkle; };
+  uint64_t n_values = 0, n_levels = 0;
+  for (size_t i = 0; i < n_trees; ++i) n_values += 4ull << (ls0 - 1 - (int)i);
+  for (size_t t = 0; t < n_trees; ++t)
+    for (int l = 0; l <= tree_of(t).max_log; ++l)
+      if (tree_of(t).layers[l]) n_levels += 8ull << l;
+  lmn_fri_commit_result& o = out.r;
+  o.n_trees = (uint32_t)n_trees;
+  o.roots = (uint8_t*)malloc_words(n_trees * 8);
+  o.alphas = malloc_words(n_trees * 4);
+  o.tree_logs = malloc_words(n_trees);
+  o.level_masks = malloc_words(n_trees);
+  o.forms = malloc_words(n_trees + 1);
+  o.values = malloc_words(n_values);
+  o.levels = malloc_words(n_levels);
+  o.n_value_words = n_values;
+  o.n_level_words = n_levels;
+  lmn_d2h(o.roots, fp.d_roots, n_trees * 32, stream_);
+  lmn_d2h(o.alphas, fp.d_alphas, n_trees * 16, stream_);
+  uint64_t at = 0;
+  for (size_t i = 0; i < n_trees; ++i) {
+    const int lg = ls0 - 1 - (int)i;
+    const uint32_t* vals = i + 1 < n_trees ? r.inner[i].vals : fp.d_last;
+    if (i + 1 < n_trees && r.inner[i].log != lg) throw LmnError(LMN_ERR_INTERNAL, "FRI: a layer of an unexpected size");
+    lmn_d2h(o.values + at, vals, 16ull << lg, stream_);
+    at += 4ull << lg;
+  }
+  at = 0;
+  for (size_t t = 0; t < n_trees; ++t) {
+    const DevMerkle& m = tree_of(t);
+    o.tree_logs[t] = (uint32_t)m.max_log;
+    o.level_masks[t] = 0;
+    for (int l = 0; l <= m.max_log; ++l) {
+      if (!m.layers[l]) continue;
+      o.level_masks[t] |= 1u << l;
+      lmn_d2h(o.levels + at, m.layers[l], 32ull << l, stream_);
+      at += 8ull << l;
+    }
+  }
+  // build_merkle_levels marks the cut it makes where it hands a leaf level to the launch above it (MerkleFold::below)
+  bool below = false;
+  for (const MerkleCut& c : r.first_merkle.cuts) below |= c.leaf_from_above;
+  o.forms[0] = below ? LMN_FRI_FIRST_TREE_BELOW : LMN_FRI_FIRST_TREE;
+  for (size_t i = 0; i < n_trees; ++i) o.forms[1 + i] = fp.forms[i];
+  lmn_sync(stream_);
+}
+
 void Context::col_accumulate(lmn_col* dst, const lmn_col* src) {
   set_device();
   if (dst->ncols != src->ncols || dst->log_size != src->log_size)
@@ -737,6 +860,17 @@ int lmn_col_gather(lmn_ctx* ctx, const lmn_col* col, const uint32_t* positions, 
     if (!positions) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "col_gather: positions is null with n = " + std::to_string(n));
     if (!host_out) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "col_gather: host_out is null with n = " + std::to_string(n));
     ctx->impl->col_gather(col, positions, n, host_out);
+  });
+}
+int lmn_col_fri_commit(lmn_ctx* ctx, const lmn_col* const* cols, uint32_t n, const uint8_t start_digest[32],
+                       lmn_fri_commit_result* result) {
+  if (result) *result = lmn_fri_commit_result{};
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  return guard2(ctx, [&] {
+    if (!result) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "fri_commit: result is null");
+    lmn::FriCommitOut o;
+    ctx->impl->col_fri_commit(cols, n, start_digest, o);
+    *result = o.release();
   });
 }
 void lmn_tree_free(lmn_ctx* ctx, lmn_tree* tree) {

@@ -67,7 +67,10 @@ void Context::plan_fri_buffers(ProofRun& r) {
   fp.d_tail = fp.tail_table.empty() ? nullptr : upload_vec(fp.tail_table);
 }
 
-void Context::run_fri_commit(ProofRun& r) {
+// The layer loop (stwo FriProver::commit without its last layer's interpolation): the first tree, every inner layer and
+// the values of the last one, then the one wait and the host's replay of roots and alphas.  prove() and lmn_col_fri_commit
+// (level2.cpp) both run this; r.fri.forms names, per layer, the form the loop took (LMN_FRI_*, luminair_hip.h).
+void Context::fri_commit_layers(ProofRun& r) {
   LMN_RUN_ALIASES(r);
   // ---- FRI commit
   auto secure_cols = [&](const uint32_t* vals, int lg, bool s, std::vector<ColRef>& out) { secure_columns(vals, lg, s, g, out); };
@@ -128,8 +131,12 @@ void Context::run_fri_commit(ProofRun& r) {
       const QM31* alpha = nullptr;
       const uint32_t* join = nullptr;   // a quotient column of the source's size that joins the layer (circle fold, accumulated)
     } pend;
+    // how the current layer's values come about (0: by a fold still pending) - recorded per layer in fp.forms
+    uint32_t produced = 0;
+    fp.forms.clear();
     auto materialise = [&](uint32_t* dst) {
       if (!pend.on) return;
+      produced = LMN_FRI_FOLD_MATERIALISED;
       fold(pend.circle, dst, false, pend.src, pend.src_log, false, pend.alpha, 0);
       if (pend.join) fold(true, dst, false, pend.join, pend.src_log, false, pend.alpha, 1);
       pend.on = false;
@@ -139,6 +146,7 @@ void Context::run_fri_commit(ProofRun& r) {
       pend = {true, true, quots[0].vals, ls0, d_alphas + (n_roots - 1)};
     } else {
       fold(true, layer, lay_sh, quots[0].vals, ls0, quots[0].sharded, d_alphas + (n_roots - 1), 0);
+      produced = LMN_FRI_FOLD_LAUNCH;
       if (quots[0].sharded && !lay_sh) gather_columns(layer, 1ull << layer_log, 4, (1ull << layer_log) >> g);
     }
     size_t qi = 1;
@@ -191,6 +199,9 @@ void Context::run_fri_commit(ProofRun& r) {
           launch_fri_tail(d_ch, d_tl, n_tail, layer_log, d_alphas + n_roots, d_roots + 8 * n_roots, stream_, &tail_pre);
         }
         for (int li = 0; li < n_tail; ++li) timings.merkle_compressions += (2ull << (layer_log - li));
+        fp.forms.push_back(produced | LMN_FRI_TREE_IN_TAIL);
+        for (int li = 1; li < n_tail; ++li) fp.forms.push_back(LMN_FRI_FOLD_IN_TAIL | LMN_FRI_TREE_IN_TAIL);
+        produced = LMN_FRI_FOLD_IN_TAIL;
         n_roots += n_tail;
         layer_log = last_size_log;
         break;
@@ -208,11 +219,13 @@ void Context::run_fri_commit(ProofRun& r) {
           mf.itw2 = itwY_[pend.src_log];
         }
         build_merkle(fl.merkle, lc, d_ch, d_alphas + n_roots, d_roots + 8 * n_roots, false, &mf);
+        produced = pend.join ? LMN_FRI_FOLD_IN_LEAVES_JOIN : LMN_FRI_FOLD_IN_LEAVES;
         pend.on = false;
       } else {
         build_merkle(fl.merkle, lc, d_ch, d_alphas + n_roots, d_roots + 8 * n_roots, lay_sh);
       }
       ++n_roots;
+      fp.forms.push_back(produced | LMN_FRI_TREE_OWN);
       const QM31* d_alpha = d_alphas + (n_roots - 1);
       const int next_log = layer_log - 1;
       const bool next_sh = sharded_log(next_log);
@@ -221,14 +234,17 @@ void Context::run_fri_commit(ProofRun& r) {
       const bool fuse_joins = !env_set("LMN_NO_JOIN_FUSION");   // (read per proof: the tests toggle it)
       if (!sh && fuse_folds && next_log > 10 && (!joins || (fuse_joins && !quots[qi].sharded))) {
         pend = {true, false, layer, layer_log, d_alpha, joins ? quots[qi].vals : nullptr};
+        produced = 0;
         if (joins) ++qi;   // (quotient sizes are distinct: at most one column joins a layer)
       } else if (!sh && fuse_folds && !joins && qi == quots.size() && next_log == fp.tail_log && next == fp.tail_first &&
                  next_log > last_size_log) {
         tail_pre.src = layer;   // the tail starts with this fold: no launch for it
         tail_pre.itw = itwX_[layer_log + 1];
         tail_pre.alpha = d_alpha;
+        produced = LMN_FRI_FOLD_TAIL_FRONT;
       } else {
         fold(false, next, next_sh, layer, layer_log, lay_sh, d_alpha, 0);
+        produced = LMN_FRI_FOLD_LAUNCH;
       }
       inner.push_back(fl);
       while (qi < quots.size() && quots[qi].log - 1 == next_log) {
@@ -242,6 +258,7 @@ void Context::run_fri_commit(ProofRun& r) {
       lay_sh = next_sh;
     }
     materialise(layer);  // a last layer larger than the fused threshold (log_last_layer > 9) is still pending
+    fp.forms.push_back(produced);   // the last layer: no tree
     hm.mark("fri enqueued");
     // one sync: roots + alphas back, then replay the transcript on the host channel
     if (qi != quots.size()) throw LmnError(LMN_ERR_INTERNAL, "FRI: unconsumed columns");
@@ -276,6 +293,11 @@ void Context::run_fri_commit(ProofRun& r) {
     }
   }
   hm.mark("fri synced+replayed");
+}
+
+void Context::run_fri_commit(ProofRun& r) {
+  fri_commit_layers(r);
+  LMN_RUN_ALIASES(r);
   // last layer: interpolate the line evaluation (bit-reversed over LineDomain(half_odds(last_log)))
   {
     std::vector<std::vector<QM31>> chunks{last_vals};

@@ -102,6 +102,7 @@ struct ProofRun {
     std::vector<FriTailLayer> tail_table;   // host copy, staged by plan_fri_buffers
     FriTailLayer* d_tail = nullptr;
     int planned_ls0 = -1;           // plan_fri_layout ran for a first layer of this size
+    std::vector<uint32_t> forms;    // per layer (inner layers, then the last): LMN_FRI_FOLD_* | LMN_FRI_TREE_* the loop took
   } fri;
   std::vector<QM31> last_vals;
   int last_log = 0;

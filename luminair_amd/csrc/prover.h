@@ -115,6 +115,7 @@ struct MerkleCut {
   int ncols;
   const uint32_t* below = nullptr;   // the launch hashed the leaf level under its start level itself (MerkleFold::below)
   int below_ncols = 0;
+  bool leaf_from_above = false;      // this IS that leaf level: never hashed by a launch of its own, a node = the hash of its leaf
 };
 
 struct DevMerkle {
@@ -146,6 +147,13 @@ struct TreeOpening {
   size_t n_hashes = 0;
   uint32_t* column_witness = nullptr;
   size_t n_column_words = 0;
+};
+
+// what lmn_col_fri_commit hands to its caller (lmn_fri_commit_result): buffers from malloc, released one by one on failure
+struct FriCommitOut {
+  lmn_fri_commit_result r{};
+  ~FriCommitOut();                      // frees what release() has not handed over
+  lmn_fri_commit_result release();
 };
 
 // the caller-facing limits of one accumulate_quotients call (level2.cpp): LMN_ERR_INVALID_ARGUMENT past them
@@ -254,6 +262,8 @@ class Context {
   void tree_decommit(const lmn_tree* t, const lmn_col* const* cols, uint32_t n_cols, const uint32_t* query_logs,
                      const uint32_t* query_counts, uint32_t n_groups, const uint32_t* queries, TreeOpening& out);
   void col_gather(const lmn_col* c, const uint32_t* positions, uint32_t n, uint32_t* host_out);
+  // FriProver::commit without the last layer's interpolation: prove()'s layer loop (fri_commit_layers) on column handles
+  void col_fri_commit(const lmn_col* const* cols, uint32_t n, const uint8_t start_digest[32], FriCommitOut& out);
   void col_accumulate(lmn_col* dst, const lmn_col* src);
   lmn_col* col_accumulate_quotients(const lmn_col* const* cols, uint32_t n, const uint32_t* sample_col,
                                     const uint32_t* sample_point, const uint32_t* sample_values, uint32_t nsamples,
@@ -308,6 +318,7 @@ class Context {
   void check_composition_identity(ProofRun& r);          // phase_oods.cpp: stwo's OODS sanity check on the sampled values
   void run_quotients(ProofRun& r);
   void run_fri_commit(ProofRun& r);
+  void fri_commit_layers(ProofRun& r);   // phase_fri.cpp: the layer loop, shared with col_fri_commit
   void run_queries(ProofRun& r);
   void run_decommit(ProofRun& r);
   std::vector<uint8_t> run_finish(ProofRun& r);

@@ -86,9 +86,11 @@ def _q(words) -> QM31:
 class Level2Kernels:
     name = "level-2 C ABI on device handles"
 
-    def __init__(self, ctx):
+    def __init__(self, ctx, fri_commit=False):
         self.ctx = ctx
         self.calls = {}
+        if fri_commit:      # oracle.prover.prove hands the whole FRI commit phase to a kernel set that has this
+            self.fri_commit_phase = self._fri_commit_phase
 
     def _count(self, what):
         self.calls[what] = self.calls.get(what, 0) + 1
@@ -212,6 +214,36 @@ class Level2Kernels:
         self._count("fold_line")
         return DSecure(vals.h.fold_line(alpha.v))
 
+    def _fri_commit_phase(self, quotients, channel, tr, config):
+        """oracle.prover.fri_commit_phase with the layer loop as ONE call of `lmn_col_fri_commit`; the host channel replays
+        the roots and must draw the alphas the loop drew.  The trees the decommitment opens are committed again from the
+        returned layers with `lmn_col_commit` and must have the roots the loop drew its alphas from."""
+        from oracle.circle import Coset, LineDomain
+        from oracle.prover import ProvingError
+        ls0 = quotients[0][0]
+        if ls0 - 1 < config.log_last_layer + config.log_blowup:
+            raise ProvingError("FRI: first line layer smaller than the last layer (largest table < 2^log_last_layer rows)")
+        res = self.ctx.fri_commit([q.h for _, q in quotients], channel.digest)
+        self._count("fri_commit")
+        first_tree = self.secure_merkle([q for _, q in quotients])
+        assert first_tree.root() == res.roots[0]
+        inner = []
+        for i in range(len(res.roots) - 1):
+            vals = DSecure(self.ctx.col_from_cpu(res.layer_values[i]))
+            mt = self.secure_merkle([vals])
+            assert mt.root() == res.roots[i + 1], "FRI layer 2^%d" % res.layer_logs[i]
+            inner.append((vals, mt, res.layer_logs[i]))
+        for root, a in zip(res.roots, res.alphas):
+            channel.mix_root(root)
+            tr.fri_roots.append(root)
+            alpha = channel.draw_felt()
+            assert tuple(alpha.v) == tuple(a), "the commit loop drew another alpha"
+            tr.fri_alphas.append(alpha)
+        line_dom = LineDomain(Coset.half_odds(ls0 - 1))
+        for _ in inner:
+            line_dom = line_dom.double()
+        return first_tree, inner, DSecure(self.ctx.col_from_cpu(res.layer_values[-1])), line_dom
+
     def secure_len(self, col: DSecure):
         return len(col)
 
@@ -219,12 +251,24 @@ class Level2Kernels:
         return _q(col.host()[:, pos])
 
 
-def prove_with_level2_only(ctx, tables, variant=None, luts=None):
-    """-> (proof bincode bytes, op-call counts)"""
+def prove_with_level2_only(ctx, tables, variant=None, luts=None, fri_commit=False):
+    """-> (proof bincode bytes, op-call counts).  fri_commit: the FRI commit phase through `Context.fri_commit` (one call)
+    instead of layer by layer; the loop's channel draws in the context's encoding, so this mode runs on a context of its
+    own: `ctx`'s configuration and device, with the proof's protocol variant."""
     from oracle.channel import ProtocolVariant
     from oracle.proof import to_bincode
     from oracle.prover import prove
-    K = Level2Kernels(ctx)
-    proof = prove([(k, np.asarray(r).astype(np.uint64)) for k, r in tables],
-                  variant=variant if variant is not None else ProtocolVariant.KAT, kernels=K, luts=luts)
-    return to_bincode(proof), K.calls
+    variant = variant if variant is not None else ProtocolVariant.KAT
+    own = None
+    if fri_commit:
+        from luminair_amd import backend
+        cfg = type(ctx.config).from_buffer_copy(ctx.config)
+        cfg.protocol_variant = int(variant)
+        ctx = own = backend.Context(ctx.device, cfg, ctx.lib)
+    try:
+        K = Level2Kernels(ctx, fri_commit)
+        proof = prove([(k, np.asarray(r).astype(np.uint64)) for k, r in tables], variant=variant, kernels=K, luts=luts)
+        return to_bincode(proof), K.calls
+    finally:
+        if own is not None:
+            own.close()

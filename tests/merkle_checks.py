@@ -28,7 +28,8 @@ the commit (`merkle_launches`, `merkle_fused_launches`) must equal the plan's, a
   fused<2>                   children only
   sub=0..3                   per-lane register subtree depth of a fused launch
 Modes 3 and 4 of k_merkle_fused (the FRI fold inside the leaf launch, and the leaf level hashed by the launch of the level
-above it) exist only inside `prove`: they stay with the proof parity tests.
+above it) exist only inside the FRI commit loop and trees stored without their register levels: tests/fri_checks.py
+compares them layer by layer through `lmn_col_fri_commit`, next to the proof parity tests.
 
 Value classes (numeric_checks.words): all 0, all P-1, alternating 0 / P-1, EDGE_WORDS, uniform random - on the leaf-count
 axis at the fused size; random elsewhere.  Axes: leaf column count (LEAF_COUNTS, thresholds of NZ and of the 16-word

@@ -2,8 +2,8 @@
 tests/merkle_checks.py: the CPU suite's matrix (tests/test_merkle_edges_emu.py) plus what only size reaches - sub = 1, 2, 3
 chosen by the planner itself (2^18 .. 2^22 leaves), interior layers of those trees in full, fused runs of 11 and of sub + 8
 levels, and the quad-cooperative DPP parents of the LDS climb, which the emulation build replaces.  Modes 3 and 4 of
-k_merkle_fused (FRI fold, leaf level under the start level) are only reachable inside `prove` and stay with the proof
-parity tests."""
+k_merkle_fused (FRI fold, leaf level under the start level) are reached through the FRI commit loop:
+tests/test_gpu_fri_commit.py."""
 import numpy as np
 import pytest
 

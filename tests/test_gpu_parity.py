@@ -666,6 +666,8 @@ def test_gpu_level2_surface_alone_reproduces_proofs(hip_lib_path, kat_bytes):
     ctx = luminair_amd.Prover(0).ctx
     got, calls = prove_with_level2_only(ctx, syn.simple_example())
     assert got == kat_bytes and calls["logup"] == 2 and calls["composition"] == 2
+    got, calls = prove_with_level2_only(ctx, syn.simple_example(), fri_commit=True)    # FRI commit as one lmn_col_fri_commit call
+    assert got == kat_bytes and calls["fri_commit"] == 1 and "fold_line" not in calls
     for tabs, variant in ((syn.chain_graph(1 << 12, 7), ProtocolVariant.KAT),
                           (syn.config3_mixed(13, 12, 12, 8), ProtocolVariant.KAT),
                           (syn.less_than_graph(3000, 5), ProtocolVariant.PINNED),
@@ -675,6 +677,8 @@ def test_gpu_level2_surface_alone_reproduces_proofs(hip_lib_path, kat_bytes):
         want = to_bincode(prove([(k, r.astype(np.uint64)) for k, r in tabs], variant=variant))
         got, _ = prove_with_level2_only(ctx, tabs, variant)
         assert got == want
+        got, calls = prove_with_level2_only(ctx, tabs, variant, fri_commit=True)
+        assert got == want and calls["fri_commit"] == 1
         # and the whole-proof entry point agrees with both
         p = luminair_amd.Prover(0, protocol_variant=int(variant))
         assert p.prove(luminair_amd.LuminairPie.from_tables(tabs)).to_bincode() == want

@@ -33,6 +33,13 @@ def test_level2_only_reproduces_the_reference_kat(emu_ctx, kat_bytes):
     assert calls["accumulate_quotients"] >= 2 and calls["fold_line"] >= 4 and calls["eval_at_point"] >= 31 + 24 + 4
 
 
+def test_level2_only_with_fri_commit_reproduces_the_reference_kat(emu_ctx, kat_bytes):
+    """the commit phase of FRI as one `lmn_col_fri_commit` call (the loop `lmn_prove` runs) instead of layer by layer"""
+    got, calls = prove_with_level2_only(emu_ctx, syn.simple_example(), fri_commit=True)
+    assert got == kat_bytes
+    assert calls["fri_commit"] == 1 and "fold_line" not in calls and "fold_circle_into_line" not in calls
+
+
 @pytest.mark.parametrize("name,tabs,variant,luts", [
     ("chain (Add+Mul+Recip, ragged)", syn.chain_graph(100, 3), ProtocolVariant.KAT, None),
     ("mixed sizes", [(0, syn.chain_graph(64, 4)[0][1]), (1, syn.chain_graph(500, 5)[1][1])], ProtocolVariant.KAT, None),
@@ -44,6 +51,8 @@ def test_level2_only_equals_oracle(emu_ctx, name, tabs, variant, luts):
     want = to_bincode(oracle_prove([(k, r.astype(np.uint64)) for k, r in tabs], variant=variant, luts=luts))
     got, _ = prove_with_level2_only(emu_ctx, tabs, variant, luts)
     assert got == want, name
+    got, calls = prove_with_level2_only(emu_ctx, tabs, variant, luts, fri_commit=True)
+    assert got == want and calls["fri_commit"] == 1, name + " (lmn_col_fri_commit)"
 
 
 def test_level2_only_with_a_lut_component(emu_ctx):

@@ -3,7 +3,7 @@ compiled for the CPU), against the hashlib and oracle references of tests/merkle
 GPU's planner, so a tree of less than 2^18 leaves takes sub = 0 unless LMN_MERKLE_SUB says otherwise: sub = 1, 2, 3 are
 reached here through that switch at 2^11..2^14, and by size alone (with the 2^17..2^22 trees, the 11-level and the sub + 8
 fused runs) in tests/test_gpu_merkle_edges.py.  Modes 3 and 4 of k_merkle_fused (FRI fold, leaf level under the start
-level) are only reachable inside `prove` and stay with the proof parity tests."""
+level) are reached through the FRI commit loop: tests/test_fri_commit_emu.py."""
 import os
 import subprocess
 
