@@ -6,7 +6,11 @@ composition.  Run against the emulation build on CPU (tests/test_numeric_edges_e
 Reference.  Up to 2^8 points every op is restated here with plain Python integers mod P (QM31 = CM31[u] / (u^2 - 2 - i),
 CM31 = M31[i] / (i^2 + 1)): evaluation by the basis definition (coefficient j multiplies y^j0 * x^j1 * pi(x)^j2 ...,
 pi(x) = 2x^2 - 1, on the bit-reversed canonic domain), folds, quotients, decompose and eval_at_point by their stwo
-definitions.  Only the domain points come from `oracle.circle` (pinned by the KAT).  These restatements also pin the
+definitions, logup from the `Rel` entries of `oracle.air.COMPONENTS` read as data (fractions, running sums, the
+coset-order scan), and of composition everything but the local constraints (the logup constraints, Z, the previous-row
+lookup, the claimed shift, the accumulate step; the local constraint sets are stated once, in the oracle, and are tied to
+the kernel by the low-degree identity on valid witnesses).  Only the domain points come from `oracle.circle` (pinned by
+the KAT).  These restatements also pin the
 numpy oracle at those sizes.  Above 2^8 the reference is `oracle.fft` / `oracle.prover` (uint64 arithmetic, exact
 because every product is < 2^62), and from 2^21 points the C oracle (`oracle.cbackend`, tied to numpy by
 test_oracle_c.py).  Algebraic identities are checked as well: interpolate(evaluate(c)) == c, a constant column
@@ -659,35 +663,315 @@ def _oracle_elems(elems):
     return [(QM31(*z), QM31(*a)) for z, a in elems]
 
 
+def q_inv(a):
+    """1 / (A + B u) = (A - B u) / (A^2 - (2 + i) B^2)"""
+    A, B = a[:2], a[2:]
+    b2 = c_mul(B, B)
+    di = c_inv(c_sub(c_mul(A, A), ((2 * b2[0] - b2[1]) % P, (b2[0] + 2 * b2[1]) % P)))
+    return c_mul(A, di) + c_mul(c_sub((0, 0), B), di)
+
+
+def coset_order(log):
+    """storage index of every coset position (the order in which the trace rows follow each other): position i is
+    circle-domain index i / 2 for even i and n - (i + 1) / 2 for odd i, stored at that index bit-reversed"""
+    n = 1 << log
+    i = np.arange(n, dtype=np.int64)
+    cd = np.where(i % 2 == 0, i // 2, n - (i + 1) // 2)
+    s = np.zeros(n, dtype=np.int64)
+    for b in range(log):
+        s |= ((cd >> b) & 1) << (log - 1 - b)
+    return s
+
+
+def _int_cols(a):
+    return [] if a is None else [[int(v) for v in col] for col in a]
+
+
+def _rel_den_num(rel, main, pre, elems, r):
+    """row r of one relation entry: (val + alpha * id - z, +-mult); main / pre are lists of Python-int columns"""
+    src = pre if rel.pre else main
+    z, alpha = elems[rel.elems]
+    den = q(src[rel.val][r], 0, 0, 0)
+    if rel.id is not None:
+        den = q_add(den, q_mul_m(alpha, src[rel.id][r]))
+    m = main[rel.mult][r]
+    return q_sub(den, z), (-m % P if rel.neg else m)
+
+
+def ref_logup(comp, main, pre, elems):
+    """the interaction trace of a component in plain integers, from its `Rel` entries read as data: group j of row r is
+    the sum of +-mult / (val + alpha * id - z) over relations 0..j; the last group is replaced by the running sum, along
+    coset order, of itself minus claimed / n.  -> ((4 * relations, n) words, claimed sum)"""
+    main, pre = _int_cols(main), _int_cols(pre)
+    n = len(main[0])
+    log = n.bit_length() - 1
+    nr = len(comp.relations)
+    out = np.zeros((4 * nr, n), dtype=U64)
+    last = []
+    for r in range(n):
+        S = Q0
+        for j, rel in enumerate(comp.relations):
+            den, num = _rel_den_num(rel, main, pre, elems, r)
+            S = q_add(S, q_mul_m(q_inv(den), num))
+            out[4 * j:4 * j + 4, r] = S
+        last.append(S)
+    claimed = Q0
+    for S in last:
+        claimed = q_add(claimed, S)
+    shift = q_mul_m(claimed, m_inv(n % P))
+    run = Q0
+    for s in coset_order(log):
+        run = q_add(run, q_sub(last[s], shift))
+        out[4 * nr - 4:, s] = run
+    return out, claimed
+
+
+def oracle_logup_last_group(comp, main, elems, pre, oracle_cols):
+    """the numpy oracle's last group before the scan, (n, 4): the group before it, which `gen_interaction_trace` returns
+    unscanned in `oracle_cols`, plus the last relation's fraction from the pieces `gen_interaction_trace` is made of"""
+    from oracle import field as F
+    from oracle.prover import combine, rel_operands
+    nr = len(comp.relations)
+    rel = comp.relations[-1]
+    z, alpha = elems[rel.elems]
+    val, idv, mult = rel_operands(rel, main, pre)
+    frac = F.q_mul_m(F.q_inv(combine(z, alpha, val, idv)), mult)
+    if nr == 1:
+        return frac
+    return F.q_add(np.ascontiguousarray(oracle_cols[4 * nr - 8:4 * nr - 4].T), frac)
+
+
+def check_logup_scan(got, claimed, last_group, what):
+    """The scan on its own, from the op's output: along coset order the first differences of the scanned column, plus
+    shift = claimed / n, are the last group's per-row sums; they must be the oracle's unscanned fractions, the column
+    must end on 0, and every prefix must be a numpy cumsum of those fractions minus their shift (words < 2^31 over at most
+    2^21 rows stay below 2^52: uint64 is exact).  The message says which part is wrong: a wrong fraction changes the
+    claimed sum, and so does a wrong block total (the op adds the claimed sum up from them); a scan that is wrong after
+    its totals leaves the sum alone."""
+    n = got.shape[1]
+    log = n.bit_length() - 1
+    assert log <= 21
+    order = coset_order(log)
+    t = got[-4:].astype(U64).T[order]                                     # (n, 4) in coset order
+    shift = np.array(q_mul_m(claimed, m_inv(n % P)), dtype=U64)
+    before = np.concatenate([np.zeros((1, 4), dtype=U64), t[:-1]])
+    s_last = (t + U64(P) - before + shift) % U64(P)
+    want_last = np.asarray(last_group, dtype=U64)[order]
+    want_claimed = tuple(int(v) for v in want_last.sum(axis=0) % U64(P))
+    want_shift = np.array(q_mul_m(want_claimed, m_inv(n % P)), dtype=U64)
+    pref = np.cumsum((want_last + U64(P) - want_shift) % U64(P), axis=0) % U64(P)
+    said = []
+    bad = np.argwhere(s_last != want_last)
+    if len(bad):
+        i, k = (int(v) for v in bad[0])
+        said.append("the last group recovered from the first differences differs from the oracle's fractions in %d words, "
+                    "first at coset position %d (storage index %d) coordinate %d: got %d want %d"
+                    % (len(bad), i, order[i], k, s_last[i, k], want_last[i, k]))
+    if t[-1].any():
+        said.append("the scanned column ends on %r, not 0" % (tuple(int(v) for v in t[-1]),))
+    bad = np.argwhere(t != pref)
+    if len(bad):
+        i, k = (int(v) for v in bad[0])
+        said.append("%d prefix words differ from the cumsum, first at coset position %d (storage index %d) coordinate %d: "
+                    "got %d want %d" % (len(bad), i, order[i], k, t[i, k], pref[i, k]))
+    if tuple(claimed) != want_claimed:
+        said.append("claimed sum %r, the oracle's fractions add up to %r" % (tuple(claimed), want_claimed))
+        verdict = "the claimed sum is wrong: the last relation's FRACTIONS, or the block totals of the scan that the sum is made of"
+    else:
+        verdict = "the claimed sum is right, so the fractions add up: the SCAN is wrong"
+    if said:
+        raise AssertionError("%s: %s: %s" % (what, verdict, "; ".join(said)))
+
+
 def check_logup_kind(ctx, kind, log, cls="random"):
-    """lmn_col_logup on full-range main columns vs oracle.prover.gen_interaction_trace"""
+    """lmn_col_logup on full-range main columns.  Up to 2^8 rows the reference is `ref_logup` (plain integers), which the
+    numpy oracle (`oracle.prover.gen_interaction_trace`) must equal too; above, the oracle is the reference and
+    `check_logup_scan` checks the scan on its own.
+
+    Not tested: a zero denominator, z = val + alpha * id in some row.  Only caller-chosen relation elements reach it (a
+    proof draws z at random); the oracle returns a value there, the kernel's one batched inverse per row makes every
+    fraction of that row 0."""
     from oracle import air
     from oracle.prover import gen_interaction_trace
     comp = air.COMPONENTS[kind]
     rng = np.random.default_rng(kind * 100 + log)
     n = 1 << log
+    tag = "logup kind %d log %d %s" % (kind, log, cls)
     main = words(cls, (comp.n_cols, n), rng)
     pre = words("random", (len(comp.pre_cols), n), rng) if comp.pre_cols else None
     elems = relation_elements(rng)
-    want_cols, want_claimed = gen_interaction_trace(comp, main, _oracle_elems(elems), list(pre) if pre is not None else ())
+    pre_l = list(pre) if pre is not None else ()
+    want_cols, want_claimed = gen_interaction_trace(comp, main, _oracle_elems(elems), pre_l)
+    want, want_claimed = np.stack(want_cols), tuple(int(v) for v in want_claimed.v)
+    if log <= PY_MAX_LOG:                        # pins the numpy oracle at this size
+        oracle, oracle_claimed = want, want_claimed
+        want, want_claimed = ref_logup(comp, main, pre, elems)
+        same(oracle, want, "numpy oracle " + tag)
+        assert oracle_claimed == want_claimed, ("numpy oracle claimed sum " + tag, oracle_claimed, want_claimed)
     hm = ctx.col_from_cpu(main)
     hp = ctx.col_from_cpu(pre) if pre is not None else None
     inter, claimed = ctx.col_logup(kind, hm, hp, {i: e for i, e in enumerate(elems)})
     got = inter.to_cpu()
-    canonical(got, "logup kind %d" % kind)
-    canonical_q(claimed, "logup claimed sum kind %d" % kind)
-    same(got, np.stack(want_cols), "logup kind %d log %d %s" % (kind, log, cls))
-    assert claimed == tuple(want_claimed.v), ("logup claimed sum kind %d log %d" % (kind, log), claimed, want_claimed.v)
     for x in (hm, hp, inter):
         if x is not None:
             x.free()
+    canonical(got, tag)
+    canonical_q(claimed, "claimed sum " + tag)
+    if log > PY_MAX_LOG:
+        same(got[:-4], want[:-4], tag + ": the groups before the last, which the fraction kernel writes and no scan touches")
+        check_logup_scan(got, claimed, oracle_logup_last_group(comp, main, _oracle_elems(elems), pre_l, want), tag)
+    same(got, want, tag)
+    assert claimed == want_claimed, ("claimed sum " + tag, claimed, want_claimed)
 
 
-def check_composition_kind(ctx, kind, log, cls, coeff_cls):
-    """lmn_col_composition (acc += sum_k c_k * coeff_k / Z) vs oracle.prover.eval_component_constraints_on_domain"""
+def check_logup_refusals(ctx):
+    """what lmn_col_logup must refuse with LMN_ERR_INVALID_ARGUMENT (-6): 2^3 and 2^27 rows (the 2^27 handles are two
+    zeroed one-column allocations of 512 MiB, kind 14), a column count that is not the kind's, a lookup kind without its
+    preprocessed columns or with them at another size, a relation element word that is not canonical.  After each
+    refusal a correct 2^4 call on the same context succeeds."""
+    from luminair_amd.backend import LuminairBackendError
     from oracle import air
+    rng = np.random.default_rng(2727)
+    good = {i: e for i, e in enumerate(relation_elements(rng))}
+
+    def cols(kind, log, extra=0):
+        return ctx.col_from_cpu(words("random", (air.COMPONENTS[kind].n_cols + extra, 1 << log), rng))
+
+    def pre_of(kind, log):
+        return ctx.col_from_cpu(words("random", (len(air.COMPONENTS[kind].pre_cols), 1 << log), rng))
+
+    def bad_elems(set_index, alpha, word, value):
+        e = {i: (list(z), list(a)) for i, (z, a) in good.items()}
+        e[set_index][alpha][word] = value
+        return e
+
+    cases = [
+        ("2^3 rows", 0, lambda: cols(0, 3), None, good),
+        ("2^27 rows", 14, lambda: ctx.col_zeros(1, 27), lambda: ctx.col_zeros(1, 27), good),
+        ("one column too many", 0, lambda: cols(0, 4, 1), None, good),
+        ("one column too few", 13, lambda: cols(13, 4, -1), None, good),
+        ("a lookup kind without its preprocessed columns", 4, lambda: cols(4, 4), None, good),
+        ("preprocessed columns of another size", 4, lambda: cols(4, 5), lambda: pre_of(4, 4), good),
+        ("z word = P", 0, lambda: cols(0, 4), None, bad_elems(0, 0, 0, P)),
+        ("alpha word = 2^32 - 1", 13, lambda: cols(13, 4), None, bad_elems(1, 1, 3, 0xFFFFFFFF)),
+    ]
+    for what, kind, make_main, make_pre, elems in cases:
+        hm = make_main()
+        hp = make_pre() if make_pre else None
+        try:
+            inter, _ = ctx.col_logup(kind, hm, hp, elems)
+        except LuminairBackendError as e:
+            assert e.code == -6, (what, e.code, str(e))
+        else:
+            inter.free()
+            raise LimitError("col_logup accepted " + what)
+        finally:
+            hm.free()
+            if hp is not None:
+                hp.free()
+        check_logup_kind(ctx, kind, 4)
+
+
+# ----------------------------------------------------------------------------- composition
+def prev_row_index(k):
+    """for every storage index s of the 2^(k+1)-point evaluation domain, the storage index of the point p_s moved back
+    by one step of the 2^k-row trace subgroup: circle-group multiplication on the coordinates, then a lookup of the
+    point.  The domain's half coset walks in steps of that subgroup's generator, and domain indices 0 and 1 are stored
+    at 0 and 2^k, so the step is p[2^k] * conj(p[0])."""
+    xs, ys = domain_points(k + 1)
+
+    def mul(a, b):
+        return ((a[0] * b[0] - a[1] * b[1]) % P, (a[0] * b[1] + a[1] * b[0]) % P)
+    step = mul((xs[1 << k], ys[1 << k]), (xs[0], -ys[0] % P))
+    back = (step[0], -step[1] % P)
+    where = {(x, y): s for s, (x, y) in enumerate(zip(xs, ys))}
+    assert len(where) == len(xs)
+    return [where[mul((x, y), back)] for x, y in zip(xs, ys)]
+
+
+def ref_composition_relations(comp, k, main, inter, pre, elems, claimed, rel_coeffs, acc0):
+    """acc0 + (sum over the relations of coeff_j * c_j) / Z on the 2^(k+1)-point domain in plain integers, the local
+    constraints left out (their coefficients are 0 in the call this is compared with):
+    c_j = (cur_j - cur_(j-1)) * den_j - (+-mult_j), and for the last relation
+    c = (cur - cur_(j-1) - last[prev(s)] + claimed / 2^k) * den - (+-mult);  Z(s) = pi^(k-1)(x_s)"""
+    main, inter, pre = _int_cols(main), _int_cols(inter), _int_cols(pre)
+    E = 2 << k
+    xs, _ = domain_points(k + 1)
+    prev = prev_row_index(k)
+    shift = q_mul_m(claimed, m_inv((1 << k) % P))
+    nr = len(comp.relations)
+    last = [q(*(inter[4 * (nr - 1) + t][s] for t in range(4))) for s in range(E)]
+    out = np.zeros((4, E), dtype=U64)
+    for s in range(E):
+        z = xs[s]
+        for _ in range(k - 1):
+            z = (2 * z * z - 1) % P
+        total, before = Q0, Q0
+        for j, rel in enumerate(comp.relations):
+            cur = q(*(inter[4 * j + t][s] for t in range(4)))
+            den, num = _rel_den_num(rel, main, pre, elems, s)
+            diff = q_sub(cur, before)
+            if j == nr - 1:
+                diff = q_add(q_sub(diff, last[prev[s]]), shift)
+            total = q_add(total, q_mul(rel_coeffs[j], q_sub(q_mul(diff, den), q(num, 0, 0, 0))))
+            before = cur
+        out[:, s] = q_add(q(*acc0[:, s]), q_mul_m(total, m_inv(z)))
+    return out
+
+
+def _oracle_composition(comp, log, main, inter, pre, elems, claimed, coeffs):
+    """(4, 2^(log+1)): sum_k c_k * coeff_k / Z by the numpy oracle"""
     from oracle.field import QM31
     from oracle.prover import ComponentInstance, eval_component_constraints_on_domain
+    ci = ComponentInstance(comp, log, (0, comp.n_cols), (0, inter.shape[0]), QM31(*claimed))
+    return eval_component_constraints_on_domain(ci, main, inter, _oracle_elems(elems), [QM31(*c) for c in coeffs], log + 1,
+                                                list(pre) if pre is not None else ()).T
+
+
+def _run_composition(ctx, kind, main, inter, pre, elems, claimed, coeffs, acc0):
+    hm, hi = ctx.col_from_cpu(main), ctx.col_from_cpu(inter)
+    hp = ctx.col_from_cpu(pre) if pre is not None else None
+    acc = ctx.col_from_cpu(acc0)
+    try:
+        ctx.col_composition(kind, hm, hi, hp, {i: el for i, el in enumerate(elems)}, claimed, coeffs, acc)
+        return acc.to_cpu()
+    finally:
+        for x in (hm, hi, hp, acc):
+            if x is not None:
+                x.free()
+
+
+def check_composition_relations(ctx, kind, log, cls, coeff_cls):
+    """lmn_col_composition with every local coefficient 0 and the relation coefficients in `coeff_cls`: what is left is
+    the logup constraints, Z, the previous-row lookup, the claimed shift and the accumulate step, all of which
+    `ref_composition_relations` restates.  The numpy oracle must equal it at the same inputs."""
+    from oracle import air
+    assert log + 1 <= PY_MAX_LOG
+    comp = air.COMPONENTS[kind]
+    rng = np.random.default_rng([kind, log, CLASSES.index(cls), CLASSES.index(coeff_cls)])
+    E = 2 << log
+    tag = "composition, relations only, kind %d log %d -> %d, columns %s, coefficients %s" % (kind, log, log + 1, cls, coeff_cls)
+    main = words(cls, (comp.n_cols, E), rng)
+    inter = words(cls, (4 * len(comp.relations), E), rng)
+    pre = words("random", (len(comp.pre_cols), E), rng) if comp.pre_cols else None
+    elems = relation_elements(rng)
+    claimed = qword("random", rng)
+    rel_coeffs = [qword(coeff_cls, rng) for _ in comp.relations]
+    coeffs = [Q0] * comp.n_local + rel_coeffs
+    acc0 = words("pm1", (4, E), rng)
+    want = ref_composition_relations(comp, log, main, inter, pre, elems, claimed, rel_coeffs, acc0)
+    oracle = (_oracle_composition(comp, log, main, inter, pre, elems, claimed, coeffs) + acc0) % U64(P)
+    same(oracle, want, "numpy oracle " + tag)
+    got = _run_composition(ctx, kind, main, inter, pre, elems, claimed, coeffs, acc0)
+    canonical(got, tag)
+    same(got, want, tag)
+
+
+def check_composition_kind(ctx, kind, log, cls, coeff_cls, acc="class"):
+    """lmn_col_composition (acc += sum_k c_k * coeff_k / Z) vs oracle.prover.eval_component_constraints_on_domain.
+    acc: what the accumulator holds before the call - "class" (all P - 1 under random columns, random words otherwise),
+    "zero", or "cancel" (P - the expected sum: every output word must then be exactly 0)"""
+    from oracle import air
     comp = air.COMPONENTS[kind]
     rng = np.random.default_rng(kind * 1000 + log * 10 + CLASSES.index(cls))
     e = log + 1
@@ -699,17 +983,130 @@ def check_composition_kind(ctx, kind, log, cls, coeff_cls):
     claimed = qword("random", rng)
     coeffs = [qword(coeff_cls, rng) for _ in range(comp.n_constraints)]
     acc0 = words("pm1" if cls == "random" else "random", (4, E), rng)
-    ci = ComponentInstance(comp, log, (0, comp.n_cols), (0, inter.shape[0]), QM31(*claimed))
-    want = eval_component_constraints_on_domain(ci, main, inter, _oracle_elems(elems), [QM31(*c) for c in coeffs], e,
-                                                list(pre) if pre is not None else ()).T
+    want = _oracle_composition(comp, log, main, inter, pre, elems, claimed, coeffs)
+    if acc == "zero":
+        acc0 = np.zeros_like(acc0)
+    elif acc == "cancel":
+        acc0 = (U64(P) - want) % U64(P)
+    else:
+        assert acc == "class"
     want = (want + acc0) % U64(P)
-    hm, hi = ctx.col_from_cpu(main), ctx.col_from_cpu(inter)
+    got = _run_composition(ctx, kind, main, inter, pre, elems, claimed, coeffs, acc0)
+    tag = "composition kind %d log %d -> %d, columns %s, coefficients %s, accumulator %s" % (kind, log, e, cls, coeff_cls, acc)
+    canonical(got, tag)
+    if acc == "cancel":
+        assert not want.any()
+    same(got, want, tag)
+
+
+COMPOSITION_COLUMN_CLASSES = ("zero", "pm1", "alt", "edge", "random")
+COMPOSITION_COEFF_CLASSES = ("zero", "pm1", "edge", "random")
+COMPOSITION_LARGE_KINDS = (0, 13, 4, 14)      # 3 and 7 node relations, a width-2 and a width-1 lookup
+
+
+def composition_class_pairs(kind, log):
+    """(column class, coefficient class) pairs of one kind at one size.  Up to 2^9 points: all twenty.  Above, where the
+    oracle takes a tenth of a second and more per case: each column class once and each coefficient class at least once,
+    the pairing rotated by the kind, so that over the 17 kinds every pair occurs; at 2^19 points (seconds per case) the
+    kinds with many columns keep random / random and edge / edge."""
+    cols, coeffs = COMPOSITION_COLUMN_CLASSES, COMPOSITION_COEFF_CLASSES
+    if log <= 8:
+        return [(c, k) for c in cols for k in coeffs]
+    if log >= 18 and kind in (0, 13):
+        return [("random", "random"), ("edge", "edge")]
+    return [(c, coeffs[(i + kind) % len(coeffs)]) for i, c in enumerate(cols)]
+
+
+# ----------------------------------------------------------------------------- the low-degree identity
+def low_degree_tail(co, k):
+    """the coefficients that vanish on a valid witness of 2^k rows: every index above 2^k.  The bound is the ORACLE's: its
+    own composition, interpolated on 2^(k+1) points, shows for all 17 kinds at k = 4 and k = 6 zeros from index 2^k + 1 on
+    and a non-zero coefficient AT index 2^k, not zeros from 2^k on.  (Degree-2 constraints over Z leave a circle polynomial
+    of degree 2^(k-1); that space has 2^k + 1 dimensions, the last of them the basis function pi^(k-1)(x) of index 2^k.)"""
+    co = np.asarray(co)
+    assert co.shape[1] == 2 << k
+    return co[:, (1 << k) + 1:]
+
+
+def valid_witness(kind, k, rng):
+    """(main columns (n_cols, 2^k), preprocessed columns or None) of a trace every constraint holds on: 2^k - 3 valid rows
+    (tests/trace_doctor_checks.py builds them from luminair_amd.synthetic; a lookup component's row is a multiplicity),
+    padded as the prover pads"""
+    import trace_doctor_checks as tdc
+    from oracle import air
+    comp = air.COMPONENTS[kind]
+    n = (1 << k) - 3
+    rows = tdc._valid_rows(kind, n, rng) if comp.n_local else rng.integers(0, 5, size=(n, 1))
+    main = air.pad_table(comp, rows)
+    assert main.shape == (comp.n_cols, 1 << k)
+    for c in comp.local([air.MV(col) for col in main]):
+        assert not np.asarray(c.a).any(), "the witness of kind %d is not valid" % kind
+    pre = words("random", (len(comp.pre_cols), 1 << k), rng) if comp.pre_cols else None
+    return main, pre
+
+
+def check_low_degree(ctx, kind, k):
+    """On a valid witness the composition is a polynomial: logup on the main columns, every column extended to 2^(k+1)
+    points, composition into a zero accumulator with random coefficients, and the accumulator interpolated has no
+    coefficient of index > 2^k in any of its four coordinate columns.  No reference is needed for that; the bound is the
+    one the oracle's own composition of the same witness shows (`low_degree_tail`), asserted of the oracle first, never
+    read off the op.  One changed main cell - the is_last flag of row 0, or row 0's multiplicity for a lookup component, with the
+    interaction trace left as it was - must leave a non-zero upper half."""
+    from oracle import air, fft
+    from oracle.prover import gen_interaction_trace
+    comp = air.COMPONENTS[kind]
+    rng = np.random.default_rng([kind, k, 5])
+    tag = "low-degree identity, kind %d, 2^%d rows" % (kind, k)
+    e = k + 1
+    main, pre = valid_witness(kind, k, rng)
+    elems = relation_elements(rng)
+    coeffs = [qword("random", rng) for _ in range(comp.n_constraints)]
+    pre_l = list(pre) if pre is not None else ()
+    # the oracle's side: it fixes the bound, and shows that the changed cell breaks it
+    o_inter, o_claimed = gen_interaction_trace(comp, main, _oracle_elems(elems), pre_l)
+    o_inter, o_claimed = np.stack(o_inter), tuple(int(v) for v in o_claimed.v)
+
+    def extend(a):
+        return fft.evaluate(fft.interpolate(np.asarray(a, dtype=U64)), e)
+    inter_e = extend(o_inter)
+    pre_e = extend(pre) if pre is not None else None
+    changed = main.copy()
+    cell = comp.padding.index(1) if comp.n_local else comp.relations[0].mult        # is_last: the padding row's only 1
+    changed[cell, 0] = (int(changed[cell, 0]) + 2) % P
+    o_vals = {}
+    for name, m in (("valid", main), ("changed", changed)):
+        o_vals[name] = _oracle_composition(comp, k, extend(m), inter_e, pre_e, elems, o_claimed, coeffs)
+        co = fft.interpolate(o_vals[name])
+        if name == "valid":
+            assert not low_degree_tail(co, k).any() and co[:, :1 << k].any(), "oracle: " + tag
+            assert co[:, 1 << k].any(), "oracle: index 2^k is zero too, the bound is lower than recorded: " + tag
+        else:
+            assert low_degree_tail(co, k).any(), "oracle: the changed cell is not seen: " + tag
+    # the ops
+    hm = ctx.col_from_cpu(main)
     hp = ctx.col_from_cpu(pre) if pre is not None else None
-    acc = ctx.col_from_cpu(acc0)
-    ctx.col_composition(kind, hm, hi, hp, {i: el for i, el in enumerate(elems)}, claimed, coeffs, acc)
-    got = acc.to_cpu()
-    canonical(got, "composition kind %d" % kind)
-    same(got, want, "composition kind %d log %d -> %d, columns %s, coefficients %s" % (kind, log, e, cls, coeff_cls))
-    for x in (hm, hi, hp, acc):
+    inter, claimed = ctx.col_logup(kind, hm, hp, {i: el for i, el in enumerate(elems)})
+    assert claimed == o_claimed, (tag, claimed, o_claimed)
+    lde = [inter.interpolate().evaluate(e), hp.interpolate().evaluate(e) if hp is not None else None]
+    for x in (hm, hp, inter):
+        if x is not None:
+            x.free()
+    for name, m in (("valid", main), ("changed", changed)):
+        hm = ctx.col_from_cpu(m)
+        me = hm.interpolate().evaluate(e)
+        acc = ctx.col_zeros(4, e)
+        ctx.col_composition(kind, me, lde[0], lde[1], {i: el for i, el in enumerate(elems)}, claimed, coeffs, acc)
+        same(acc.to_cpu(), o_vals[name], "%s, %s witness: composition values" % (tag, name))
+        co = acc.interpolate().to_cpu()
+        canonical(co, tag)
+        for x in (hm, me, acc):
+            x.free()
+        if name == "valid":
+            up = low_degree_tail(co, k)
+            assert not up.any(), "%s: %d non-zero coefficients of index > 2^%d, first at (column, index) %s" % (
+                tag, np.count_nonzero(up), k, tuple(np.argwhere(up)[0] + [0, (1 << k) + 1]))
+        else:
+            assert low_degree_tail(co, k).any(), "%s: a changed main cell leaves the upper coefficients zero" % tag
+    for x in lde:
         if x is not None:
             x.free()

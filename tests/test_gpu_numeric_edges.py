@@ -1,6 +1,8 @@
 """Value and shape edges of the level-2 field ops on a real MI355X, against the references of tests/numeric_checks.py:
 the CPU suite's matrix (tests/test_numeric_edges_emu.py) plus the sizes above 2^20 - the two-pass FFT up to 2^22, the
-three-pass sizes 2^23 and 2^25 (the C oracle is the reference there), and cpb remainders once tiles reach 512 / 2048."""
+three-pass sizes 2^23 and 2^25 (the C oracle is the reference there), cpb remainders once tiles reach 512 / 2048, logup
+at the lane and batch counts of its block-total scan (2^15 to 2^21 rows) and composition on 2^19 points."""
+import numpy as np
 import pytest
 
 import numeric_checks as nc
@@ -119,3 +121,80 @@ def test_gpu_composition_every_kind(ctx, log):
         for cls in ("pm1", "random"):
             for coeff_cls in ("pm1", "random"):
                 nc.check_composition_kind(ctx, kind, log, cls, coeff_cls)
+
+
+# ---- logup at every scan shape: the CPU suite's sizes with all 17 kinds, plus the lane and batch counts of the
+# block-total scan: 2^8 totals on 256 lanes, every lane loaded (15), two totals per lane (16), eight per lane on the last
+# 256-lane size (18), 1024 lanes in 16 waves (19), sixteen per lane, so a second batch of eight (21)
+LOGUP_SMALL_CLASSES = ("random", "pm1", "edge", "alt")
+LOGUP_DIRTY_LOGS = (11, 13, 19)
+
+
+@pytest.mark.parametrize("log", [4, 5, 7, 8])
+def test_gpu_logup_small_every_kind_and_class_against_plain_integers(ctx, log):
+    from oracle import air
+    assert log <= nc.PY_MAX_LOG
+    for kind in sorted(air.COMPONENTS):
+        for cls in LOGUP_SMALL_CLASSES:
+            nc.check_logup_kind(ctx, kind, log, cls)
+
+
+@pytest.mark.parametrize("log", [9, 10, 11, 12, 13])
+def test_gpu_logup_scan_shapes(ctx, log):
+    from oracle import air
+    if log in LOGUP_DIRTY_LOGS:
+        nc.dirty_context(ctx, np.random.default_rng(log))
+    for kind in sorted(air.COMPONENTS):
+        nc.check_logup_kind(ctx, kind, log, "random")
+
+
+@pytest.mark.parametrize("log,kind,cls", [(log, kind, cls) for log in (15, 16, 18, 19)
+                                          for kind, cls in ((4, "random"), (4, "pm1"), (13, "random"))] + [(21, 4, "random")])
+def test_gpu_logup_block_total_scan_shapes(ctx, log, kind, cls):
+    """one case per test: the numpy oracle takes seconds at these sizes (kind 13 stops at 2^19, 2^21 is kind 4 alone)"""
+    if log in LOGUP_DIRTY_LOGS and (kind, cls) == (4, "random"):
+        nc.dirty_context(ctx, np.random.default_rng(log))
+    nc.check_logup_kind(ctx, kind, log, cls)
+
+
+def test_gpu_logup_refusals(ctx):
+    nc.check_logup_refusals(ctx)
+
+
+# ---- composition
+@pytest.mark.parametrize("log", [4, 5, 7])
+def test_gpu_composition_relations_against_plain_integers(ctx, log):
+    from oracle import air
+    for kind in sorted(air.COMPONENTS):
+        for cls in ("random", "pm1", "edge", "alt"):
+            for coeff_cls in ("random", "pm1"):
+                nc.check_composition_relations(ctx, kind, log, cls, coeff_cls)
+
+
+@pytest.mark.parametrize("log", [4, 5, 7, 8, 12, 13])
+def test_gpu_composition_shapes_and_classes(ctx, log):
+    from oracle import air
+    for kind in sorted(air.COMPONENTS):
+        for cls, coeff_cls in nc.composition_class_pairs(kind, log):
+            nc.check_composition_kind(ctx, kind, log, cls, coeff_cls)
+
+
+@pytest.mark.parametrize("kind", nc.COMPOSITION_LARGE_KINDS)
+def test_gpu_composition_2_19_points(ctx, kind):
+    for cls, coeff_cls in nc.composition_class_pairs(kind, 18):
+        nc.check_composition_kind(ctx, kind, 18, cls, coeff_cls)
+
+
+@pytest.mark.parametrize("log", [5, 12])
+def test_gpu_composition_accumulator_zero_and_cancelling(ctx, log):
+    from oracle import air
+    for kind in sorted(air.COMPONENTS) if log == 5 else nc.COMPOSITION_LARGE_KINDS:
+        for acc in ("zero", "cancel"):
+            nc.check_composition_kind(ctx, kind, log, "random", "random", acc=acc)
+
+
+@pytest.mark.parametrize("k", [4, 6])
+def test_gpu_composition_of_a_valid_witness_is_low_degree(ctx, k):
+    from oracle import air
+    for kind in sorted(air.COMPONENTS):
+        nc.check_low_degree(ctx, kind, k)

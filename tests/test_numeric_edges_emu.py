@@ -4,6 +4,7 @@ sizes above 2^20, is tests/test_gpu_numeric_edges.py."""
 import os
 import subprocess
 
+import numpy as np
 import pytest
 
 import numeric_checks as nc
@@ -125,3 +126,66 @@ def test_composition_every_kind(ctx, log):
         for cls in ("pm1", "random"):
             for coeff_cls in ("pm1", "random"):
                 nc.check_composition_kind(ctx, kind, log, cls, coeff_cls)
+
+
+# ---- logup at every scan shape.  Fractions: a partly filled 256-lane block (logs 4 to 7), exactly one block (8).  Scan:
+# one partly filled block (4), two blocks and the first block's total as the second's offset (11: the only such size, the
+# coalesced scan takes over at 12), one workgroup of the coalesced scan (12), two workgroups with paired regions (13).
+LOGUP_SMALL_CLASSES = ("random", "pm1", "edge", "alt")
+LOGUP_DIRTY_LOGS = (11, 13, 19)         # block totals land in arena words that held other data
+
+
+@pytest.mark.parametrize("log", [4, 5, 7, 8])
+def test_logup_small_every_kind_and_class_against_plain_integers(ctx, log):
+    from oracle import air
+    assert log <= nc.PY_MAX_LOG
+    for kind in sorted(air.COMPONENTS):
+        for cls in LOGUP_SMALL_CLASSES:
+            nc.check_logup_kind(ctx, kind, log, cls)
+
+
+@pytest.mark.parametrize("log", [9, 10, 11, 12, 13])
+def test_logup_scan_shapes(ctx, log):
+    """kinds 4, 0 and 13: 1, 3 and 7 relations; kind 14 (a width-1 lookup) where the scan changes form"""
+    if log in LOGUP_DIRTY_LOGS:
+        nc.dirty_context(ctx, np.random.default_rng(log))
+    for kind in (4, 0, 13) + ((14,) if log in (11, 13) else ()):
+        nc.check_logup_kind(ctx, kind, log, "random")
+
+
+def test_logup_refusals(ctx):
+    nc.check_logup_refusals(ctx)
+
+
+# ---- composition
+@pytest.mark.parametrize("log", [4, 5, 7])
+def test_composition_relations_against_plain_integers(ctx, log):
+    from oracle import air
+    for kind in sorted(air.COMPONENTS):
+        for cls in ("random", "pm1", "edge", "alt"):
+            for coeff_cls in ("random", "pm1"):
+                nc.check_composition_relations(ctx, kind, log, cls, coeff_cls)
+
+
+@pytest.mark.parametrize("log", [4, 5, 7, 8, 12, 13])
+def test_composition_shapes_and_classes(ctx, log):
+    """2^5 points: a partly filled block; 2^8: exactly one block"""
+    from oracle import air
+    for kind in sorted(air.COMPONENTS):
+        for cls, coeff_cls in nc.composition_class_pairs(kind, log):
+            nc.check_composition_kind(ctx, kind, log, cls, coeff_cls)
+
+
+@pytest.mark.parametrize("log", [5, 12])
+def test_composition_accumulator_zero_and_cancelling(ctx, log):
+    from oracle import air
+    for kind in sorted(air.COMPONENTS) if log == 5 else nc.COMPOSITION_LARGE_KINDS:
+        for acc in ("zero", "cancel"):
+            nc.check_composition_kind(ctx, kind, log, "random", "random", acc=acc)
+
+
+@pytest.mark.parametrize("k", [4, 6])
+def test_composition_of_a_valid_witness_is_low_degree(ctx, k):
+    from oracle import air
+    for kind in sorted(air.COMPONENTS):
+        nc.check_low_degree(ctx, kind, k)
