@@ -427,6 +427,34 @@ int lmn_trace_max_reduce(lmn_ctx* ctx, const int32_t* input_dev, uint64_t front,
 int lmn_trace_sum_reduce(lmn_ctx* ctx, const int32_t* input_dev, uint64_t front, uint64_t dim, uint64_t back,
                          const lmn_node_info* info, uint32_t* rows_dev, uint64_t row_offset, int32_t* out_dev);
 
+/* ---- The eval forms of the producers: `Operator::process`, the forward pass that `gen_circuit_settings` runs in front
+ * of gen_trace (crates/graph/src/graph.rs:61-159) because a Sin / Exp2 / Log2 node's LUT range is the min..max of its
+ * source buffer (crates/graph/src/utils.rs:44-82).  Each call computes the node's output tensor exactly as the
+ * lmn_trace_* call of the same operands leaves it in out_dev - the same kernels' value rules, the producers' contract above -
+ * and writes no rows.  In the same launch:
+ *  - minmax_dev (int32_t[2] on the device, may be NULL) receives the minimum and maximum of the n values written; the
+ *    call sets it to (INT32_MAX, INT32_MIN) first.  A refused element's 0 takes part: the buffer holds it.
+ *  - refused_dev (a uint32_t counter on the device, may be NULL) grows by the number of refused elements - the rows whose
+ *    output-value column the trace call marks with P.  It is never reset by a call: one counter serves a whole graph.
+ * No call waits for the device.  Argument errors (null pointers, a view whose shape product is not n, more than 16
+ * ranges, n = 0) return LMN_ERR_INVALID_ARGUMENT and lmn_last_error names the argument. */
+/* every elementwise kind of lmn_trace_elementwise_v, and LMN_KIND_LESS_THAN (no multiplicity table is touched) */
+int lmn_eval_elementwise_v(lmn_ctx* ctx, uint32_t kind, const int32_t* lhs_dev, const lmn_view* lhs_view, const int32_t* rhs_dev,
+                           const lmn_view* rhs_view, uint64_t n, int32_t* out_dev, int32_t* minmax_dev, uint32_t* refused_dev);
+/* SumReduce (is_max = 0) / MaxReduce of `dim` on a contiguous (front, dim, back) tensor: front * back values.  The running
+ * sum is kept in 64 bits; only an input or a group result outside the value range is refused. */
+int lmn_eval_reduce(lmn_ctx* ctx, uint32_t is_max, const int32_t* input_dev, uint64_t front, uint64_t dim, uint64_t back,
+                    int32_t* out_dev, int32_t* minmax_dev, uint32_t* refused_dev);
+/* how lmn_eval_reduce maps (dim, back) onto lanes: 0 = one lane per output element, 1 = one wave per reduction group */
+uint32_t lmn_eval_reduce_split(uint64_t dim, uint64_t back);
+/* out = lut_col1[LookupLayout::find_index(input)] over `ranges` (as lmn_trace_lut_ranges; no multiplicities).  An input
+ * outside every range is a refused element (0 written, counted), not an error: a dry run does not wait per node. */
+int lmn_eval_lut_ranges(lmn_ctx* ctx, uint32_t kind, const int32_t* input_dev, const lmn_view* view, uint64_t n,
+                        const uint32_t* lut_col1_dev, const lmn_range* ranges, uint32_t n_ranges, int32_t* out_dev,
+                        int32_t* minmax_dev, uint32_t* refused_dev);
+/* the range of a buffer that no eval call produced */
+int lmn_tensor_range(lmn_ctx* ctx, const int32_t* buf_dev, uint64_t n, int32_t* minmax_dev);
+
 /* ---- Row sinks: host trace rows streamed to the GPU while they are produced.  The reference builds its pie on the
  * host node by node - every operator's `process_trace` appends with `table.add_row(...)`
  * (crates/graph/src/op/prim.rs:75, 412, 992, 1117) - and hands `prove` the finished pie (crates/prover/src/prover.rs:28-31,

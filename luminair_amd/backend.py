@@ -229,7 +229,8 @@ EXPORTS = ["lmn_abi_version", "lmn_kind_padding_row", "lmn_strerror", "lmn_last_
            "lmn_col_accumulate", "lmn_col_accumulate_quotients", "lmn_col_fold_line", "lmn_col_fold_circle_into_line",
            "lmn_col_decompose", "lmn_col_logup", "lmn_col_composition", "lmn_kind_constraints", "lmn_kind_relations", "lmn_ctx_set_shard", "lmn_rccl_unique_id", "lmn_ctx_set_shard_rccl", "lmn_ctx_clear_shard",
            "lmn_rows_open", "lmn_rows_push", "lmn_rows_push_pinned", "lmn_rows_sync", "lmn_rows_finish", "lmn_rows_count",
-           "lmn_rows_reset", "lmn_rows_close", "lmn_trace_check"]
+           "lmn_rows_reset", "lmn_rows_close", "lmn_trace_check",
+           "lmn_eval_elementwise_v", "lmn_eval_reduce", "lmn_eval_reduce_split", "lmn_eval_lut_ranges", "lmn_tensor_range"]
 
 
 class LuminairBackendError(RuntimeError):
@@ -389,6 +390,19 @@ class Library:
                                              C.POINTER(LmnNodeInfo), C.c_void_p, C.c_uint64, C.c_void_p]
         lib.lmn_trace_elementwise.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
                                               C.POINTER(LmnNodeInfo), C.c_void_p, C.c_uint64, C.c_void_p]
+        lib.lmn_eval_elementwise_v.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(LmnView), C.c_void_p,
+                                               C.POINTER(LmnView), C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.lmn_eval_reduce.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]
+        lib.lmn_eval_reduce_split.argtypes = [C.c_uint64, C.c_uint64]
+        lib.lmn_eval_reduce_split.restype = C.c_uint32
+        lib.lmn_eval_lut_ranges.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(LmnView), C.c_uint64, C.c_void_p,
+                                            C.POINTER(LmnRange), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.lmn_tensor_range.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+
+    def eval_reduce_split(self, dim: int, back: int) -> int:
+        """How `lmn_eval_reduce` maps (dim, back) onto lanes: 0 = one lane per output element, 1 = one wave per group."""
+        return int(self.lib.lmn_eval_reduce_split(dim, back))
 
     def host_rows(self, shape, dtype=np.uint32) -> "PinnedArray":
         """A page-locked numpy array (`lmn_host_alloc`): trace rows written here reach the GPU by direct DMA."""
@@ -1102,6 +1116,48 @@ class Context:
             C.byref(rhs_view) if rhs_view is not None else None, n, C.byref(info), range_check_mult.ptr, rows.ptr,
             row_offset, out.ptr))
         return rows, out
+
+    # ---- lmn_eval_*: the producers' forward pass (values, their range, the refused elements; no rows, no waiting).
+    # `minmax`: two int32 words on the device, set to the range of what the call wrote; `refused`: a uint32 counter on the
+    # device that grows by the refused elements.  Both optional.  Returns the output DeviceBuffer.
+    def eval_elementwise(self, kind: int, lhs: DeviceBuffer, rhs: Optional[DeviceBuffer], n: int,
+                         lhs_view: Optional[LmnView] = None, rhs_view: Optional[LmnView] = None,
+                         out: Optional[DeviceBuffer] = None, minmax: Optional[DeviceBuffer] = None,
+                         refused: Optional[DeviceBuffer] = None) -> DeviceBuffer:
+        """`Operator::process` of an elementwise node (LessThan included) on int32 Fixed<12> device tensors."""
+        out = out or self.alloc(max(n, 1) * 4)
+        ptr = lambda b: b.ptr if b is not None else None
+        self._check(self.lib.lib.lmn_eval_elementwise_v(
+            self.handle, kind, ptr(lhs), C.byref(lhs_view) if lhs_view is not None else None, ptr(rhs),
+            C.byref(rhs_view) if rhs_view is not None else None, n, out.ptr, ptr(minmax), ptr(refused)))
+        return out
+
+    def eval_reduce(self, inp: DeviceBuffer, front: int, dim: int, back: int, maximum: bool = False,
+                    out: Optional[DeviceBuffer] = None, minmax: Optional[DeviceBuffer] = None,
+                    refused: Optional[DeviceBuffer] = None) -> DeviceBuffer:
+        """SumReduce / MaxReduce of `dim` on a contiguous (front, dim, back) int32 device tensor."""
+        out = out or self.alloc(max(front * back, 1) * 4)
+        ptr = lambda b: b.ptr if b is not None else None
+        self._check(self.lib.lib.lmn_eval_reduce(self.handle, 1 if maximum else 0, ptr(inp), front, dim, back, out.ptr,
+                                                 ptr(minmax), ptr(refused)))
+        return out
+
+    def eval_lut(self, kind: int, inp: DeviceBuffer, n: int, lut_col1: DeviceBuffer, ranges: Sequence[Tuple[int, int]],
+                 view: Optional[LmnView] = None, out: Optional[DeviceBuffer] = None,
+                 minmax: Optional[DeviceBuffer] = None, refused: Optional[DeviceBuffer] = None) -> DeviceBuffer:
+        """Sin / Exp2 / Log2: out = lut_col1[find_index(input)] over `ranges`; an input outside them is refused."""
+        out = out or self.alloc(max(n, 1) * 4)
+        ptr = lambda b: b.ptr if b is not None else None
+        arr = (LmnRange * max(len(ranges), 1))(*[LmnRange(int(a), int(b)) for a, b in ranges])
+        self._check(self.lib.lib.lmn_eval_lut_ranges(self.handle, kind, ptr(inp), C.byref(view) if view is not None else None,
+                                                     n, ptr(lut_col1), arr, len(ranges), out.ptr, ptr(minmax), ptr(refused)))
+        return out
+
+    def tensor_range(self, buf: DeviceBuffer, n: int, minmax: Optional[DeviceBuffer] = None) -> DeviceBuffer:
+        """The (min, max) of an int32 device buffer that no eval call produced, left in `minmax` (two int32 words)."""
+        minmax = minmax or self.alloc(8)
+        self._check(self.lib.lib.lmn_tensor_range(self.handle, buf.ptr if buf is not None else None, n, minmax.ptr))
+        return minmax
 
     def _marshal_tables(self, tables, luts):
         """-> (LmnTable array, n, LmnSettings, objects that must stay alive while the library reads them)"""

@@ -483,6 +483,45 @@ int lmn_trace_max_reduce(lmn_ctx* ctx, const int32_t* input_dev, uint64_t front,
   return guard(ctx, [&] { ctx->impl->trace_reduce(true, input_dev, front, dim, back, *info, rows_dev, row_offset, out_dev); });
 }
 
+int lmn_eval_elementwise_v(lmn_ctx* ctx, uint32_t kind, const int32_t* lhs_dev, const lmn_view* lhs_view, const int32_t* rhs_dev,
+                           const lmn_view* rhs_view, uint64_t n, int32_t* out_dev, int32_t* minmax_dev, uint32_t* refused_dev) {
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  if (!lhs_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_eval_elementwise_v: null lhs_dev");
+  if (!out_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_eval_elementwise_v: null out_dev");
+  return guard(ctx, [&] {
+    ctx->impl->eval_elementwise(kind, lhs_dev, lhs_view, rhs_dev, rhs_view, n, out_dev, minmax_dev, refused_dev);
+  });
+}
+
+int lmn_eval_reduce(lmn_ctx* ctx, uint32_t is_max, const int32_t* input_dev, uint64_t front, uint64_t dim, uint64_t back,
+                    int32_t* out_dev, int32_t* minmax_dev, uint32_t* refused_dev) {
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  if (!input_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_eval_reduce: null input_dev");
+  if (!out_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_eval_reduce: null out_dev");
+  return guard(ctx, [&] { ctx->impl->eval_reduce(is_max != 0, input_dev, front, dim, back, out_dev, minmax_dev, refused_dev); });
+}
+
+uint32_t lmn_eval_reduce_split(uint64_t dim, uint64_t back) { return lmn::eval_reduce_by_wave(dim, back) ? 1u : 0u; }
+
+int lmn_eval_lut_ranges(lmn_ctx* ctx, uint32_t kind, const int32_t* input_dev, const lmn_view* view, uint64_t n,
+                        const uint32_t* lut_col1_dev, const lmn_range* ranges, uint32_t n_ranges, int32_t* out_dev,
+                        int32_t* minmax_dev, uint32_t* refused_dev) {
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  if (!input_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_eval_lut_ranges: null input_dev");
+  if (!lut_col1_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_eval_lut_ranges: null lut_col1_dev");
+  if (!out_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_eval_lut_ranges: null out_dev");
+  return guard(ctx, [&] {
+    ctx->impl->eval_lut(kind, input_dev, view, n, lut_col1_dev, ranges, n_ranges, out_dev, minmax_dev, refused_dev);
+  });
+}
+
+int lmn_tensor_range(lmn_ctx* ctx, const int32_t* buf_dev, uint64_t n, int32_t* minmax_dev) {
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  if (!buf_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_tensor_range: null buf_dev");
+  if (!minmax_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_tensor_range: null minmax_dev");
+  return guard(ctx, [&] { ctx->impl->tensor_range(buf_dev, n, minmax_dev); });
+}
+
 int lmn_trace_check(lmn_ctx* ctx, const lmn_table* tables, size_t n_tables, const lmn_settings* settings,
                     lmn_trace_report* report) {
   if (!ctx) return LMN_ERR_INVALID_ARGUMENT;

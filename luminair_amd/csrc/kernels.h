@@ -326,6 +326,19 @@ void launch_trace_lut(const int32_t* input, const TraceView& view, uint64_t n, c
 void launch_trace_reduce(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back,
                          const TraceNode& nd, uint32_t* rows, int32_t* out, lmn_stream_t s);
 
+// ---- the eval forms of the producers (lmn_eval_*): values only, plus the range of what was written in minmax[0 .. 1]
+// (atomicMin / atomicMax: initialise with launch_eval_init) and the refused elements added to *refused; both may be null
+void launch_eval_init(int32_t* minmax, lmn_stream_t s);
+void launch_eval_elementwise(int kind, const int32_t* lhs, const TraceView& lv, const int32_t* rhs, const TraceView& rv,
+                             uint64_t n, int32_t* out, int32_t* minmax, uint32_t* refused, lmn_stream_t s);
+void launch_eval_lut(const int32_t* input, const TraceView& view, uint64_t n, const uint32_t* lut_col1, const LutRanges& ranges,
+                     int32_t* out, int32_t* minmax, uint32_t* refused, lmn_stream_t s);
+// true: one wave per reduction group; false: one lane per output element (back large enough for coalesced steps)
+bool eval_reduce_by_wave(uint64_t dim, uint64_t back);
+void launch_eval_reduce(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back, int32_t* out,
+                        int32_t* minmax, uint32_t* refused, lmn_stream_t s);
+void launch_tensor_range(const int32_t* buf, uint64_t n, int32_t* minmax, lmn_stream_t s);
+
 // ---- lmn_trace_check (trace_gen.cpp): which rows break a local constraint, which logup tuples do not balance.
 // One open-addressing table per relation element set: entry i = {keys[i] = val | id << 31 (TC_EMPTY: free), sums[i] = the
 // sum of the signed multiplicity words (u64: below 2^26 rows x 7 relations x 2^31 it cannot overflow), firsts[i] = the

@@ -174,6 +174,51 @@ LMN_D int64_t isqrt_u64(int64_t v) {
   return r;
 }
 
+// The value rule of one element, stated once for the trace form (k_trace_elementwise: rows + output) and the eval form
+// (k_eval_elementwise: output only).  out = what the output tensor receives (0 for a refused element), aux = the kind's
+// second derived word as an exact integer (Mul: low 12 bits of the product, Recip / Sqrt: rem, Rem: quo, LessThan: diff;
+// 0 for a refused element).  No value-dependent work for a refused element: it divides by 1, takes the root of 0.
+struct ElemValue {
+  bool ok;
+  int64_t out, aux;
+};
+template <int KIND>
+LMN_D ElemValue elem_value(int64_t a, int64_t b) {
+  if (KIND == 16 || KIND == 15) {   // Contiguous (prim.rs:229-301), CopyToStwo / Inputs (prim.rs:52-88): out = input
+    const bool ok = fixed_ok(a);
+    return {ok, ok ? a : 0, 0};
+  } else if (KIND == 7) {
+    // Sqrt (prim.rs:573-660): out = floor(sqrt(input * scale)), rem = input * scale - out^2 (natural identity; numerair's
+    // form is unpinned).  input >= 0: a refused element takes the square root of 0
+    const bool ok = a >= 0 && a <= FIXED_MAX;
+    const int64_t x = ok ? a * 4096ll : 0, o = isqrt_u64(x);
+    return {ok, o, x - o * o};
+  } else if (KIND == 8) {
+    // Rem (prim.rs:1323-1421), lhs >= 0, rhs > 0: lhs = rhs * quotient + rem; the out relation carries rem.
+    // A refused element divides 0 by 1.
+    const bool ok = a >= 0 && a <= FIXED_MAX && b > 0 && b <= FIXED_MAX;
+    const uint32_t num = ok ? (uint32_t)a : 0u, den = ok ? (uint32_t)b : 1u;
+    const uint32_t quo = num / den, rem = num - quo * den;
+    return {ok, (int64_t)rem, (int64_t)quo};
+  } else if (KIND == 13) {
+    // LessThan (prim.rs:1203-1295): out = 1.0 iff lhs < rhs; diff = rhs - lhs (+ P with borrow)
+    // (a refused element has zero diff)
+    const bool ok = fixed_ok(a) && fixed_ok(b), lt = ok && a < b;
+    const int64_t diff = ok ? b - a + (lt ? 0 : (int64_t)P31) : 0;  // 1 .. 2^31 - 2, or P for equal operands
+    return {ok, lt ? 4096 : 0, diff};
+  } else if (KIND == 2) {
+    // Recip: input > 0 (4096^2 / input and its remainder fit 32 bits): a refused element divides by 1
+    const bool ok = a > 0 && a <= FIXED_MAX;
+    const uint32_t sc2 = 4096u * 4096u, den = ok ? (uint32_t)a : 1u;
+    const uint32_t o = sc2 / den, rem = sc2 - den * o;
+    return {ok, ok ? (int64_t)o : 0, ok ? (int64_t)rem : 0};
+  } else {
+    const int64_t prod = a * b, o = KIND == 0 ? a + b : prod >> 12;  // Mul: floor
+    const bool ok = fixed_ok(a) && fixed_ok(b) && fixed_ok(o);
+    return {ok, ok ? o : 0, KIND == 1 && ok ? (prod & 4095) : 0};
+  }
+}
+
 template <int KIND>
 LMN_KERNEL k_trace_elementwise(const int32_t* __restrict__ lhs, TraceView lv, const int32_t* __restrict__ rhs,
                                TraceView rv, uint64_t n, TraceNode nd, uint32_t* __restrict__ rows,
@@ -201,46 +246,36 @@ LMN_KERNEL k_trace_elementwise(const int32_t* __restrict__ lhs, TraceView lv, co
       t[8] = ok ? fixed_to_m31(a) : P31; t[9] = nd.lhs_mult; t[10] = nd.out_mult;
       if (out && r < nd.out_n) out[r] = ok ? (int32_t)a : 0;
     } else if (KIND == 16 || KIND == 7) {
-      // Contiguous (prim.rs:229-301): out = input.  Sqrt (prim.rs:573-660): out = floor(sqrt(input * scale)),
-      // rem = input * scale - out^2 (natural identity; numerair's form is unpinned)
+      // Contiguous: input, out.  Sqrt: input, out, rem, scale
+      const ElemValue e = elem_value<KIND>(a, 0);
       t[0] = nd.node_id; t[1] = nd.lhs_id; t[2] = idx; t[3] = last;
       t[4] = nd.node_id; t[5] = nd.lhs_id; t[6] = idx + 1u;
       t[7] = fixed_to_m31(a);
+      t[8] = e.ok ? fixed_to_m31(e.out) : P31;
       if (KIND == 16) {
-        const bool ok = fixed_ok(a);
-        t[8] = ok ? fixed_to_m31(a) : P31; t[9] = nd.lhs_mult; t[10] = nd.out_mult;
-        if (out) out[r] = ok ? (int32_t)a : 0;
+        t[9] = nd.lhs_mult; t[10] = nd.out_mult;
       } else {
-        // input >= 0: a refused element takes the square root of 0
-        const bool ok = a >= 0 && a <= FIXED_MAX;
-        const int64_t x = ok ? a * 4096ll : 0, o = isqrt_u64(x);
-        t[8] = ok ? fixed_to_m31(o) : P31; t[9] = fixed_to_m31(x - o * o); t[10] = 4096u;
+        t[9] = fixed_to_m31(e.aux); t[10] = 4096u;
         t[11] = nd.lhs_mult; t[12] = nd.out_mult;
-        if (out) out[r] = ok ? (int32_t)o : 0;
       }
+      if (out) out[r] = (int32_t)e.out;
     } else if (KIND == 8 || KIND == 13) {
       const int64_t b = rhs[view_offset(rv, r)];
       t[0] = nd.node_id; t[1] = nd.lhs_id; t[2] = nd.rhs_id; t[3] = idx; t[4] = last;
       t[5] = nd.node_id; t[6] = nd.lhs_id; t[7] = nd.rhs_id; t[8] = idx + 1u;
       t[9] = fixed_to_m31(a); t[10] = fixed_to_m31(b);
+      const ElemValue e = elem_value<KIND>(a, b);
+      t[11] = e.ok ? (uint32_t)e.out : P31;   // Rem: rem; LessThan: 1.0 or 0
       if (KIND == 8) {
-        // Rem (prim.rs:1323-1421), lhs >= 0, rhs > 0: lhs = rhs * quotient + rem; the out relation carries rem.
-        // A refused element divides 0 by 1.
-        const bool ok = a >= 0 && a <= FIXED_MAX && b > 0 && b <= FIXED_MAX;
-        const uint32_t num = ok ? (uint32_t)a : 0u, den = ok ? (uint32_t)b : 1u;
-        const uint32_t quo = num / den, rem = num - quo * den;
-        t[11] = ok ? rem : P31; t[12] = quo;
+        t[12] = (uint32_t)e.aux;              // quo
         t[13] = nd.lhs_mult; t[14] = nd.rhs_mult; t[15] = nd.out_mult;
-        if (out) out[r] = (int32_t)rem;
       } else {
-        // LessThan (prim.rs:1203-1295): out = 1.0 iff lhs < rhs; diff = rhs - lhs (+ P with borrow) in four
-        // range-checked 8-bit limbs; aux = the RangeCheckLookup multiplicity column (256 entries)
+        // diff in four range-checked 8-bit limbs; aux = the RangeCheckLookup multiplicity column (256 entries)
         // (a refused element has zero diff, borrow and limbs and adds nothing to the multiplicities)
-        const bool ok = fixed_ok(a) && fixed_ok(b), lt = ok && a < b;
-        const int64_t diff = ok ? b - a + (lt ? 0 : (int64_t)P31) : 0;  // 1 .. 2^31 - 2, or P for equal operands
-        t[11] = ok ? (lt ? 4096u : 0u) : P31;
+        const bool ok = e.ok;
+        const int64_t diff = e.aux;
         t[12] = fixed_to_m31(diff);
-        t[13] = ok && !lt ? 1u : 0u;
+        t[13] = ok && e.out == 0 ? 1u : 0u;   // borrow: not less
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const uint32_t limb = (uint32_t)(diff >> (8 * k)) & 0xFFu;
@@ -248,40 +283,36 @@ LMN_KERNEL k_trace_elementwise(const int32_t* __restrict__ lhs, TraceView lv, co
           if (ok) atomicAdd(&aux[limb], 1u);
         }
         t[18] = nd.lhs_mult; t[19] = nd.rhs_mult; t[20] = nd.out_mult; t[21] = 1u;
-        if (out) out[r] = lt ? 4096 : 0;
       }
+      if (out) out[r] = (int32_t)e.out;
     } else if (KIND == 15) {
       // CopyToStwo / Inputs (prim.rs:52-88): node, idx, is_last, next_node, next_idx, val, multiplicity
-      const bool ok = fixed_ok(a);
+      const ElemValue e = elem_value<KIND>(a, 0);
       t[0] = nd.node_id; t[1] = idx; t[2] = last; t[3] = nd.node_id; t[4] = idx + 1u;
-      t[5] = ok ? fixed_to_m31(a) : P31; t[6] = nd.out_mult;
-      if (out) out[r] = ok ? (int32_t)a : 0;
+      t[5] = e.ok ? fixed_to_m31(a) : P31; t[6] = nd.out_mult;
+      if (out) out[r] = (int32_t)e.out;
     } else if (KIND == 2) {
       // node, input, idx, is_last, next_node, next_input, next_idx, input, out, rem, scale, in_mult, out_mult
-      // input > 0 (4096^2 / input and its remainder fit 32 bits): a refused element divides by 1
-      const bool ok = a > 0 && a <= FIXED_MAX;
-      const uint32_t sc2 = 4096u * 4096u, den = ok ? (uint32_t)a : 1u;
-      const uint32_t o = sc2 / den, rem = sc2 - den * o;
+      const ElemValue e = elem_value<KIND>(a, 0);
       t[0] = nd.node_id; t[1] = nd.lhs_id; t[2] = idx; t[3] = last;
       t[4] = nd.node_id; t[5] = nd.lhs_id; t[6] = idx + 1u;
-      t[7] = fixed_to_m31(a); t[8] = ok ? o : P31; t[9] = ok ? rem : 0u; t[10] = 4096u;
+      t[7] = fixed_to_m31(a); t[8] = e.ok ? (uint32_t)e.out : P31; t[9] = (uint32_t)e.aux; t[10] = 4096u;
       t[11] = nd.lhs_mult; t[12] = nd.out_mult;
-      if (out) out[r] = ok ? (int32_t)o : 0;
+      if (out) out[r] = (int32_t)e.out;
     } else {
       const int64_t b = rhs[view_offset(rv, r)];
       t[0] = nd.node_id; t[1] = nd.lhs_id; t[2] = nd.rhs_id; t[3] = idx; t[4] = last;
       t[5] = nd.node_id; t[6] = nd.lhs_id; t[7] = nd.rhs_id; t[8] = idx + 1u;
       t[9] = fixed_to_m31(a); t[10] = fixed_to_m31(b);
-      const int64_t prod = a * b, o = KIND == 0 ? a + b : prod >> 12;  // Mul: floor
-      const bool ok = fixed_ok(a) && fixed_ok(b) && fixed_ok(o);
-      t[11] = ok ? fixed_to_m31(o) : P31;
+      const ElemValue e = elem_value<KIND>(a, b);
+      t[11] = e.ok ? fixed_to_m31(e.out) : P31;
       if (KIND == 0) {
         t[12] = nd.lhs_mult; t[13] = nd.rhs_mult; t[14] = nd.out_mult;
       } else {
-        t[12] = ok ? (uint32_t)(prod & 4095) : 0u;
+        t[12] = (uint32_t)e.aux;
         t[13] = nd.lhs_mult; t[14] = nd.rhs_mult; t[15] = nd.out_mult;
       }
-      if (out) out[r] = ok ? (int32_t)o : 0;
+      if (out) out[r] = (int32_t)e.out;
     }
   }
   __syncthreads();
@@ -404,6 +435,17 @@ void launch_trace_elementwise(int kind, const int32_t* lhs, const TraceView& lv,
   }
 }
 
+// LookupLayout::find_index: the LUT row of the range that holds `a`, -1 when no range does (few ranges: a linear scan of
+// block-uniform bounds)
+LMN_D int64_t lut_find_index(const LutRanges& rg, int64_t a) {
+  int64_t li = -1;
+  for (int k = 0; k < rg.n; ++k)
+    if (a >= (int64_t)rg.lo[k] && a <= (int64_t)rg.hi[k]) li = (int64_t)rg.base[k] + (a - (int64_t)rg.lo[k]);
+  return li;
+}
+// a LUT output word as the tensor value it stands for
+LMN_D int32_t lut_out_value(uint32_t ow) { return ow > (P31 >> 1) ? (int32_t)ow - (int32_t)P31 : (int32_t)ow; }
+
 // Sin / Exp2 / Log2 rows (sin/table.rs: node, input, idx, is_last, next_node, next_input, next_idx, input, out,
 // input_mult, out_mult, lookup_mult) with out read from the LUT's output column, plus the LUT multiplicities.
 LMN_KERNEL k_trace_lut(const int32_t* __restrict__ input, TraceView view, uint64_t n, TraceNode nd,
@@ -415,10 +457,7 @@ LMN_KERNEL k_trace_lut(const int32_t* __restrict__ input, TraceView view, uint64
   const uint64_t r = row0 + threadIdx.x;
   if (r < n) {
     const int64_t a = input[view_offset(view, r)];
-    // LookupLayout::find_index: the range that holds `a` (few ranges: a linear scan of block-uniform bounds)
-    int64_t li = -1;
-    for (int k = 0; k < rg.n; ++k)
-      if (a >= (int64_t)rg.lo[k] && a <= (int64_t)rg.hi[k]) li = (int64_t)rg.base[k] + (a - (int64_t)rg.lo[k]);
+    const int64_t li = lut_find_index(rg, a);
     uint32_t ow = P31;  // an input outside every range: the call fails, and its row is marked as well
     if (li < 0) {
       *err_flag = 1u;
@@ -430,7 +469,7 @@ LMN_KERNEL k_trace_lut(const int32_t* __restrict__ input, TraceView view, uint64
     t[0] = nd.node_id; t[1] = nd.lhs_id; t[2] = (uint32_t)r; t[3] = r + 1 == n ? 1u : 0u;
     t[4] = nd.node_id; t[5] = nd.lhs_id; t[6] = (uint32_t)r + 1u;
     t[7] = fixed_to_m31(a); t[8] = ow; t[9] = nd.lhs_mult; t[10] = nd.out_mult; t[11] = 1u;
-    if (out) out[r] = ow > (P31 >> 1) ? (int32_t)ow - (int32_t)P31 : (int32_t)ow;
+    if (out) out[r] = lut_out_value(ow);
   }
   __syncthreads();
   const uint64_t rows_here = n - row0 < (uint64_t)TPB ? n - row0 : (uint64_t)TPB;
@@ -444,6 +483,222 @@ void launch_trace_lut(const int32_t* input, const TraceView& view, uint64_t n, c
                       int32_t* out, uint32_t* err_flag, lmn_stream_t s) {
   LMN_LAUNCH(k_trace_lut, dim3(cdiv(n, TPB)), dim3(TPB), 0, s, input, view, n, nd, lut_col1, ranges, mult, rows, out,
              err_flag);
+}
+
+// =============================================================================================
+// The eval forms (`Operator::process`, the forward pass in front of gen_trace): the same value rules, no rows.  Every launch
+// also leaves the minimum and maximum of the values it wrote in minmax[0 .. 1] - the range of a buffer is known when the
+// buffer is produced (`buffer.min_max()` of gen_circuit_settings, crates/graph/src/utils.rs:44-82) - and adds the number
+// of refused elements to *refused; a refused element's 0 takes part in the range, the buffer holds it.
+// =============================================================================================
+LMN_D int32_t wave_min_i32(int32_t v) {
+  for (int m = 32; m > 0; m >>= 1) {
+    const int32_t o = (int32_t)lmn_shfl_xor((uint32_t)v, m);
+    v = o < v ? o : v;
+  }
+  return v;
+}
+LMN_D int32_t wave_max_i32(int32_t v) {
+  for (int m = 32; m > 0; m >>= 1) {
+    const int32_t o = (int32_t)lmn_shfl_xor((uint32_t)v, m);
+    v = o > v ? o : v;
+  }
+  return v;
+}
+LMN_D uint32_t wave_sum_u32(uint32_t v) {
+  for (int m = 32; m > 0; m >>= 1) v += (uint32_t)lmn_shfl_xor(v, m);
+  return v;
+}
+// End of every eval kernel, reached by all TPB lanes: lo / hi = the lane's own range (INT32_MAX / INT32_MIN for a lane that
+// wrote nothing), wave_bad = the wave's refused elements (wave-uniform).  Per wave by xor shuffles, per workgroup through
+// LDS, then one atomicMin, one atomicMax and - only when something was refused - one atomicAdd per workgroup.
+LMN_D void eval_finish(int32_t lo, int32_t hi, uint32_t wave_bad, int32_t* __restrict__ minmax, uint32_t* __restrict__ refused) {
+  LMN_SHARED int32_t s_lo[TPB / 64], s_hi[TPB / 64];
+  LMN_SHARED uint32_t s_bad[TPB / 64];
+  lo = wave_min_i32(lo);
+  hi = wave_max_i32(hi);
+  const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  if (lane == 0u) {
+    s_lo[wave] = lo;
+    s_hi[wave] = hi;
+    s_bad[wave] = wave_bad;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0u) {
+    uint32_t bad = 0u;
+    for (int w = 0; w < TPB / 64; ++w) {
+      lo = s_lo[w] < lo ? s_lo[w] : lo;
+      hi = s_hi[w] > hi ? s_hi[w] : hi;
+      bad += s_bad[w];
+    }
+    if (minmax && lo <= hi) {
+      atomicMin(&minmax[0], lo);
+      atomicMax(&minmax[1], hi);
+    }
+    if (refused && bad) atomicAdd(refused, bad);
+  }
+}
+LMN_D uint32_t wave_count(bool pred) { return (uint32_t)__builtin_popcountll(lmn_ballot(pred)); }
+
+LMN_KERNEL k_eval_init(int32_t* __restrict__ minmax) {
+  if (blockIdx.x == 0u && threadIdx.x == 0u) {
+    minmax[0] = INT32_MAX;
+    minmax[1] = INT32_MIN;
+  }
+}
+void launch_eval_init(int32_t* minmax, lmn_stream_t s) { LMN_LAUNCH(k_eval_init, dim3(1), dim3(64), 0, s, minmax); }
+
+// One lane per element, operands through their views, coalesced int32 stores; no LDS tile, and LessThan touches no
+// multiplicity table.
+template <int KIND>
+LMN_KERNEL k_eval_elementwise(const int32_t* __restrict__ lhs, TraceView lv, const int32_t* __restrict__ rhs, TraceView rv,
+                              uint64_t n, int32_t* __restrict__ out, int32_t* __restrict__ minmax,
+                              uint32_t* __restrict__ refused) {
+  constexpr bool BINARY = KIND == 0 || KIND == 1 || KIND == 8 || KIND == 13;
+  const uint64_t r = (uint64_t)blockIdx.x * TPB + threadIdx.x;
+  const bool on = r < n;
+  int32_t o = 0;
+  bool bad = false;
+  if (on) {
+    const int64_t a = lhs[view_offset(lv, r)];
+    const int64_t b = BINARY ? (int64_t)rhs[view_offset(rv, r)] : 0;
+    const ElemValue e = elem_value<KIND>(a, b);
+    o = (int32_t)e.out;
+    bad = !e.ok;
+    out[r] = o;
+  }
+  eval_finish(on ? o : INT32_MAX, on ? o : INT32_MIN, wave_count(bad), minmax, refused);
+}
+
+void launch_eval_elementwise(int kind, const int32_t* lhs, const TraceView& lv, const int32_t* rhs, const TraceView& rv,
+                             uint64_t n, int32_t* out, int32_t* minmax, uint32_t* refused, lmn_stream_t s) {
+  dim3 g(cdiv(n, TPB)), b(TPB);
+  switch (kind) {
+    case 0: LMN_LAUNCH(k_eval_elementwise<0>, g, b, 0, s, lhs, lv, rhs, rv, n, out, minmax, refused); break;
+    case 1: LMN_LAUNCH(k_eval_elementwise<1>, g, b, 0, s, lhs, lv, rhs, rv, n, out, minmax, refused); break;
+    case 2: LMN_LAUNCH(k_eval_elementwise<2>, g, b, 0, s, lhs, lv, rhs, rv, n, out, minmax, refused); break;
+    case 7: LMN_LAUNCH(k_eval_elementwise<7>, g, b, 0, s, lhs, lv, rhs, rv, n, out, minmax, refused); break;
+    case 8: LMN_LAUNCH(k_eval_elementwise<8>, g, b, 0, s, lhs, lv, rhs, rv, n, out, minmax, refused); break;
+    case 13: LMN_LAUNCH(k_eval_elementwise<13>, g, b, 0, s, lhs, lv, rhs, rv, n, out, minmax, refused); break;
+    case 15: LMN_LAUNCH(k_eval_elementwise<15>, g, b, 0, s, lhs, lv, rhs, rv, n, out, minmax, refused); break;
+    case 16: LMN_LAUNCH(k_eval_elementwise<16>, g, b, 0, s, lhs, lv, rhs, rv, n, out, minmax, refused); break;
+    default: throw LmnError(-100, "eval_elementwise: unsupported kind");
+  }
+}
+
+// out = lut_col1[find_index(input)]; an input outside every range is a refused element (the trace form fails the call
+// instead: a dry run must not wait per node).  No multiplicity increments.
+LMN_KERNEL k_eval_lut(const int32_t* __restrict__ input, TraceView view, uint64_t n, const uint32_t* __restrict__ lut1,
+                      LutRanges rg, int32_t* __restrict__ out, int32_t* __restrict__ minmax, uint32_t* __restrict__ refused) {
+  const uint64_t r = (uint64_t)blockIdx.x * TPB + threadIdx.x;
+  const bool on = r < n;
+  int32_t o = 0;
+  bool bad = false;
+  if (on) {
+    const int64_t li = lut_find_index(rg, (int64_t)input[view_offset(view, r)]);
+    bad = li < 0;
+    if (!bad) o = lut_out_value(lut1[li]);
+    out[r] = o;
+  }
+  eval_finish(on ? o : INT32_MAX, on ? o : INT32_MIN, wave_count(bad), minmax, refused);
+}
+void launch_eval_lut(const int32_t* input, const TraceView& view, uint64_t n, const uint32_t* lut_col1, const LutRanges& ranges,
+                     int32_t* out, int32_t* minmax, uint32_t* refused, lmn_stream_t s) {
+  LMN_LAUNCH(k_eval_lut, dim3(cdiv(n, TPB)), dim3(TPB), 0, s, input, view, n, lut_col1, ranges, out, minmax, refused);
+}
+
+// The group rule of SumReduce / MaxReduce, as k_trace_reduce's rows state it: an input outside the value range marks its
+// row, the last step's row is marked when its input or the group result is outside it, and only then 0 is written; the
+// running sum (int64) may leave the range.  The refused count is the number of marked rows.
+template <bool MAX>
+LMN_D int64_t reduce_op(int64_t a, int64_t b) { return MAX ? (a > b ? a : b) : a + b; }
+
+// One lane per output element g = i * back + j, walking its group at stride `back`: consecutive lanes read consecutive
+// words on every step.  For back >= 64 (a whole wave on one run of words).
+template <bool MAX>
+LMN_KERNEL k_eval_reduce_lane(const int32_t* __restrict__ input, uint64_t dim, uint64_t back, uint64_t n_out,
+                              int32_t* __restrict__ out, int32_t* __restrict__ minmax, uint32_t* __restrict__ refused) {
+  const uint64_t g = (uint64_t)blockIdx.x * TPB + threadIdx.x;
+  const bool on = g < n_out;
+  int32_t o = 0;
+  uint32_t bad = 0u;
+  if (on) {
+    const int32_t* p = input + (g / back) * dim * back + g % back;
+    int64_t acc = MAX ? INT64_MIN : 0;
+    int64_t v = 0;
+    for (uint64_t k = 0; k < dim; ++k) {
+      v = (int64_t)p[k * back];
+      acc = reduce_op<MAX>(acc, v);
+      if (!fixed_ok(v) && k + 1 < dim) ++bad;
+    }
+    const bool ok = fixed_ok(v) && fixed_ok(acc);
+    if (!ok) ++bad;
+    o = ok ? (int32_t)acc : 0;
+    out[g] = o;
+  }
+  eval_finish(on ? o : INT32_MAX, on ? o : INT32_MIN, wave_sum_u32(bad), minmax, refused);
+}
+// One wave per group: lane l reduces steps l, l + 64, ... (back words apart: for a small `back` a wave's 64 loads fall into
+// a few cache lines), the wave combines by xor shuffles - the int64 partial as two words.
+template <bool MAX>
+LMN_KERNEL k_eval_reduce_wave(const int32_t* __restrict__ input, uint64_t dim, uint64_t back, uint64_t n_out,
+                              int32_t* __restrict__ out, int32_t* __restrict__ minmax, uint32_t* __restrict__ refused) {
+  const unsigned lane = threadIdx.x & 63u;
+  const uint64_t g = (uint64_t)blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);   // wave-uniform
+  const bool on = g < n_out;
+  int64_t acc = MAX ? INT64_MIN : 0;
+  uint32_t bad = 0u;
+  bool last_ok = true;
+  if (on) {
+    const int32_t* p = input + (g / back) * dim * back + g % back;
+    for (uint64_t k = lane; k < dim; k += 64) {
+      const int64_t v = (int64_t)p[k * back];
+      acc = reduce_op<MAX>(acc, v);
+      if (k + 1 < dim) bad += fixed_ok(v) ? 0u : 1u;
+      else last_ok = fixed_ok(v);
+    }
+  }
+  for (int m = 32; m > 0; m >>= 1) {
+    const uint32_t lo = (uint32_t)lmn_shfl_xor((uint32_t)(uint64_t)acc, m), hi = (uint32_t)lmn_shfl_xor((uint32_t)((uint64_t)acc >> 32), m);
+    acc = reduce_op<MAX>(acc, (int64_t)((uint64_t)hi << 32 | lo));
+  }
+  bad = wave_sum_u32(bad);
+  const bool ok = wave_count(!last_ok) == 0u && fixed_ok(acc);
+  const int32_t o = ok ? (int32_t)acc : 0;
+  const bool writer = on && lane == 0u;
+  if (writer) out[g] = o;
+  eval_finish(writer ? o : INT32_MAX, writer ? o : INT32_MIN, on ? bad + (ok ? 0u : 1u) : 0u, minmax, refused);
+}
+
+bool eval_reduce_by_wave(uint64_t dim, uint64_t back) { return back < 64; }
+
+void launch_eval_reduce(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back, int32_t* out,
+                        int32_t* minmax, uint32_t* refused, lmn_stream_t s) {
+  const uint64_t n_out = front * back;
+  if (eval_reduce_by_wave(dim, back)) {
+    const dim3 g(cdiv(n_out, TPB / 64)), b(TPB);
+    if (is_max) LMN_LAUNCH(k_eval_reduce_wave<true>, g, b, 0, s, input, dim, back, n_out, out, minmax, refused);
+    else LMN_LAUNCH(k_eval_reduce_wave<false>, g, b, 0, s, input, dim, back, n_out, out, minmax, refused);
+  } else {
+    const dim3 g(cdiv(n_out, TPB)), b(TPB);
+    if (is_max) LMN_LAUNCH(k_eval_reduce_lane<true>, g, b, 0, s, input, dim, back, n_out, out, minmax, refused);
+    else LMN_LAUNCH(k_eval_reduce_lane<false>, g, b, 0, s, input, dim, back, n_out, out, minmax, refused);
+  }
+}
+
+// lmn_tensor_range: the range of a buffer no eval call produced.  Grid-stride over at most 1024 workgroups.
+LMN_KERNEL k_tensor_range(const int32_t* __restrict__ buf, uint64_t n, int32_t* __restrict__ minmax) {
+  int32_t lo = INT32_MAX, hi = INT32_MIN;
+  for (uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * TPB) {
+    const int32_t v = buf[i];
+    lo = v < lo ? v : lo;
+    hi = v > hi ? v : hi;
+  }
+  eval_finish(lo, hi, 0u, minmax, nullptr);
+}
+void launch_tensor_range(const int32_t* buf, uint64_t n, int32_t* minmax, lmn_stream_t s) {
+  const unsigned blocks = cdiv(n, TPB);
+  LMN_LAUNCH(k_tensor_range, dim3(blocks < 1024u ? blocks : 1024u), dim3(TPB), 0, s, buf, n, minmax);
 }
 
 // =============================================================================================

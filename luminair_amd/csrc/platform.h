@@ -301,6 +301,17 @@ inline unsigned long long atomicMin(unsigned long long* p, unsigned long long v)
   if (v < o) *p = v;
   return o;
 }
+// the range words of the eval kernels (kernels_trace.hip eval_finish)
+inline int atomicMin(int* p, int v) {
+  int o = *p;
+  if (v < o) *p = v;
+  return o;
+}
+inline int atomicMax(int* p, int v) {
+  int o = *p;
+  if (v > o) *p = v;
+  return o;
+}
 // the 64-bit atomics of k_trace_check / k_trace_check_collect (kernels_trace.hip)
 inline unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) {
   unsigned long long o = *p;

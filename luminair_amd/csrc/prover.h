@@ -291,6 +291,14 @@ class Context {
   void trace_lut(uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t n, const lmn_node_info& info,
                  const uint32_t* lut_col1, const lmn_range* ranges, uint32_t n_ranges, uint32_t* mult, uint32_t* rows,
                  uint64_t row_offset, int32_t* out);
+  // lmn_eval_* (trace_gen.cpp): the producers' forward pass - values, their range, the refused elements; no rows
+  void eval_elementwise(uint32_t kind, const int32_t* lhs, const lmn_view* lv, const int32_t* rhs, const lmn_view* rv, uint64_t n,
+                        int32_t* out, int32_t* minmax, uint32_t* refused);
+  void eval_reduce(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back, int32_t* out, int32_t* minmax,
+                   uint32_t* refused);
+  void eval_lut(uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t n, const uint32_t* lut_col1,
+                const lmn_range* ranges, uint32_t n_ranges, int32_t* out, int32_t* minmax, uint32_t* refused);
+  void tensor_range(const int32_t* buf, uint64_t n, int32_t* minmax);
   void device_free(void* p);
   // lmn_trace_check (trace_gen.cpp): the rows that break a local constraint and the logup tuples that do not balance
   void trace_check(const lmn_table* tables, size_t n_tables, const lmn_settings* settings, lmn_trace_report& report);
@@ -411,6 +419,7 @@ class Context {
     return (T*)stage_upload(v.data(), v.size() * sizeof(T));
   }
   void fetch_root_async(DevMerkle& m);   // m.root_pinned valid after the next sync
+  void eval_begin(int32_t* minmax);   // selects the device; the range words start at (INT32_MAX, INT32_MIN), on the stream
   uint32_t* bad_flag_ = nullptr;  // two device words: [0] marked when a trace table holds a non-canonical M31 word, [1] trace_lut's
   uint32_t bad_epoch_ = 1;        // the mark of the current unsharded proof (see Context::prove)
   char* pin_base_ = nullptr;

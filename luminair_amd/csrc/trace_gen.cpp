@@ -112,6 +112,89 @@ void Context::trace_elementwise(uint32_t kind, const int32_t* lhs, const lmn_vie
                            stream_);  // stream-ordered with every later call on this context
 }
 
+// ------------------------------------------------------------------------------------ lmn_eval_*
+// `Operator::process` of the same operators: the forward pass in front of gen_trace (gen_circuit_settings' dry run,
+// crates/graph/src/graph.rs:61-159).  Values only; every call also leaves the range of what it wrote and adds its refused
+// elements to a counter, and none waits for the device.
+namespace {
+void eval_bad(const char* call, const std::string& why) { throw LmnError(LMN_ERR_INVALID_ARGUMENT, std::string(call) + ": " + why); }
+TraceView eval_view(const char* call, const char* name, const lmn_view* v, uint64_t n) {
+  try {
+    return trace_view(v, n);
+  } catch (const LmnError& e) {
+    throw LmnError(e.code, std::string(call) + ": " + name + ": " + e.what());
+  }
+}
+}  // namespace
+
+void Context::eval_begin(int32_t* minmax) {
+#ifndef LMN_EMU
+  LMN_HIP_CHECK(hipSetDevice(device_));
+#endif
+  if (minmax) launch_eval_init(minmax, stream_);
+}
+
+void Context::eval_elementwise(uint32_t kind, const int32_t* lhs, const lmn_view* lv, const int32_t* rhs, const lmn_view* rv,
+                               uint64_t n, int32_t* out, int32_t* minmax, uint32_t* refused) {
+  const char* call = "lmn_eval_elementwise_v";
+  const bool binary = kind == LMN_KIND_ADD || kind == LMN_KIND_MUL || kind == LMN_KIND_REM || kind == LMN_KIND_LESS_THAN;
+  const bool unary = kind == LMN_KIND_RECIP || kind == LMN_KIND_SQRT || kind == LMN_KIND_CONTIGUOUS || kind == LMN_KIND_INPUTS;
+  if (!(binary || unary)) eval_bad(call, "kind " + std::to_string(kind) + " is not an elementwise kind");
+  if (binary && !rhs) eval_bad(call, "null rhs_dev for a binary kind");
+  if (n == 0) eval_bad(call, "n is 0");
+  if (n >= (1ull << 31)) eval_bad(call, "n: tensor too large");
+  const TraceView tlv = eval_view(call, "lhs_view", lv, n);
+  const TraceView trv = binary ? eval_view(call, "rhs_view", rv, n) : TraceView{};
+  eval_begin(minmax);
+  launch_eval_elementwise((int)kind, lhs, tlv, rhs, trv, n, out, minmax, refused, stream_);
+}
+
+void Context::eval_reduce(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back, int32_t* out,
+                          int32_t* minmax, uint32_t* refused) {
+  const char* call = "lmn_eval_reduce";
+  if (front == 0) eval_bad(call, "front is 0");
+  if (dim == 0) eval_bad(call, "dim is 0");
+  if (back == 0) eval_bad(call, "back is 0");
+  if (front >= (1ull << 31) || dim >= (1ull << 31) || back >= (1ull << 31) || front * back >= (1ull << 31) ||
+      front * back * dim >= (1ull << 31))
+    eval_bad(call, "front * dim * back: tensor too large");
+  eval_begin(minmax);
+  launch_eval_reduce(is_max, input, front, dim, back, out, minmax, refused, stream_);
+}
+
+void Context::eval_lut(uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t n, const uint32_t* lut_col1,
+                       const lmn_range* ranges, uint32_t n_ranges, int32_t* out, int32_t* minmax, uint32_t* refused) {
+  const char* call = "lmn_eval_lut_ranges";
+  if (kind != LMN_KIND_SIN && kind != LMN_KIND_EXP2 && kind != LMN_KIND_LOG2) eval_bad(call, "kind must be Sin, Exp2 or Log2");
+  if (n == 0) eval_bad(call, "n is 0");
+  if (n >= (1ull << 31)) eval_bad(call, "n: tensor too large");
+  if (!ranges) eval_bad(call, "null ranges");
+  if (n_ranges == 0 || n_ranges > (uint32_t)LUT_MAX_RANGES) eval_bad(call, "n_ranges must be 1..16");
+  LutRanges rg{};
+  rg.n = (int)n_ranges;
+  uint64_t base = 0;
+  for (uint32_t k = 0; k < n_ranges; ++k) {   // the rules of lmn_trace_lut_ranges
+    if (ranges[k].hi < ranges[k].lo || ranges[k].lo <= -(1ll << 30) || ranges[k].hi >= (1ll << 30) ||
+        (k > 0 && ranges[k].lo <= ranges[k - 1].hi))
+      eval_bad(call, "ranges must be ascending, disjoint and inside (-2^30, 2^30)");
+    rg.lo[k] = (int32_t)ranges[k].lo;
+    rg.hi[k] = (int32_t)ranges[k].hi;
+    rg.base[k] = (uint32_t)base;
+    base += (uint64_t)(ranges[k].hi - ranges[k].lo + 1);
+    if (base > (1ull << 26)) eval_bad(call, "ranges: LUT larger than 2^26 rows");
+  }
+  const TraceView tv = eval_view(call, "view", view, n);
+  eval_begin(minmax);
+  launch_eval_lut(input, tv, n, lut_col1, rg, out, minmax, refused, stream_);
+}
+
+void Context::tensor_range(const int32_t* buf, uint64_t n, int32_t* minmax) {
+  if (n == 0) eval_bad("lmn_tensor_range", "n is 0");
+  if (n >= (1ull << 31)) eval_bad("lmn_tensor_range", "n: tensor too large");
+  eval_begin(minmax);
+  launch_tensor_range(buf, n, minmax, stream_);
+}
+
 // `LuminairContiguous::process_trace` in the reference's own row rule (prim.rs:229-301): max(in_size, out_size) rows
 void Context::trace_contiguous(const int32_t* input, uint64_t in_size, const lmn_view* view, uint64_t out_size,
                                const lmn_node_info& info, uint32_t* rows, uint64_t row_offset, int32_t* out) {

@@ -95,6 +95,26 @@ def _as_view(t) -> TensorView:
     return TensorView(t, t.shape, tuple(reversed(strides)))
 
 
+def _lmn_view(v: TensorView):
+    """the `lmn_view` of a TensorView; None for the whole tensor in its own order"""
+    if v.strides == _as_view(v.base).strides and v.shape == v.base.shape and not v.offset:
+        return None
+    return backend.LmnView.make(v.shape, v.strides, v.offset)
+
+
+def _padded_lut_range(name: str, buf_min: int, buf_max: int) -> Tuple[int, int]:
+    """`compute_padded_range_from_srcs` (crates/graph/src/utils.rs:44-82) for one Sin / Exp2 / Log2 node: the min..max of
+    its source buffer padded by 10 % of the span, rounded to nearest; log2 clipped at the smallest positive value."""
+    S = 4096.0
+    lo_f, hi_f = float(buf_min) / S, float(buf_max) / S
+    delta = (hi_f - lo_f) * 0.10
+    rnd = lambda x: int(np.floor(abs(x) * S + 0.5)) * (1 if x >= 0 else -1)
+    lo, hi = rnd(lo_f - delta), rnd(hi_f + delta)
+    if name == "log2":
+        lo = max(lo, 1)
+    return lo, hi
+
+
 @dataclass
 class _Node:
     kind: int
@@ -111,6 +131,7 @@ class DeviceGraph:
         self._next_id = 0
         self.luts: Dict[str, tuple] = {}
         self.lut_ranges: Dict[str, list] = {}      # LUTs declared with several ranges (set_lut_ranges)
+        self._dry_bufs: list = []                  # device allocations of dry_run_device (release_dry_run)
 
     def _tensor(self, shape) -> GraphTensor:
         t = GraphTensor(self._next_id, tuple(int(s) for s in shape))
@@ -301,8 +322,8 @@ class DeviceGraph:
         Context.prove_tables(tables, luts); buffers = every device allocation made (free them after proving)."""
         ctx = self.ctx
         K = TraceTableKind
-        view_of = lambda v: None if v.strides == _as_view(v.base).strides and v.shape == v.base.shape and not v.offset \
-            else backend.LmnView.make(v.shape, v.strides, v.offset)
+        self.release_dry_run()     # (its slab goes back to the context's cache: the lease below may take it)
+        view_of = _lmn_view
         reduces = (int(K.SumReduce), int(K.MaxReduce))
         ref_contig = lambda n: n.kind == int(K.Contiguous) and n.inputs[0].expansion == 1
 
@@ -462,7 +483,83 @@ class DeviceGraph:
             vals[n.out.node_id] = np.asarray(out, dtype=np.int64).reshape(-1)
         return vals
 
-    def gen_circuit_settings(self):
+    # ---- the same dry run on the device: the eval forms of the producers (lmn_eval_*), ranges fused into the launches
+    def release_dry_run(self) -> None:
+        """Give back what `dry_run_device` allocated (`gen_trace` does it too).  The nodes' tensors are gone after it."""
+        for b in self._dry_bufs:
+            b.free()
+        if self._dry_bufs:
+            for n in self.nodes:
+                n.out.buf = None
+        self._dry_bufs = []
+
+    def dry_run_device(self) -> Dict[str, list]:
+        """Every node's values computed in HBM by `lmn_eval_*`, in node order, in one slab; every launch leaves the range
+        of the buffer it wrote in the node's two-word slot.  At a Sin / Exp2 / Log2 node the two words of its source
+        BUFFER come to the host (the one round trip of that node), the padded range is computed as in
+        `gen_circuit_settings`, its columns come from `lmn_lut_from_ranges`, and column 1 goes up for `eval_lut` - so
+        the dry run's LUT outputs are the ones `gen_trace` reads.  Returns {lut name: [(lo, hi) per node]} and leaves
+        every tensor readable (`read`) until `gen_trace` or `release_dry_run`.  Raises ValueError when an element was
+        refused (outside the producers' contract: the host dry run divides by zero or goes on with garbage there)."""
+        ctx = self.ctx
+        K = TraceTableKind
+        self.release_dry_run()
+        al = lambda nbytes: (nbytes + 255) & ~255
+        n_nodes = len(self.nodes)
+        # staged in one upload: the refused counter (zero), the range slots, the graph inputs
+        parts, off, cur = [np.zeros(64 + 2 * n_nodes, dtype=np.uint32)], {}, al((64 + 2 * n_nodes) * 4)
+        parts.append(np.zeros((cur - parts[0].nbytes) // 4, dtype=np.uint32))
+        for n in self.nodes:
+            if n.host is not None:
+                a = np.ascontiguousarray(n.host.astype(np.int32, copy=False)).reshape(-1).view(np.uint32)
+                off[n.out.node_id] = (cur, a.nbytes)
+                parts += [a, np.zeros((al(a.nbytes) - a.nbytes) // 4, dtype=np.uint32)]
+                cur += al(a.nbytes)
+        slab = _lease_slab(ctx, cur + sum(al(n.out.size * 4) for n in self.nodes))
+        self._dry_bufs = [slab]
+        per_fn: Dict[str, list] = {"sin": [], "exp2": [], "log2": []}
+        try:
+            ctx.upload_to(slab.view(0, cur), np.concatenate(parts))
+            refused = slab.view(0, 4)
+            slot = {n.out.node_id: slab.view(256 + 8 * i, 8) for i, n in enumerate(self.nodes)}
+            for n in self.nodes:
+                t = n.out
+                t.buf = slab.view(cur, t.size * 4)
+                cur += al(t.size * 4)
+                common = dict(out=t.buf, minmax=slot[t.node_id], refused=refused)
+                if n.kind == int(K.Inputs):
+                    ctx.eval_elementwise(n.kind, slab.view(*off[t.node_id]), None, t.size, **common)
+                elif n.kind in (int(K.SumReduce), int(K.MaxReduce)):
+                    a = n.inputs[0].base
+                    front = int(np.prod(a.shape[:n.axis])) if n.axis else 1
+                    back = int(np.prod(a.shape[n.axis + 1:])) if n.axis + 1 < len(a.shape) else 1
+                    ctx.eval_reduce(a.buf, front, a.shape[n.axis], back, maximum=n.kind == int(K.MaxReduce), **common)
+                elif n.kind in _LUT_OF:
+                    name = _LUT_OF[n.kind][0]
+                    v = n.inputs[0]
+                    lo, hi = (int(w) for w in ctx.download(slot[v.base.node_id], np.int32))   # of the BUFFER, not the view
+                    rg = _padded_lut_range(name, lo, hi)
+                    per_fn[name].append(rg)
+                    col1 = ctx.upload(ctx.lib.lut_from_ranges(name, [rg])[1])
+                    self._dry_bufs.append(col1)
+                    ctx.eval_lut(n.kind, v.base.buf, t.size, col1, [rg], view=_lmn_view(v), **common)
+                else:
+                    ins = n.inputs
+                    ctx.eval_elementwise(n.kind, ins[0].base.buf, ins[1].base.buf if len(ins) > 1 else None, t.size,
+                                         lhs_view=_lmn_view(ins[0]), rhs_view=_lmn_view(ins[1]) if len(ins) > 1 else None,
+                                         **common)
+            n_refused = int(ctx.download(refused)[0])
+        except Exception:
+            self.release_dry_run()
+            raise
+        if n_refused:
+            self.release_dry_run()
+            raise ValueError("dry run: %d elements refused (a value outside [-(2^30-1), 2^30-1], Recip of a value <= 0, Sqrt "
+                             "of a negative value, Rem outside lhs >= 0 and rhs > 0, or a LUT input outside its range)"
+                             % n_refused)
+        return per_fn
+
+    def gen_circuit_settings(self, device: bool = False):
         """`LuminairGraph::gen_circuit_settings` (crates/graph/src/graph.rs:61-159): dry-run the graph, give every
         Sin / Exp2 / Log2 node the min..max of its source BUFFER padded by 10 % of the span
         (`compute_padded_range_from_srcs` / `buffer_range`, crates/graph/src/utils.rs:44-82), coalesce overlapping or
@@ -470,22 +567,20 @@ class DeviceGraph:
         LessThan node exists.  Declares the LUTs on this graph (`set_lut_ranges`) and returns the `CircuitSettings` in
         the reference's own (serialisable) form.  Unpinned: `Fixed::from_f64` of the padded bounds is taken as
         round-to-nearest (numerair is un-vendored); a log2 range whose padding reaches <= 0 is clipped at the smallest
-        positive value (the reference would emit LUT rows from log2 of a non-positive number there)."""
+        positive value (the reference would emit LUT rows from log2 of a non-positive number there).
+        device=True: the dry run runs on the GPU (`dry_run_device`) - its LUT outputs are the LUT columns' own, and
+        `read(t)` returns its tensors until `gen_trace` or `release_dry_run`; the default is the host dry run."""
         from .pie import CircuitSettings, Lookup, LookupLayout, RangeCheckLookup
-        S = 4096.0
-        vals = self._dry_run()
-        per_fn = {"sin": [], "exp2": [], "log2": []}
-        for n in self.nodes:
-            if n.kind in _LUT_OF:
-                buf = vals[n.inputs[0].base.node_id]
-                lo_f, hi_f = float(buf.min()) / S, float(buf.max()) / S
-                delta = (hi_f - lo_f) * 0.10
-                rnd = lambda x: int(np.floor(abs(x) * S + 0.5)) * (1 if x >= 0 else -1)
-                lo, hi = rnd(lo_f - delta), rnd(hi_f + delta)
-                name = _LUT_OF[n.kind][0]
-                if name == "log2":
-                    lo = max(lo, 1)
-                per_fn[name].append((lo, hi))
+        if device:
+            per_fn = self.dry_run_device()
+        else:
+            vals = self._dry_run()
+            per_fn = {"sin": [], "exp2": [], "log2": []}
+            for n in self.nodes:
+                if n.kind in _LUT_OF:
+                    buf = vals[n.inputs[0].base.node_id]
+                    name = _LUT_OF[n.kind][0]
+                    per_fn[name].append(_padded_lut_range(name, int(buf.min()), int(buf.max())))
         layouts = {}
         for name, rg in per_fn.items():
             if not rg:
