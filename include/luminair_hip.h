@@ -646,10 +646,15 @@ int lmn_op_fold_circle_into_line(lmn_ctx* ctx, uint32_t* dst, const uint32_t* sr
 /* GrindOps::grind: smallest nonce accepted by the proof-of-work check of `protocol_variant` (LMN_PV_POW_PREFIXED,
  * LMN_PV_MIX_U64_HASHED) on channel state `digest` (host). */
 int lmn_op_grind(const uint8_t digest[32], uint32_t pow_bits, uint32_t protocol_variant, uint64_t* nonce_out);
-/* lmn_ctx_grind returns the same nonce as lmn_op_grind, found on the context's GPU (serialised with its proofs; the
- * lock-step batch library has no device grind and returns LMN_ERR_INVALID_ARGUMENT). */
+/* lmn_ctx_grind returns the same nonce as lmn_op_grind, found on the context's GPU (serialised with its proofs). */
 int lmn_ctx_grind(lmn_ctx* ctx, const uint8_t digest[32], uint32_t pow_bits, uint32_t protocol_variant,
                   uint64_t* nonce_out);                                                            /* GrindOps::grind on the device */
+/* The same for n channel digests ground together, one kernel over all of them: nonces_out[i] is lmn_op_grind's nonce
+ * for digests[32 * i .. 32 * i + 32).  n == 0 is LMN_OK and touches nothing; a null pointer, n > LMN_GRIND_MANY_MAX,
+ * pow_bits > 40 or unknown variant bits are LMN_ERR_INVALID_ARGUMENT, and lmn_last_error names the argument. */
+#define LMN_GRIND_MANY_MAX 1024
+int lmn_ctx_grind_many(lmn_ctx* ctx, const uint8_t* digests /* 32 * n bytes */, uint32_t n, uint32_t pow_bits,
+                       uint32_t protocol_variant, uint64_t* nonces_out /* n */);
 /* PolyOps::evaluate restricted to one aligned block of rows (single-commitment sharding over GPUs):
  * rows [block * 2^(log_domain - log_blocks), (block + 1) * 2^(log_domain - log_blocks)) of every column's
  * evaluation on the 2^log_domain domain, computed from the coefficients alone (1 <= log_blocks <= 3).

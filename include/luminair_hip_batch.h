@@ -25,7 +25,7 @@ int lmn_batch_create(int device, const lmn_config* cfg, uint32_t slots, lmn_batc
 int lmn_batch_prove(lmn_batch* batch, uint32_t n, const lmn_table* const* tables, size_t n_tables,
                     const lmn_settings* settings, uint8_t** proofs, size_t* lens, int* rcs);
 const char* lmn_batch_last_error(const lmn_batch* batch);
-uint64_t lmn_batch_counter(const lmn_batch* batch, int which); /* so far - 0: batched kernel launches, 1: host waits, 2: batched transfer launches, 3: transfers issued one by one */
+uint64_t lmn_batch_counter(const lmn_batch* batch, int which); /* so far - 0: batched kernel launches, 1: host waits, 2: batched transfer launches, 3: transfers issued one by one, 7: proof-of-work grinds on the device (one per batch), 8: host waits inside them (0 and 1 count lock-step rendezvous only: they do not depend on the nonces) */
 void lmn_batch_destroy(lmn_batch* batch);
 
 #ifdef __cplusplus

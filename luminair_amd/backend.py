@@ -219,7 +219,7 @@ EXPORTS = ["lmn_abi_version", "lmn_kind_padding_row", "lmn_strerror", "lmn_last_
            "lmn_host_alloc", "lmn_host_free", "lmn_host_register", "lmn_host_unregister",
            "lmn_op_interpolate", "lmn_op_evaluate", "lmn_op_merkle_root", "lmn_op_eval_at_point",
            "lmn_op_fft_selftest", "lmn_op_accumulate_quotients", "lmn_op_fold_line", "lmn_op_fold_circle_into_line",
-           "lmn_op_grind", "lmn_ctx_grind", "lmn_device_alloc", "lmn_download", "lmn_trace_elementwise", "lmn_trace_sum_reduce",
+           "lmn_op_grind", "lmn_ctx_grind", "lmn_ctx_grind_many", "lmn_device_alloc", "lmn_download", "lmn_trace_elementwise", "lmn_trace_sum_reduce",
            "lmn_trace_elementwise_v", "lmn_trace_contiguous", "lmn_trace_lut", "lmn_trace_lut_ranges", "lmn_trace_less_than", "lmn_trace_max_reduce", "lmn_upload_to", "lmn_device_copy", "lmn_op_evaluate_block",
            "lmn_verify_with_config", "lmn_verify_diagnose", "lmn_kind_constraint_layout", "lmn_lut_log_size", "lmn_lut_from_ranges", "lmn_lut_from_ranges_r", "lmn_col_alloc", "lmn_col_from_cpu", "lmn_col_to_cpu", "lmn_col_free", "lmn_col_ncols",
            "lmn_col_log_size", "lmn_col_device_ptr", "lmn_col_view", "lmn_col_bit_reverse", "lmn_col_precompute_twiddles",
@@ -300,6 +300,8 @@ class Library:
         lib.lmn_op_fold_circle_into_line.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.lmn_op_grind.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
         lib.lmn_ctx_grind.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+        lib.lmn_ctx_grind_many.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                           C.POINTER(C.c_uint64)]
         lib.lmn_device_alloc.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
         lib.lmn_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         lib.lmn_upload_to.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -1329,6 +1331,16 @@ class Context:
         out = C.c_uint64()
         self._check(self.lib.lib.lmn_ctx_grind(self.handle, digest, pow_bits, variant, C.byref(out)))
         return int(out.value)
+
+    def grind_many(self, digests, pow_bits: int, variant: int = VARIANT_KAT) -> List[int]:
+        """GrindOps::grind for several 32-byte channel digests ground together on the context's GPU (lmn_ctx_grind_many):
+        the nonces Library.grind finds for each of them, in order."""
+        digests = [bytes(d) for d in digests]
+        if any(len(d) != 32 for d in digests):
+            raise ValueError("every digest must be 32 bytes")
+        out = (C.c_uint64 * max(1, len(digests)))()
+        self._check(self.lib.lib.lmn_ctx_grind_many(self.handle, b"".join(digests), len(digests), pow_bits, variant, out))
+        return [int(v) for v in out[:len(digests)]]
 
     def fft_selftest(self, log_size: int, ncols: int = 2):
         self._check(self.lib.lib.lmn_op_fft_selftest(self.handle, log_size, ncols))

@@ -87,7 +87,8 @@ class BatchProver:
         return {"launches": int(c(self.handle, 0)), "host_waits": int(c(self.handle, 1)),
                 "copy_launches": int(c(self.handle, 2)), "direct_copies": int(c(self.handle, 3)),
                 "arrival_skew_ms": int(c(self.handle, 4)) / 1e6, "leader_ms": int(c(self.handle, 5)) / 1e6,
-                "member_busy_ms": int(c(self.handle, 6)) / 1e6}
+                "member_busy_ms": int(c(self.handle, 6)) / 1e6,
+                "grinds": int(c(self.handle, 7)), "grind_rounds": int(c(self.handle, 8))}
 
     def close(self):
         if self.handle:

@@ -401,7 +401,8 @@ static void complete_rendezvous(BatchGroup& g, BatchMember& me) {
         BatchMember& m = g.member[i];
         if (!m.present) continue;
         if (m.kind != me.kind || (me.kind == 1 && (m.fn != me.fn || m.bx != me.bx || m.by != me.by || m.smem != me.smem ||
-                                                   m.slot_bytes != me.slot_bytes)))
+                                                   m.slot_bytes != me.slot_bytes)) ||
+            (me.kind == 3 && m.coll_fn != me.coll_fn))
           g.failed.store(1);
       }
     }
@@ -431,6 +432,14 @@ static void complete_rendezvous(BatchGroup& g, BatchMember& me) {
         stream_wait(g.stream);
         g.flush_top[me.epoch & 1] = 0;
         g.syncs++;
+      } else if (me.kind == 3) {
+        // the deposits of the members present, in slot order; `me` may be any of them (batch_leave completes the
+        // rendezvous on behalf of the first one present), so nothing here depends on who runs it
+        std::vector<BatchCollectiveItem> items;
+        for (int i = 0; i < g.slots; ++i)
+          if (g.member[i].present) items.push_back(g.member[i].coll);
+        g.collective_waits += me.coll_fn(me.coll_arg, items.data(), (int)items.size(), g.stream);
+        g.collectives++;
       }
     }
   } catch (...) {
@@ -508,6 +517,20 @@ void batch_sync(hipStream_t s) {
   auto& outs = bounce_out_list();
   for (auto& b : outs) memcpy(b.dst, b.slot, b.bytes);
   outs.clear();
+}
+
+void batch_stream_wait(hipStream_t s) { stream_wait(s); }
+
+void batch_collective(BatchCollectiveFn fn, void* arg, const void* in, uint32_t n, void* out, hipStream_t s) {
+  BatchGroup& g = batch_current_group();
+  BatchMember& me = g.member[tls_batch_group ? tls_batch_member : 0];
+  if (g.solo) g.stream = s;
+  throw_if_failed(g);
+  me.kind = 3;
+  me.coll_fn = fn;
+  me.coll_arg = arg;
+  me.coll = BatchCollectiveItem{in, n, out};
+  arrive(g, me);
 }
 
 void batch_leave() {
@@ -846,6 +869,8 @@ uint64_t lmn_batch_counter(const lmn_batch* b, int which) {
     case 3: return b->group.direct_copies;
     case 4: return b->group.ns_skew;
     case 5: return b->group.ns_leader;
+    case 7: return b->group.collectives;
+    case 8: return b->group.collective_waits;
     default: return b->group.ns_busy;
   }
 }

@@ -77,6 +77,19 @@ struct BatchCopy {
 };
 constexpr uint32_t BATCH_COPY_CHUNK = 16u << 10;   // one workgroup per chunk
 
+// A COLLECTIVE is the third kind of rendezvous (after launch and wait): every arriving member deposits a small input and
+// an output pointer, and the member that completes the rendezvous runs ONE function over the inputs of all members
+// present, on the group's stream, launching and waiting as often as it needs (its own launches and transfers go straight
+// to the runtime: nobody else moves), before it releases everybody.  Used where the number of launches depends on the
+// data, which lock-step members may not show: the proof-of-work grind (phase_decommit.cpp).
+struct BatchCollectiveItem {
+  const void* in;    // the member's input: `n` elements of whatever the function expects
+  uint32_t n;
+  void* out;         // the member's result
+};
+// returns the host waits it spent (lmn_batch_counter 8); an exception fails the group like a failed launch
+typedef uint64_t (*BatchCollectiveFn)(void* arg, const BatchCollectiveItem* items, int n_items, hipStream_t stream);
+
 // per-member state of the rendezvous in progress; written by the member alone, read by the last arriver
 struct alignas(128) BatchMember {
   const void* fn = nullptr;      // trampoline instantiation the member wants to launch
@@ -86,7 +99,10 @@ struct alignas(128) BatchMember {
   uint32_t gx = 0, gy = 0, bx = 0, by = 0;
   size_t smem = 0, slot_bytes = 0;
   size_t region = 0;             // the member's own view of the launch's table region (identical on all members)
-  int kind = 0;                  // 1 launch, 2 wait
+  int kind = 0;                  // 1 launch, 2 wait, 3 collective
+  BatchCollectiveFn coll_fn = nullptr;   // kind 3: the function (the same for every member) and this member's own
+  void* coll_arg = nullptr;              // argument and deposit; the completing member runs the function with the
+  BatchCollectiveItem coll{};            // argument of ANY present member (all describe the same work)
   bool present = false;          // arrived at the rendezvous in progress
   uint64_t t_arrive = 0, t_resume = 0, ns_busy = 0;   // instrumentation: the member's own host time between rendezvous
   bool active = false;           // still part of the group
@@ -128,6 +144,7 @@ struct BatchGroup {
   size_t smem = 0, region = 0, slot_bytes = 0;
   uint64_t launches = 0, syncs = 0, copy_launches = 0, direct_copies = 0;
   uint64_t ns_skew = 0, ns_leader = 0, ns_busy = 0;   // where a batch's host time goes (lmn_batch_counter 4, 5, 6)
+  uint64_t collectives = 0, collective_waits = 0;     // lmn_batch_counter 7, 8 (the grind is the one collective)
 };
 // a transfer of a group member: true = taken over (runs before the next launch / wait of the group), false = the
 // caller issues it itself (solo thread, or too large for the bounce memory)
@@ -144,6 +161,9 @@ unsigned char* batch_launch_begin(BatchGroup& g, const void* fn, void (*do_launc
                                   size_t smem, size_t slot_bytes, hipStream_t stream);
 void batch_launch_end(BatchGroup& g);                    // arrive; the last arriver launches for everybody
 void batch_sync(hipStream_t s);                          // rendezvous + one stream wait for the whole group
+// collective rendezvous: deposit (in, n, out), return once the function has run over all present members' deposits
+void batch_collective(BatchCollectiveFn fn, void* arg, const void* in, uint32_t n, void* out, hipStream_t s);
+void batch_stream_wait(hipStream_t s);                   // the completing member's own wait inside a collective
 void batch_leave();                                      // the calling member stops taking part (normal end or exception)
 void batch_check_hip(hipError_t e, const char* what);
 

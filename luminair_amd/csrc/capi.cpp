@@ -411,6 +411,22 @@ int lmn_ctx_grind(lmn_ctx* ctx, const uint8_t digest[32], uint32_t pow_bits, uin
   });
 }
 
+int lmn_ctx_grind_many(lmn_ctx* ctx, const uint8_t* digests, uint32_t n, uint32_t pow_bits, uint32_t protocol_variant,
+                       uint64_t* nonces_out) {
+  if (!ctx) {
+    g_create_error = "lmn_ctx_grind_many: ctx is null";
+    return LMN_ERR_INVALID_ARGUMENT;
+  }
+  if (n == 0) return LMN_OK;
+  if (!digests) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_ctx_grind_many: digests is null");
+  if (!nonces_out) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_ctx_grind_many: nonces_out is null");
+  if (n > LMN_GRIND_MANY_MAX) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_ctx_grind_many: n exceeds LMN_GRIND_MANY_MAX");
+  if (pow_bits > 40) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_ctx_grind_many: pow_bits exceeds 40");
+  if (protocol_variant & ~LMN_PV_ALL)
+    return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_ctx_grind_many: protocol_variant has unknown bits");
+  return guard(ctx, [&] { ctx->impl->op_grind_many(digests, n, pow_bits, protocol_variant, nonces_out); });
+}
+
 int lmn_device_alloc(lmn_ctx* ctx, size_t bytes, void** device_out) {
   if (!ctx || !device_out) return LMN_ERR_INVALID_ARGUMENT;
   return guard(ctx, [&] { *device_out = ctx->impl->device_alloc(bytes); });

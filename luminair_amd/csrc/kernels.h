@@ -291,6 +291,12 @@ struct PowWords {
 };
 void launch_pow_grind(const PowWords& w, bool kat, uint64_t base, int window_log, uint32_t pow_bits,
                       unsigned long long* best, lmn_stream_t s);
+// The same for many digests at once: one launch examines [base, base + 2^window_log) for the digests
+// digests[pending[y]], y < n_pending (<= 65535), and lowers best[pending[y]] (one u64 per digest, device).  A digest whose
+// best already lies below a block's nonces costs that block one load.  digests, pending and best are device memory that
+// nothing else writes during the launch.
+void launch_grind_many(const PowWords* digests, const uint32_t* pending, uint32_t n_pending, bool kat, uint64_t base,
+                       int window_log, uint32_t pow_bits, unsigned long long* best, lmn_stream_t s);
 
 // ---- trace generation for the elementwise primitives (the producer of the hot path's input)
 struct TraceNode {

@@ -1204,6 +1204,27 @@ LMN_D unsigned long long pow_best_now(const unsigned long long* best) {
 #endif
 }
 
+// one nonce: the compression of its form with the zero message words folded out (blake2s.h b2_half_z)
+template <bool KAT>
+LMN_D bool pow_nonce_passes(const PowWords& pw, uint64_t nonce, uint64_t mask) {
+  uint32_t m[16], h[8];
+  if constexpr (KAT) {
+    for (int i = 0; i < 8; ++i) h[i] = pw.w[i];
+    m[0] = (uint32_t)nonce;
+    m[1] = (uint32_t)(nonce >> 32);
+    for (int i = 2; i < 16; ++i) m[i] = 0u;
+    b2_compress_cv_nz<2>(h, m, 0u, 0u);
+  } else {
+    for (int i = 0; i < 8; ++i) m[i] = pw.w[i];
+    m[8] = (uint32_t)nonce;
+    m[9] = (uint32_t)(nonce >> 32);
+    for (int i = 10; i < 16; ++i) m[i] = 0u;
+    b2_compress_fresh_nz<10>(h, m, 40u);
+  }
+  // trailing zeros of words 0..3 (little-endian) >= pow_bits <=> the low pow_bits bits of words 0..1 are zero (pow_bits <= 40)
+  return (((uint64_t)h[1] << 32 | h[0]) & mask) == 0u;
+}
+
 template <bool KAT>
 LMN_KERNEL k_pow_grind(PowWords pw, uint64_t base, uint64_t mask, unsigned long long* best) {
   const uint64_t lo = base + (uint64_t)blockIdx.x * (POW_TPB * POW_NPT);
@@ -1211,28 +1232,53 @@ LMN_KERNEL k_pow_grind(PowWords pw, uint64_t base, uint64_t mask, unsigned long 
   uint64_t found = ~0ull;
   for (uint32_t k = 0; k < POW_NPT; ++k) {
     const uint64_t nonce = lo + k * POW_TPB + threadIdx.x;
-    uint32_t m[16], h[8];
-    if constexpr (KAT) {
-      for (int i = 0; i < 8; ++i) h[i] = pw.w[i];
-      m[0] = (uint32_t)nonce;
-      m[1] = (uint32_t)(nonce >> 32);
-      for (int i = 2; i < 16; ++i) m[i] = 0u;
-      b2_compress_cv_nz<2>(h, m, 0u, 0u);
-    } else {
-      for (int i = 0; i < 8; ++i) m[i] = pw.w[i];
-      m[8] = (uint32_t)nonce;
-      m[9] = (uint32_t)(nonce >> 32);
-      for (int i = 10; i < 16; ++i) m[i] = 0u;
-      b2_compress_fresh_nz<10>(h, m, 40u);
-    }
-    // trailing zeros of words 0..3 (little-endian) >= pow_bits <=> the low pow_bits bits of words 0..1 are zero (pow_bits <= 40)
-    if ((((uint64_t)h[1] << 32 | h[0]) & mask) == 0u) {
+    if (pow_nonce_passes<KAT>(pw, nonce, mask)) {
       found = nonce;
       break;
     }
   }
   if (found != ~0ull) atomicMin(best, (unsigned long long)found);
 }
+
+// The same examination for MANY digests in one launch (kernels.h launch_grind_many): blockIdx.y selects an entry of the
+// pending table, the entry a digest of `digests` and its word of `best`; blockIdx.x is k_pow_grind's block.  The entry
+// and the eight digest words are the same for the whole workgroup: they are read through the scalar cache (constant
+// address space, as k_quotients reads its entry table - nothing writes either table during the launch).
+template <bool KAT>
+LMN_KERNEL k_grind_many(const PowWords* __restrict__ digests, const uint32_t* __restrict__ pending, uint64_t base,
+                        uint64_t mask, unsigned long long* best_of) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(LMN_EMU)
+  typedef const uint32_t __attribute__((address_space(4))) * ConstWords;
+  const uint32_t idx = ((ConstWords)(uintptr_t)pending)[blockIdx.y];
+  const ConstWords dw = (ConstWords)(uintptr_t)(digests + idx);
+#else
+  const uint32_t idx = pending[blockIdx.y];
+  const uint32_t* dw = digests[idx].w;
+#endif
+  unsigned long long* best = best_of + idx;
+  const uint64_t lo = base + (uint64_t)blockIdx.x * (POW_TPB * POW_NPT);
+  if (pow_best_now(best) < lo) return;
+  PowWords pw;
+  for (int i = 0; i < 8; ++i) pw.w[i] = dw[i];
+  uint64_t found = ~0ull;
+  for (uint32_t k = 0; k < POW_NPT; ++k) {
+    const uint64_t nonce = lo + k * POW_TPB + threadIdx.x;
+    if (pow_nonce_passes<KAT>(pw, nonce, mask)) {
+      found = nonce;
+      break;
+    }
+  }
+  if (found != ~0ull) atomicMin(best, (unsigned long long)found);
+}
+#ifdef LMN_BATCH
+// the batch build's kernels are device functions behind the trampoline; the leader of a grind collective launches this
+// one itself (batch.cpp k_batch_copy is the precedent), so it gets an entry of its own
+template <bool KAT>
+__global__ void k_grind_many_entry(const PowWords* __restrict__ digests, const uint32_t* __restrict__ pending, uint64_t base,
+                                   uint64_t mask, unsigned long long* best_of) {
+  k_grind_many<KAT>(digests, pending, base, mask, best_of);
+}
+#endif
 
 void launch_pow_grind(const PowWords& w, bool kat, uint64_t base, int window_log, uint32_t pow_bits,
                       unsigned long long* best, lmn_stream_t s) {
@@ -1245,6 +1291,28 @@ void launch_pow_grind(const PowWords& w, bool kat, uint64_t base, int window_log
   } else {
     LMN_LAUNCH(k_pow_grind<false>, grid, dim3(POW_TPB), 0, s, w, base, mask, best);
   }
+}
+
+void launch_grind_many(const PowWords* digests, const uint32_t* pending, uint32_t n_pending, bool kat, uint64_t base,
+                       int window_log, uint32_t pow_bits, unsigned long long* best, lmn_stream_t s) {
+  if (window_log < POW_MIN_WINDOW_LOG || window_log > 32 || pow_bits > 40 || n_pending == 0 || n_pending > 65535u)
+    throw LmnError(-100, "grind_many: bad window");
+  const uint64_t mask = (1ull << pow_bits) - 1u;
+  const dim3 grid(1u << (window_log - POW_MIN_WINDOW_LOG), n_pending);
+#ifdef LMN_BATCH
+  // issued by the one member that runs the collective, not by every member: past the trampoline
+  if (kat)
+    hipLaunchKernelGGL(k_grind_many_entry<true>, grid, dim3(POW_TPB), 0, s, digests, pending, base, mask, best);
+  else
+    hipLaunchKernelGGL(k_grind_many_entry<false>, grid, dim3(POW_TPB), 0, s, digests, pending, base, mask, best);
+  batch_check_hip(hipGetLastError(), "grind_many launch");
+#else
+  if (kat) {
+    LMN_LAUNCH(k_grind_many<true>, grid, dim3(POW_TPB), 0, s, digests, pending, base, mask, best);
+  } else {
+    LMN_LAUNCH(k_grind_many<false>, grid, dim3(POW_TPB), 0, s, digests, pending, base, mask, best);
+  }
+#endif
 }
 
 }  // namespace lmn

@@ -180,6 +180,26 @@ uint64_t Context::op_grind(const Hash32& digest, uint32_t pow_bits, uint32_t var
   return device_grind(ch, pow_bits);
 }
 
+void Context::op_grind_many(const uint8_t* digests, uint32_t n, uint32_t pow_bits, uint32_t variant, uint64_t* nonces_out) {
+  if (pow_bits > 40 || (variant & ~LMN_PV_ALL)) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "grind_many: bad pow_bits / variant");
+  begin_op();
+  const bool prefixed = (variant & LMN_PV_POW_PREFIXED) != 0;
+  const bool kat = !prefixed && !(variant & LMN_PV_MIX_U64_HASHED);
+  std::vector<PowWords> w(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    Hash32 d;
+    memcpy(d.w, digests + 32 * (size_t)i, 32);
+    if (prefixed) {
+      Channel ch(variant);
+      ch.set_digest(d);
+      d = ch.pow_prefixed_digest(pow_bits);
+    }
+    memcpy(w[i].w, d.w, 32);
+  }
+  const std::vector<uint64_t> nonces = grind_many(w.data(), n, kat, pow_bits);
+  memcpy(nonces_out, nonces.data(), n * sizeof(uint64_t));
+}
+
 // tiled FFT vs one-layer-per-launch kernels on pseudo-random data (device-side differential check)
 void Context::op_fft_selftest(uint32_t log_size, uint32_t ncols) {
   check_op_log(log_size, "fft_selftest");

@@ -4,24 +4,34 @@
 
 namespace lmn {
 
+// the words one nonce is hashed with: the channel's digest, or its prefixed digest in the prefixed form
+static PowWords pow_words_of(const Channel& ch, uint32_t pow_bits, bool& kat) {
+  const bool prefixed = (ch.flags() & LMN_PV_POW_PREFIXED) != 0;
+  kat = !prefixed && !(ch.flags() & LMN_PV_MIX_U64_HASHED);
+  PowWords w;
+  const Hash32 src = prefixed ? ch.pow_prefixed_digest(pow_bits) : ch.digest();
+  memcpy(w.w, src.w, sizeof w.w);
+  return w;
+}
+
 // Proof of work on the device (k_pow_grind): windows of 2^wlog nonces in ascending order, POW_WINDOWS_PER_WAIT per wait,
 // until one holds a passing nonce; its minimum is the host loop's answer (Channel::grind).  The window grows with
 // pow_bits (about two expected hits per window) up to pow_window_log_, the cap that keeps one launch well under a
 // millisecond (2^24 nonces: 0.24 ms measured), so that other contexts' launches interleave.
+//
+// Launches queued per host wait, here and in grind_many's rounds: one behind the launch that found a nonce returns at
+// once (every block sees the smaller nonce at its start), so the queue costs a few us of launches and saves waits while
+// nothing has been found.  (grind_many on 64 digests at pow_bits 20: 4 is within the spread of 8, 16 is 5 - 8 % slower.)
+constexpr int POW_WINDOWS_PER_WAIT = 8;
+
 uint64_t Context::device_grind(const Channel& ch, uint32_t pow_bits) {
+  bool kat;
+  const PowWords w = pow_words_of(ch, pow_bits, kat);
 #ifdef LMN_BATCH
-  (void)ch;
-  (void)pow_bits;
-  throw LmnError(LMN_ERR_INVALID_ARGUMENT, "the lock-step batch library grinds on the host only (no device grind)");
+  // lock-step members must issue identical sequences, and this loop's length depends on the digest: the members grind
+  // together, in one collective (grind_many below); a thread outside any batch is a group of one
+  return grind_many(&w, 1, kat, pow_bits)[0];
 #else
-  // launches queued per host wait: one behind the launch that found a nonce returns at once (every block sees the smaller
-  // nonce at its start), so the queue costs a few us of launches and saves waits while nothing has been found
-  constexpr int POW_WINDOWS_PER_WAIT = 8;
-  const bool prefixed = (ch.flags() & LMN_PV_POW_PREFIXED) != 0;
-  const bool kat = !prefixed && !(ch.flags() & LMN_PV_MIX_U64_HASHED);
-  PowWords w;
-  const Hash32 src = prefixed ? ch.pow_prefixed_digest(pow_bits) : ch.digest();
-  memcpy(w.w, src.w, sizeof w.w);
   if (!pow_best_) pow_best_ = (unsigned long long*)lmn_dev_malloc(sizeof(unsigned long long));
   unsigned long long* found = (unsigned long long*)pin_alloc(sizeof(unsigned long long));
   const int wlog = std::min(pow_window_log_, std::max(POW_MIN_WINDOW_LOG, (int)pow_bits + 1));
@@ -36,10 +46,116 @@ uint64_t Context::device_grind(const Channel& ch, uint32_t pow_bits) {
 #endif
 }
 
-uint64_t Context::grind(const Channel& ch, uint32_t pow_bits) {
-#ifndef LMN_BATCH
-  if ((int)pow_bits >= pow_device_min_bits_) return device_grind(ch, pow_bits);
+// Many digests ground together (k_grind_many): every round uploads the table of the digests still pending, queues
+// POW_WINDOWS_PER_WAIT launches of consecutive windows over all of them, downloads best[] and waits; digests with a hit
+// leave the table and base advances by the whole round.  Invariant: every pending digest has been examined on exactly
+// [0, base) - so a digest's first hit is the minimum over [0, end of its round), the host loop's answer, whatever the
+// window was in each round.  The window shrinks with the number of pending digests so that ONE launch examines at most
+// 2^pow_window_log_ nonces in all (the rule that keeps a grind launch short for the other contexts; the smallest window,
+// one block per digest, is the floor) and grows again as digests finish.  Returns the host waits spent.
+#ifdef LMN_BATCH
+// (the batch build runs this inside a collective, on one member's thread while the others wait: transfers and waits
+// go straight to the runtime instead of into the member's copy list and the group's rendezvous)
+static void pow_h2d(void* d, const void* h, size_t n, lmn_stream_t s) {
+  batch_check_hip(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, s), "grind_many upload");
+}
+static void pow_d2h(void* h, const void* d, size_t n, lmn_stream_t s) {
+  batch_check_hip(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, s), "grind_many download");
+}
+static void pow_wait(lmn_stream_t s) { batch_stream_wait(s); }
+#else
+static void pow_h2d(void* d, const void* h, size_t n, lmn_stream_t s) { lmn_h2d(d, h, n, s); }
+static void pow_d2h(void* h, const void* d, size_t n, lmn_stream_t s) { lmn_d2h(h, d, n, s); }
+static void pow_wait(lmn_stream_t s) { lmn_sync(s); }
 #endif
+
+uint64_t Context::grind_rounds(const PowWords* w, uint32_t n, bool kat, uint32_t pow_bits, uint64_t* nonces) {
+  typedef unsigned long long u64;
+  constexpr size_t PER_DIGEST = sizeof(PowWords) + sizeof(u64) + sizeof(uint32_t);   // digests | best | pending
+  if (n > pow_many_cap_) {
+    if (pow_many_dev_) lmn_dev_free(pow_many_dev_);
+    if (pow_many_host_) lmn_host_free_pinned(pow_many_host_);
+    pow_many_dev_ = pow_many_host_ = nullptr;
+    pow_many_cap_ = 0;
+    const uint32_t cap = std::max(64u, n);
+    pow_many_dev_ = (char*)lmn_dev_malloc(cap * PER_DIGEST);
+    pow_many_host_ = (char*)lmn_host_alloc_pinned(cap * PER_DIGEST);
+    pow_many_cap_ = cap;
+  }
+  const size_t cap = pow_many_cap_;
+  PowWords* d_w = (PowWords*)pow_many_dev_;
+  u64* d_best = (u64*)(pow_many_dev_ + cap * sizeof(PowWords));
+  uint32_t* d_pend = (uint32_t*)(pow_many_dev_ + cap * (sizeof(PowWords) + sizeof(u64)));
+  PowWords* h_w = (PowWords*)pow_many_host_;
+  u64* h_best = (u64*)(pow_many_host_ + cap * sizeof(PowWords));
+  uint32_t* h_pend = (uint32_t*)(pow_many_host_ + cap * (sizeof(PowWords) + sizeof(u64)));
+  memcpy(h_w, w, n * sizeof(PowWords));
+  for (uint32_t i = 0; i < n; ++i) {
+    h_best[i] = ~0ull;
+    h_pend[i] = i;
+  }
+  pow_h2d(d_w, h_w, n * sizeof(PowWords), stream_);
+  pow_h2d(d_best, h_best, n * sizeof(u64), stream_);
+  uint64_t waits = 0;
+  uint32_t n_pending = n;
+  for (uint64_t base = 0; n_pending;) {
+    int lg = 0;
+    while ((1u << lg) < n_pending) ++lg;
+    const int wlog = std::max(POW_MIN_WINDOW_LOG, std::min((int)pow_bits + 1, pow_window_log_ - lg));
+    pow_h2d(d_pend, h_pend, n_pending * sizeof(uint32_t), stream_);
+    for (int k = 0; k < POW_WINDOWS_PER_WAIT; ++k)
+      launch_grind_many(d_w, d_pend, n_pending, kat, base + ((uint64_t)k << wlog), wlog, pow_bits, d_best, stream_);
+    pow_d2h(h_best, d_best, n * sizeof(u64), stream_);
+    pow_wait(stream_);
+    ++waits;
+    uint32_t kept = 0;   // (the table just uploaded is read by launches that have finished: it may be rewritten)
+    for (uint32_t i = 0; i < n_pending; ++i)
+      if (h_best[h_pend[i]] == ~0ull) h_pend[kept++] = h_pend[i];
+    n_pending = kept;
+    base += (uint64_t)POW_WINDOWS_PER_WAIT << wlog;
+  }
+  for (uint32_t i = 0; i < n; ++i) nonces[i] = h_best[i];
+  return waits;
+}
+
+#ifdef LMN_BATCH
+// the grind collective (batch.h): run by the member that completes the rendezvous, with the context of any present member
+// (`arg`; the members of a batch share one config, hence pow_bits and form) over the digests of all of them
+struct GrindJob {
+  Context* ctx;
+  bool kat;
+  uint32_t pow_bits;
+};
+uint64_t Context::grind_collective(void* arg, const BatchCollectiveItem* items, int n_items, hipStream_t) {
+  const GrindJob& job = *static_cast<const GrindJob*>(arg);
+  std::vector<PowWords> all;
+  for (int i = 0; i < n_items; ++i) {
+    const PowWords* w = static_cast<const PowWords*>(items[i].in);
+    all.insert(all.end(), w, w + items[i].n);
+  }
+  std::vector<uint64_t> nonces(all.size());
+  const uint64_t waits = job.ctx->grind_rounds(all.data(), (uint32_t)all.size(), job.kat, job.pow_bits, nonces.data());
+  size_t at = 0;
+  for (int i = 0; i < n_items; at += items[i].n, ++i)
+    memcpy(items[i].out, nonces.data() + at, items[i].n * sizeof(uint64_t));
+  return waits;
+}
+#endif
+
+std::vector<uint64_t> Context::grind_many(const PowWords* w, uint32_t n, bool kat, uint32_t pow_bits) {
+  std::vector<uint64_t> nonces(n);
+  if (n == 0) return nonces;
+#ifdef LMN_BATCH
+  GrindJob job{this, kat, pow_bits};
+  batch_collective(&Context::grind_collective, &job, w, n, nonces.data(), stream_);
+#else
+  grind_rounds(w, n, kat, pow_bits, nonces.data());
+#endif
+  return nonces;
+}
+
+uint64_t Context::grind(const Channel& ch, uint32_t pow_bits) {
+  if ((int)pow_bits >= pow_device_min_bits_) return device_grind(ch, pow_bits);
   return ch.grind(pow_bits);
 }
 

@@ -236,6 +236,11 @@ class Context {
   void op_fold(int circle, uint32_t* dst, const uint32_t* src, uint32_t log_src, const uint32_t alpha[4]);
   // GrindOps::grind on the device (lmn_ctx_grind): the smallest nonce the proof-of-work check of `variant` accepts
   uint64_t op_grind(const Hash32& digest, uint32_t pow_bits, uint32_t variant);
+  // the same for n digests in one go (lmn_ctx_grind_many): nonces_out[i] for digests[32 * i ..]
+  void op_grind_many(const uint8_t* digests, uint32_t n, uint32_t pow_bits, uint32_t variant, uint64_t* nonces_out);
+  // n digests ground together on the device (k_grind_many): result[i] = Channel::grind's nonce for w[i].  In the lock-step
+  // batch build this is a collective: the members' digests are ground in one go by whoever arrives last.
+  std::vector<uint64_t> grind_many(const PowWords* w, uint32_t n, bool kat, uint32_t pow_bits);
 
   // single-proof sharding (lmn_ctx_set_shard / lmn_ctx_set_shard_rccl)
   static void check_shard_args(uint32_t rank, uint32_t world, uint32_t fri_min_log, const lmn_collective* coll);
@@ -446,6 +451,13 @@ class Context {
   unsigned long long* pow_best_ = nullptr;   // device: the smallest passing nonce found so far (allocated on first use)
   uint64_t grind(const Channel& ch, uint32_t pow_bits);          // the proof's path: device or host by pow_device_min_bits_
   uint64_t device_grind(const Channel& ch, uint32_t pow_bits);
+  // grind_many's rounds; its tables (digests | best | pending, device and page-locked host) grow on demand
+  uint64_t grind_rounds(const PowWords* w, uint32_t n, bool kat, uint32_t pow_bits, uint64_t* nonces);
+  char *pow_many_dev_ = nullptr, *pow_many_host_ = nullptr;
+  uint32_t pow_many_cap_ = 0;
+#ifdef LMN_BATCH
+  static uint64_t grind_collective(void* arg, const BatchCollectiveItem* items, int n_items, hipStream_t s);
+#endif
   bool merkle_cut_ = false;       // inside prove() of an unsharded proof: trees are stored without their register levels
   Arena arena_;
   int tw_max_log_ = 0;
