@@ -776,6 +776,25 @@ typedef struct lmn_fri_commit_result lmn_fri_commit_result;
 int lmn_col_fri_commit(lmn_ctx* ctx, const lmn_col* const* cols, uint32_t n, const uint8_t start_digest[32],
                        lmn_fri_commit_result* result);
 int lmn_col_accumulate(lmn_ctx* ctx, lmn_col* dst, const lmn_col* src);     /* AccumulationOps::accumulate: dst += src (same shape) */
+/* FieldOps<BaseField>::batch_inverse and FieldOps<SecureField>::batch_inverse on whole columns, on the device.
+ *   lmn_col_batch_inverse:        dst[j][i] = src[j][i]^-1 in M31 for every column j and row i.
+ *   lmn_col_batch_inverse_secure: src, dst = 4 coordinate columns (SecureColumnByCoords); element i is
+ *                                 (src[0][i], src[1][i], src[2][i], src[3][i]) in QM31.
+ * Shape: dst has src's ncols and log_size; the secure form needs ncols == 4; every log size from 0 to 27 is accepted;
+ *   views (lmn_col_view) are accepted on either side.
+ * Aliasing: dst may be src itself, or a handle over exactly the same device range (the in-place form), or disjoint from
+ *   src; ranges that overlap without being identical are refused.
+ * Zero: stwo's inverse() panics on zero; a device op cannot panic per element, so a zero element's result is 0, it
+ *   changes no other element's result, and zero elements are counted.  n_zero_out == NULL: the call enqueues the work on
+ *   the context's stream and returns, as the other column ops do.  n_zero_out != NULL: the call waits and writes the
+ *   number of zero elements - words for the M31 form, QM31 elements for the secure form (an element is zero exactly when
+ *   its norm down to M31 is zero: QM31 is a field).
+ * Words: inputs are canonical by the handle's contract; every output word is canonical (< 2^31 - 1).
+ * Errors: a null handle, a shape mismatch, a secure form on a handle that is not 4 columns, a partial overlap give
+ *   LMN_ERR_INVALID_ARGUMENT with a text (lmn_last_error) that names the argument; they are raised before anything is
+ *   launched, nothing is written, and the context and the handles stay usable. */
+int lmn_col_batch_inverse(lmn_ctx* ctx, const lmn_col* src, lmn_col* dst, uint64_t* n_zero_out);
+int lmn_col_batch_inverse_secure(lmn_ctx* ctx, const lmn_col* src, lmn_col* dst, uint64_t* n_zero_out);
 /* QuotientOps::accumulate_quotients (one LDE size; samples and limits as in lmn_op_accumulate_quotients: at most 4
  * distinct sample points and 512 samples, else LMN_ERR_INVALID_ARGUMENT): out = 4 coordinate columns */
 int lmn_col_accumulate_quotients(lmn_ctx* ctx, const lmn_col* const* cols, uint32_t n, const uint32_t* sample_col,

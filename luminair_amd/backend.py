@@ -227,7 +227,7 @@ EXPORTS = ["lmn_abi_version", "lmn_kind_padding_row", "lmn_strerror", "lmn_last_
            "lmn_col_commit", "lmn_tree_root", "lmn_tree_log_size", "lmn_tree_layer_to_cpu", "lmn_tree_free",
            "lmn_tree_decommit", "lmn_col_gather", "lmn_col_fri_commit",
            "lmn_col_accumulate", "lmn_col_accumulate_quotients", "lmn_col_fold_line", "lmn_col_fold_circle_into_line",
-           "lmn_col_decompose", "lmn_col_logup", "lmn_col_composition", "lmn_kind_constraints", "lmn_kind_relations", "lmn_ctx_set_shard", "lmn_rccl_unique_id", "lmn_ctx_set_shard_rccl", "lmn_ctx_clear_shard",
+           "lmn_col_decompose", "lmn_col_batch_inverse", "lmn_col_batch_inverse_secure", "lmn_col_logup", "lmn_col_composition", "lmn_kind_constraints", "lmn_kind_relations", "lmn_ctx_set_shard", "lmn_rccl_unique_id", "lmn_ctx_set_shard_rccl", "lmn_ctx_clear_shard",
            "lmn_rows_open", "lmn_rows_push", "lmn_rows_push_pinned", "lmn_rows_sync", "lmn_rows_finish", "lmn_rows_count",
            "lmn_rows_reset", "lmn_rows_close", "lmn_trace_check",
            "lmn_eval_elementwise_v", "lmn_eval_reduce", "lmn_eval_reduce_split", "lmn_eval_lut_ranges", "lmn_tensor_range"]
@@ -350,6 +350,8 @@ class Library:
         lib.lmn_col_fold_line.argtypes = [VP, VP, VP, C.POINTER(VP)]
         lib.lmn_col_fold_circle_into_line.argtypes = [VP, VP, VP, VP]
         lib.lmn_col_decompose.argtypes = [VP, VP, C.POINTER(VP), VP]
+        lib.lmn_col_batch_inverse.argtypes = [VP, VP, VP, C.POINTER(C.c_uint64)]
+        lib.lmn_col_batch_inverse_secure.argtypes = [VP, VP, VP, C.POINTER(C.c_uint64)]
         lib.lmn_col_logup.argtypes = [VP, U32, VP, VP, VP, C.POINTER(VP), VP]
         lib.lmn_col_composition.argtypes = [VP, U32, VP, VP, VP, VP, VP, VP, U32, VP]
         lib.lmn_kind_constraints.argtypes = [U32]
@@ -739,6 +741,22 @@ class Col:
         lam = (C.c_uint32 * 4)()
         self.ctx._check(self.ctx.lib.lib.lmn_col_decompose(self.ctx.handle, self.handle, C.byref(out), lam))
         return Col(self.ctx, out), tuple(int(v) for v in lam)
+
+    def _batch_inverse(self, fn, out, count_zeros):
+        dst = self if out is None else out
+        n_zero = C.c_uint64()
+        self.ctx._check(fn(self.ctx.handle, self.handle, dst.handle, C.byref(n_zero) if count_zeros else None))
+        return (dst, int(n_zero.value)) if count_zeros else dst
+
+    def batch_inverse(self, out: Optional["Col"] = None, count_zeros: bool = False):
+        """FieldOps<BaseField>::batch_inverse: out = self^-1 word by word in M31 (`out=None`: in place).  A zero word
+        gives 0.  -> the destination, or (destination, number of zero words) with `count_zeros` (which waits)."""
+        return self._batch_inverse(self.ctx.lib.lib.lmn_col_batch_inverse, out, count_zeros)
+
+    def batch_inverse_secure(self, out: Optional["Col"] = None, count_zeros: bool = False):
+        """FieldOps<SecureField>::batch_inverse on 4 coordinate columns: element i is (self[0][i], .., self[3][i]) in
+        QM31.  A zero element gives 0; `count_zeros` counts QM31 elements."""
+        return self._batch_inverse(self.ctx.lib.lib.lmn_col_batch_inverse_secure, out, count_zeros)
 
 
 class Tree:

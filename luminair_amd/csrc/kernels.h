@@ -82,6 +82,12 @@ void launch_bit_reverse(uint32_t* data, uint64_t col_stride, int ncols, int log_
 // g = f - lambda on the first half, f + lambda on the second.  scratch: decompose_num_blocks(log_n) QM31 values.
 int decompose_num_blocks(int log_n);
 void launch_decompose(const uint32_t* f, int log_n, uint32_t* g, QM31* lambda_out, QM31* scratch, lmn_stream_t s);
+// FieldOps::batch_inverse of whole columns: dst[j][i] = src[j][i]^-1 for ncols columns of 2^log_n words col_stride words
+// apart (M31), or of ONE secure column given as 4 coordinate columns 2^log_n words apart (QM31).  A zero element gives 0
+// and is added to *n_zero (a device word the caller cleared; nullptr: not counted).  dst == src is the in-place form.
+void launch_batch_inverse_m31(const uint32_t* src, uint32_t* dst, uint64_t col_stride, int ncols, int log_n,
+                              unsigned long long* n_zero, lmn_stream_t s);
+void launch_batch_inverse_qm31(const uint32_t* src, uint32_t* dst, int log_n, unsigned long long* n_zero, lmn_stream_t s);
 
 // ---- a4: Blake2s Merkle layer.  out[i] = H(prev[2i] || prev[2i+1] || cols[0][i] .. cols[ncols-1][i])
 void launch_merkle_layer(const uint32_t* prev, const uint32_t* const* cols, int ncols, uint32_t size, uint32_t* out,

@@ -867,7 +867,7 @@ void launch_trace_check_collect(const TcSet& set, uint32_t set_index, unsigned l
 }
 
 // =============================================================================================
-// level-2 column ops: bit reversal, FriOps::decompose
+// level-2 column ops: bit reversal, FriOps::decompose, FieldOps::batch_inverse
 // =============================================================================================
 LMN_KERNEL k_bit_reverse(uint32_t* __restrict__ data, uint64_t col_stride, int log_n) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -936,6 +936,127 @@ void launch_decompose(const uint32_t* f, int log_n, uint32_t* g, QM31* lambda_ou
   int e = (31 - (log_n % 31)) % 31;  // 2^-log_n mod P
   LMN_LAUNCH(k_decompose_lambda, dim3(1), dim3(TPB), 0, s, scratch, nb, 1u << e, lambda_out);
   LMN_LAUNCH(k_decompose_apply, dim3(cdiv(1ull << log_n, TPB)), dim3(TPB), 0, s, f, log_n, g, lambda_out);
+}
+
+// ---- FieldOps::batch_inverse (lmn_col_batch_inverse / _secure): Montgomery's trick inside a lane.  A workgroup owns a tile
+// of TPB * E consecutive words of one column (blockIdx.y: the flat index of ncols << log_n words is never formed); lane t
+// owns the words t, t + TPB, ... of it, so every load and store of a wave is one contiguous run of 64 dwords.  The lane
+// reads its E elements, multiplies them up (E - 1 products), inverts the total once (m_inv: 37 products) and walks back
+// (2 products per element): 3 + 37 / E products per element instead of 37.  A zero enters the chain as 1 and leaves as 0,
+// and so does a word past the column's end, which is neither stored nor counted.  Every store of a lane depends on the
+// one inverse, which depends on all of its loads: a lane has read all it owns before it writes, so dst may be src.
+// E: profiles/field_ops_rate.json (tools/field_ops_rate.py; docs/HISTORY.md has the sweep).
+constexpr int BATCH_INV_E_M31 = 16;
+constexpr int BATCH_INV_E_QM31 = 8;
+
+// the zeros the lanes of a workgroup saw, reached by all TPB lanes: per wave by xor shuffles, per workgroup through LDS,
+// then - only when there was one - one atomicAdd per workgroup (as eval_finish)
+LMN_D void zero_count_finish(uint32_t lane_zeros, unsigned long long* n_zero) {
+  LMN_SHARED uint32_t s_zeros[TPB / 64];
+  const uint32_t wave_zeros = wave_sum_u32(lane_zeros);
+  if ((threadIdx.x & 63u) == 0u) s_zeros[threadIdx.x >> 6] = wave_zeros;
+  __syncthreads();
+  if (threadIdx.x == 0u) {
+    uint32_t z = 0u;
+    for (int w = 0; w < TPB / 64; ++w) z += s_zeros[w];
+    if (z) atomicAdd(n_zero, (unsigned long long)z);
+  }
+}
+
+// x[0 .. E) non-zero -> their inverses, in place
+template <int E>
+LMN_D void m_inv_chain(uint32_t (&x)[E]) {
+  uint32_t pre[E];  // pre[e] = x[0] * ... * x[e]
+  pre[0] = x[0];
+#pragma unroll
+  for (int e = 1; e < E; ++e) pre[e] = m_mul(pre[e - 1], x[e]);
+  uint32_t inv = m_inv(pre[E - 1]);  // (x[0] * ... * x[e])^-1 while the walk is at e
+#pragma unroll
+  for (int e = E - 1; e > 0; --e) {
+    const uint32_t r = m_mul(inv, pre[e - 1]);
+    inv = m_mul(inv, x[e]);
+    x[e] = r;
+  }
+  x[0] = inv;
+}
+
+template <int E>
+LMN_KERNEL k_batch_inverse_m(const uint32_t* src, uint32_t* dst, uint64_t col_stride, uint32_t n, unsigned long long* n_zero) {
+  const uint32_t* s = src + (uint64_t)blockIdx.y * col_stride;
+  uint32_t* d = dst + (uint64_t)blockIdx.y * col_stride;
+  const uint32_t i0 = blockIdx.x * (uint32_t)(TPB * E) + threadIdx.x;  // n <= 2^27: no wrap
+  uint32_t x[E];
+  uint32_t zero_mask = 0u, zeros = 0u;
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    const uint32_t i = i0 + (uint32_t)e * TPB;
+    const bool in = i < n;
+    const uint32_t v = in ? ld_ub(s, i) : 0u;
+    const bool zero = v == 0u;
+    zeros += in && zero ? 1u : 0u;
+    zero_mask |= (zero ? 1u : 0u) << e;
+    x[e] = zero ? 1u : v;
+  }
+  m_inv_chain<E>(x);
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    const uint32_t i = i0 + (uint32_t)e * TPB;
+    if (i < n) st_ub(d, i, (zero_mask >> e) & 1u ? 0u : x[e]);
+  }
+  if (n_zero) zero_count_finish(zeros, n_zero);
+}
+
+// QM31 through the norms (q_inv's own route, its one m_inv shared by the lane's E elements): per element
+// den = A^2 - (2 + i) B^2 in CM31 and nrm = |den|^2 in M31; the norms go through the chain; then den^-1 = conj(den) / nrm
+// and the result is (A den^-1, -B den^-1).  QM31 is a field, so nrm == 0 exactly for the zero element.  All words are
+// canonical, so the bytes are q_inv's whatever E is.
+template <int E>
+LMN_KERNEL k_batch_inverse_q(const uint32_t* src, uint32_t* dst, uint32_t n, unsigned long long* n_zero) {
+  const uint32_t i0 = blockIdx.x * (uint32_t)(TPB * E) + threadIdx.x;
+  CM31 A[E], B[E], den[E];
+  uint32_t nrm[E];
+  uint32_t zero_mask = 0u, zeros = 0u;
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    const uint32_t i = i0 + (uint32_t)e * TPB;
+    const bool in = i < n;
+    const QM31 v = in ? load_secure_ub(src, n, i) : q_zero();
+    A[e] = {v.a, v.b};
+    B[e] = {v.c, v.d};
+    den[e] = c_sub(c_mul(A[e], A[e]), c_mul_r(c_mul(B[e], B[e])));
+    const uint32_t nn = c_norm(den[e]);
+    const bool zero = nn == 0u;
+    zeros += in && zero ? 1u : 0u;
+    zero_mask |= (zero ? 1u : 0u) << e;
+    nrm[e] = zero ? 1u : nn;
+  }
+  m_inv_chain<E>(nrm);
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    const uint32_t i = i0 + (uint32_t)e * TPB;
+    if (i >= n) continue;
+    const CM31 di{m_mul(den[e].a, nrm[e]), m_mul(m_neg(den[e].b), nrm[e])};
+    const CM31 lo = c_mul(A[e], di), hi = c_mul(B[e], di);
+    const bool zero = (zero_mask >> e) & 1u;
+    st_ub(dst, i, zero ? 0u : lo.a);
+    st_ub(dst + n, i, zero ? 0u : lo.b);
+    st_ub(dst + 2ull * n, i, zero ? 0u : m_neg(hi.a));
+    st_ub(dst + 3ull * n, i, zero ? 0u : m_neg(hi.b));
+  }
+  if (n_zero) zero_count_finish(zeros, n_zero);
+}
+
+void launch_batch_inverse_m31(const uint32_t* src, uint32_t* dst, uint64_t col_stride, int ncols, int log_n,
+                              unsigned long long* n_zero, lmn_stream_t s) {
+  if (log_n < 0 || log_n > 27 || ncols < 1 || ncols > 65535) throw LmnError(-100, "batch_inverse: bad shape");
+  constexpr int E = BATCH_INV_E_M31;
+  LMN_LAUNCH(k_batch_inverse_m<E>, dim3(cdiv(1ull << log_n, TPB * E), ncols), dim3(TPB), 0, s, src, dst, col_stride,
+             1u << log_n, n_zero);
+}
+void launch_batch_inverse_qm31(const uint32_t* src, uint32_t* dst, int log_n, unsigned long long* n_zero, lmn_stream_t s) {
+  if (log_n < 0 || log_n > 27) throw LmnError(-100, "batch_inverse_secure: bad shape");
+  constexpr int E = BATCH_INV_E_QM31;
+  LMN_LAUNCH(k_batch_inverse_q<E>, dim3(cdiv(1ull << log_n, TPB * E)), dim3(TPB), 0, s, src, dst, 1u << log_n, n_zero);
 }
 
 }  // namespace lmn

@@ -642,6 +642,40 @@ lmn_col* Context::col_decompose(const lmn_col* f, uint32_t lambda_out[4]) {
   return gg.release();
 }
 
+// FieldOps::batch_inverse on handles.  Everything is refused before anything is launched; dst over exactly src's range is
+// the in-place form (a lane of k_batch_inverse_* reads all it owns before it writes), any other overlap is refused.
+void Context::col_batch_inverse(const lmn_col* src, lmn_col* dst, bool secure, uint64_t* n_zero_out) {
+  const std::string F = secure ? "batch_inverse_secure: " : "batch_inverse: ";
+  auto refuse = [&](const std::string& what) { throw LmnError(LMN_ERR_INVALID_ARGUMENT, F + what); };
+  if (!src) refuse("src is null");
+  if (!dst) refuse("dst is null");
+  if (secure && src->ncols != 4) refuse("src has " + u32s(src->ncols) + " columns, a secure column has 4 coordinate columns");
+  if (secure && dst->ncols != 4) refuse("dst has " + u32s(dst->ncols) + " columns, a secure column has 4 coordinate columns");
+  if (dst->ncols != src->ncols || dst->log_size != src->log_size)
+    refuse("dst is " + u32s(dst->ncols) + " x 2^" + u32s(dst->log_size) + ", src is " + u32s(src->ncols) + " x 2^" +
+           u32s(src->log_size) + ": shapes differ");
+  if (src->log_size > COL_MAX_LOG) refuse("src has log size " + u32s(src->log_size) + ", the largest is " + u32s(COL_MAX_LOG));
+  const uint32_t *s0 = src->d, *s1 = s0 + src->words(), *d0 = dst->d, *d1 = d0 + dst->words();
+  if (d0 != s0 && d0 < s1 && s0 < d1) refuse("dst overlaps src without being the same range");
+  unsigned long long* d_zero = nullptr;
+  if (n_zero_out) {
+    arena_.reserve(8u << 20);
+    begin_op();
+    d_zero = (unsigned long long*)arena_.alloc_bytes(sizeof(unsigned long long));
+    lmn_memset(d_zero, 0, sizeof(unsigned long long), stream_);
+  } else {
+    set_device();
+  }
+  if (secure)
+    launch_batch_inverse_qm31(src->d, dst->d, (int)src->log_size, d_zero, stream_);
+  else
+    launch_batch_inverse_m31(src->d, dst->d, 1ull << src->log_size, (int)src->ncols, (int)src->log_size, d_zero, stream_);
+  if (!n_zero_out) return;
+  const unsigned long long* z = (const unsigned long long*)stage_download(d_zero, sizeof(unsigned long long));
+  lmn_sync(stream_);
+  *n_zero_out = *z;
+}
+
 // ---- the per-component stages on handles (the same launches Context::prove makes)
 static const ComponentSpec* spec_or_throw(uint32_t kind, const char* what) {
   const ComponentSpec* sp = component_spec((int)kind);
@@ -940,5 +974,13 @@ int lmn_col_decompose(lmn_ctx* ctx, const lmn_col* f, lmn_col** g_out, uint32_t 
   if (!ctx || !f || !g_out || !lambda_out) return LMN_ERR_INVALID_ARGUMENT;
   *g_out = nullptr;
   return guard2(ctx, [&] { *g_out = ctx->impl->col_decompose(f, lambda_out); });
+}
+int lmn_col_batch_inverse(lmn_ctx* ctx, const lmn_col* src, lmn_col* dst, uint64_t* n_zero_out) {
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  return guard2(ctx, [&] { ctx->impl->col_batch_inverse(src, dst, false, n_zero_out); });
+}
+int lmn_col_batch_inverse_secure(lmn_ctx* ctx, const lmn_col* src, lmn_col* dst, uint64_t* n_zero_out) {
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  return guard2(ctx, [&] { ctx->impl->col_batch_inverse(src, dst, true, n_zero_out); });
 }
 }  // extern "C"

@@ -276,6 +276,9 @@ class Context {
   lmn_col* col_fold_line(const lmn_col* src, const uint32_t alpha[4]);
   void col_fold_circle_into_line(lmn_col* dst, const lmn_col* src, const uint32_t alpha[4]);
   lmn_col* col_decompose(const lmn_col* f, uint32_t lambda_out[4]);
+  // FieldOps::batch_inverse (M31, or QM31 on 4 coordinate columns): dst = src^-1 element by element, 0 for a zero element;
+  // n_zero_out != nullptr waits and reports how many elements were zero
+  void col_batch_inverse(const lmn_col* src, lmn_col* dst, bool secure, uint64_t* n_zero_out);
   lmn_col* col_logup(uint32_t kind, const lmn_col* main, const lmn_col* pre, const uint32_t* elems, uint32_t claimed_out[4]);
   void col_composition(uint32_t kind, const lmn_col* main_lde, const lmn_col* inter_lde, const lmn_col* pre_lde,
                        const uint32_t* elems, const uint32_t claimed[4], const uint32_t* coeffs, uint32_t n_coeffs,
