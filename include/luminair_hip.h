@@ -427,6 +427,59 @@ int lmn_trace_max_reduce(lmn_ctx* ctx, const int32_t* input_dev, uint64_t front,
 int lmn_trace_sum_reduce(lmn_ctx* ctx, const int32_t* input_dev, uint64_t front, uint64_t dim, uint64_t back,
                          const lmn_node_info* info, uint32_t* rows_dev, uint64_t row_offset, int32_t* out_dev);
 
+/* ---- The many-member producers: one call - one launch - fills the rows of ONE graph node for n_members pies of one shape, the
+ * producers in front of a lock-step batch, which proves the same graph on many input sets (luminair_hip_batch.h; with the
+ * single forms above that costs one call per node per pie).  Every call takes the arguments of its single form, plus n_members, one
+ * member stride per device pointer and a trailing refused_dev; member m works on `base + m * member_stride`.  `info`, the
+ * views, the sizes and `row_offset` are common to all members (a lock-step batch needs identical shapes anyway).
+ *  - Strides: operands and output tensors in elements, rows_dev in ROWS of the kind (so a member's table holds
+ *    rows_member_stride rows), multiplicity tables in words.
+ *  - Shared operands: an operand stride of 0 means that all members read the same operand (weights, constants).  Rows are
+ *    still written per member: the Inputs rows of a shared weight tensor appear in every pie.
+ *  - Shared output tensors: out_member_stride == 0 is accepted only when every operand stride the kind reads is 0; out_dev is
+ *    then ONE tensor, stored by member 0 alone (no racing stores).  Any other out stride of 0 is LMN_ERR_INVALID_ARGUMENT.
+ *    out_dev may be NULL as in the single forms (its stride is then ignored).
+ *  - Refused before any launch, with the argument named by lmn_last_error: n_members > LMN_TRACE_MANY_MAX; a
+ *    rows_member_stride smaller than row_offset + the node's row count; an out stride smaller than the output's element
+ *    count (unless it is 0 as above); a multiplicity stride smaller than the table (256 words for the range check, the LUT
+ *    rows the ranges enumerate for a LUT), 0 included; null pointers where the single form refuses them; and the single
+ *    forms' own shape errors with their codes (a view whose shape product is not n, n = 0: LMN_ERR_EMPTY_TRACE, ...).
+ *  - n_members == 0 is LMN_OK and touches nothing (as lmn_ctx_grind_many).
+ *  - The producers' contract (lmn_trace_elementwise above) holds per element, unchanged: a refused element gets the word P in
+ *    its row's output-value column, zeros in the other derived words, 0 in the output tensor, and adds nothing to any
+ *    multiplicity table.  Here a Sin / Exp2 / Log2 input outside every range is such a refused element too - marked and
+ *    counted, the call neither fails nor waits (as lmn_eval_lut_ranges; the single lmn_trace_lut* forms wait once per call to
+ *    report it, and keep doing so).
+ *  - refused_dev (n_members uint32_t counters on the device, may be NULL): counter m grows by member m's refused elements.
+ *    Never reset by a call: one set of counters is accumulated over a whole graph and downloaded once.
+ *  - No call waits for the device; all are ordered on the context's stream with every other call of that context. */
+#define LMN_TRACE_MANY_MAX 1024 /* the largest n_members */
+/* the kinds of lmn_trace_elementwise_v; LMN_KIND_LESS_THAN too, with range_check_mult_dev (256 zero-initialised words per
+ * member, ignored for the other kinds) as in lmn_trace_less_than */
+int lmn_trace_many_elementwise_v(lmn_ctx* ctx, uint32_t kind, const int32_t* lhs_dev, const lmn_view* lhs_view,
+                                 uint64_t lhs_member_stride, const int32_t* rhs_dev, const lmn_view* rhs_view,
+                                 uint64_t rhs_member_stride, uint64_t n, const lmn_node_info* info, uint32_t n_members,
+                                 uint32_t* rows_dev, uint64_t row_offset, uint64_t rows_member_stride, int32_t* out_dev,
+                                 uint64_t out_member_stride, uint32_t* range_check_mult_dev,
+                                 uint64_t range_check_mult_member_stride, uint32_t* refused_dev);
+/* the reference's buffer rule, as lmn_trace_contiguous: max(in_size, out_size) rows per member */
+int lmn_trace_many_contiguous(lmn_ctx* ctx, const int32_t* input_dev, uint64_t input_member_stride, uint64_t in_size,
+                              const lmn_view* view, uint64_t out_size, const lmn_node_info* info, uint32_t n_members,
+                              uint32_t* rows_dev, uint64_t row_offset, uint64_t rows_member_stride, int32_t* out_dev,
+                              uint64_t out_member_stride, uint32_t* refused_dev);
+/* lmn_trace_sum_reduce (is_max = 0) / lmn_trace_max_reduce: front * dim * back rows and front * back outputs per member */
+int lmn_trace_many_reduce(lmn_ctx* ctx, uint32_t is_max, const int32_t* input_dev, uint64_t input_member_stride, uint64_t front,
+                          uint64_t dim, uint64_t back, const lmn_node_info* info, uint32_t n_members, uint32_t* rows_dev,
+                          uint64_t row_offset, uint64_t rows_member_stride, int32_t* out_dev, uint64_t out_member_stride,
+                          uint32_t* refused_dev);
+/* lmn_trace_lut_ranges (the single range of lmn_trace_lut is one range): lut_col1_dev is shared by all members, mult_dev is
+ * per member (mult_member_stride words apart, zero-initialised by the caller) */
+int lmn_trace_many_lut_ranges(lmn_ctx* ctx, uint32_t kind, const int32_t* input_dev, const lmn_view* view,
+                              uint64_t input_member_stride, uint64_t n, const lmn_node_info* info, const uint32_t* lut_col1_dev,
+                              const lmn_range* ranges, uint32_t n_ranges, uint32_t n_members, uint32_t* mult_dev,
+                              uint64_t mult_member_stride, uint32_t* rows_dev, uint64_t row_offset, uint64_t rows_member_stride,
+                              int32_t* out_dev, uint64_t out_member_stride, uint32_t* refused_dev);
+
 /* ---- The eval forms of the producers: `Operator::process`, the forward pass that `gen_circuit_settings` runs in front
  * of gen_trace (crates/graph/src/graph.rs:61-159) because a Sin / Exp2 / Log2 node's LUT range is the min..max of its
  * source buffer (crates/graph/src/utils.rs:44-82).  Each call computes the node's output tensor exactly as the

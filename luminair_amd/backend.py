@@ -230,7 +230,9 @@ EXPORTS = ["lmn_abi_version", "lmn_kind_padding_row", "lmn_strerror", "lmn_last_
            "lmn_col_decompose", "lmn_col_batch_inverse", "lmn_col_batch_inverse_secure", "lmn_col_logup", "lmn_col_composition", "lmn_kind_constraints", "lmn_kind_relations", "lmn_ctx_set_shard", "lmn_rccl_unique_id", "lmn_ctx_set_shard_rccl", "lmn_ctx_clear_shard",
            "lmn_rows_open", "lmn_rows_push", "lmn_rows_push_pinned", "lmn_rows_sync", "lmn_rows_finish", "lmn_rows_count",
            "lmn_rows_reset", "lmn_rows_close", "lmn_trace_check",
-           "lmn_eval_elementwise_v", "lmn_eval_reduce", "lmn_eval_reduce_split", "lmn_eval_lut_ranges", "lmn_tensor_range"]
+           "lmn_eval_elementwise_v", "lmn_eval_reduce", "lmn_eval_reduce_split", "lmn_eval_lut_ranges", "lmn_tensor_range",
+           "lmn_trace_many_elementwise_v", "lmn_trace_many_contiguous", "lmn_trace_many_reduce", "lmn_trace_many_lut_ranges"]
+TRACE_MANY_MAX = 1024   # LMN_TRACE_MANY_MAX
 
 
 class LuminairBackendError(RuntimeError):
@@ -403,6 +405,15 @@ class Library:
         lib.lmn_eval_lut_ranges.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(LmnView), C.c_uint64, C.c_void_p,
                                             C.POINTER(LmnRange), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.lmn_tensor_range.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        U64 = C.c_uint64
+        lib.lmn_trace_many_elementwise_v.argtypes = [VP, U32, VP, C.POINTER(LmnView), U64, VP, C.POINTER(LmnView), U64, U64,
+                                                     C.POINTER(LmnNodeInfo), U32, VP, U64, U64, VP, U64, VP, U64, VP]
+        lib.lmn_trace_many_contiguous.argtypes = [VP, VP, U64, U64, C.POINTER(LmnView), U64, C.POINTER(LmnNodeInfo), U32, VP,
+                                                  U64, U64, VP, U64, VP]
+        lib.lmn_trace_many_reduce.argtypes = [VP, U32, VP, U64, U64, U64, U64, C.POINTER(LmnNodeInfo), U32, VP, U64, U64, VP,
+                                              U64, VP]
+        lib.lmn_trace_many_lut_ranges.argtypes = [VP, U32, VP, C.POINTER(LmnView), U64, U64, C.POINTER(LmnNodeInfo), VP,
+                                                  C.POINTER(LmnRange), U32, U32, VP, U64, VP, U64, U64, VP, U64, VP]
 
     def eval_reduce_split(self, dim: int, back: int) -> int:
         """How `lmn_eval_reduce` maps (dim, back) onto lanes: 0 = one lane per output element, 1 = one wave per group."""
@@ -1135,6 +1146,75 @@ class Context:
             self.handle, lhs.ptr, C.byref(lhs_view) if lhs_view is not None else None, rhs.ptr,
             C.byref(rhs_view) if rhs_view is not None else None, n, C.byref(info), range_check_mult.ptr, rows.ptr,
             row_offset, out.ptr))
+        return rows, out
+
+    # ---- lmn_trace_many_*: one call (one launch) fills a node's rows for `n_members` pies of one shape.  Member m works on
+    # base + m * stride: operand and `out` strides in elements (0 = shared), `rows_stride` in rows of the kind, multiplicity
+    # strides in words.  `refused`: n_members uint32 counters on the device, grown by each member's refused elements.
+    # rows / out must be given (the caller lays out the members' regions); nothing waits.
+    def trace_many_elementwise(self, kind: int, lhs: DeviceBuffer, rhs: Optional[DeviceBuffer], n: int, n_members: int,
+                               node_id: int, input_ids, num_consumers: int, rows: DeviceBuffer, rows_stride: int,
+                               out: Optional[DeviceBuffer], out_stride: int, lhs_stride: int = 0, rhs_stride: int = 0,
+                               is_final_output: bool = False, input_mults=(-1, -1), row_offset: int = 0,
+                               lhs_view: Optional[LmnView] = None, rhs_view: Optional[LmnView] = None,
+                               range_check_mult: Optional[DeviceBuffer] = None, range_check_mult_stride: int = 0,
+                               refused: Optional[DeviceBuffer] = None):
+        """`lmn_trace_many_elementwise_v`: every kind of `trace_elementwise`, and LessThan with `range_check_mult`."""
+        ids = list(input_ids) + [0] * (2 - len(input_ids))
+        mults = list(input_mults) + [0] * (2 - len(input_mults))
+        info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(*ids), num_consumers, 1 if is_final_output else 0,
+                           (C.c_int32 * 2)(*mults))
+        ptr = lambda b: b.ptr if b is not None else None
+        self._check(self.lib.lib.lmn_trace_many_elementwise_v(
+            self.handle, kind, ptr(lhs), C.byref(lhs_view) if lhs_view is not None else None, lhs_stride, ptr(rhs),
+            C.byref(rhs_view) if rhs_view is not None else None, rhs_stride, n, C.byref(info), n_members, ptr(rows),
+            row_offset, rows_stride, ptr(out), out_stride, ptr(range_check_mult), range_check_mult_stride, ptr(refused)))
+        return rows, out
+
+    def trace_many_contiguous(self, inp: DeviceBuffer, in_size: int, out_size: int, n_members: int, node_id: int,
+                              input_id: int, num_consumers: int, rows: DeviceBuffer, rows_stride: int,
+                              out: Optional[DeviceBuffer], out_stride: int, inp_stride: int = 0,
+                              is_final_output: bool = False, input_mult: int = -1, view: Optional[LmnView] = None,
+                              row_offset: int = 0, refused: Optional[DeviceBuffer] = None):
+        """`lmn_trace_many_contiguous`: the reference's buffer rule, max(in_size, out_size) rows per member."""
+        info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(input_id, 0), num_consumers, 1 if is_final_output else 0,
+                           (C.c_int32 * 2)(input_mult, 0))
+        ptr = lambda b: b.ptr if b is not None else None
+        self._check(self.lib.lib.lmn_trace_many_contiguous(
+            self.handle, ptr(inp), inp_stride, in_size, C.byref(view) if view is not None else None, out_size, C.byref(info),
+            n_members, ptr(rows), row_offset, rows_stride, ptr(out), out_stride, ptr(refused)))
+        return rows, out
+
+    def trace_many_reduce(self, inp: DeviceBuffer, front: int, dim: int, back: int, n_members: int, node_id: int,
+                          input_id: int, num_consumers: int, rows: DeviceBuffer, rows_stride: int,
+                          out: Optional[DeviceBuffer], out_stride: int, inp_stride: int = 0, maximum: bool = False,
+                          is_final_output: bool = False, input_mult: int = -1, row_offset: int = 0,
+                          refused: Optional[DeviceBuffer] = None):
+        """`lmn_trace_many_reduce`: SumReduce, or MaxReduce with maximum=True, of a (front, dim, back) tensor per member."""
+        info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(input_id, 0), num_consumers, 1 if is_final_output else 0,
+                           (C.c_int32 * 2)(input_mult, 0))
+        ptr = lambda b: b.ptr if b is not None else None
+        self._check(self.lib.lib.lmn_trace_many_reduce(
+            self.handle, 1 if maximum else 0, ptr(inp), inp_stride, front, dim, back, C.byref(info), n_members, ptr(rows),
+            row_offset, rows_stride, ptr(out), out_stride, ptr(refused)))
+        return rows, out
+
+    def trace_many_lut(self, kind: int, inp: DeviceBuffer, n: int, n_members: int, node_id: int, input_id: int,
+                       num_consumers: int, lut_col1: DeviceBuffer, ranges: Sequence[Tuple[int, int]], mult: DeviceBuffer,
+                       mult_stride: int, rows: DeviceBuffer, rows_stride: int, out: Optional[DeviceBuffer], out_stride: int,
+                       inp_stride: int = 0, is_final_output: bool = False, input_mult: int = -1,
+                       view: Optional[LmnView] = None, row_offset: int = 0, refused: Optional[DeviceBuffer] = None):
+        """`lmn_trace_many_lut_ranges`: Sin / Exp2 / Log2 over `ranges` (one (lo, hi) pair for a single-range LUT);
+        `lut_col1` is shared, `mult` holds one multiplicity table per member.  An input outside every range is a refused
+        element (marked, counted), not an error."""
+        info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(input_id, 0), num_consumers, 1 if is_final_output else 0,
+                           (C.c_int32 * 2)(input_mult, 0))
+        ptr = lambda b: b.ptr if b is not None else None
+        arr = (LmnRange * max(len(ranges), 1))(*[LmnRange(int(a), int(b)) for a, b in ranges])
+        self._check(self.lib.lib.lmn_trace_many_lut_ranges(
+            self.handle, kind, ptr(inp), C.byref(view) if view is not None else None, inp_stride, n, C.byref(info),
+            ptr(lut_col1), arr, len(ranges), n_members, ptr(mult), mult_stride, ptr(rows), row_offset, rows_stride, ptr(out),
+            out_stride, ptr(refused)))
         return rows, out
 
     # ---- lmn_eval_*: the producers' forward pass (values, their range, the refused elements; no rows, no waiting).

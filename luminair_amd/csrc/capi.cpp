@@ -499,6 +499,75 @@ int lmn_trace_max_reduce(lmn_ctx* ctx, const int32_t* input_dev, uint64_t front,
   return guard(ctx, [&] { ctx->impl->trace_reduce(true, input_dev, front, dim, back, *info, rows_dev, row_offset, out_dev); });
 }
 
+// ---- the many-member producers: n_members == 0 is LMN_OK and touches nothing (as lmn_ctx_grind_many); null pointers are
+// refused where the single forms refuse them, with the argument's name in lmn_last_error
+int lmn_trace_many_elementwise_v(lmn_ctx* ctx, uint32_t kind, const int32_t* lhs_dev, const lmn_view* lhs_view,
+                                 uint64_t lhs_member_stride, const int32_t* rhs_dev, const lmn_view* rhs_view,
+                                 uint64_t rhs_member_stride, uint64_t n, const lmn_node_info* info, uint32_t n_members,
+                                 uint32_t* rows_dev, uint64_t row_offset, uint64_t rows_member_stride, int32_t* out_dev,
+                                 uint64_t out_member_stride, uint32_t* range_check_mult_dev,
+                                 uint64_t range_check_mult_member_stride, uint32_t* refused_dev) {
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  if (n_members == 0) return LMN_OK;
+  if (!lhs_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_elementwise_v: null lhs_dev");
+  if (!info) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_elementwise_v: null info");
+  if (!rows_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_elementwise_v: null rows_dev");
+  return guard(ctx, [&] {
+    ctx->impl->trace_many_elementwise(kind, lhs_dev, lhs_view, lhs_member_stride, rhs_dev, rhs_view, rhs_member_stride, n, *info,
+                                      n_members, rows_dev, row_offset, rows_member_stride, out_dev, out_member_stride,
+                                      range_check_mult_dev, range_check_mult_member_stride, refused_dev);
+  });
+}
+
+int lmn_trace_many_contiguous(lmn_ctx* ctx, const int32_t* input_dev, uint64_t input_member_stride, uint64_t in_size,
+                              const lmn_view* view, uint64_t out_size, const lmn_node_info* info, uint32_t n_members,
+                              uint32_t* rows_dev, uint64_t row_offset, uint64_t rows_member_stride, int32_t* out_dev,
+                              uint64_t out_member_stride, uint32_t* refused_dev) {
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  if (n_members == 0) return LMN_OK;
+  if (!input_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_contiguous: null input_dev");
+  if (!info) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_contiguous: null info");
+  if (!rows_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_contiguous: null rows_dev");
+  return guard(ctx, [&] {
+    ctx->impl->trace_many_contiguous(input_dev, input_member_stride, in_size, view, out_size, *info, n_members, rows_dev,
+                                     row_offset, rows_member_stride, out_dev, out_member_stride, refused_dev);
+  });
+}
+
+int lmn_trace_many_reduce(lmn_ctx* ctx, uint32_t is_max, const int32_t* input_dev, uint64_t input_member_stride, uint64_t front,
+                          uint64_t dim, uint64_t back, const lmn_node_info* info, uint32_t n_members, uint32_t* rows_dev,
+                          uint64_t row_offset, uint64_t rows_member_stride, int32_t* out_dev, uint64_t out_member_stride,
+                          uint32_t* refused_dev) {
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  if (n_members == 0) return LMN_OK;
+  if (!input_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_reduce: null input_dev");
+  if (!info) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_reduce: null info");
+  if (!rows_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_reduce: null rows_dev");
+  return guard(ctx, [&] {
+    ctx->impl->trace_many_reduce(is_max != 0, input_dev, input_member_stride, front, dim, back, *info, n_members, rows_dev,
+                                 row_offset, rows_member_stride, out_dev, out_member_stride, refused_dev);
+  });
+}
+
+int lmn_trace_many_lut_ranges(lmn_ctx* ctx, uint32_t kind, const int32_t* input_dev, const lmn_view* view,
+                              uint64_t input_member_stride, uint64_t n, const lmn_node_info* info, const uint32_t* lut_col1_dev,
+                              const lmn_range* ranges, uint32_t n_ranges, uint32_t n_members, uint32_t* mult_dev,
+                              uint64_t mult_member_stride, uint32_t* rows_dev, uint64_t row_offset, uint64_t rows_member_stride,
+                              int32_t* out_dev, uint64_t out_member_stride, uint32_t* refused_dev) {
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  if (n_members == 0) return LMN_OK;
+  if (!input_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_lut_ranges: null input_dev");
+  if (!info) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_lut_ranges: null info");
+  if (!lut_col1_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_lut_ranges: null lut_col1_dev");
+  if (!mult_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_lut_ranges: null mult_dev");
+  if (!rows_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_lut_ranges: null rows_dev");
+  return guard(ctx, [&] {
+    ctx->impl->trace_many_lut(kind, input_dev, view, input_member_stride, n, *info, lut_col1_dev, ranges, n_ranges, n_members,
+                              mult_dev, mult_member_stride, rows_dev, row_offset, rows_member_stride, out_dev,
+                              out_member_stride, refused_dev);
+  });
+}
+
 int lmn_eval_elementwise_v(lmn_ctx* ctx, uint32_t kind, const int32_t* lhs_dev, const lmn_view* lhs_view, const int32_t* rhs_dev,
                            const lmn_view* rhs_view, uint64_t n, int32_t* out_dev, int32_t* minmax_dev, uint32_t* refused_dev) {
   if (!ctx) return LMN_ERR_INVALID_ARGUMENT;

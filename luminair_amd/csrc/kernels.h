@@ -338,6 +338,22 @@ void launch_trace_lut(const int32_t* input, const TraceView& view, uint64_t n, c
 void launch_trace_reduce(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back,
                          const TraceNode& nd, uint32_t* rows, int32_t* out, lmn_stream_t s);
 
+// ---- the many-member forms (lmn_trace_many_*): one launch fills a node's rows for n_members pies, grid.y = the member.
+// Member m works on base + m * stride (`*_ms`: operands and outputs in elements, rows / aux / mult in WORDS here - the host
+// side converts row strides); an operand stride of 0 shares the operand, out_ms == 0 stores the shared output from member 0
+// only.  refused (n_members counters, may be null) grows by each member's refused elements; a LUT input outside every range
+// is one of them.
+void launch_trace_many_elementwise(int kind, const int32_t* lhs, const TraceView& lv, uint64_t lhs_ms, const int32_t* rhs,
+                                   const TraceView& rv, uint64_t rhs_ms, uint64_t n, const TraceNode& nd, uint32_t n_members,
+                                   uint32_t* rows, uint64_t rows_ms, int32_t* out, uint64_t out_ms, uint32_t* aux, uint64_t aux_ms,
+                                   uint32_t* refused, lmn_stream_t s);
+void launch_trace_many_reduce(bool is_max, const int32_t* input, uint64_t in_ms, uint64_t front, uint64_t dim, uint64_t back,
+                              const TraceNode& nd, uint32_t n_members, uint32_t* rows, uint64_t rows_ms, int32_t* out,
+                              uint64_t out_ms, uint32_t* refused, lmn_stream_t s);
+void launch_trace_many_lut(const int32_t* input, const TraceView& view, uint64_t in_ms, uint64_t n, const TraceNode& nd,
+                           const uint32_t* lut_col1, const LutRanges& ranges, uint32_t n_members, uint32_t* mult, uint64_t mult_ms,
+                           uint32_t* rows, uint64_t rows_ms, int32_t* out, uint64_t out_ms, uint32_t* refused, lmn_stream_t s);
+
 // ---- the eval forms of the producers (lmn_eval_*): values only, plus the range of what was written in minmax[0 .. 1]
 // (atomicMin / atomicMax: initialise with launch_eval_init) and the refused elements added to *refused; both may be null
 void launch_eval_init(int32_t* minmax, lmn_stream_t s);

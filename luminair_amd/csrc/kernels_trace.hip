@@ -166,6 +166,8 @@ LMN_HD constexpr int trace_ncols(int kind) {
   return kind == 0 ? 15 : kind == 1 ? 16 : kind == 2 ? 13 : kind == 7 ? 13 : kind == 8 ? 16 : kind == 13 ? 22
                                                                                        : kind == 16 ? 11 : 7;
 }
+// the output-value column of a kind's row: where a refused element carries the word P
+LMN_HD constexpr int trace_mark_col(int kind) { return kind == 0 || kind == 1 || kind == 8 || kind == 13 ? 11 : kind == 15 ? 5 : 8; }
 // floor(sqrt(v)) for 0 <= v < 2^44, exact (double sqrt + one correction step each way)
 LMN_D int64_t isqrt_u64(int64_t v) {
   int64_t r = (int64_t)sqrt((double)v);
@@ -219,15 +221,27 @@ LMN_D ElemValue elem_value(int64_t a, int64_t b) {
   }
 }
 
-template <int KIND>
-LMN_KERNEL k_trace_elementwise(const int32_t* __restrict__ lhs, TraceView lv, const int32_t* __restrict__ rhs,
-                               TraceView rv, uint64_t n, TraceNode nd, uint32_t* __restrict__ rows,
-                               int32_t* __restrict__ out, uint32_t* __restrict__ aux) {
+LMN_D uint32_t wave_count(bool pred) { return (uint32_t)__builtin_popcountll(lmn_ballot(pred)); }
+// the refused elements of a many-member launch: one atomicAdd per wave that holds any, to the member's counter.  Reached by
+// all TPB lanes.
+LMN_D void trace_count_refused(bool bad, uint32_t* __restrict__ refused) {
+  const uint32_t c = wave_count(bad);
+  if (refused && c && (threadIdx.x & 63u) == 0u) atomicAdd(refused, c);
+}
+
+// The row rule of the elementwise kinds, stated once for k_trace_elementwise (one tensor per launch) and
+// k_trace_many_elementwise (blockIdx.y = the member): the pointers are the launch's own or the member's bases, blockIdx.x is
+// the tile of TPB rows in both.  MANY: the refused elements are counted in *refused (may be null).
+template <int KIND, bool MANY>
+LMN_D void trace_elementwise_rows(const int32_t* __restrict__ lhs, const TraceView& lv, const int32_t* __restrict__ rhs,
+                                  const TraceView& rv, uint64_t n, const TraceNode& nd, uint32_t* __restrict__ rows,
+                                  int32_t* __restrict__ out, uint32_t* __restrict__ aux, uint32_t* __restrict__ refused) {
   constexpr int NC = trace_ncols(KIND);
   constexpr int ST = NC | 1;  // odd LDS row stride: conflict-free column writes
   LMN_SHARED uint32_t tile[TPB * ST];
   const uint64_t row0 = (uint64_t)blockIdx.x * TPB;
   const uint64_t r = row0 + threadIdx.x;
+  bool bad = false;   // this lane's element is refused (its row carries the mark)
   if (r < n) {
     uint32_t* t = tile + threadIdx.x * ST;
     const bool ref_contig = KIND == 16 && nd.phys_n != 0;
@@ -314,12 +328,38 @@ LMN_KERNEL k_trace_elementwise(const int32_t* __restrict__ lhs, TraceView lv, co
       }
       if (out) out[r] = (int32_t)e.out;
     }
+    if constexpr (MANY) bad = t[trace_mark_col(KIND)] == P31;
   }
+  if constexpr (MANY) trace_count_refused(bad, refused);
   __syncthreads();
   const uint64_t rows_here = n - row0 < (uint64_t)TPB ? n - row0 : (uint64_t)TPB;
   const uint32_t words = (uint32_t)rows_here * NC;
   uint32_t* dst = rows + row0 * NC;
   for (uint32_t w = threadIdx.x; w < words; w += TPB) dst[w] = tile[(w / NC) * ST + (w % NC)];
+}
+
+template <int KIND>
+LMN_KERNEL k_trace_elementwise(const int32_t* __restrict__ lhs, TraceView lv, const int32_t* __restrict__ rhs,
+                               TraceView rv, uint64_t n, TraceNode nd, uint32_t* __restrict__ rows,
+                               int32_t* __restrict__ out, uint32_t* __restrict__ aux) {
+  trace_elementwise_rows<KIND, false>(lhs, lv, rhs, rv, n, nd, rows, out, aux, nullptr);
+}
+
+// Member m of a many-member launch works on base + m * member stride (blockIdx.y is uniform over the workgroup: the bases are
+// formed once, as 64-bit scalars, in front of the per-lane work).  A stride of 0 shares an operand; a shared output tensor
+// (out_ms == 0, all operands shared) is stored by member 0 alone.
+LMN_D int32_t* many_out_base(int32_t* out, uint64_t out_ms, uint64_t m) {
+  return !out ? nullptr : out_ms ? out + m * out_ms : m == 0 ? out : nullptr;
+}
+template <int KIND>
+LMN_KERNEL k_trace_many_elementwise(const int32_t* __restrict__ lhs, TraceView lv, uint64_t lhs_ms,
+                                    const int32_t* __restrict__ rhs, TraceView rv, uint64_t rhs_ms, uint64_t n, TraceNode nd,
+                                    uint32_t* __restrict__ rows, uint64_t rows_ms, int32_t* __restrict__ out, uint64_t out_ms,
+                                    uint32_t* __restrict__ aux, uint64_t aux_ms, uint32_t* __restrict__ refused) {
+  const uint64_t m = blockIdx.y;
+  trace_elementwise_rows<KIND, true>(lhs + m * lhs_ms, lv, rhs ? rhs + m * rhs_ms : nullptr, rv, n, nd, rows + m * rows_ms,
+                                     many_out_base(out, out_ms, m), aux ? aux + m * aux_ms : nullptr,
+                                     refused ? refused + m : nullptr);
 }
 
 // SumReduce rows (prim.rs:1486-1510, 1536-1561): row r = (i*back + j)*dim + k holds input[i, k, j], the
@@ -328,9 +368,12 @@ LMN_KERNEL k_trace_elementwise(const int32_t* __restrict__ lhs, TraceView lv, co
 // the block's first row), rows leave through LDS.
 // MAX: MaxReduce rows (prim.rs:1591-1734): the running maximum starts at the group's first element, is_max marks
 // the rows whose input becomes the new maximum (strict comparison).
-template <bool MAX>
-LMN_KERNEL k_trace_reduce(const int32_t* __restrict__ input, uint64_t dim, uint64_t back, uint64_t n_rows,
-                          uint64_t n_out, TraceNode nd, uint32_t* __restrict__ rows, int32_t* __restrict__ out) {
+// (the row rule once, for k_trace_reduce and k_trace_many_reduce: `input` is the launch's or the member's own tensor, so the
+// cooperative carry-in reads the member's own input)
+template <bool MAX, bool MANY>
+LMN_D void trace_reduce_rows(const int32_t* __restrict__ input, uint64_t dim, uint64_t back, uint64_t n_rows, uint64_t n_out,
+                             const TraceNode& nd, uint32_t* __restrict__ rows, int32_t* __restrict__ out,
+                             uint32_t* __restrict__ refused) {
   constexpr int NC = MAX ? 15 : 14, ST = MAX ? 17 : 15;
   LMN_SHARED uint32_t tile[TPB * ST];
   LMN_SHARED int64_t scan[TPB];   // inclusive segmented scan of the block's inputs (segment = reduction group)
@@ -374,6 +417,7 @@ LMN_KERNEL k_trace_reduce(const int32_t* __restrict__ input, uint64_t dim, uint6
     if (take) scan[threadIdx.x] = op(scan[threadIdx.x], add);
     __syncthreads();
   }
+  bool bad = false;   // this lane's row carries the mark
   if (on) {
     // exclusive value: everything of the group before step k (inside the block, plus the carry for the straddling group)
     const bool first_seg = k == k0 + threadIdx.x;  // this lane's group began before the block
@@ -401,12 +445,28 @@ LMN_KERNEL k_trace_reduce(const int32_t* __restrict__ input, uint64_t dim, uint6
       t[12] = nd.lhs_mult; t[13] = last_step ? nd.out_mult : 0u;
     }
     if (last_step && out) out[g] = ok ? (int32_t)next : 0;
+    bad = !ok;
   }
+  if constexpr (MANY) trace_count_refused(bad, refused);
   __syncthreads();
   const uint64_t rows_here = n_rows - row0 < (uint64_t)TPB ? n_rows - row0 : (uint64_t)TPB;
   const uint32_t words = (uint32_t)rows_here * NC;
   uint32_t* dst = rows + row0 * NC;
   for (uint32_t w = threadIdx.x; w < words; w += TPB) dst[w] = tile[(w / NC) * ST + (w % NC)];
+}
+
+template <bool MAX>
+LMN_KERNEL k_trace_reduce(const int32_t* __restrict__ input, uint64_t dim, uint64_t back, uint64_t n_rows,
+                          uint64_t n_out, TraceNode nd, uint32_t* __restrict__ rows, int32_t* __restrict__ out) {
+  trace_reduce_rows<MAX, false>(input, dim, back, n_rows, n_out, nd, rows, out, nullptr);
+}
+template <bool MAX>
+LMN_KERNEL k_trace_many_reduce(const int32_t* __restrict__ input, uint64_t in_ms, uint64_t dim, uint64_t back, uint64_t n_rows,
+                               uint64_t n_out, TraceNode nd, uint32_t* __restrict__ rows, uint64_t rows_ms,
+                               int32_t* __restrict__ out, uint64_t out_ms, uint32_t* __restrict__ refused) {
+  const uint64_t m = blockIdx.y;
+  trace_reduce_rows<MAX, true>(input + m * in_ms, dim, back, n_rows, n_out, nd, rows + m * rows_ms, many_out_base(out, out_ms, m),
+                               refused ? refused + m : nullptr);
 }
 
 void launch_trace_reduce(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back,
@@ -416,6 +476,17 @@ void launch_trace_reduce(bool is_max, const int32_t* input, uint64_t front, uint
     LMN_LAUNCH(k_trace_reduce<true>, dim3(cdiv(n_rows, TPB)), dim3(TPB), 0, s, input, dim, back, n_rows, n_out, nd, rows, out);
   else
     LMN_LAUNCH(k_trace_reduce<false>, dim3(cdiv(n_rows, TPB)), dim3(TPB), 0, s, input, dim, back, n_rows, n_out, nd, rows, out);
+}
+
+void launch_trace_many_reduce(bool is_max, const int32_t* input, uint64_t in_ms, uint64_t front, uint64_t dim, uint64_t back,
+                              const TraceNode& nd, uint32_t n_members, uint32_t* rows, uint64_t rows_ms, int32_t* out,
+                              uint64_t out_ms, uint32_t* refused, lmn_stream_t s) {
+  const uint64_t n_out = front * back, n_rows = n_out * dim;
+  const dim3 g(cdiv(n_rows, TPB), n_members), b(TPB);
+  if (is_max)
+    LMN_LAUNCH(k_trace_many_reduce<true>, g, b, 0, s, input, in_ms, dim, back, n_rows, n_out, nd, rows, rows_ms, out, out_ms, refused);
+  else
+    LMN_LAUNCH(k_trace_many_reduce<false>, g, b, 0, s, input, in_ms, dim, back, n_rows, n_out, nd, rows, rows_ms, out, out_ms, refused);
 }
 
 void launch_trace_elementwise(int kind, const int32_t* lhs, const TraceView& lv, const int32_t* rhs, const TraceView& rv,
@@ -435,6 +506,24 @@ void launch_trace_elementwise(int kind, const int32_t* lhs, const TraceView& lv,
   }
 }
 
+void launch_trace_many_elementwise(int kind, const int32_t* lhs, const TraceView& lv, uint64_t lhs_ms, const int32_t* rhs,
+                                   const TraceView& rv, uint64_t rhs_ms, uint64_t n, const TraceNode& nd, uint32_t n_members,
+                                   uint32_t* rows, uint64_t rows_ms, int32_t* out, uint64_t out_ms, uint32_t* aux, uint64_t aux_ms,
+                                   uint32_t* refused, lmn_stream_t s) {
+  const dim3 g(cdiv(n, TPB), n_members), b(TPB);
+#define LMN_MANY_CASE(K)                                                                                                       \
+  case K:                                                                                                                      \
+    LMN_LAUNCH(k_trace_many_elementwise<K>, g, b, 0, s, lhs, lv, lhs_ms, rhs, rv, rhs_ms, n, nd, rows, rows_ms, out, out_ms, aux, \
+               aux_ms, refused);                                                                                               \
+    break;
+  switch (kind) {
+    LMN_MANY_CASE(0) LMN_MANY_CASE(1) LMN_MANY_CASE(2) LMN_MANY_CASE(7) LMN_MANY_CASE(8) LMN_MANY_CASE(13) LMN_MANY_CASE(15)
+    LMN_MANY_CASE(16)
+    default: throw LmnError(-100, "trace_many_elementwise: unsupported kind");
+  }
+#undef LMN_MANY_CASE
+}
+
 // LookupLayout::find_index: the LUT row of the range that holds `a`, -1 when no range does (few ranges: a linear scan of
 // block-uniform bounds)
 LMN_D int64_t lut_find_index(const LutRanges& rg, int64_t a) {
@@ -448,19 +537,25 @@ LMN_D int32_t lut_out_value(uint32_t ow) { return ow > (P31 >> 1) ? (int32_t)ow 
 
 // Sin / Exp2 / Log2 rows (sin/table.rs: node, input, idx, is_last, next_node, next_input, next_idx, input, out,
 // input_mult, out_mult, lookup_mult) with out read from the LUT's output column, plus the LUT multiplicities.
-LMN_KERNEL k_trace_lut(const int32_t* __restrict__ input, TraceView view, uint64_t n, TraceNode nd,
-                       const uint32_t* __restrict__ lut1, LutRanges rg, uint32_t* __restrict__ mult,
-                       uint32_t* __restrict__ rows, int32_t* __restrict__ out, uint32_t* __restrict__ err_flag) {
+// (the row rule once, for k_trace_lut and k_trace_many_lut.  An input outside every range: its row is marked; the single form
+// also raises *err_flag - the call fails - the many form counts it as a refused element in *refused)
+template <bool MANY>
+LMN_D void trace_lut_rows(const int32_t* __restrict__ input, const TraceView& view, uint64_t n, const TraceNode& nd,
+                          const uint32_t* __restrict__ lut1, const LutRanges& rg, uint32_t* __restrict__ mult,
+                          uint32_t* __restrict__ rows, int32_t* __restrict__ out, uint32_t* __restrict__ err_flag,
+                          uint32_t* __restrict__ refused) {
   constexpr int NC = 12, ST = 13;
   LMN_SHARED uint32_t tile[TPB * ST];
   const uint64_t row0 = (uint64_t)blockIdx.x * TPB;
   const uint64_t r = row0 + threadIdx.x;
+  bool bad = false;
   if (r < n) {
     const int64_t a = input[view_offset(view, r)];
     const int64_t li = lut_find_index(rg, a);
-    uint32_t ow = P31;  // an input outside every range: the call fails, and its row is marked as well
+    uint32_t ow = P31;  // an input outside every range
     if (li < 0) {
-      *err_flag = 1u;
+      bad = true;
+      if constexpr (!MANY) *err_flag = 1u;
     } else {
       ow = lut1[li];
       atomicAdd(&mult[li], 1u);
@@ -471,6 +566,7 @@ LMN_KERNEL k_trace_lut(const int32_t* __restrict__ input, TraceView view, uint64
     t[7] = fixed_to_m31(a); t[8] = ow; t[9] = nd.lhs_mult; t[10] = nd.out_mult; t[11] = 1u;
     if (out) out[r] = lut_out_value(ow);
   }
+  if constexpr (MANY) trace_count_refused(bad, refused);
   __syncthreads();
   const uint64_t rows_here = n - row0 < (uint64_t)TPB ? n - row0 : (uint64_t)TPB;
   const uint32_t words = (uint32_t)rows_here * NC;
@@ -478,11 +574,33 @@ LMN_KERNEL k_trace_lut(const int32_t* __restrict__ input, TraceView view, uint64
   for (uint32_t w = threadIdx.x; w < words; w += TPB) dst[w] = tile[(w / NC) * ST + (w % NC)];
 }
 
+LMN_KERNEL k_trace_lut(const int32_t* __restrict__ input, TraceView view, uint64_t n, TraceNode nd,
+                       const uint32_t* __restrict__ lut1, LutRanges rg, uint32_t* __restrict__ mult,
+                       uint32_t* __restrict__ rows, int32_t* __restrict__ out, uint32_t* __restrict__ err_flag) {
+  trace_lut_rows<false>(input, view, n, nd, lut1, rg, mult, rows, out, err_flag, nullptr);
+}
+// lut1 is shared by all members; the multiplicity atomics go to the member's own table
+LMN_KERNEL k_trace_many_lut(const int32_t* __restrict__ input, TraceView view, uint64_t in_ms, uint64_t n, TraceNode nd,
+                            const uint32_t* __restrict__ lut1, LutRanges rg, uint32_t* __restrict__ mult, uint64_t mult_ms,
+                            uint32_t* __restrict__ rows, uint64_t rows_ms, int32_t* __restrict__ out, uint64_t out_ms,
+                            uint32_t* __restrict__ refused) {
+  const uint64_t m = blockIdx.y;
+  trace_lut_rows<true>(input + m * in_ms, view, n, nd, lut1, rg, mult + m * mult_ms, rows + m * rows_ms,
+                       many_out_base(out, out_ms, m), nullptr, refused ? refused + m : nullptr);
+}
+
 void launch_trace_lut(const int32_t* input, const TraceView& view, uint64_t n, const TraceNode& nd,
                       const uint32_t* lut_col1, const LutRanges& ranges, uint32_t* mult, uint32_t* rows,
                       int32_t* out, uint32_t* err_flag, lmn_stream_t s) {
   LMN_LAUNCH(k_trace_lut, dim3(cdiv(n, TPB)), dim3(TPB), 0, s, input, view, n, nd, lut_col1, ranges, mult, rows, out,
              err_flag);
+}
+
+void launch_trace_many_lut(const int32_t* input, const TraceView& view, uint64_t in_ms, uint64_t n, const TraceNode& nd,
+                           const uint32_t* lut_col1, const LutRanges& ranges, uint32_t n_members, uint32_t* mult, uint64_t mult_ms,
+                           uint32_t* rows, uint64_t rows_ms, int32_t* out, uint64_t out_ms, uint32_t* refused, lmn_stream_t s) {
+  LMN_LAUNCH(k_trace_many_lut, dim3(cdiv(n, TPB), n_members), dim3(TPB), 0, s, input, view, in_ms, n, nd, lut_col1, ranges, mult,
+             mult_ms, rows, rows_ms, out, out_ms, refused);
 }
 
 // =============================================================================================
@@ -538,7 +656,6 @@ LMN_D void eval_finish(int32_t lo, int32_t hi, uint32_t wave_bad, int32_t* __res
     if (refused && bad) atomicAdd(refused, bad);
   }
 }
-LMN_D uint32_t wave_count(bool pred) { return (uint32_t)__builtin_popcountll(lmn_ballot(pred)); }
 
 LMN_KERNEL k_eval_init(int32_t* __restrict__ minmax) {
   if (blockIdx.x == 0u && threadIdx.x == 0u) {

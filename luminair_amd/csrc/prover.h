@@ -299,6 +299,22 @@ class Context {
   void trace_lut(uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t n, const lmn_node_info& info,
                  const uint32_t* lut_col1, const lmn_range* ranges, uint32_t n_ranges, uint32_t* mult, uint32_t* rows,
                  uint64_t row_offset, int32_t* out);
+  // lmn_trace_many_* (trace_gen.cpp): the same producers for n_members pies of one shape, one launch per node; member m
+  // works on base + m * member stride (`*_ms`: operands / outputs in elements, rows in rows of the kind, tables in words)
+  void trace_many_elementwise(uint32_t kind, const int32_t* lhs, const lmn_view* lv, uint64_t lhs_ms, const int32_t* rhs,
+                              const lmn_view* rv, uint64_t rhs_ms, uint64_t n, const lmn_node_info& info, uint32_t n_members,
+                              uint32_t* rows, uint64_t row_offset, uint64_t rows_ms, int32_t* out, uint64_t out_ms,
+                              uint32_t* rc_mult, uint64_t rc_ms, uint32_t* refused);
+  void trace_many_contiguous(const int32_t* input, uint64_t in_ms, uint64_t in_size, const lmn_view* view, uint64_t out_size,
+                             const lmn_node_info& info, uint32_t n_members, uint32_t* rows, uint64_t row_offset, uint64_t rows_ms,
+                             int32_t* out, uint64_t out_ms, uint32_t* refused);
+  void trace_many_reduce(bool is_max, const int32_t* input, uint64_t in_ms, uint64_t front, uint64_t dim, uint64_t back,
+                         const lmn_node_info& info, uint32_t n_members, uint32_t* rows, uint64_t row_offset, uint64_t rows_ms,
+                         int32_t* out, uint64_t out_ms, uint32_t* refused);
+  void trace_many_lut(uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t in_ms, uint64_t n,
+                      const lmn_node_info& info, const uint32_t* lut_col1, const lmn_range* ranges, uint32_t n_ranges,
+                      uint32_t n_members, uint32_t* mult, uint64_t mult_ms, uint32_t* rows, uint64_t row_offset, uint64_t rows_ms,
+                      int32_t* out, uint64_t out_ms, uint32_t* refused);
   // lmn_eval_* (trace_gen.cpp): the producers' forward pass - values, their range, the refused elements; no rows
   void eval_elementwise(uint32_t kind, const int32_t* lhs, const lmn_view* lv, const int32_t* rhs, const lmn_view* rv, uint64_t n,
                         int32_t* out, int32_t* minmax, uint32_t* refused);

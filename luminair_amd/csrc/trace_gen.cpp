@@ -18,14 +18,19 @@ static TraceNode trace_node(const lmn_node_info& info) {
   return nd;
 }
 
+// the shape rules of the reduce producers (single and many-member form)
+static void check_reduce_shape(uint64_t front, uint64_t dim, uint64_t back) {
+  if (front == 0 || dim == 0 || back == 0) throw LmnError(LMN_ERR_EMPTY_TRACE, "TraceError::EmptyTrace");
+  if (front * back * dim >= (1ull << 31)) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "tensor too large");
+}
+
 // `LuminairSumReduce::process_trace` (prim.rs:1450-1565) on a contiguous (front, dim, back) device tensor
 void Context::trace_reduce(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back,
                            const lmn_node_info& info, uint32_t* rows, uint64_t row_offset, int32_t* out) {
 #ifndef LMN_EMU
   LMN_HIP_CHECK(hipSetDevice(device_));
 #endif
-  if (front == 0 || dim == 0 || back == 0) throw LmnError(LMN_ERR_EMPTY_TRACE, "TraceError::EmptyTrace");
-  if (front * back * dim >= (1ull << 31)) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "tensor too large");
+  check_reduce_shape(front, dim, back);
   launch_trace_reduce(is_max, input, front, dim, back, trace_node(info), rows + row_offset * (is_max ? 15ull : 14ull), out,
                       stream_);  // stream-ordered with every later call on this context (lmn_prove, lmn_download)
 }
@@ -49,13 +54,8 @@ static TraceView trace_view(const lmn_view* v, uint64_t n) {
   return t;
 }
 
-// `process_trace` of a Sin / Exp2 / Log2 node on a device tensor; fills the LUT multiplicity column too
-void Context::trace_lut(uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t n, const lmn_node_info& info,
-                        const uint32_t* lut_col1, const lmn_range* ranges, uint32_t n_ranges, uint32_t* mult, uint32_t* rows,
-                        uint64_t row_offset, int32_t* out) {
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
+// the argument rules of the LUT producers (single and many-member form); lut_rows = the LUT rows the ranges enumerate
+static LutRanges trace_lut_ranges(uint32_t kind, uint64_t n, const lmn_range* ranges, uint32_t n_ranges, uint64_t& lut_rows) {
   if (kind != LMN_KIND_SIN && kind != LMN_KIND_EXP2 && kind != LMN_KIND_LOG2)
     throw LmnError(LMN_ERR_INVALID_ARGUMENT, "trace_lut: kind must be Sin, Exp2 or Log2");
   if (n == 0) throw LmnError(LMN_ERR_EMPTY_TRACE, "TraceError::EmptyTrace");
@@ -76,6 +76,19 @@ void Context::trace_lut(uint32_t kind, const int32_t* input, const lmn_view* vie
     base += (uint64_t)(ranges[k].hi - ranges[k].lo + 1);
     if (base > (1ull << 26)) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "trace_lut: LUT larger than 2^26 rows");
   }
+  lut_rows = base;
+  return rg;
+}
+
+// `process_trace` of a Sin / Exp2 / Log2 node on a device tensor; fills the LUT multiplicity column too
+void Context::trace_lut(uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t n, const lmn_node_info& info,
+                        const uint32_t* lut_col1, const lmn_range* ranges, uint32_t n_ranges, uint32_t* mult, uint32_t* rows,
+                        uint64_t row_offset, int32_t* out) {
+#ifndef LMN_EMU
+  LMN_HIP_CHECK(hipSetDevice(device_));
+#endif
+  uint64_t lut_rows = 0;
+  const LutRanges rg = trace_lut_ranges(kind, n, ranges, n_ranges, lut_rows);
   const TraceView tv = trace_view(view, n);
   // bad_flag_[1] is zero between calls; the kernel sets it when an input misses every range
   launch_trace_lut(input, tv, n, trace_node(info), lut_col1, rg, mult, rows + row_offset * 12ull, out, bad_flag_ + 1, stream_);
@@ -90,14 +103,13 @@ void Context::trace_lut(uint32_t kind, const int32_t* input, const lmn_view* vie
   }
 }
 
-void Context::trace_elementwise(uint32_t kind, const int32_t* lhs, const lmn_view* lv, const int32_t* rhs,
-                                const lmn_view* rv, uint64_t n, const lmn_node_info& info, uint32_t* rows,
-                                uint64_t row_offset, int32_t* out, uint32_t* aux) {
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
+// the argument rules of the elementwise producers (single and many-member form)
+static bool elementwise_binary(uint32_t kind) {
+  return kind == LMN_KIND_ADD || kind == LMN_KIND_MUL || kind == LMN_KIND_REM || kind == LMN_KIND_LESS_THAN;
+}
+static const ComponentSpec* check_elementwise(uint32_t kind, const int32_t* rhs, const uint32_t* aux, uint64_t n) {
   const ComponentSpec* sp = component_spec((int)kind);
-  const bool binary = kind == LMN_KIND_ADD || kind == LMN_KIND_MUL || kind == LMN_KIND_REM || kind == LMN_KIND_LESS_THAN;
+  const bool binary = elementwise_binary(kind);
   const bool unary = kind == LMN_KIND_RECIP || kind == LMN_KIND_SQRT || kind == LMN_KIND_CONTIGUOUS || kind == LMN_KIND_INPUTS;
   if (!sp || !(binary || unary))
     throw LmnError(LMN_ERR_INVALID_ARGUMENT, "trace_elementwise: not an elementwise kind");
@@ -106,6 +118,16 @@ void Context::trace_elementwise(uint32_t kind, const int32_t* lhs, const lmn_vie
     throw LmnError(LMN_ERR_INVALID_ARGUMENT, "trace_elementwise: LessThan needs the range-check multiplicity table");
   if (n == 0) throw LmnError(LMN_ERR_EMPTY_TRACE, "TraceError::EmptyTrace");
   if (n >= (1ull << 31)) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "tensor too large");
+  return sp;
+}
+
+void Context::trace_elementwise(uint32_t kind, const int32_t* lhs, const lmn_view* lv, const int32_t* rhs,
+                                const lmn_view* rv, uint64_t n, const lmn_node_info& info, uint32_t* rows,
+                                uint64_t row_offset, int32_t* out, uint32_t* aux) {
+#ifndef LMN_EMU
+  LMN_HIP_CHECK(hipSetDevice(device_));
+#endif
+  const ComponentSpec* sp = check_elementwise(kind, rhs, aux, n);
   const TraceNode nd = trace_node(info);
   const TraceView tlv = trace_view(lv, n), trv = trace_view(rv, n);
   launch_trace_elementwise((int)kind, lhs, tlv, rhs, trv, n, nd, rows + row_offset * (uint64_t)sp->n_cols, out, aux,
@@ -195,15 +217,10 @@ void Context::tensor_range(const int32_t* buf, uint64_t n, int32_t* minmax) {
   launch_tensor_range(buf, n, minmax, stream_);
 }
 
-// `LuminairContiguous::process_trace` in the reference's own row rule (prim.rs:229-301): max(in_size, out_size) rows
-void Context::trace_contiguous(const int32_t* input, uint64_t in_size, const lmn_view* view, uint64_t out_size,
-                               const lmn_node_info& info, uint32_t* rows, uint64_t row_offset, int32_t* out) {
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
+// the argument rules of the buffer-rule Contiguous producers (single and many-member form); fills nd.phys_n / nd.out_n
+static TraceView check_contiguous(uint64_t in_size, const lmn_view* view, uint64_t out_size, TraceNode& nd) {
   if (in_size == 0 || out_size == 0) throw LmnError(LMN_ERR_EMPTY_TRACE, "TraceError::EmptyTrace");
   if (in_size >= (1ull << 31) || out_size >= (1ull << 31)) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "tensor too large");
-  TraceNode nd = trace_node(info);
   nd.phys_n = in_size;
   nd.out_n = out_size;
   const TraceView tv = trace_view(view, out_size);
@@ -216,9 +233,115 @@ void Context::trace_contiguous(const int32_t* input, uint64_t in_size, const lmn
     }
   else if (out_size > in_size)
     throw LmnError(LMN_ERR_INVALID_ARGUMENT, "contiguous: output larger than the input buffer without a view");
+  return tv;
+}
+
+// `LuminairContiguous::process_trace` in the reference's own row rule (prim.rs:229-301): max(in_size, out_size) rows
+void Context::trace_contiguous(const int32_t* input, uint64_t in_size, const lmn_view* view, uint64_t out_size,
+                               const lmn_node_info& info, uint32_t* rows, uint64_t row_offset, int32_t* out) {
+#ifndef LMN_EMU
+  LMN_HIP_CHECK(hipSetDevice(device_));
+#endif
+  TraceNode nd = trace_node(info);
+  const TraceView tv = check_contiguous(in_size, view, out_size, nd);
   const uint64_t n = std::max(in_size, out_size);
   launch_trace_elementwise(LMN_KIND_CONTIGUOUS, input, tv, nullptr, TraceView{}, n, nd, rows + row_offset * 11ull, out, nullptr,
                            stream_);
+}
+
+// ------------------------------------------------------------------------------------ lmn_trace_many_*
+// One launch per graph node for n_members pies of one shape (the producers in front of lmn_batch_prove): member m works on
+// base + m * member stride.  Everything is refused here, before any launch, and the text names the argument; no call waits.
+namespace {
+void many_bad(const char* call, const std::string& why) { throw LmnError(LMN_ERR_INVALID_ARGUMENT, std::string(call) + ": " + why); }
+// the single form's own argument rules, with the many form's name in front of the text
+template <class F>
+auto many_rules(const char* call, F&& f) {
+  try {
+    return f();
+  } catch (const LmnError& e) {
+    throw LmnError(e.code, std::string(call) + ": " + e.what());
+  }
+}
+// rows_ms in rows of the kind; out_n = elements of one member's output; shared_in = every operand the kind reads has stride 0
+void many_strides(const char* call, uint32_t n_members, uint64_t rows_ms, uint64_t row_offset, uint64_t n_rows, const int32_t* out,
+                  uint64_t out_ms, uint64_t out_n, bool shared_in) {
+  if (n_members > LMN_TRACE_MANY_MAX) many_bad(call, "n_members exceeds LMN_TRACE_MANY_MAX");
+  if (row_offset >= (1ull << 31) || rows_ms >= (1ull << 40)) many_bad(call, "row_offset / rows_member_stride: table too large");
+  if (rows_ms < row_offset + n_rows)
+    many_bad(call, "rows_member_stride is smaller than row_offset + the node's " + std::to_string(n_rows) + " rows");
+  if (out && out_ms == 0 && !shared_in)
+    many_bad(call, "out_member_stride 0 (a shared output tensor) needs every operand stride to be 0");
+  if (out && out_ms != 0 && out_ms < out_n)
+    many_bad(call, "out_member_stride is smaller than the output's " + std::to_string(out_n) + " elements");
+}
+}  // namespace
+
+void Context::trace_many_elementwise(uint32_t kind, const int32_t* lhs, const lmn_view* lv, uint64_t lhs_ms, const int32_t* rhs,
+                                     const lmn_view* rv, uint64_t rhs_ms, uint64_t n, const lmn_node_info& info, uint32_t n_members,
+                                     uint32_t* rows, uint64_t row_offset, uint64_t rows_ms, int32_t* out, uint64_t out_ms,
+                                     uint32_t* rc_mult, uint64_t rc_ms, uint32_t* refused) {
+  const char* call = "lmn_trace_many_elementwise_v";
+#ifndef LMN_EMU
+  LMN_HIP_CHECK(hipSetDevice(device_));
+#endif
+  const ComponentSpec* sp = many_rules(call, [&] { return check_elementwise(kind, rhs, rc_mult, n); });
+  const bool binary = elementwise_binary(kind);
+  const TraceView tlv = many_rules(call, [&] { return trace_view(lv, n); });
+  const TraceView trv = binary ? many_rules(call, [&] { return trace_view(rv, n); }) : TraceView{};
+  many_strides(call, n_members, rows_ms, row_offset, n, out, out_ms, n, lhs_ms == 0 && (!binary || rhs_ms == 0));
+  const bool lt = kind == LMN_KIND_LESS_THAN;
+  if (lt && rc_ms < 256) many_bad(call, "range_check_mult_member_stride is smaller than the table's 256 words");
+  launch_trace_many_elementwise((int)kind, lhs, tlv, lhs_ms, binary ? rhs : nullptr, trv, rhs_ms, n, trace_node(info), n_members,
+                                rows + row_offset * (uint64_t)sp->n_cols, rows_ms * (uint64_t)sp->n_cols, out, out_ms,
+                                lt ? rc_mult : nullptr, rc_ms, refused, stream_);
+}
+
+void Context::trace_many_contiguous(const int32_t* input, uint64_t in_ms, uint64_t in_size, const lmn_view* view, uint64_t out_size,
+                                    const lmn_node_info& info, uint32_t n_members, uint32_t* rows, uint64_t row_offset,
+                                    uint64_t rows_ms, int32_t* out, uint64_t out_ms, uint32_t* refused) {
+  const char* call = "lmn_trace_many_contiguous";
+#ifndef LMN_EMU
+  LMN_HIP_CHECK(hipSetDevice(device_));
+#endif
+  TraceNode nd = trace_node(info);
+  const TraceView tv = many_rules(call, [&] { return check_contiguous(in_size, view, out_size, nd); });
+  const uint64_t n = std::max(in_size, out_size);
+  many_strides(call, n_members, rows_ms, row_offset, n, out, out_ms, out_size, in_ms == 0);
+  launch_trace_many_elementwise(LMN_KIND_CONTIGUOUS, input, tv, in_ms, nullptr, TraceView{}, 0, n, nd, n_members,
+                                rows + row_offset * 11ull, rows_ms * 11ull, out, out_ms, nullptr, 0, refused, stream_);
+}
+
+void Context::trace_many_reduce(bool is_max, const int32_t* input, uint64_t in_ms, uint64_t front, uint64_t dim, uint64_t back,
+                                const lmn_node_info& info, uint32_t n_members, uint32_t* rows, uint64_t row_offset,
+                                uint64_t rows_ms, int32_t* out, uint64_t out_ms, uint32_t* refused) {
+  const char* call = "lmn_trace_many_reduce";
+#ifndef LMN_EMU
+  LMN_HIP_CHECK(hipSetDevice(device_));
+#endif
+  many_rules(call, [&] { check_reduce_shape(front, dim, back); return 0; });
+  many_strides(call, n_members, rows_ms, row_offset, front * dim * back, out, out_ms, front * back, in_ms == 0);
+  const uint64_t nc = is_max ? 15ull : 14ull;
+  launch_trace_many_reduce(is_max, input, in_ms, front, dim, back, trace_node(info), n_members, rows + row_offset * nc,
+                           rows_ms * nc, out, out_ms, refused, stream_);
+}
+
+void Context::trace_many_lut(uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t in_ms, uint64_t n,
+                             const lmn_node_info& info, const uint32_t* lut_col1, const lmn_range* ranges, uint32_t n_ranges,
+                             uint32_t n_members, uint32_t* mult, uint64_t mult_ms, uint32_t* rows, uint64_t row_offset,
+                             uint64_t rows_ms, int32_t* out, uint64_t out_ms, uint32_t* refused) {
+  const char* call = "lmn_trace_many_lut_ranges";
+#ifndef LMN_EMU
+  LMN_HIP_CHECK(hipSetDevice(device_));
+#endif
+  uint64_t lut_rows = 0;
+  const LutRanges rg = many_rules(call, [&] { return trace_lut_ranges(kind, n, ranges, n_ranges, lut_rows); });
+  const TraceView tv = many_rules(call, [&] { return trace_view(view, n); });
+  many_strides(call, n_members, rows_ms, row_offset, n, out, out_ms, n, in_ms == 0);
+  if (mult_ms < lut_rows)
+    many_bad(call, "mult_member_stride is smaller than the " + std::to_string(lut_rows) + " LUT rows the ranges enumerate");
+  launch_trace_many_lut(input, tv, in_ms, n, trace_node(info), lut_col1, rg, n_members, mult, mult_ms, rows + row_offset * 12ull,
+                        rows_ms * 12ull, out, out_ms, refused, stream_);
 }
 
 // ------------------------------------------------------------------------------------ lmn_trace_check

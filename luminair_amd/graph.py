@@ -54,13 +54,14 @@ def _lease_slab(ctx, need: int) -> _SlabLease:
     return _SlabLease(ctx, b.ptr, b.nbytes)
 
 
-@dataclass
+@dataclass(eq=False)          # a tensor is itself (a key of gen_trace_many's `feeds`), not its fields
 class GraphTensor:
     node_id: int
     shape: Tuple[int, ...]
     consumers: int = 0
     is_output: bool = False
-    buf: Optional[backend.DeviceBuffer] = None     # set by gen_trace
+    buf: Optional[backend.DeviceBuffer] = None     # set by gen_trace / gen_trace_many
+    member_stride: int = 0                         # gen_trace_many: elements between members in `buf` (0: one shared tensor)
 
     @property
     def size(self) -> int:
@@ -122,6 +123,7 @@ class _Node:
     inputs: List[GraphTensor]
     host: Optional[np.ndarray] = None      # graph inputs
     axis: int = 0                          # SumReduce
+    per_member: bool = False               # graph inputs: one tensor per member of gen_trace_many (fed through `feeds`)
 
 
 class DeviceGraph:
@@ -138,11 +140,12 @@ class DeviceGraph:
         self._next_id += 1
         return t
 
-    def input(self, values: np.ndarray) -> GraphTensor:
-        """A graph input holding Fixed<12> integers (`CopyToStwo`, prim.rs:52-88)."""
+    def input(self, values: np.ndarray, per_member: bool = False) -> GraphTensor:
+        """A graph input holding Fixed<12> integers (`CopyToStwo`, prim.rs:52-88).  per_member: `gen_trace_many` gives every
+        member its own tensor of this shape (through `feeds`); `values` is what `gen_trace` and the dry runs use."""
         v = np.ascontiguousarray(values, dtype=np.int32)
         t = self._tensor(v.shape)
-        self.nodes.append(_Node(int(TraceTableKind.Inputs), t, [], host=v))
+        self.nodes.append(_Node(int(TraceTableKind.Inputs), t, [], host=v, per_member=per_member))
         return t
 
     def constant(self, value: int) -> GraphTensor:
@@ -396,6 +399,7 @@ class DeviceGraph:
             lut_tables[int(K.RangeCheckLookup)] = (rc_mult, 256)
         for n in self.nodes:
             t = n.out
+            t.member_stride = 0
             common = dict(num_consumers=t.consumers, is_final_output=t.is_output, rows=tables[n.kind],
                           row_offset=offset[n.kind], out=carve(t.size * 4))
             if n.kind == int(K.Inputs):
@@ -434,8 +438,160 @@ class DeviceGraph:
         out = [(k, tables[k], total[k]) for k in tables] + [(k, b, n) for k, (b, n) in lut_tables.items()]
         return sorted(out, key=lambda e: e[0]), luts_out, bufs
 
-    def read(self, t: GraphTensor) -> np.ndarray:
-        return self.ctx.download(t.buf, np.int32).reshape(t.shape)
+    def gen_trace_many(self, n_members: int, feeds):
+        """`gen_trace` for `n_members` pies of this graph at once - the producers in front of `BatchProver.prove_batch`:
+        one `lmn_trace_many_*` call (one launch) per node instead of one per node per pie.  `feeds` maps every input tensor
+        created with per_member=True to an array of shape (n_members, *shape); all other inputs are shared by the members.
+        The slab discipline is `gen_trace`'s: one lease, one staged upload (shared inputs once, per-member inputs packed),
+        per kind one region of n_members x total_rows[kind] rows, per node one region of n_members x size output words - or
+        `size` words when everything the node reads is shared.  The call ends with ONE download, of the n_members refused
+        counters: the only wait, and what orders the producers' stream in front of whoever proves the tables.
+        LUT ranges are what the graph declares (set_lut, set_lut_ranges or an earlier gen_circuit_settings): a batch shares
+        one settings object.  Returns (pies, luts, bufs, refused): pies[m] = [(kind, DeviceBuffer view, n_rows)] for
+        `BatchProver.prove_batch(pies, luts)` (or `Context.prove_tables(pies[m], luts)`), refused[m] = member m's refused
+        elements - nothing is raised for them: the prover refuses such a member's pie alone."""
+        ctx = self.ctx
+        K = TraceTableKind
+        n_members = int(n_members)
+        if not 1 <= n_members <= backend.TRACE_MANY_MAX:
+            raise ValueError("gen_trace_many: 1..%d members" % backend.TRACE_MANY_MAX)
+        self.release_dry_run()
+        fed = {}
+        for t, arr in (feeds.items() if hasattr(feeds, "items") else feeds):
+            fed[t.node_id] = np.ascontiguousarray(arr, dtype=np.int32)
+        reduces = (int(K.SumReduce), int(K.MaxReduce))
+        ref_contig = lambda n: n.kind == int(K.Contiguous) and n.inputs[0].expansion == 1
+
+        def rows_of(n):
+            if n.kind in reduces:
+                return n.inputs[0].size
+            if ref_contig(n):
+                return max(n.inputs[0].base.size, n.out.size)
+            return n.out.size
+        total: Dict[int, int] = {}
+        varying = set()            # tensors that differ between members: the per-member inputs and what depends on them
+        for n in self.nodes:
+            total[n.kind] = total.get(n.kind, 0) + rows_of(n)
+            if n.per_member or any(i.base.node_id in varying for i in n.inputs):
+                varying.add(n.out.node_id)
+            if n.kind in _LUT_OF and _LUT_OF[n.kind][0] not in self.luts:
+                raise ValueError("no LUT for %r: call gen_circuit_settings() (or set_lut / set_lut_ranges) before gen_trace_many"
+                                 % _LUT_OF[n.kind][0])
+            if n.per_member:
+                a = fed.get(n.out.node_id)
+                if a is None or a.shape != (n_members,) + n.out.shape:
+                    raise ValueError("gen_trace_many: feeds must hold an array of shape (n_members, *shape) for input %d"
+                                     % n.out.node_id)
+        extra = set(fed) - {n.out.node_id for n in self.nodes if n.per_member}
+        if extra:
+            raise ValueError("gen_trace_many: feeds name tensors that are no per_member inputs: %s" % sorted(extra))
+        al = lambda nbytes: (nbytes + 255) & ~255
+        stage_parts, stage_off, cursor_h = [], {}, [0]
+
+        def stage(key, arr):
+            a = np.ascontiguousarray(arr).reshape(-1).view(np.uint32)
+            stage_off[key] = (cursor_h[0], a.nbytes)
+            pad = (al(a.nbytes) - a.nbytes) // 4
+            stage_parts.append(a)
+            if pad:
+                stage_parts.append(np.zeros(pad, dtype=np.uint32))
+            cursor_h[0] += al(a.nbytes)
+
+        stage(("refused",), np.zeros(n_members, dtype=np.uint32))
+        for n in self.nodes:
+            if n.host is not None:
+                stage(("in", n.out.node_id), fed[n.out.node_id] if n.per_member else n.host.astype(np.int32, copy=False))
+        luts_out, lut_len, lut_rg = {}, {}, {}
+        for kind in sorted(total):
+            if kind in _LUT_OF:
+                name, _ = _LUT_OF[kind]
+                lo, hi, (c0, c1) = self.luts[name]
+                lut_len[name] = len(c0)
+                lut_rg[name] = self.lut_ranges.get(name) or [(lo, hi)]
+                stage(("lut1", name), c1)
+                stage(("lutm", name), np.zeros(n_members * len(c0), dtype=np.uint32))
+                luts_out[name] = (c0, c1)
+        if int(K.LessThan) in total:
+            stage(("rc",), np.zeros(n_members * 256, dtype=np.uint32))
+        out_words = lambda n: n.out.size * (n_members if n.out.node_id in varying else 1)
+        need = sum(al(n_members * total[k] * _NCOLS[k] * 4) for k in total) + sum(al(out_words(n) * 4) for n in self.nodes) \
+            + cursor_h[0]
+        slab = _lease_slab(ctx, need)
+        cursor = [0]
+
+        def carve(nbytes):
+            v = slab.view(cursor[0], nbytes)
+            cursor[0] += al(nbytes)
+            return v
+
+        staged = carve(cursor_h[0])
+        ctx.upload_to(staged, np.concatenate(stage_parts))
+        dev_of = lambda key: staged.view(*stage_off[key])
+        refused = dev_of(("refused",))
+        tables = {k: carve(n_members * total[k] * _NCOLS[k] * 4) for k in total}
+        offset = {k: 0 for k in total}
+        stride_of = lambda t: t.member_stride          # of a tensor that has been produced
+        for n in self.nodes:
+            t = n.out
+            t.member_stride = t.size if t.node_id in varying else 0
+            t.buf = carve(out_words(n) * 4)
+            common = dict(n_members=n_members, node_id=t.node_id, num_consumers=t.consumers, is_final_output=t.is_output,
+                          rows=tables[n.kind], rows_stride=total[n.kind], row_offset=offset[n.kind], out=t.buf,
+                          out_stride=t.member_stride, refused=refused)
+            if n.kind == int(K.Inputs):
+                ctx.trace_many_elementwise(n.kind, dev_of(("in", t.node_id)), None, t.size, input_ids=(), input_mults=(),
+                                           lhs_stride=t.member_stride, **common)
+            elif n.kind in reduces:
+                a = n.inputs[0].base
+                front = int(np.prod(a.shape[:n.axis])) if n.axis else 1
+                back = int(np.prod(a.shape[n.axis + 1:])) if n.axis + 1 < len(a.shape) else 1
+                ctx.trace_many_reduce(a.buf, front, a.shape[n.axis], back, input_id=a.node_id, inp_stride=stride_of(a),
+                                      maximum=n.kind == int(K.MaxReduce), **common)
+            elif ref_contig(n):
+                v = n.inputs[0]
+                ctx.trace_many_contiguous(v.base.buf, v.base.size, t.size, input_id=v.base.node_id,
+                                          inp_stride=stride_of(v.base), view=_lmn_view(v), **common)
+            elif n.kind in _LUT_OF:
+                name = _LUT_OF[n.kind][0]
+                v = n.inputs[0]
+                ctx.trace_many_lut(n.kind, v.base.buf, t.size, input_id=v.base.node_id, lut_col1=dev_of(("lut1", name)),
+                                   ranges=lut_rg[name], mult=dev_of(("lutm", name)), mult_stride=lut_len[name],
+                                   inp_stride=stride_of(v.base), view=_lmn_view(v), **common)
+            else:
+                ins = n.inputs
+                lt = n.kind == int(K.LessThan)
+                ctx.trace_many_elementwise(
+                    n.kind, ins[0].base.buf, ins[1].base.buf if len(ins) > 1 else None, t.size,
+                    input_ids=tuple(i.base.node_id for i in ins), input_mults=tuple(-1 for _ in ins),
+                    lhs_stride=stride_of(ins[0].base), rhs_stride=stride_of(ins[1].base) if len(ins) > 1 else 0,
+                    lhs_view=_lmn_view(ins[0]), rhs_view=_lmn_view(ins[1]) if len(ins) > 1 else None,
+                    range_check_mult=dev_of(("rc",)) if lt else None, range_check_mult_stride=256 if lt else 0, **common)
+            offset[n.kind] += rows_of(n)
+        counts = [int(c) for c in ctx.download(refused)[:n_members]]      # the one wait
+        pies = []
+        for m in range(n_members):
+            pie = [(k, tables[k].view(m * total[k] * _NCOLS[k] * 4, total[k] * _NCOLS[k] * 4), total[k]) for k in tables]
+            for kind in total:
+                if kind in _LUT_OF:
+                    name, lookup_kind = _LUT_OF[kind]
+                    ln = lut_len[name]
+                    off, _ = stage_off[("lutm", name)]
+                    pie.append((lookup_kind, staged.view(off + m * ln * 4, ln * 4), ln))
+            if int(K.LessThan) in total:
+                off, _ = stage_off[("rc",)]
+                pie.append((int(K.RangeCheckLookup), staged.view(off + m * 1024, 1024), 256))
+            pies.append(sorted(pie, key=lambda e: e[0]))
+        return pies, luts_out, [slab], counts
+
+    def read(self, t: GraphTensor, member: Optional[int] = None) -> np.ndarray:
+        """The tensor's values.  After `gen_trace_many`: member `member`'s tensor, or the shared tensor of a node that
+        depends on no per-member input (for which `member` is ignored)."""
+        buf = t.buf
+        if t.member_stride:
+            if member is None:
+                raise ValueError("read: tensor %d differs between members: pass member=" % t.node_id)
+            buf = buf.view(int(member) * t.member_stride * 4, t.size * 4)
+        return self.ctx.download(buf, np.int32).reshape(t.shape)
 
     # ---- gen_circuit_settings (crates/graph/src/graph.rs:61-159): a HOST dry run, as in the reference
     def _dry_run(self) -> Dict[int, np.ndarray]:
