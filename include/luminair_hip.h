@@ -229,6 +229,48 @@ void lmn_free(void* p);
  * returns.  A caller keeps N proofs in flight from one thread with N contexts: submit on each, then wait on each. */
 int lmn_prove_submit(lmn_ctx* ctx, const lmn_table* tables, size_t n_tables, const lmn_settings* settings);
 int lmn_prove_wait(lmn_ctx* ctx, uint8_t** proof_bincode, size_t* proof_len);
+
+/* ---- Settings prepared once.  CircuitSettings are fixed per model, and so is everything about the preprocessed tree
+ * (tree 0) of its proofs: the LUT columns, the 8-bit range-check column, their coefficients, their low-degree extension,
+ * the Merkle layers and the root.  lmn_prove redoes that work for every proof - a host loop over the LUT words, an
+ * upload, the transforms, the tree and a host wait for a root that is the same bytes every time.  lmn_settings_prepare
+ * does it ONCE, on a stream of its own, and returns after waiting; the object it hands out is immutable, lives in device
+ * memory of its own (no context's arena) and is shared read-only by every context, batch object and thread of its device
+ * that proves with it.  The proofs are byte-identical to lmn_prove's.
+ *  - lookups: the LMN_LOOKUP_* bits of the lookup components the pies WILL contain (LMN_LOOKUP_RANGE_CHECK when the
+ *    graph has LessThan).  settings->luts must carry the columns of every sin / exp2 / log2 bit set (a LUT whose bit is
+ *    clear is validated and left out); settings->has_lookups is not read.  lookups == 0 is valid (settings may then be
+ *    NULL): the empty tree, root = blake2s("").
+ *  - The LUT words are checked on the device (canonical M31) and the range-check column is written there; the caller's
+ *    LUT arrays are free again as soon as the call returns.
+ *  - LMN_ERR_INVALID_ARGUMENT (text: lmn_last_error(NULL) for prepare, the context's / batch's for the prove entries):
+ *    a non-canonical LUT word (of a LUT in use), a lookup bit without its LUT, a duplicate LUT, a null column, a LUT of
+ *    fewer than 2^4 rows or too large for the prover, unknown bits; at prove time a pie whose lookup tables are not
+ *    exactly `lookups`, a lookup table whose padded size is not its LUT's, a context whose log_blowup or device differs
+ *    from the object's, a sharded context (tree 0 has another layout there).  The context stays usable.
+ *  - Lifetime: the library holds a reference from the start of a prove / submit / batch call until its proof has been
+ *    returned (lmn_prove_wait for submits); lmn_prepared_destroy drops the caller's reference only, at any time.
+ *  - lmn_prepared_root: the root of tree 0 = proof.commitments[0] of every proof made with the object. */
+typedef struct lmn_prepared lmn_prepared;
+int lmn_settings_prepare(int device, const lmn_config* cfg, const lmn_settings* settings, uint32_t lookups,
+                         lmn_prepared** out);
+int lmn_prepared_root(const lmn_prepared* p, uint8_t root_out[32]);
+uint32_t lmn_prepared_lookups(const lmn_prepared* p);
+void lmn_prepared_destroy(lmn_prepared* p);
+int lmn_prove_prepared(lmn_ctx* ctx, const lmn_table* tables, size_t n_tables, const lmn_prepared* prepared,
+                       uint8_t** proof_bincode, size_t* proof_len);
+/* collected with lmn_prove_wait, like lmn_prove_submit's */
+int lmn_prove_submit_prepared(lmn_ctx* ctx, const lmn_table* tables, size_t n_tables, const lmn_prepared* prepared);
+/* The lock-step batch form (luminair_hip_batch.h: `batch`, n, tables, proofs, lens, rcs as lmn_batch_prove takes them) with the
+ * settings prepared once by the batch library: every member reads the one prepared tree 0, so no member checks or uploads a
+ * LUT, transforms or commits tree 0, or waits for its root - fewer launches, host waits and transfers per batch
+ * (lmn_batch_counter 0, 1, 2 + 3), the same proof bytes.  Declared here, next to the other prepared entries, and exported by
+ * both libraries so that one binding covers them; batch objects exist in libluminair_hip_batch.so alone, so the main
+ * library answers LMN_ERR_INVALID_ARGUMENT. */
+typedef struct lmn_batch lmn_batch;
+int lmn_batch_prove_prepared(lmn_batch* batch, uint32_t n, const lmn_table* const* tables, size_t n_tables,
+                             const lmn_prepared* prepared, uint8_t** proofs, size_t* lens, int* rcs);
+
 /* Per-stage / per-kernel HIP-event timing is off by default (every event record costs a few
  * microseconds between dependent kernels); enable it for the proofs whose lmn_timings you want. */
 int lmn_set_profiling(lmn_ctx* ctx, int enabled);

@@ -65,6 +65,8 @@ class LmnSettings(C.Structure):
 
 
 LUT_KINDS = {"sin": 0, "exp2": 1, "log2": 2}   # LMN_LUT_*
+LOOKUP_SIN, LOOKUP_EXP2, LOOKUP_LOG2, LOOKUP_RANGE_CHECK = 1, 2, 4, 8   # LMN_LOOKUP_*
+LOOKUP_BITS = {"sin": LOOKUP_SIN, "exp2": LOOKUP_EXP2, "log2": LOOKUP_LOG2, "range_check": LOOKUP_RANGE_CHECK}
 
 
 class LmnView(C.Structure):
@@ -231,7 +233,9 @@ EXPORTS = ["lmn_abi_version", "lmn_kind_padding_row", "lmn_strerror", "lmn_last_
            "lmn_rows_open", "lmn_rows_push", "lmn_rows_push_pinned", "lmn_rows_sync", "lmn_rows_finish", "lmn_rows_count",
            "lmn_rows_reset", "lmn_rows_close", "lmn_trace_check",
            "lmn_eval_elementwise_v", "lmn_eval_reduce", "lmn_eval_reduce_split", "lmn_eval_lut_ranges", "lmn_tensor_range",
-           "lmn_trace_many_elementwise_v", "lmn_trace_many_contiguous", "lmn_trace_many_reduce", "lmn_trace_many_lut_ranges"]
+           "lmn_trace_many_elementwise_v", "lmn_trace_many_contiguous", "lmn_trace_many_reduce", "lmn_trace_many_lut_ranges",
+           "lmn_settings_prepare", "lmn_prepared_root", "lmn_prepared_lookups", "lmn_prepared_destroy", "lmn_prove_prepared",
+           "lmn_prove_submit_prepared", "lmn_batch_prove_prepared"]
 TRACE_MANY_MAX = 1024   # LMN_TRACE_MANY_MAX
 
 
@@ -276,6 +280,18 @@ class Library:
                                   C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
         lib.lmn_prove_submit.argtypes = [C.c_void_p, C.POINTER(LmnTable), C.c_size_t, C.POINTER(LmnSettings)]
         lib.lmn_prove_wait.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
+        lib.lmn_settings_prepare.argtypes = [C.c_int, C.POINTER(LmnConfig), C.POINTER(LmnSettings), C.c_uint32,
+                                             C.POINTER(C.c_void_p)]
+        lib.lmn_prepared_root.argtypes = [C.c_void_p, C.c_void_p]
+        lib.lmn_prepared_lookups.argtypes = [C.c_void_p]
+        lib.lmn_prepared_lookups.restype = C.c_uint32
+        lib.lmn_prepared_destroy.argtypes = [C.c_void_p]
+        lib.lmn_prepared_destroy.restype = None
+        lib.lmn_prove_prepared.argtypes = [C.c_void_p, C.POINTER(LmnTable), C.c_size_t, C.c_void_p,
+                                           C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]
+        lib.lmn_prove_submit_prepared.argtypes = [C.c_void_p, C.POINTER(LmnTable), C.c_size_t, C.c_void_p]
+        lib.lmn_batch_prove_prepared.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(LmnTable)), C.c_size_t, C.c_void_p,
+                                                 C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
         lib.lmn_free.argtypes = [C.c_void_p]
         lib.lmn_get_timings.argtypes = [C.c_void_p, C.POINTER(LmnTimings)]
         lib.lmn_set_profiling.argtypes = [C.c_void_p, C.c_int]
@@ -823,6 +839,77 @@ class Tree:
             self.handle = None
 
 
+class PreparedSettings:
+    """`lmn_prepared`: a circuit's preprocessed tree (tree 0) - LUT and range-check columns, coefficients, low-degree
+    extension, Merkle layers, root - built once on the device and shared read-only by every proof that names it with
+    `prepared=` (`Context.prove_tables` / `prove_submit`, `Prover.prove`, `ProverPool.prove_many`, and - made with the batch
+    library - `BatchProver.prove_batch`, `BatchPool.prove_many`).  The proofs are byte-identical to the ones made with the
+    LUTs handed over per proof.
+
+    luts: {"sin" | "exp2" | "log2": (col0, col1)} as `Context.prove_tables` takes them (free again when this returns);
+    lookups: LOOKUP_* bits of the lookup components the pies will contain - LOOKUP_RANGE_CHECK for a graph with LessThan;
+    None = the bits of `luts`.  A prepared object works with contexts of its own library, device and log_blowup."""
+
+    def __init__(self, device: int = 0, config: Optional[LmnConfig] = None, luts=None, lookups: Optional[int] = None,
+                 library: Optional[Library] = None):
+        self.lib = library or default_library()
+        self.device = device
+        self.handle = None
+        cfg = config or self.lib.default_config()
+        luts = luts or {}
+        if lookups is None:
+            lookups = 0
+            for name in luts:
+                lookups |= LOOKUP_BITS[name]
+        _arr, _n, settings, _keep = Context._marshal_tables(None, [], luts)
+        h = C.c_void_p()
+        rc = self.lib.lib.lmn_settings_prepare(device, C.byref(cfg), C.byref(settings), int(lookups), C.byref(h))
+        if rc != LMN_OK:
+            msg = self.lib.lib.lmn_last_error(None).decode() or self.lib.lib.lmn_strerror(rc).decode()
+            raise LuminairBackendError(rc, msg)
+        self.handle = h
+
+    def _handle_for(self, library: Library):
+        """the C handle, for a call into `library` (which must be the library that made it)"""
+        if not self.handle:
+            raise LuminairBackendError(ERR_INVALID_ARGUMENT, "the prepared settings are closed")
+        if os.path.realpath(library.path) != os.path.realpath(self.lib.path):
+            raise LuminairBackendError(ERR_INVALID_ARGUMENT, "prepared settings made by %s cannot be used with %s"
+                                       % (self.lib.path, library.path))
+        return self.handle
+
+    @property
+    def root(self) -> bytes:
+        """the root of tree 0: `commitments[0]` of every proof made with this object"""
+        out = (C.c_uint8 * 32)()
+        rc = self.lib.lib.lmn_prepared_root(self._handle_for(self.lib), out)
+        if rc != LMN_OK:
+            raise LuminairBackendError(rc, self.lib.lib.lmn_strerror(rc).decode())
+        return bytes(out)
+
+    @property
+    def lookups(self) -> int:
+        return int(self.lib.lib.lmn_prepared_lookups(self._handle_for(self.lib)))
+
+    def close(self):
+        """drops this reference; proofs in flight keep the object alive until they have been returned"""
+        if getattr(self, "handle", None):
+            self.lib.lib.lmn_prepared_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self) -> "PreparedSettings":
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """One prover context per GPU (`lmn_ctx`)."""
 
@@ -1299,13 +1386,19 @@ class Context:
         """`lmn_rows_open`: a table of `kind` to be filled with up to `capacity_rows` host rows while they are produced."""
         return RowSink(self, kind, capacity_rows)
 
-    def prove_tables(self, tables: Sequence[Tuple[int, object, int]], luts=None) -> bytes:
+    def prove_tables(self, tables: Sequence[Tuple[int, object, int]], luts=None,
+                     prepared: Optional[PreparedSettings] = None) -> bytes:
         """tables: [(kind, rows, n_rows)] where rows is a uint32 ndarray (host), a DeviceBuffer or a finished RowSink;
-        luts: {"sin" | "exp2" | "log2": (col0, col1)} preprocessed LUT columns (uint32, 2^k words each)."""
-        arr, n, settings, _keep = self._marshal_tables(tables, luts)
+        luts: {"sin" | "exp2" | "log2": (col0, col1)} preprocessed LUT columns (uint32, 2^k words each);
+        prepared: a `PreparedSettings` in place of `luts` (`lmn_prove_prepared`): tree 0 is read from it."""
+        arr, n, settings, _keep = self._marshal_tables(tables, None if prepared is not None else luts)
         out = C.POINTER(C.c_uint8)()
         out_len = C.c_size_t()
-        self._check(self.lib.lib.lmn_prove(self.handle, arr, n, C.byref(settings), C.byref(out), C.byref(out_len)))
+        if prepared is not None:
+            self._check(self.lib.lib.lmn_prove_prepared(self.handle, arr, n, prepared._handle_for(self.lib), C.byref(out),
+                                                        C.byref(out_len)))
+        else:
+            self._check(self.lib.lib.lmn_prove(self.handle, arr, n, C.byref(settings), C.byref(out), C.byref(out_len)))
         data = C.string_at(out, out_len.value)
         self.lib.lib.lmn_free(out)
         return data
@@ -1319,11 +1412,15 @@ class Context:
         self._check(self.lib.lib.lmn_trace_check(self.handle, arr, n, C.byref(settings), C.byref(rep)))
         return TraceReport.from_c(rep)
 
-    def prove_submit(self, tables: Sequence[Tuple[int, object, int]], luts=None):
-        """`lmn_prove_submit`: start the proof on the context's own worker thread and return; collect it with
-        `prove_wait()`.  One thread keeps N proofs in flight with N contexts."""
-        arr, n, settings, keep = self._marshal_tables(tables, luts)
-        self._check(self.lib.lib.lmn_prove_submit(self.handle, arr, n, C.byref(settings)))
+    def prove_submit(self, tables: Sequence[Tuple[int, object, int]], luts=None,
+                     prepared: Optional[PreparedSettings] = None):
+        """`lmn_prove_submit` (`lmn_prove_submit_prepared` with `prepared=`): start the proof on the context's own worker
+        thread and return; collect it with `prove_wait()`.  One thread keeps N proofs in flight with N contexts."""
+        arr, n, settings, keep = self._marshal_tables(tables, None if prepared is not None else luts)
+        if prepared is not None:
+            self._check(self.lib.lib.lmn_prove_submit_prepared(self.handle, arr, n, prepared._handle_for(self.lib)))
+        else:
+            self._check(self.lib.lib.lmn_prove_submit(self.handle, arr, n, C.byref(settings)))
         self._pending = keep          # borrowed by the library until prove_wait returns
 
     def prove_wait(self) -> bytes:

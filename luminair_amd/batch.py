@@ -36,6 +36,7 @@ class BatchProver:
         for k, v in pcs.items():
             setattr(cfg, k, v)
         self.slots = slots
+        self.config = cfg
         self.handle = C.c_void_p()
         rc = lib.lmn_batch_create(device, C.byref(cfg), slots, C.byref(self.handle))
         if rc != 0:
@@ -59,17 +60,25 @@ class BatchProver:
             settings = settings or st
         return ("marshalled", n, arrs, n_tables, settings, keep)
 
-    def prove_batch(self, pies, luts=None) -> List[bytes]:
+    def prepare(self, luts=None, lookups: Optional[int] = None, device: int = 0) -> "backend.PreparedSettings":
+        """`backend.PreparedSettings` made by THIS library and config, for `prove_batch(..., prepared=)`"""
+        return backend.PreparedSettings(device, self.config, luts, lookups, self.lib)
+
+    def prove_batch(self, pies, luts=None, prepared: Optional["backend.PreparedSettings"] = None) -> List[bytes]:
         """pies[i] = [(kind, rows, n_rows)] like `Context.prove_tables`; all pies must have the same kinds and row counts.
-        Or what `marshal(pies, luts)` returned."""
+        Or what `marshal(pies, luts)` returned.  prepared: settings prepared once with the batch library (`prepare`) in
+        place of `luts` - `lmn_batch_prove_prepared`: no member handles a LUT, builds tree 0 or waits for its root."""
         if not (isinstance(pies, tuple) and len(pies) == 6 and pies[0] == "marshalled"):
-            pies = self.marshal(pies, luts)
+            pies = self.marshal(pies, None if prepared is not None else luts)
         _, n, arrs, n_tables, settings, keep = pies
         proofs = (C.POINTER(C.c_uint8) * n)()
         lens = (C.c_size_t * n)()
         rcs = (C.c_int * n)()
         lib = self.lib.lib
-        rc = lib.lmn_batch_prove(self.handle, n, arrs, n_tables, C.byref(settings), proofs, lens, rcs)
+        if prepared is not None:
+            rc = lib.lmn_batch_prove_prepared(self.handle, n, arrs, n_tables, prepared._handle_for(self.lib), proofs, lens, rcs)
+        else:
+            rc = lib.lmn_batch_prove(self.handle, n, arrs, n_tables, C.byref(settings), proofs, lens, rcs)
         out = []
         for i in range(n):
             if proofs[i]:
@@ -126,8 +135,14 @@ class BatchPool:
                 del os.environ["LMN_BATCH_THREADS"]
         self.slots = slots
 
-    def prove_many(self, pies: Sequence[Sequence[Tuple[int, object, int]]], luts=None) -> List[bytes]:
-        """all pies of identical shape (as in `BatchProver.prove_batch`); any number of them"""
+    def prepare(self, luts=None, lookups: Optional[int] = None, device: int = 0) -> "backend.PreparedSettings":
+        """`backend.PreparedSettings` for `prove_many(..., prepared=)`: one object for all groups"""
+        return self.groups[0].prepare(luts, lookups, device)
+
+    def prove_many(self, pies: Sequence[Sequence[Tuple[int, object, int]]], luts=None,
+                   prepared: Optional["backend.PreparedSettings"] = None) -> List[bytes]:
+        """all pies of identical shape (as in `BatchProver.prove_batch`); any number of them.  prepared: as in
+        `BatchProver.prove_batch` - every group reads the one prepared object."""
         import threading
         chunks = [(i, pies[i:i + self.slots]) for i in range(0, len(pies), self.slots)]
         out: List[Optional[bytes]] = [None] * len(pies)
@@ -141,7 +156,7 @@ class BatchPool:
                         return
                     at, chunk = chunks.pop(0)
                 try:
-                    out[at:at + len(chunk)] = bp.prove_batch(chunk, luts)
+                    out[at:at + len(chunk)] = bp.prove_batch(chunk, luts, prepared)
                 except BaseException as e:  # noqa: BLE001 - re-raised by the caller's thread
                     with lock:
                         errors.append(e)

@@ -575,6 +575,7 @@ struct lmn_batch {
   const lmn_table* const* tables = nullptr;
   size_t n_tables = 0;
   const lmn_settings* settings = nullptr;
+  std::shared_ptr<const lmn::Prepared> prepared;   // lmn_batch_prove_prepared: the members' shared tree 0, held for the call
   std::vector<std::vector<uint8_t>> out;
   std::vector<int> rc;
   std::vector<std::string> err;
@@ -586,7 +587,7 @@ static void run_member(lmn_batch* b, uint32_t me) {
   int rc = LMN_OK;
   std::string msg;
   try {
-    b->out[me] = b->ctx[me]->prove(b->tables[me], b->n_tables, b->settings);
+    b->out[me] = b->ctx[me]->prove(b->tables[me], b->n_tables, b->settings, b->prepared.get());
   } catch (const LmnError& e) {
     rc = (e.code == -100 || (e.code <= -1 && e.code >= -10)) ? e.code : LMN_ERR_INTERNAL;
     msg = e.what();
@@ -777,10 +778,29 @@ void lmn_batch_destroy(lmn_batch* b) {
 
 const char* lmn_batch_last_error(const lmn_batch* b) { return b ? b->last_error.c_str() : "null batch"; }
 
-int lmn_batch_prove(lmn_batch* b, uint32_t n, const lmn_table* const* tables, size_t n_tables, const lmn_settings* settings,
-                    uint8_t** proofs, size_t* lens, int* rcs) {
+static int batch_prove(lmn_batch* b, uint32_t n, const lmn_table* const* tables, size_t n_tables, const lmn_settings* settings,
+                       const lmn_prepared* prepared, bool with_prepared, uint8_t** proofs, size_t* lens, int* rcs) {
   if (!b || !tables || !proofs || !lens || n == 0 || n > b->slots || n_tables == 0) return LMN_ERR_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> call(b->call_mu);
+  // every member of the call reads the one prepared object, so all of them skip the same steps; the batch holds its
+  // reference until the proofs have been handed out
+  struct PreparedScope {
+    lmn_batch* b;
+    ~PreparedScope() { b->prepared.reset(); }
+  } prepared_scope{b};
+  if (with_prepared) {
+    try {
+      b->prepared = lmn::prepared_ref(prepared);
+    } catch (const LmnError& e) {
+      for (uint32_t i = 0; i < n; ++i) {
+        proofs[i] = nullptr;
+        lens[i] = 0;
+        if (rcs) rcs[i] = e.code;
+      }
+      b->last_error = e.what();
+      return e.code;
+    }
+  }
   for (uint32_t i = 0; i < n; ++i) {
     proofs[i] = nullptr;
     lens[i] = 0;
@@ -858,6 +878,16 @@ int lmn_batch_prove(lmn_batch* b, uint32_t n, const lmn_table* const* tables, si
     lens[i] = b->out[i].size();
   }
   return first;
+}
+
+int lmn_batch_prove(lmn_batch* b, uint32_t n, const lmn_table* const* tables, size_t n_tables, const lmn_settings* settings,
+                    uint8_t** proofs, size_t* lens, int* rcs) {
+  return batch_prove(b, n, tables, n_tables, settings, nullptr, false, proofs, lens, rcs);
+}
+
+int lmn_batch_prove_prepared(lmn_batch* b, uint32_t n, const lmn_table* const* tables, size_t n_tables,
+                             const lmn_prepared* prepared, uint8_t** proofs, size_t* lens, int* rcs) {
+  return batch_prove(b, n, tables, n_tables, nullptr, prepared, true, proofs, lens, rcs);
 }
 
 uint64_t lmn_batch_counter(const lmn_batch* b, int which) {

@@ -32,6 +32,16 @@ int guard(lmn_ctx* ctx, F&& f) {
 thread_local std::string g_create_error;
 }  // namespace
 
+namespace lmn {
+const char prepared_tag = 0;
+std::shared_ptr<const Prepared> prepared_ref(const lmn_prepared* p) {
+  if (!p || !p->impl) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "null prepared settings");
+  if (p->made_by != &prepared_tag)
+    throw LmnError(LMN_ERR_INVALID_ARGUMENT, "prepared settings were made by another library (the main and the batch library each prepare their own)");
+  return p->impl;
+}
+}  // namespace lmn
+
 extern "C" {
 
 const char* lmn_strerror(int code) {
@@ -126,7 +136,8 @@ void lmn_ctx_destroy(lmn_ctx* ctx) {
 
 // ---- asynchronous form of lmn_prove: the reference's callers are single-threaded (SURVEY.md §8b "threading"); with
 // submit / wait one thread keeps a proof in flight on each of several contexts
-int lmn_prove_submit(lmn_ctx* ctx, const lmn_table* tables, size_t n_tables, const lmn_settings* settings) {
+static int prove_submit(lmn_ctx* ctx, const lmn_table* tables, size_t n_tables, const lmn_settings* settings,
+                        std::shared_ptr<const lmn::Prepared> prepared) {
   if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
   std::unique_lock<std::mutex> create_lock(ctx->async_mu);
   if (!ctx->async) {
@@ -140,9 +151,10 @@ int lmn_prove_submit(lmn_ctx* ctx, const lmn_table* tables, size_t n_tables, con
         const lmn_table* t = a->tables;
         const size_t n = a->n_tables;
         const lmn_settings* st = a->settings;
+        const std::shared_ptr<const lmn::Prepared> pp = a->prepared;
         lk.unlock();
         std::vector<uint8_t> bytes;
-        const int rc = guard(ctx, [&] { bytes = ctx->impl->prove(t, n, st); });
+        const int rc = guard(ctx, [&] { bytes = ctx->impl->prove(t, n, st, pp.get()); });
         lk.lock();
         a->rc = rc;
         a->proof.swap(bytes);
@@ -163,6 +175,7 @@ int lmn_prove_submit(lmn_ctx* ctx, const lmn_table* tables, size_t n_tables, con
       a->tables = tables;
       a->n_tables = n_tables;
       a->settings = settings;
+      a->prepared = std::move(prepared);
       a->state = lmn_async::SUBMITTED;
     }
   }
@@ -170,6 +183,10 @@ int lmn_prove_submit(lmn_ctx* ctx, const lmn_table* tables, size_t n_tables, con
                              "lmn_prove_submit: a submitted proof has not been collected with lmn_prove_wait");
   a->cv.notify_all();
   return LMN_OK;
+}
+
+int lmn_prove_submit(lmn_ctx* ctx, const lmn_table* tables, size_t n_tables, const lmn_settings* settings) {
+  return prove_submit(ctx, tables, n_tables, settings, nullptr);
 }
 
 int lmn_prove_wait(lmn_ctx* ctx, uint8_t** proof_bincode, size_t* proof_len) {
@@ -189,6 +206,7 @@ int lmn_prove_wait(lmn_ctx* ctx, uint8_t** proof_bincode, size_t* proof_len) {
   }
   a->cv.wait(lk, [&] { return a->state == lmn_async::DONE; });
   const int rc = a->rc;
+  a->prepared.reset();
   if (rc == LMN_OK) {
     uint8_t* p = (uint8_t*)malloc(a->proof.size() ? a->proof.size() : 1);
     if (!p) {
@@ -221,6 +239,70 @@ int lmn_prove(lmn_ctx* ctx, const lmn_table* tables, size_t n_tables, const lmn_
 }
 
 void lmn_free(void* p) { free(p); }
+
+// ---- settings prepared once (prover.h Prepared)
+int lmn_settings_prepare(int device, const lmn_config* cfg, const lmn_settings* settings, uint32_t lookups, lmn_prepared** out) {
+  if (!out) return LMN_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  lmn_config c;
+  lmn_default_config(&c);
+  if (cfg) c = *cfg;
+  lmn_ctx err{nullptr, {}};   // collects the error text only
+  const int rc = guard(&err, [&] {
+    auto impl = std::make_shared<const lmn::Prepared>(device, c, settings, lookups);
+    *out = new lmn_prepared{std::move(impl), &lmn::prepared_tag};
+  });
+  if (rc != LMN_OK) g_create_error = err.last_error;
+  return rc;
+}
+
+int lmn_prepared_root(const lmn_prepared* p, uint8_t root_out[32]) {
+  if (!p || !p->impl || !root_out) return LMN_ERR_INVALID_ARGUMENT;
+  memcpy(root_out, p->impl->tree.merkle.root.w, 32);
+  return LMN_OK;
+}
+
+uint32_t lmn_prepared_lookups(const lmn_prepared* p) { return p && p->impl ? p->impl->lookups : 0u; }
+
+void lmn_prepared_destroy(lmn_prepared* p) { delete p; }
+
+int lmn_prove_prepared(lmn_ctx* ctx, const lmn_table* tables, size_t n_tables, const lmn_prepared* prepared,
+                       uint8_t** proof_bincode, size_t* proof_len) {
+  if (!ctx || !proof_bincode || !proof_len) return LMN_ERR_INVALID_ARGUMENT;
+  *proof_bincode = nullptr;
+  *proof_len = 0;
+  return guard(ctx, [&] {
+    const std::shared_ptr<const lmn::Prepared> pp = lmn::prepared_ref(prepared);   // this proof's own reference
+    std::vector<uint8_t> bytes = ctx->impl->prove(tables, n_tables, nullptr, pp.get());
+    uint8_t* p = (uint8_t*)malloc(bytes.size());
+    if (!p) throw std::bad_alloc();
+    memcpy(p, bytes.data(), bytes.size());
+    *proof_bincode = p;
+    *proof_len = bytes.size();
+  });
+}
+
+#ifndef LMN_BATCH
+// batch objects exist in the batch library alone (batch.cpp defines this entry there): no handle this library could be given is one
+int lmn_batch_prove_prepared(lmn_batch*, uint32_t n, const lmn_table* const*, size_t, const lmn_prepared*, uint8_t** proofs,
+                             size_t* lens, int* rcs) {
+  for (uint32_t i = 0; i < n && n <= 256; ++i) {
+    if (proofs) proofs[i] = nullptr;
+    if (lens) lens[i] = 0;
+    if (rcs) rcs[i] = LMN_ERR_INVALID_ARGUMENT;
+  }
+  g_create_error = "lmn_batch_prove_prepared: lock-step batches are proved by libluminair_hip_batch.so";
+  return LMN_ERR_INVALID_ARGUMENT;
+}
+#endif
+
+int lmn_prove_submit_prepared(lmn_ctx* ctx, const lmn_table* tables, size_t n_tables, const lmn_prepared* prepared) {
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  std::shared_ptr<const lmn::Prepared> pp;
+  const int rc = guard(ctx, [&] { pp = lmn::prepared_ref(prepared); });
+  if (rc != LMN_OK) return rc;
+  return prove_submit(ctx, tables, n_tables, nullptr, std::move(pp));
+}
 
 int lmn_set_profiling(lmn_ctx* ctx, int enabled) {
   if (!ctx) return LMN_ERR_INVALID_ARGUMENT;

@@ -1,6 +1,7 @@
 // Shared by the extern "C" translation units (capi.cpp, level2.cpp): the opaque context and the exception guard.
 #pragma once
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <string>
@@ -18,6 +19,7 @@ struct lmn_async {
   const lmn_table* tables = nullptr;
   size_t n_tables = 0;
   const lmn_settings* settings = nullptr;
+  std::shared_ptr<const lmn::Prepared> prepared;   // lmn_prove_submit_prepared: held until lmn_prove_wait has returned the proof
   int rc = 0;
   std::vector<uint8_t> proof;
 };
@@ -32,7 +34,16 @@ struct lmn_ctx {
   std::mutex async_mu;   // guards the lazy creation of `async` (two first submits from different threads)
 };
 
+// lmn_settings_prepare's handle: the caller's reference to the shared object; proofs in flight hold their own
+struct lmn_prepared {
+  std::shared_ptr<const lmn::Prepared> impl;
+  const void* made_by;   // &lmn::prepared_tag of the library that made it (the main and the batch library are two)
+};
+
 namespace lmn {
+extern const char prepared_tag;
+// the shared object behind a caller's handle; refuses a null handle and one made by another library
+std::shared_ptr<const Prepared> prepared_ref(const lmn_prepared* p);
 template <typename F>
 int capi_guard(lmn_ctx* ctx, F&& f) {
   std::unique_lock<std::recursive_mutex> lock;

@@ -31,7 +31,7 @@ void* Arena::alloc_bytes(size_t bytes) {
 
 // ------------------------------------------------------------------------------------ context
 
-Context::Context(int device, const lmn_config& c) : cfg(c), device_(device) {
+Context::Context(int device, const lmn_config& c, size_t pin_bytes) : cfg(c), device_(device) {
   // validate before acquiring anything: a throwing constructor does not run the destructor
   if (cfg.log_blowup < 1 || cfg.log_blowup > 3) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "log_blowup must be 1, 2 or 3");
   if (cfg.n_queries == 0 || cfg.n_queries > 1024) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "bad n_queries");
@@ -73,7 +73,7 @@ Context::Context(int device, const lmn_config& c) : cfg(c), device_(device) {
   pow_device_min_bits_ = std::max(0, env_int("LMN_POW_DEVICE_MIN_BITS", POW_DEVICE_MIN_BITS));
   pow_window_log_ = std::max(POW_MIN_WINDOW_LOG, std::min(30, env_int("LMN_POW_WINDOW_LOG", POW_WINDOW_LOG)));
   event_log = new EventLog();
-  pin_cap_ = 32u << 20;
+  pin_cap_ = pin_bytes;
   pin_base_ = (char*)lmn_host_alloc_pinned(pin_cap_);
   {
     const uint32_t zero[2] = {0u, 0u};

@@ -34,6 +34,18 @@ constexpr int CHUNK_ROWS = 256;      // table rows per workgroup, aligned in the
 constexpr int CHUNK_MAX_COLS = 30;   // CHUNK_ROWS * (ncols | 1) * 4 B of LDS <= 31 744 B: two workgroups per CU and more
 void launch_rows_chunk(const uint32_t* chunk, uint64_t r0, uint64_t n, int ncols, uint32_t* cols, uint64_t stride,
                        const PadRow& pad, uint32_t* bad_word, lmn_stream_t s);
+// lmn_settings_prepare: the tree-0 columns of a prepared settings object, checked and completed where they lie.  Column
+// c < n_luts (a LUT column of n[c] words): *flag = c + 1 if it holds a word that is not a canonical M31 (any such column
+// may win).  range_check (may be null): row r of its range_n rows is set to r.
+constexpr int PREPARE_MAX_LUT_COLS = 6;
+struct PrepareCols {
+  const uint32_t* lut[PREPARE_MAX_LUT_COLS];
+  uint32_t n[PREPARE_MAX_LUT_COLS];
+  int n_luts;
+  uint32_t* range_check;
+  uint32_t range_n;
+};
+void launch_settings_prepare(const PrepareCols& cols, uint32_t* flag, lmn_stream_t s);
 
 // ---- a4: circle FFT passes.  data = ncols columns of 2^log_n words at stride col_stride.
 // dst may equal src (in place).  launch_fft zero-extends src (2^log_src words) to 2^log_n (LDE).
@@ -244,9 +256,12 @@ struct TwGen {
 void launch_twiddles(int bits, const TwGen& g, int coord, uint32_t* tw, uint32_t* itw, uint32_t* tw2, uint32_t* itw2,
                      lmn_stream_t s);
 
-// ---- gather: out[dst_off[e] + k] = arena[src_off[e] + k], k < len[e]
+// ---- gather: out[dst_off[e] + k] = base[src_off[e] + k], k < len[e]; base = the context's arena, or - for an entry whose
+// src_off carries GATHER_SHARED - the slab of the proof's prepared settings (lmn_settings_prepare), which lies outside
+// every arena
+constexpr uint64_t GATHER_SHARED = 1ull << 63;
 struct GatherEntry {
-  uint64_t src_off;  // word offset into arena
+  uint64_t src_off;  // word offset into the arena, or GATHER_SHARED | word offset into the shared slab
   uint32_t len;      // words
   uint32_t dst_off;  // word offset into out
 };
@@ -264,8 +279,8 @@ struct MerkleRecompute {
   int depth;
   uint32_t dst_off;
 };
-void launch_gather(const uint32_t* arena, const GatherEntry* entries, uint32_t n_entries, const MerkleRecompute* jobs,
-                   uint32_t n_jobs, uint32_t* out, lmn_stream_t s);
+void launch_gather(const uint32_t* arena, const uint32_t* shared, const GatherEntry* entries, uint32_t n_entries,
+                   const MerkleRecompute* jobs, uint32_t n_jobs, uint32_t* out, lmn_stream_t s);
 
 // ---- decommitment of a level-2 tree (lmn_tree_decommit): the tree's slab and the column handles are separate
 // allocations, so an entry names its source through a table of base pointers instead of an arena offset.  The plan holds

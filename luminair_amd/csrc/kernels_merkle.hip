@@ -1097,12 +1097,15 @@ void launch_fri_tail(DevChannel* ch, const FriTailLayer* layers, int n_layers, i
 // =============================================================================================
 // gather
 // =============================================================================================
-LMN_KERNEL k_gather(const uint32_t* __restrict__ arena, const GatherEntry* __restrict__ entries, uint32_t n,
-                    const MerkleRecompute* __restrict__ jobs, uint32_t n_jobs, uint32_t* __restrict__ out) {
+LMN_KERNEL k_gather(const uint32_t* __restrict__ arena, const uint32_t* __restrict__ shared,
+                    const GatherEntry* __restrict__ entries, uint32_t n, const MerkleRecompute* __restrict__ jobs,
+                    uint32_t n_jobs, uint32_t* __restrict__ out) {
   uint32_t e = blockIdx.x;
   if (e < n) {
     GatherEntry g = entries[e];
-    for (uint32_t k = threadIdx.x; k < g.len; k += blockDim.x) out[g.dst_off + k] = arena[g.src_off + k];
+    // (block-uniform: one entry per workgroup)
+    const uint32_t* src = (g.src_off & GATHER_SHARED) ? shared + (g.src_off & ~GATHER_SHARED) : arena + g.src_off;
+    for (uint32_t k = threadIdx.x; k < g.len; k += blockDim.x) out[g.dst_off + k] = src[k];
     return;
   }
   e -= n;
@@ -1137,10 +1140,10 @@ LMN_KERNEL k_gather(const uint32_t* __restrict__ arena, const GatherEntry* __res
   }
 }
 
-void launch_gather(const uint32_t* arena, const GatherEntry* entries, uint32_t n_entries, const MerkleRecompute* jobs,
-                   uint32_t n_jobs, uint32_t* out, lmn_stream_t s) {
+void launch_gather(const uint32_t* arena, const uint32_t* shared, const GatherEntry* entries, uint32_t n_entries,
+                   const MerkleRecompute* jobs, uint32_t n_jobs, uint32_t* out, lmn_stream_t s) {
   if (n_entries + n_jobs == 0) return;
-  LMN_LAUNCH(k_gather, dim3(n_entries + n_jobs), dim3(64), 0, s, arena, entries, n_entries, jobs, n_jobs, out);
+  LMN_LAUNCH(k_gather, dim3(n_entries + n_jobs), dim3(64), 0, s, arena, shared, entries, n_entries, jobs, n_jobs, out);
 }
 
 // =============================================================================================

@@ -984,6 +984,29 @@ void launch_trace_check_collect(const TcSet& set, uint32_t set_index, unsigned l
 }
 
 // =============================================================================================
+// lmn_settings_prepare: blockIdx.y selects the column.  A LUT column is only read - a word that is not a canonical M31
+// names its column in the object's flag word (plain stores; whichever offender stores last wins, any of them refuses the
+// settings) - and the 8-bit range-check column, the last y, is written: row r holds r (preprocessed.rs:289-296).
+// =============================================================================================
+LMN_KERNEL k_settings_prepare(PrepareCols p, uint32_t* __restrict__ flag) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int c = (int)blockIdx.y;
+  if (c < p.n_luts) {
+    if (i < p.n[c] && p.lut[c][i] >= P31) *flag = (uint32_t)c + 1u;
+  } else if (p.range_check && i < p.range_n) {
+    p.range_check[i] = (uint32_t)i;
+  }
+}
+void launch_settings_prepare(const PrepareCols& cols, uint32_t* flag, lmn_stream_t s) {
+  if (cols.n_luts < 0 || cols.n_luts > PREPARE_MAX_LUT_COLS) throw LmnError(-100, "settings_prepare: bad column count");
+  uint32_t longest = cols.range_check ? cols.range_n : 0u;
+  for (int c = 0; c < cols.n_luts; ++c) longest = std::max(longest, cols.n[c]);
+  const int ny = cols.n_luts + (cols.range_check ? 1 : 0);
+  if (ny == 0 || longest == 0) return;
+  LMN_LAUNCH(k_settings_prepare, dim3(cdiv(longest, TPB), ny), dim3(TPB), 0, s, cols, flag);
+}
+
+// =============================================================================================
 // level-2 column ops: bit reversal, FriOps::decompose, FieldOps::batch_inverse
 // =============================================================================================
 LMN_KERNEL k_bit_reverse(uint32_t* __restrict__ data, uint64_t col_stride, int log_n) {

@@ -237,10 +237,13 @@ void Context::run_decommit(ProofRun& r) {
     std::vector<std::pair<int, uint32_t>>& runs = hs.runs;  // (owner, len) in output order
     runs.clear();
     uint32_t out_words = 0;
+    const Prepared* const shared = r.prepared;
     auto add_refs = [&](const std::vector<Ref>& refs) {
       for (auto& r : refs) {
         if (r.job >= 0)
           hs.jobs[r.job].dst_off = out_words;   // unsharded proofs only: one output slot
+        else if (shared && shared->holds(r.ptr))   // the prepared tree 0 lies outside the arena: its own base
+          entries.push_back({GATHER_SHARED | shared->word_offset(r.ptr), r.len, out_words});
         else if (r.owner < 0 || r.owner == (int)shard_.rank)
           entries.push_back({arena_.word_offset(r.ptr), r.len, out_words});
         if (sh) runs.push_back({r.owner, r.len});
@@ -269,7 +272,7 @@ void Context::run_decommit(ProofRun& r) {
       uint32_t* d_o = sh ? arena_.alloc_words((size_t)slots * out_words) : (uint32_t*)result_block((size_t)out_words * 4);
       hm.mark("decommit planned");
       if (hm.on) fprintf(stderr, "[host] decommit: %zu runs gathered, %zu tree nodes recomputed\n", entries.size(), hs.jobs.size());
-      launch_gather(arena_.base_words(), d_e, (uint32_t)entries.size(), d_j, (uint32_t)hs.jobs.size(), d_o, stream_);
+      launch_gather(arena_.base_words(), shared ? shared->base_words() : nullptr, d_e, (uint32_t)entries.size(), d_j, (uint32_t)hs.jobs.size(), d_o, stream_);
       if (sh) gather_columns(d_o, 0, 1, out_words);
       gathered = sh ? (const uint32_t*)stage_download(d_o, (size_t)slots * out_words * 4) : d_o;
       lmn_sync(stream_);

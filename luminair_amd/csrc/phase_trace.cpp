@@ -17,6 +17,37 @@ void Context::run_preprocessed(ProofRun& r) {
     ci.log_size = ti.log_size;
     inst.push_back(ci);
   }
+  if (r.prepared) {
+    // Settings prepared once: tree 0 - columns, coefficients, LDE, Merkle layers, root - is the prepared object's, shared
+    // read-only with every other proof that uses it.  Nothing is checked on the host, uploaded, transformed or hashed, and
+    // the host does not wait: the root is known.
+    const Prepared& pp = *r.prepared;
+    uint32_t present = 0;
+    for (auto& ti : infos) {
+      if (ti.spec->kind == LMN_KIND_SIN_LOOKUP) present |= LMN_LOOKUP_SIN;
+      if (ti.spec->kind == LMN_KIND_EXP2_LOOKUP) present |= LMN_LOOKUP_EXP2;
+      if (ti.spec->kind == LMN_KIND_LOG2_LOOKUP) present |= LMN_LOOKUP_LOG2;
+      if (ti.spec->kind == LMN_KIND_RANGE_CHECK_LOOKUP) present |= LMN_LOOKUP_RANGE_CHECK;
+    }
+    if (present & ~pp.lookups)
+      throw LmnError(LMN_ERR_INVALID_ARGUMENT, "the pie holds a lookup table the settings were not prepared for");
+    if (pp.lookups & ~present)
+      throw LmnError(LMN_ERR_INVALID_ARGUMENT, "the settings were prepared for a lookup whose table is not in the pie");
+    for (auto& ci : inst)
+      for (int k = 0; k < ci.spec->n_pre; ++k)
+        if (ci.log_size != pp.log_of_pre[ci.spec->pre_id[k]])
+          throw LmnError(LMN_ERR_INVALID_ARGUMENT, ci.spec->pre_id[k] == PRE_RANGE_CHECK
+                                                       ? "RangeCheckLookup table must have exactly 256 rows"
+                                                       : "lookup table rows must match the LUT column size");
+    // (the same components of the same sizes: the same tree-0 order as the prepared object's)
+    const std::vector<int> logs = assign_preprocessed(inst);
+    if (logs.size() != pp.tree.cols.size()) throw LmnError(LMN_ERR_INTERNAL, "prepared settings: tree-0 layout differs");
+    tree0.cols = pp.tree.cols;
+    tree0.merkle = pp.tree.merkle;
+    pre_evals = pp.evals;
+    channel.mix_root(tree0.merkle.root);
+    return;
+  }
   {
     uint32_t present = 0;
     const lmn_lut* lut_of[3] = {nullptr, nullptr, nullptr};
@@ -76,6 +107,120 @@ void Context::run_preprocessed(ProofRun& r) {
     }
   }
   channel.mix_root(tree0.merkle.root);
+}
+
+// ---- lmn_settings_prepare: PHASE 0 of every proof of one circuit, done once.  Runs on the private context of `out`
+// (own stream, own arena: reserved here and never reset or grown, so the object's pointers stay valid for its lifetime).
+Prepared::Prepared(int device_, const lmn_config& cfg, const lmn_settings* settings, uint32_t lookups_) {
+  for (int& l : log_of_pre) l = -1;
+  ctx_ = new Context(device_, cfg, 1u << 20);
+  try {
+    ctx_->build_prepared(*this, settings, lookups_);
+  } catch (...) {
+    delete ctx_;
+    ctx_ = nullptr;
+    throw;
+  }
+}
+Prepared::~Prepared() { delete ctx_; }
+
+void Context::build_prepared(Prepared& out, const lmn_settings* settings, uint32_t lookups) {
+#ifndef LMN_EMU
+  LMN_HIP_CHECK(hipSetDevice(device_));
+#endif
+  const int lb = (int)cfg.log_blowup;
+  out.device = device_;
+  out.lookups = lookups;
+  out.log_blowup = cfg.log_blowup;
+  if (lookups & ~(LMN_LOOKUP_SIN | LMN_LOOKUP_EXP2 | LMN_LOOKUP_LOG2 | LMN_LOOKUP_RANGE_CHECK))
+    throw LmnError(LMN_ERR_INVALID_ARGUMENT, "lmn_settings_prepare: unknown bits in `lookups`");
+  const lmn_lut* lut_of[3] = {nullptr, nullptr, nullptr};
+  if (settings && settings->n_luts) {
+    if (!settings->luts) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "null luts pointer");
+    for (uint32_t i = 0; i < settings->n_luts; ++i) {
+      const lmn_lut& l = settings->luts[i];
+      if (l.kind > LMN_LUT_LOG2 || !l.col0 || !l.col1 || lut_of[l.kind])
+        throw LmnError(LMN_ERR_INVALID_ARGUMENT, "bad or duplicate LUT in settings (unknown kind, null column, or a kind given twice)");
+      // the bounds run_setup puts on the lookup table that will have the LUT's size
+      if (l.log_size < 4 || l.log_size > 26 || (int)l.log_size + lb + 2 > MAX_LOG - 2)
+        throw LmnError(LMN_ERR_INVALID_ARGUMENT, "LUT log_size " + std::to_string(l.log_size) +
+                                                     " is outside what the prover takes (at least 4, and at most what a trace table may have)");
+      lut_of[l.kind] = &l;
+    }
+  }
+  static const int kLookupKind[3] = {LMN_KIND_SIN_LOOKUP, LMN_KIND_EXP2_LOOKUP, LMN_KIND_LOG2_LOOKUP};
+  static const char* const kLookupName[3] = {"sin", "exp2", "log2"};
+  std::vector<Instance> inst;   // the lookup components of the pies to come, in gen_trace order (ascending kind)
+  for (int k = 0; k < 3; ++k) {
+    if (!(lookups & (1u << k))) continue;
+    if (!lut_of[k])
+      throw LmnError(LMN_ERR_INVALID_ARGUMENT, std::string("lookups announce ") + kLookupName[k] + " but the settings carry no LUT columns for it");
+    Instance ci{};
+    ci.spec = component_spec(kLookupKind[k]);
+    ci.log_size = (int)lut_of[k]->log_size;
+    inst.push_back(ci);
+  }
+  if (lookups & LMN_LOOKUP_RANGE_CHECK) {
+    Instance ci{};
+    ci.spec = component_spec(LMN_KIND_RANGE_CHECK_LOOKUP);
+    ci.log_size = 8;
+    inst.push_back(ci);
+  }
+  const std::vector<int> logs = assign_preprocessed(inst);
+  if (logs.empty()) {
+    build_merkle(out.tree.merkle, {});   // root = blake2s("")
+    return;
+  }
+  size_t words = 1u << 18;   // the flag word, alignment, a scattered level's pointer table
+  for (int lg : logs) words += (2ull << lg) + (1ull << (lg + lb));           // evals + coeffs + lde
+  words += 16ull << (logs[0] + lb);                                          // every Merkle layer: 2 x 2^max_log nodes of 8 words
+  ensure_twiddles(logs[0] + lb);
+  arena_.reserve(words * 4);
+  arena_.reset();
+  pin_off_ = 0;
+  out.base_ = arena_.base_words();
+  out.bytes_ = arena_.capacity();
+  uint32_t* flag = arena_.alloc_words(1);
+  lmn_memset(flag, 0, 4, stream_);
+  out.tree.cols.resize(logs.size());
+  out.evals.assign(logs.size(), nullptr);
+  PrepareCols pc{};
+  int pc_col[PREPARE_MAX_LUT_COLS] = {0};   // PRE_* id of each LUT column handed to the check
+  for (auto& ci : inst)
+    for (int k = 0; k < ci.spec->n_pre; ++k) {
+      const uint64_t n = 1ull << ci.log_size;
+      const int id = ci.spec->pre_id[k];
+      uint32_t* evals = arena_.alloc_words(n);
+      if (id == PRE_RANGE_CHECK) {
+        pc.range_check = evals;
+        pc.range_n = (uint32_t)n;
+      } else {
+        const lmn_lut* l = lut_of[id / 2];
+        lmn_h2d(evals, (id & 1) ? l->col1 : l->col0, n * 4, stream_);
+        pc_col[pc.n_luts] = id;
+        pc.lut[pc.n_luts] = evals;
+        pc.n[pc.n_luts++] = (uint32_t)n;
+      }
+      out.log_of_pre[id] = ci.log_size;
+      out.evals[ci.pre_idx[k]] = evals;
+    }
+  launch_settings_prepare(pc, flag, stream_);
+  for (auto& ci : inst)
+    for (int k = 0; k < ci.spec->n_pre; ++k) {
+      const uint64_t n = 1ull << ci.log_size;
+      uint32_t* coeffs = arena_.alloc_words(n);
+      launch_ifft(coeffs, n, out.evals[ci.pre_idx[k]], n, 1, ci.log_size, itw(ci.log_size), stream_);
+      out.tree.cols[ci.pre_idx[k]] = {ci.log_size, coeffs, nullptr};
+    }
+  lde_and_merkle(out.tree);
+  const uint32_t* h_flag = (const uint32_t*)stage_download(flag, 4);
+  lmn_sync(stream_);   // the one wait: later proofs, on whatever stream, start after it
+  out.tree.merkle.finish_root();
+  if (*h_flag) {
+    const int id = pc_col[std::min<uint32_t>(*h_flag, (uint32_t)pc.n_luts) - 1];
+    throw LmnError(LMN_ERR_INVALID_ARGUMENT, std::string("LUT value is not a canonical M31 (") + kLookupName[id / 2] + "_lut_" +
+                                                 std::to_string(id & 1) + ")");
+  }
 }
 
 void Context::run_main_trace(ProofRun& r) {

@@ -27,11 +27,22 @@ void Context::prepare_for(const lmn_table* tables, size_t n_tables) {
 
 // ------------------------------------------------------------------------------------ prove
 // The phases of one proof, in transcript order; each is a Context member in the file named.
-std::vector<uint8_t> Context::prove(const lmn_table* tables, size_t n_tables, const lmn_settings* settings) {
+std::vector<uint8_t> Context::prove(const lmn_table* tables, size_t n_tables, const lmn_settings* settings,
+                                    const Prepared* prepared) {
 #ifndef LMN_EMU
   LMN_HIP_CHECK(hipSetDevice(device_));
 #endif
   if (!tables || n_tables == 0) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "no trace tables");
+  if (prepared) {   // refused before anything is launched, copied or exchanged
+    if (shard_.active)
+      throw LmnError(LMN_ERR_INVALID_ARGUMENT, "prepared settings cannot be used on a sharded context (tree 0 is split into row blocks there)");
+    if (prepared->device != device_)
+      throw LmnError(LMN_ERR_INVALID_ARGUMENT, "prepared settings live on device " + std::to_string(prepared->device) +
+                                                   ", this context on device " + std::to_string(device_));
+    if (prepared->log_blowup != cfg.log_blowup)
+      throw LmnError(LMN_ERR_INVALID_ARGUMENT, "prepared settings were extended by log_blowup " + std::to_string(prepared->log_blowup) +
+                                                   ", this context proves with log_blowup " + std::to_string(cfg.log_blowup));
+  }
   struct InFlight {
     InFlight() { g_proofs_in_flight.fetch_add(1, std::memory_order_relaxed); }
     ~InFlight() { g_proofs_in_flight.fetch_sub(1, std::memory_order_relaxed); }
@@ -59,6 +70,7 @@ std::vector<uint8_t> Context::prove(const lmn_table* tables, size_t n_tables, co
   r.tables = tables;
   r.n_tables = n_tables;
   r.settings = settings;
+  r.prepared = prepared;
   r.lb = (int)cfg.log_blowup;
   r.n_slots = claim_slots(cfg.protocol_variant);
   r.log = g_log(this);
@@ -139,7 +151,7 @@ void Context::run_setup(ProofRun& r) {
     uint64_t cells = (uint64_t)(sp->n_cols + 4 * sp->n_rel) << ls;
     words += cells * 2 + row_split(cells << lb);               // evals + coeffs + lde (this rank's row block)
     if (!infos.back().on_device && !infos.back().cols_on_device) words += tb.n_rows * sp->n_cols;  // staging
-    words += (uint64_t)sp->n_pre * ((2ull << ls) + row_split(2ull << ls));  // preprocessed columns: evals + coeffs + lde
+    if (!r.prepared) words += (uint64_t)sp->n_pre * ((2ull << ls) + row_split(2ull << ls));  // preprocessed columns: evals + coeffs + lde
     words += (4ull << ls) * 2;                                 // logup temps
     words += (4ull << (ls + 1)) * 3;                           // per-size composition scratch
     if (lb != 1) words += (uint64_t)(sp->n_cols + 4 * sp->n_rel + sp->n_pre) << (ls + 1);   // columns on the constraint domain

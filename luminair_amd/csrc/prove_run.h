@@ -34,6 +34,7 @@ struct ProofRun {
   const lmn_table* tables = nullptr;
   size_t n_tables = 0;
   const lmn_settings* settings = nullptr;
+  const Prepared* prepared = nullptr;   // settings prepared once: tree 0 is read from it (run_preprocessed, run_decommit)
   // set-up
   int lb = 0, n_slots = 0, comp_log = 0;
   HostMarks hm;

@@ -205,15 +205,49 @@ class RowSink {
 // otherwise); the proof stream is made to wait for the sink's finish event - the host does not wait
 void rows_sink_attach(const lmn_table& tb, int device, lmn_stream_t proof_stream);
 
+// Settings prepared once (lmn_settings_prepare): everything about tree 0 that does not depend on the pie - the LUT and
+// range-check columns on their trace domain, their coefficients, their LDE, every Merkle layer and the root - in device
+// memory of its own, immutable after construction and read by any number of proofs at once.  The memory is the arena of
+// a private context that exists for this object alone (own stream; reserved once, never reset, so nothing moves).
+class Context;
+class Prepared {
+ public:
+  Prepared(int device, const lmn_config& cfg, const lmn_settings* settings, uint32_t lookups);
+  ~Prepared();
+  Prepared(const Prepared&) = delete;
+  Prepared& operator=(const Prepared&) = delete;
+  int device = 0;
+  uint32_t lookups = 0;                // LMN_LOOKUP_* bits of the lookup components its pies contain
+  uint32_t log_blowup = 0;
+  int log_of_pre[N_PRE_IDS];           // log size of each preprocessed column present, -1 otherwise
+  DevTree tree;                        // columns in tree-0 order (assign_preprocessed); no cut levels: every layer is in memory
+  std::vector<uint32_t*> evals;        // the columns on their trace domain, tree-0 order
+  // the one slab everything above lies in (k_gather's second base)
+  const uint32_t* base_words() const { return base_; }
+  bool holds(const void* p) const { return (const char*)p >= (const char*)base_ && (const char*)p < (const char*)base_ + bytes_; }
+  uint64_t word_offset(const void* p) const { return (uint64_t)((const char*)p - (const char*)base_) / 4; }
+
+ private:
+  friend class Context;
+  Context* ctx_ = nullptr;
+  const uint32_t* base_ = nullptr;
+  size_t bytes_ = 0;
+};
+
 struct StageTimer;
 
 struct ProofRun;   // state of one proof across the phases of Context::prove (prove_run.h)
 
 class Context {
  public:
-  Context(int device, const lmn_config& cfg);
+  // pin_bytes: page-locked staging of the context (a proving context stages plans, tables and results of megabytes)
+  Context(int device, const lmn_config& cfg, size_t pin_bytes = 32u << 20);
   ~Context();
-  std::vector<uint8_t> prove(const lmn_table* tables, size_t n_tables, const lmn_settings* settings);
+  // prepared != nullptr (lmn_prove_prepared): tree 0 is the prepared object's, `settings` is not read
+  std::vector<uint8_t> prove(const lmn_table* tables, size_t n_tables, const lmn_settings* settings,
+                             const Prepared* prepared = nullptr);
+  // lmn_settings_prepare, on the private context of `out`: checks, places, transforms and commits tree 0 once, then waits
+  void build_prepared(Prepared& out, const lmn_settings* settings, uint32_t lookups);
 #ifdef LMN_BATCH
   // lock-step batches (batch.h): every member context issues its work on the group's one stream
   void adopt_stream(lmn_stream_t s);

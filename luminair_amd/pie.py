@@ -152,6 +152,24 @@ class CircuitSettings:
                     out[name] = lib.lut_from_ranges(name, lk.layout.ranges, lk.layout.log_size)
         return out
 
+    def prepare(self, device: int = 0, config=None, library=None, lookups: Optional[int] = None):
+        """`backend.PreparedSettings` of these settings: tree 0 of every proof of the circuit, built once on the device.
+        Pass it as `prepared=` to `Prover.prove` / `ProverPool.prove_many` (or, made with the batch library, to
+        `BatchProver.prove_batch` / `BatchPool.prove_many`).  config: the provers' `LmnConfig` (its log_blowup must be
+        theirs); lookups: LOOKUP_* bits of the lookup components the pies contain - default: the LUTs described here, plus
+        the range check when `range_check` is set."""
+        from . import backend
+        lib = library or backend.default_library()
+        luts = self.lut_columns(lib)
+        if lookups is None:
+            lookups = backend.LOOKUP_RANGE_CHECK if self.range_check is not None or "range_check" in (self.lookups or {}) else 0
+            for name in luts:
+                lookups |= backend.LOOKUP_BITS[name]
+        try:
+            return backend.PreparedSettings(device, config, luts, lookups, lib)
+        except backend.LuminairBackendError as e:
+            raise LuminairError("InvalidArgument" if e.code == backend.ERR_INVALID_ARGUMENT else "Internal", str(e), e.code) from e
+
     # ---- bincode 1.3 (fixed-width little-endian ints, u64 lengths, Option = one tag byte): numerair's `Fixed` is a
     # newtype over i64 and serialises as that i64; `AtomicU32` as u32; `[u32; 1]` (serde_as) without a length
     def to_bincode(self, kat_era: bool = False) -> bytes:

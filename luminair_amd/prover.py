@@ -37,11 +37,14 @@ class Prover:
         except backend.LuminairBackendError as e:
             raise LuminairError(_ERR_VARIANT.get(e.code, "Internal"), str(e), e.code) from e
 
-    def prove(self, pie: LuminairPie, settings: Optional[CircuitSettings] = None) -> LuminairProof:
+    def prove(self, pie: LuminairPie, settings: Optional[CircuitSettings] = None,
+              prepared: Optional[backend.PreparedSettings] = None) -> LuminairProof:
+        """prepared: what `settings.prepare(...)` returned, in place of `settings` - the same proof bytes without the
+        per-proof work on tree 0."""
         tables = [(int(t.kind), t.rows, t.n_rows) for t in pie.trace_tables]
-        luts = settings.lut_columns(self.ctx.lib) if settings is not None else None
+        luts = settings.lut_columns(self.ctx.lib) if settings is not None and prepared is None else None
         try:
-            return LuminairProof(self.ctx.prove_tables(tables, luts))
+            return LuminairProof(self.ctx.prove_tables(tables, luts, prepared))
         except backend.LuminairBackendError as e:
             raise LuminairError(_ERR_VARIANT.get(e.code, "Internal"), str(e), e.code) from e
 
@@ -67,7 +70,8 @@ class ProverPool:
     def __init__(self, device: int = 0, n: int = 12, protocol_variant: int = backend.VARIANT_KAT, library=None, **pcs):
         self.provers = [Prover(device, protocol_variant, library, **pcs) for _ in range(max(1, n))]
 
-    def prove_many(self, pies, settings: Optional[CircuitSettings] = None):
+    def prove_many(self, pies, settings: Optional[CircuitSettings] = None,
+                   prepared: Optional[backend.PreparedSettings] = None):
         out, in_flight = [], []          # in_flight: context indices in submit order
         n = len(self.provers)
 
@@ -83,9 +87,9 @@ class ProverPool:
                 if len(in_flight) == n:
                     out.append(collect(in_flight.pop(0)))        # context k holds the oldest submission
                 tables = [(int(t.kind), t.rows, t.n_rows) for t in pie.trace_tables]
-                luts = settings.lut_columns(self.provers[k].ctx.lib) if settings is not None else None
+                luts = settings.lut_columns(self.provers[k].ctx.lib) if settings is not None and prepared is None else None
                 try:
-                    self.provers[k].ctx.prove_submit(tables, luts)
+                    self.provers[k].ctx.prove_submit(tables, luts, prepared)
                 except backend.LuminairBackendError as e:
                     raise LuminairError(_ERR_VARIANT.get(e.code, "Internal"), str(e), e.code) from e
                 in_flight.append(k)
