@@ -16,6 +16,17 @@ did not write == `plan()`'s; every output word < P; the per-layer form codes == 
 LMN_NO_FOLD_FUSION=1 and LMN_NO_JOIN_FUSION=1 give identical roots, alphas and layer values (and the forms `plan()` names for
 those switches) - every case, the large GPU ones included: the reference is computed once per case.  `plan()` restates phase_fri.cpp's conditions and the `sub` / `below` thresholds of commit.cpp.
 
+The transcript's value edges (REDRAW_CASES): start digests found by tools/find_redraw.cpp (tests/golden/transcript_redraw_seeds.json,
+pinned against hashlib by tests/test_transcript_redraw_seeds.py) at which the draw behind a chosen tree goes round its loop a second
+time (a word >= 2P; the exact words 0xFFFFFFFE and 0xFFFFFFFF, among words 0..3 and among words 4..7, which `draw_felt` never uses),
+or accepts 0xFFFFFFFD (-> P - 1) or a word P (-> 0).  Random columns put the event at tree 0, whose root no alpha reaches - the
+redrawn alpha is then used by every fold behind it; all-zero and constant columns fold to constants whatever alpha is, so every
+root is known beforehand and the event can sit at an inner tree or at the first, a middle or the last layer of k_fri_tail - the
+alphas are asserted directly and the layers behind the redraw show that the digest was carried on.  The reference runs on a
+counting channel and must have met the event at that tree and nowhere else before the library is asked
+(`check_redraw_reference`): a seed that a protocol change has made stale fails, it does not pass.  Two redraws in a row
+(about 2^56 trials) are out of reach.
+
 Two things the loop's construction rules out, so no case can hold them:
   * a tail of 10 layers: the tail starts at 2^10 at most and ends above the last layer of 2^(log_last_layer + log_blowup)
     values, and a context refuses log_blowup < 1 - 9 layers (2^10 .. 2^2) is the longest tail there is (TAIL_MAX_LAYERS;
@@ -67,6 +78,7 @@ class Plan:
     layer_forms: list
     absent: list            # per tree: the levels the loop does not write
     n_tail: int
+    first_launches: list = None     # the first tree's Merkle launches, leaves first: (the level a launch reads, levels it hashes above)
 
     def forms(self):
         out = {self.first_form}
@@ -75,8 +87,10 @@ class Plan:
         return out
 
 
-def tree_absent(ncols, max_log, fold, sub_env, below_min_log):
-    """commit.cpp build_merkle_levels inside prove (with cuts) -> (levels not written, leaf level hashed from above)"""
+def tree_absent(ncols, max_log, fold, sub_env, below_min_log, launches=None):
+    """commit.cpp build_merkle_levels inside prove (with cuts) -> (levels not written, leaf level hashed from above);
+    `launches`: a list that receives (the level a launch reads, the levels it hashes above that one), leaves first - a launch
+    that reads a level <= 10 is k_merkle_small"""
     absent, below, prev, level = set(), False, False, max_log
     below_min_log = max(12, below_min_log)
     while level >= 0:
@@ -98,6 +112,8 @@ def tree_absent(ncols, max_log, fold, sub_env, below_min_log):
                 sub = min(sub_env, nfused, MERKLE_MAX_SUB)
             nfused = min(nfused, sub + 8)
             absent |= {level - l for l in range(sub)}
+        if launches is not None:
+            launches.append((level, nfused))
         prev, level = True, level - nfused - 1
     return absent, below
 
@@ -109,7 +125,8 @@ def plan(logs, last_log, fuse_folds=True, fuse_joins=True, sub_env=None, below_m
     tail_log = min(10, ls0 - 1, logs[-1] - 1)
     if tail_log <= last_log:
         tail_log = -1
-    first_absent, below = tree_absent({lg: 4 for lg in logs}, ls0, False, sub_env, below_min_log)
+    first_launches = []
+    first_absent, below = tree_absent({lg: 4 for lg in logs}, ls0, False, sub_env, below_min_log, first_launches)
     absent, forms, n_tail = [first_absent], [], 0
     layer_log, qi = ls0 - 1, 1
     pend, pend_join = fuse_folds, False
@@ -147,7 +164,7 @@ def plan(logs, last_log, fuse_folds=True, fuse_joins=True, sub_env=None, below_m
         produced = MATERIALISED
     forms.append(produced)
     assert qi == n
-    return Plan(FIRST_TREE_BELOW if below else FIRST_TREE, [ls0 - 1 - i for i in range(len(forms))], forms, absent, n_tail)
+    return Plan(FIRST_TREE_BELOW if below else FIRST_TREE, [ls0 - 1 - i for i in range(len(forms))], forms, absent, n_tail, first_launches)
 
 
 # ----------------------------------------------------------------------------- reference
@@ -193,10 +210,11 @@ class Ref:
     layers: list = field(default_factory=list)    # (4, 2^log) uint64, the last layer last
 
 
-def ref_commit(cols, digest, variant, last_log):
-    """oracle/prover.py fri_commit_phase, on (4, 2^log) columns of strictly decreasing sizes, without the degree check"""
+def ref_commit(cols, digest, variant, last_log, channel=None):
+    """oracle/prover.py fri_commit_phase, on (4, 2^log) columns of strictly decreasing sizes, without the degree check;
+    `channel`: the (counting) channel to run it on"""
     from oracle.channel import Blake2sChannel
-    ch = Blake2sChannel(variant)
+    ch = Blake2sChannel(variant) if channel is None else channel
     ch.digest = digest
     R = Ref()
 
@@ -230,6 +248,8 @@ def ref_commit(cols, digest, variant, last_log):
 def column(cls, log, rng):
     """(4, 2^log) uint32 in a value class; sum0: pairs (a, P - a), f0 = 0; equal: pairs (a, a), f1 = 0"""
     n = 1 << log
+    if cls == "const":          # one non-zero QM31 everywhere: every fold of it is constant whatever alpha is
+        return np.repeat(rng.integers(1, P, size=(4, 1), dtype=U64), n, axis=1).astype(U32)
     if cls in ("sum0", "equal"):
         a = nc.words("random", (4, n // 2), rng)
         c = np.empty((4, n), dtype=U64)
@@ -249,6 +269,8 @@ class Case:
     sub: int = None         # LMN_MERKLE_SUB
     below: int = None       # LMN_MERKLE_BELOW_MIN_LOG
     cls: object = "random"  # a value class for every column, or one per column
+    search: str = None      # REDRAW_CASES: the search (REDRAW_SEARCHES) whose record gives the start digest ...
+    layer: int = None       # ... and the tree at which the event happens
 
     @property
     def last_log(self):
@@ -314,6 +336,109 @@ CLASS_CASES = [_c("%s fused join front tail" % cls, [13, 12], cls=cls) for cls i
               [_c("%s tail only" % cls, [9], cls=cls) for cls in VALUE_CLASSES] + \
               [_c("%s small joins" % cls, [8, 7, 5], cls=cls) for cls in ("zero", "sum0", "equal", "edge")] + HALF_ZERO_CASES
 CASES = SHAPE_CASES + CLASS_CASES
+
+# The transcript's value edges (tests/transcript_seeds.py): one search of tools/find_redraw.cpp each, one record - a start
+# digest - per listed tree.  Random columns: the event at tree 0, whose root no alpha reaches; the redrawn alpha is used by
+# every fold behind it.  "zero" / "const" columns fold to a constant whatever alpha is, so every root is fixed and the event
+# can be placed at any tree: [11] = the first tree, then a tail of 9 (trees 1 .. 9); [12] = the first tree, layer 2^11 as an
+# inner tree of its own (tree 1), then the tail behind its front fold (tree 2 = its first layer).  value: the exact word;
+# lo, hi: the word indices the event may lie at (a redraw: no rejected word outside them).
+def _s(name, logs, event, layers=(0,), value="any", lo=0, hi=7, **kw):
+    return dict(name=name, logs=tuple(logs), event=event, layers=tuple(layers), value=value, lo=lo, hi=hi, u32=kw.pop("u32", False),
+                cls=kw.pop("cls", "random"))
+
+
+REDRAW_SEARCHES = [
+    _s("redraw tree 0 small FFFFFFFE in words 0 to 3", [10], "redraw", value="FFFFFFFE", hi=3),
+    _s("redraw tree 0 small FFFFFFFF in words 4 to 7 u32", [10], "redraw", value="FFFFFFFF", lo=4, u32=True),
+    _s("redraw tree 0 large FFFFFFFF in words 0 to 3", [12], "redraw", value="FFFFFFFF", hi=3),
+    _s("redraw tree 0 large FFFFFFFE in words 4 to 7 u32", [12], "redraw", value="FFFFFFFE", lo=4, u32=True),
+    _s("accept edge tree 0 small", [10], "accept-edge", hi=3),
+    _s("accept edge tree 0 large u32", [12], "accept-edge", hi=3, u32=True),
+    _s("reduce edge tree 0 large", [12], "reduce-edge", hi=3),
+    _s("reduce edge tree 0 small u32", [10], "reduce-edge", hi=3, u32=True),
+    _s("redraw zero tail", [11], "redraw", layers=(1, 5, 9), cls="zero"),
+    _s("redraw const tail u32", [11], "redraw", layers=(1, 5, 9), cls="const", u32=True),
+    _s("redraw const inner and front tail", [12], "redraw", layers=(1, 2), cls="const"),
+    _s("redraw zero inner and front tail u32", [12], "redraw", layers=(1, 2), cls="zero", u32=True),
+]
+REDRAW_CASES = [_c("%s tree %d" % (s["name"], t), s["logs"], u32=s["u32"], cls=s["cls"], search=s["name"], layer=t)
+                for s in REDRAW_SEARCHES for t in s["layers"]]
+SEARCH_OF = {s["name"]: s for s in REDRAW_SEARCHES}
+DRAW_SITES = {"k_merkle_small, the whole first tree", "k_merkle_small, the top of the first tree", "k_merkle_small, inner tree", "k_fri_tail, first layer",
+              "k_fri_tail, first layer behind the front fold", "k_fri_tail, middle layer", "k_fri_tail, last layer"}
+
+
+def draw_site(case, fuse_folds=True):
+    """which statement of the draw loop the case's event reaches, from plan() alone"""
+    pl, t = case.plan(fuse_folds), case.layer
+    if t == 0:
+        # the launch that reaches the root mixes it and draws: k_merkle_small if it reads a level <= 10 and hashes up to level
+        # 0 (anything else would leave the root to the single-lane k_chan_mix_root_draw)
+        level, above = pl.first_launches[-1]
+        assert pl.first_form == FIRST_TREE and level <= 10 and level - above == 0, (case.name, pl.first_launches)
+        if len(pl.first_launches) == 1:
+            assert level == case.logs[0], (case.name, pl.first_launches)
+            return "k_merkle_small, the whole first tree"
+        assert pl.first_launches[0][0] == case.logs[0] > 10, (case.name, pl.first_launches)
+        return "k_merkle_small, the top of the first tree"      # behind the fused launches of the levels above 10
+    f = pl.layer_forms[t - 1]
+    if f & TREE_OWN:
+        return "k_merkle_small, inner tree"
+    assert f & TREE_IN_TAIL, (case.name, hex(f))
+    k = t - 1 - next(i for i, g in enumerate(pl.layer_forms) if g & TREE_IN_TAIL)
+    if k == 0:
+        return "k_fri_tail, first layer" + (" behind the front fold" if f & 0xff == TAIL_FRONT else "")
+    return "k_fri_tail, %s layer" % ("last" if k == pl.n_tail - 1 else "middle")
+
+
+def check_redraw_cases_reach_every_draw(cases):
+    """Between them the redraws reach every statement of the draw loop an unsharded context can, in both encodings per kernel.
+    Every tree's top is hashed by k_merkle_small (step kind 0: chan_mix_root_draw_block) or lies in k_fri_tail (the same
+    function, the digest carried in registers).  The single-lane k_chan_mix_root_draw is out of reach here: commit.cpp
+    launches it only when no k_merkle_small launch reaches the root with the channel - the root level itself scattered over
+    more runs of columns than a launch takes (columns of one value: no FRI column is), or the tree of a sharded context with
+    one shard, whose root is hashed before the gather.  `lmn_col_fri_commit` refuses a sharded context."""
+    redraws = [c for c in cases if SEARCH_OF[c.search]["event"] == "redraw"]
+    sites = {draw_site(c) for c in redraws}
+    assert sites == DRAW_SITES, sorted(DRAW_SITES ^ sites)
+    for kernel in ("k_merkle_small", "k_fri_tail"):
+        assert {c.u32 for c in redraws if draw_site(c).startswith(kernel)} == {False, True}, kernel
+    # LMN_NO_FOLD_FUSION=1 takes the front fold out of the tail: the same seeds meet the tail behind a fold launch
+    assert "k_fri_tail, first layer" in {draw_site(c, False) for c in redraws if "front" in draw_site(c)}
+    assert {SEARCH_OF[c.search]["event"] for c in cases} == {"redraw", "accept-edge", "reduce-edge"}
+    values = {(SEARCH_OF[c.search]["value"], SEARCH_OF[c.search]["lo"] >= 4) for c in redraws}
+    assert {("FFFFFFFE", False), ("FFFFFFFF", False), ("FFFFFFFE", True), ("FFFFFFFF", True)} <= values, values
+
+
+def case_columns(case, seed=0):
+    """-> (columns, the generator behind them): a redraw case's columns are its search's"""
+    rng = np.random.default_rng(seed + zlib.crc32((case.search or case.name).encode()))
+    classes = [case.cls] * len(case.logs) if isinstance(case.cls, str) else list(case.cls)
+    assert len(classes) == len(case.logs), case.name
+    return [column(cls, lg, rng) for cls, lg in zip(classes, case.logs)], classes, rng
+
+
+def check_redraw_reference(case, rec, chan, ref):
+    """the reference met the event where the record says, and nowhere else, before the library is asked: a seed that a
+    protocol change has made stale fails here"""
+    import transcript_seeds as ts
+    s, n = SEARCH_OF[case.search], len(ref.roots)
+    given = n if case.cls in ("zero", "const") else 1
+    assert [r.hex() for r in ref.roots[:given]] == rec["roots"], "%s: the searcher was given other roots than the reference's" % case.name
+    assert rec["event"] == s["event"] and rec["encoding"] == (37 if case.u32 else 64) and rec["layer"] == case.layer, case.name
+    assert s["lo"] <= rec["word_index"] <= s["hi"] and s["value"] in ("any", rec["word_value"][2:]), (case.name, rec)
+    ts.check_chain(rec, chan, n, case.name)
+    a = ref.alphas[case.layer]
+    if rec["event"] == "accept-edge":
+        assert a[rec["word_index"]] == P - 1, (case.name, a)
+    elif rec["event"] == "reduce-edge":
+        assert a[rec["word_index"]] == 0, (case.name, a)
+    else:   # the alpha is that of the second draw
+        w = ts.draw_words(chan.digest_after[case.layer], 1, rec["encoding"])
+        assert a == tuple(x % P for x in w[:4]) and a != tuple(x % P for x in ts.draw_words(chan.digest_after[case.layer], 0, rec["encoding"])[:4])
+    if case.cls == "const":
+        assert all(l.any() and (l == l[:, :1]).all() for l in ref.layers), case.name
 
 
 def check_matrix_reaches_every_form(cases):
@@ -415,13 +540,17 @@ def compare(case, got, ref, pl, tag):
 def check_case(ctxs, case, seed=0):
     """-> the reference (for callers that assert more)"""
     ctx = ctxs.get(case)
-    rng = np.random.default_rng(seed + zlib.crc32(case.name.encode()))
-    classes = [case.cls] * len(case.logs) if isinstance(case.cls, str) else list(case.cls)
-    assert len(classes) == len(case.logs), case.name
-    cols = [column(cls, lg, rng) for cls, lg in zip(classes, case.logs)]
+    cols, classes, rng = case_columns(case, seed)
     digest = bytes(int(v) for v in rng.integers(0, 256, size=32))
     from oracle.channel import ProtocolVariant
-    ref = ref_commit(cols, digest, ProtocolVariant.DRAW_CTR_U32 if case.u32 else ProtocolVariant.KAT, case.last_log)
+    variant, chan = ProtocolVariant.DRAW_CTR_U32 if case.u32 else ProtocolVariant.KAT, None
+    if case.search:
+        import transcript_seeds as ts
+        rec = ts.chain_record(case.search, case.layer)
+        digest, chan = bytes.fromhex(rec["digest"]), ts.CountingChannel(variant)
+    ref = ref_commit(cols, digest, variant, case.last_log, chan)
+    if case.search:
+        check_redraw_reference(case, rec, chan, ref)
     if case.cls == "zero":      # the zero-landing join: the reference says so before the kernel is asked
         assert not any(l.any() for l in ref.layers), case.name
     elif classes[0] == "zero":  # alpha^2 * prev = 0 at the first join, the joining column's fold live
@@ -516,3 +645,32 @@ def check_sharded_context_refused(ctxs):
         ctx.clear_shard()
         h.free()
     check_case(ctxs, case)
+
+
+# ----------------------------------------------------------------------------- the searcher's inputs
+def search_roots(name):
+    """the roots tools/find_redraw.cpp is given: all of them for constant columns (no alpha moves them), the first tree's
+    for random ones"""
+    from oracle.channel import ProtocolVariant
+    case = next(c for c in REDRAW_CASES if c.search == name)
+    cols, _, _ = case_columns(case)
+    ref = ref_commit(cols, bytes(32), ProtocolVariant.DRAW_CTR_U32 if case.u32 else ProtocolVariant.KAT, case.last_log)
+    return [r.hex() for r in (ref.roots if case.cls in ("zero", "const") else ref.roots[:1])]
+
+
+def search_command(s, threads=8, seed=1):
+    return 'tools/bin/find_redraw chain "%s" %d %s %s %s %d %d %d %d %s' % (
+        s["name"], 37 if s["u32"] else 64, s["event"], ",".join(str(t) for t in s["layers"]), s["value"], s["lo"], s["hi"], threads,
+        seed, " ".join(search_roots(s["name"])))
+
+
+if __name__ == "__main__":
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    if sys.argv[1:2] == ["roots"] and len(sys.argv) == 3:
+        print(" ".join(search_roots(sys.argv[2])))
+    elif sys.argv[1:] == ["commands"]:
+        for s_ in REDRAW_SEARCHES:
+            print(search_command(s_))
+    else:
+        sys.exit("usage: fri_checks.py roots <search name> | commands")

@@ -8,6 +8,7 @@ import subprocess
 import pytest
 
 import fri_checks as fc
+import transcript_seeds as ts
 from luminair_amd import backend
 
 
@@ -49,6 +50,18 @@ def test_value_class(ctxs, case):
     """all 0, all P-1, alternating, EDGE_WORDS, random, pairs with a + b = 0 and with a == b in every input column; all 0 in
     cols[0] alone and in the joining columns alone"""
     fc.check_case(ctxs, case)
+
+
+def test_redraw_cases_reach_every_draw():
+    fc.check_redraw_cases_reach_every_draw(fc.REDRAW_CASES)
+
+
+@pytest.mark.parametrize("case", fc.REDRAW_CASES, ids=lambda c: c.id)
+def test_redraw(ctxs, case):
+    """the transcript's value edges (tests/golden/transcript_redraw_seeds.json): a redraw, the accepted word 0xFFFFFFFD and a
+    word P at a chosen tree; the reference must have met the event there, and only there, before the loop is asked.  A loop
+    that never leaves its redraw fails the case at the limit"""
+    ts.bounded(ts.LIMIT, fc.check_case, ctxs, case)
 
 
 def test_refusals_leave_context_and_handles_usable(ctxs):

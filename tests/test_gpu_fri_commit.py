@@ -33,6 +33,19 @@ def test_gpu_matrix_reaches_every_form():
     assert {len(a) for c in BIG_CASES for a in c.plan().absent} >= {0, 1, 2, 3}
 
 
+def test_gpu_redraw_cases_reach_every_draw():
+    """which draw implementation each redraw reaches, from plan(): k_merkle_small's step for the first tree and for an inner
+    tree, k_fri_tail's first (with and without the front fold), middle and last layer, in both draw encodings per kernel; the
+    single-lane k_chan_mix_root_draw cannot be reached by an unsharded context (fri_checks.check_redraw_cases_reach_every_draw
+    states commit.cpp's condition)"""
+    fc.check_redraw_cases_reach_every_draw(fc.REDRAW_CASES)
+
+
+@pytest.mark.parametrize("case", fc.REDRAW_CASES, ids=lambda c: c.id)
+def test_gpu_redraw(ctxs, case):
+    fc.check_case(ctxs, case)
+
+
 @pytest.mark.parametrize("case", fc.SHAPE_CASES, ids=lambda c: c.id)
 def test_gpu_shape(ctxs, case):
     fc.check_case(ctxs, case)
