@@ -108,7 +108,7 @@ uint32_t lmn_abi_version(void);
 /* Replaces PcsConfig::default() (prover.rs:36) + DEFAULT_FP_SCALE (crates/air/src/lib.rs:23-24). */
 typedef struct lmn_config {
   uint32_t pow_bits;         /* default 5 */
-  uint32_t log_blowup;       /* default 1 (= blow-up 2, PcsConfig::default()); 1..3 accepted, sharded proofs: 1 only */
+  uint32_t log_blowup;       /* default 1 (= blow-up 2, PcsConfig::default()); 1..3 accepted, sharded proofs included */
   uint32_t log_last_layer;   /* default 0 */
   uint32_t n_queries;        /* default 3 */
   uint32_t fp_scale;         /* default 12 */
@@ -870,6 +870,38 @@ struct lmn_fri_commit_result {
 typedef struct lmn_fri_commit_result lmn_fri_commit_result;
 int lmn_col_fri_commit(lmn_ctx* ctx, const lmn_col* const* cols, uint32_t n, const uint8_t start_digest[32],
                        lmn_fri_commit_result* result);
+/* What FriProver::commit and the query phase do BEHIND the layer loop, on the device and in one call: the last layer's
+ * polynomial (line interpolation of `last_layer`: 4 coordinate columns of 2^(log_last_layer + log_blowup) rows, bit-reversed
+ * over LineDomain(half_odds), as lmn_col_fri_commit leaves the last layer), its degree check, Channel::mix_felts over the
+ * first 2^log_last_layer coefficients starting from `start_digest` (the channel behind the last folding alpha), the proof
+ * of work (GrindOps::grind at the context's pow_bits), Channel::mix_u64 of the nonce, and Queries::generate: n_queries
+ * positions drawn 8 per draw_random_words, masked to log_query_domain bits, ascending and distinct.  The context's
+ * log_last_layer, log_blowup, pow_bits, n_queries and protocol_variant apply.  The chain is k_fri_close, 8 grind windows
+ * and k_fri_queries behind ONE host wait, whatever LMN_POW_DEVICE_MIN_BITS says (as lmn_ctx_grind); a nonce beyond the
+ * queued windows is found by further grind rounds (grind_rounds counts their host waits) and the rest replayed on the host.
+ * A layer of too high a degree is LMN_OK with first_bad set: the transcript goes on over the truncated coefficients, and
+ * the caller decides.  LMN_ERR_INVALID_ARGUMENT with a text naming the argument, the result zeroed, context and handles
+ * usable: a null pointer, a handle that is not 4 columns of 2^(log_last_layer + log_blowup) rows, log_query_domain > 31, a
+ * sharded context.  coeffs and positions are released with lmn_free. */
+struct lmn_fri_close_result {
+  uint32_t n_coeffs;      /* 2^log_last_layer */
+  uint32_t first_bad;     /* lowest index >= n_coeffs of a non-zero coefficient; 0xffffffff: degree ok */
+  uint32_t n_positions;   /* distinct query positions */
+  uint32_t grind_rounds;  /* host waits spent grinding after the chain's own wait (0: found in the queued windows) */
+  uint64_t nonce;
+  uint32_t* coeffs;       /* 4 words per coefficient (a,b,c,d), as proof.last_layer_coeffs; lmn_free */
+  uint32_t* positions;    /* ascending, distinct; lmn_free */
+  uint8_t digest_after_coeffs[32], digest_after_nonce[32], digest_end[32];
+  uint32_t n_sent_end, reserved;
+};
+typedef struct lmn_fri_close_result lmn_fri_close_result;
+int lmn_col_fri_close(lmn_ctx* ctx, const lmn_col* last_layer, const uint8_t start_digest[32],
+                      uint32_t log_query_domain /* 0..31 */, lmn_fri_close_result* result);
+/* Counters of a context since its creation, in lmn_batch_counter's numbering where it applies - 7: proof-of-work grinds
+ * started on the device, 8: host waits spent inside grind rounds, 9: proofs whose transcript was closed on the device
+ * (lmn_prove under LMN_DEVICE_FRI_CLOSE=1 at pow_bits >= LMN_POW_DEVICE_MIN_BITS, unsharded), 10: those among them whose nonce
+ * lay beyond the queued windows (the host went on grinding).  Any other number, or a null context: 0. */
+uint64_t lmn_ctx_counter(const lmn_ctx* ctx, int which);
 int lmn_col_accumulate(lmn_ctx* ctx, lmn_col* dst, const lmn_col* src);     /* AccumulationOps::accumulate: dst += src (same shape) */
 /* FieldOps<BaseField>::batch_inverse and FieldOps<SecureField>::batch_inverse on whole columns, on the device.
  *   lmn_col_batch_inverse:        dst[j][i] = src[j][i]^-1 in M31 for every column j and row i.

@@ -214,6 +214,32 @@ class TraceReport:
                            bool(r.constraints_truncated), int(r.n_unbalanced), tup, bool(r.tuples_truncated))
 
 
+class LmnFriCloseResult(C.Structure):
+    """`lmn_fri_close_result`"""
+    _fields_ = [("n_coeffs", C.c_uint32), ("first_bad", C.c_uint32), ("n_positions", C.c_uint32), ("grind_rounds", C.c_uint32),
+                ("nonce", C.c_uint64), ("coeffs", C.c_void_p), ("positions", C.c_void_p),
+                ("digest_after_coeffs", C.c_uint8 * 32), ("digest_after_nonce", C.c_uint8 * 32), ("digest_end", C.c_uint8 * 32),
+                ("n_sent_end", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+@dataclass
+class FriClose:
+    """What `Context.fri_close` returns: the last layer's coefficients, the degree check, the nonce, the query positions and
+    the channel after each step."""
+    coeffs: List[Tuple[int, int, int, int]]   # the first 2^log_last_layer
+    first_bad: Optional[int]                  # lowest index past them of a non-zero coefficient, None: degree ok
+    nonce: int
+    grind_rounds: int                         # host waits spent grinding after the chain's own wait
+    positions: List[int]                      # ascending, distinct
+    digest_after_coeffs: bytes
+    digest_after_nonce: bytes
+    digest_end: bytes
+    n_sent_end: int
+
+
+# lmn_ctx_counter
+COUNTER_GRINDS, COUNTER_GRIND_WAITS, COUNTER_DEVICE_CLOSES, COUNTER_DEVICE_CLOSE_FALLBACKS = 7, 8, 9, 10
+
 API_VERSION = 6   # LMN_API_VERSION of include/luminair_hip.h
 
 EXPORTS = ["lmn_abi_version", "lmn_kind_padding_row", "lmn_strerror", "lmn_last_error", "lmn_default_config", "lmn_kind_columns", "lmn_ctx_create",
@@ -227,7 +253,7 @@ EXPORTS = ["lmn_abi_version", "lmn_kind_padding_row", "lmn_strerror", "lmn_last_
            "lmn_col_log_size", "lmn_col_device_ptr", "lmn_col_view", "lmn_col_bit_reverse", "lmn_col_precompute_twiddles",
            "lmn_col_interpolate", "lmn_col_evaluate", "lmn_col_evaluate_block", "lmn_col_extend", "lmn_col_eval_at_point",
            "lmn_col_commit", "lmn_tree_root", "lmn_tree_log_size", "lmn_tree_layer_to_cpu", "lmn_tree_free",
-           "lmn_tree_decommit", "lmn_col_gather", "lmn_col_fri_commit",
+           "lmn_tree_decommit", "lmn_col_gather", "lmn_col_fri_commit", "lmn_col_fri_close", "lmn_ctx_counter",
            "lmn_col_accumulate", "lmn_col_accumulate_quotients", "lmn_col_fold_line", "lmn_col_fold_circle_into_line",
            "lmn_col_decompose", "lmn_col_batch_inverse", "lmn_col_batch_inverse_secure", "lmn_col_logup", "lmn_col_composition", "lmn_kind_constraints", "lmn_kind_relations", "lmn_ctx_set_shard", "lmn_rccl_unique_id", "lmn_ctx_set_shard_rccl", "lmn_ctx_clear_shard",
            "lmn_rows_open", "lmn_rows_push", "lmn_rows_push_pinned", "lmn_rows_sync", "lmn_rows_finish", "lmn_rows_count",
@@ -361,6 +387,9 @@ class Library:
                                           C.POINTER(VP), C.POINTER(C.c_size_t), C.POINTER(VP), C.POINTER(C.c_size_t)]
         lib.lmn_col_gather.argtypes = [VP, VP, VP, U32, VP]
         lib.lmn_col_fri_commit.argtypes = [VP, C.POINTER(VP), U32, VP, C.POINTER(LmnFriCommitResult)]
+        lib.lmn_col_fri_close.argtypes = [VP, VP, VP, U32, C.POINTER(LmnFriCloseResult)]
+        lib.lmn_ctx_counter.argtypes = [VP, C.c_int]
+        lib.lmn_ctx_counter.restype = C.c_uint64
         lib.lmn_tree_free.argtypes = [VP, VP]
         lib.lmn_tree_free.restype = None
         lib.lmn_col_accumulate.argtypes = [VP, VP, VP]
@@ -1018,6 +1047,31 @@ class Context:
                 if p:
                     L.lmn_free(p)
 
+    def fri_close(self, col: Col, start_digest: bytes, log_query_domain: int) -> FriClose:
+        """`lmn_col_fri_close`: what stands between FRI's layer loop and the decommitment, on the device - the last layer's
+        polynomial (`col`: 4 coordinate columns of 2^(log_last_layer + log_blowup) rows) and its degree check, mix_felts
+        from the channel digest `start_digest`, the grind, mix_u64 and the query positions of a domain of
+        2^log_query_domain rows."""
+        L = self.lib.lib
+        if len(start_digest) != 32:
+            raise ValueError("start_digest is 32 bytes")
+        dig = (C.c_uint8 * 32)(*start_digest)
+        res = LmnFriCloseResult()
+        try:
+            self._check(L.lmn_col_fri_close(self.handle, col.handle, dig, log_query_domain, C.byref(res)))
+            nc, npos = int(res.n_coeffs), int(res.n_positions)
+            coeffs = np.frombuffer(C.string_at(res.coeffs, 16 * nc), dtype=np.uint32).reshape(nc, 4)
+            positions = np.frombuffer(C.string_at(res.positions, 4 * npos), dtype=np.uint32) if npos else []
+            return FriClose([tuple(int(v) for v in c) for c in coeffs],
+                            None if res.first_bad == 0xffffffff else int(res.first_bad), int(res.nonce), int(res.grind_rounds),
+                            [int(v) for v in positions], bytes(res.digest_after_coeffs), bytes(res.digest_after_nonce),
+                            bytes(res.digest_end), int(res.n_sent_end))
+        finally:
+            for name in ("coeffs", "positions"):
+                p = getattr(res, name)
+                if p:
+                    L.lmn_free(p)
+
     def col_accumulate_quotients(self, cols: Sequence[Col], samples, points, alpha) -> Col:
         """As `accumulate_quotients`, on resident columns; returns the secure column (4 coordinate columns)."""
         arr = (C.c_void_p * len(cols))(*[c.handle for c in cols])
@@ -1526,6 +1580,11 @@ class Context:
         out = C.c_uint64()
         self._check(self.lib.lib.lmn_ctx_grind(self.handle, digest, pow_bits, variant, C.byref(out)))
         return int(out.value)
+
+    def counter(self, which: int) -> int:
+        """`lmn_ctx_counter` - 7: device grinds started, 8: host waits inside grind rounds, 9: proofs whose transcript was
+        closed on the device, 10: those among them that went on grinding on the host's rounds."""
+        return int(self.lib.lib.lmn_ctx_counter(self.handle, which))
 
     def grind_many(self, digests, pow_bits: int, variant: int = VARIANT_KAT) -> List[int]:
         """GrindOps::grind for several 32-byte channel digests ground together on the context's GPU (lmn_ctx_grind_many):

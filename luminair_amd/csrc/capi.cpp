@@ -493,6 +493,8 @@ int lmn_ctx_grind(lmn_ctx* ctx, const uint8_t digest[32], uint32_t pow_bits, uin
   });
 }
 
+uint64_t lmn_ctx_counter(const lmn_ctx* ctx, int which) { return ctx && ctx->impl ? ctx->impl->counter(which) : 0; }
+
 int lmn_ctx_grind_many(lmn_ctx* ctx, const uint8_t* digests, uint32_t n, uint32_t pow_bits, uint32_t protocol_variant,
                        uint64_t* nonces_out) {
   if (!ctx) {

@@ -92,6 +92,7 @@ class Channel {
   explicit Channel(uint32_t flags) : variant_(flags) { memset(digest_.w, 0, sizeof digest_.w); }
   uint32_t flags() const { return variant_; }
   const Hash32& digest() const { return digest_; }
+  uint32_t n_sent() const { return n_sent_; }
   void set_digest(const Hash32& d) { update(d); }
 
   void mix_root(const Hash32& root) {

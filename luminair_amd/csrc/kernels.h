@@ -307,6 +307,11 @@ constexpr uint32_t POW_NPT = 8;         // nonces per lane and launch
 constexpr int POW_MIN_WINDOW_LOG = 11;  // one block: POW_TPB * POW_NPT nonces
 constexpr int POW_WINDOW_LOG = 24;      // default cap of one launch's window (Context: LMN_POW_WINDOW_LOG)
 constexpr int POW_DEVICE_MIN_BITS = 11; // prove() grinds on the device from this pow_bits on (LMN_POW_DEVICE_MIN_BITS; measured crossover)
+// Launches queued per host wait, in device_grind, in grind_many's rounds and behind k_fri_close: one behind the launch that
+// found a nonce returns at once (every block sees the smaller nonce at its start), so the queue costs a few us of launches
+// and saves waits while nothing has been found.  (grind_many on 64 digests at pow_bits 20: 4 is within the spread of 8, 16
+// is 5 - 8 % slower.)
+constexpr int POW_WINDOWS_PER_WAIT = 8;
 struct PowWords {
   uint32_t w[8];
 };
@@ -318,6 +323,45 @@ void launch_pow_grind(const PowWords& w, bool kat, uint64_t base, int window_log
 // nothing else writes during the launch.
 void launch_grind_many(const PowWords* digests, const uint32_t* pending, uint32_t n_pending, bool kat, uint64_t base,
                        int window_log, uint32_t pow_bits, unsigned long long* best, lmn_stream_t s);
+
+// ---- the close of the FRI transcript on the device (phase_fri.cpp enqueue_fri_close): what stands between the last
+// folding alpha and the decommitment - the last layer's polynomial, its degree check, mix_felts, the proof of work, mix_u64
+// and the query positions - as a chain of single-workgroup kernels with launch_grind_many's windows in between:
+//   k_fri_close | POW_WINDOWS_PER_WAIT x k_grind_many (one digest) | k_fri_queries
+constexpr int FRI_CLOSE_MAX_LOG = 13;        // the last layer: at most 2^(10 + 3) values (log_last_layer + log_blowup)
+constexpr int FRI_CLOSE_LDS_LOG = 11;        // up to this size the interpolation's passes stay in LDS, above in `scratch`
+constexpr int FRI_CLOSE_MAX_BOUND_LOG = 10;  // log_last_layer
+constexpr uint32_t FRI_CLOSE_MAX_QUERIES = 1024;
+struct FriCloseItw {
+  const uint32_t* p[FRI_CLOSE_MAX_LOG + 1];  // p[d], d >= 1: the 1/x twiddles of the line domain of log size d (fold_line's)
+};
+// device memory between the kernels of the chain
+struct FriCloseState {
+  PowWords pow;              // what the grind hashes: the digest behind mix_felts, or its prefixed digest
+  unsigned long long best;   // the grind's answer, ~0 while there is none
+  uint32_t pending;          // the grind's pending table: its one entry, 0
+  uint32_t first_bad;        // lowest index >= 2^log_bound of a non-zero coefficient, 0xffffffff: none
+  uint32_t digest_after_coeffs[8];
+};
+// the result block (page-locked): this header, n_queries words of positions, then 4 words per coefficient
+struct FriCloseHeader {
+  uint32_t found;            // 0: no nonce in the queued windows - nothing else is written
+  uint32_t first_bad, n_positions, n_sent_end;
+  uint32_t nonce_lo, nonce_hi, pad[2];
+  uint32_t digest_after_coeffs[8], digest_after_nonce[8], digest_end[8];
+};
+// last: 4 coordinate columns of 2^log_n words, bit-reversed over the line domain (FriPlan::d_last).  Interpolates (the
+// butterflies of fold_line, scale n_inv = 1/2^log_n), writes all 2^log_n coefficients to coeffs (4 words each), checks the
+// degree against 2^log_bound, runs Channel::mix_felts over the first 2^log_bound coefficients on *ch and fills *st.
+// scratch: 4 x 2^log_n words of device memory when log_n > FRI_CLOSE_LDS_LOG, unused otherwise.
+void launch_fri_close(DevChannel* ch, const uint32_t* last, int log_n, int log_bound, const FriCloseItw& itw, uint32_t n_inv,
+                      uint32_t* scratch, uint32_t* coeffs, bool pow_prefixed, uint32_t pow_bits, FriCloseState* st,
+                      lmn_stream_t s);
+// behind the grind: with a nonce in st->best, mix_u64 (hashed: LMN_PV_MIX_U64_HASHED), n_queries positions drawn 8 per
+// draw_random_words and masked with pos_mask, sorted and made distinct; header, positions and the first n_coeff_words of
+// coeffs go to `out` (FriCloseHeader's layout).  Without one: out->found = 0.
+void launch_fri_queries(DevChannel* ch, const FriCloseState* st, const uint32_t* coeffs, uint32_t n_coeff_words,
+                        bool hashed, uint32_t n_queries, uint32_t pos_mask, uint32_t* out, lmn_stream_t s);
 
 // ---- trace generation for the elementwise primitives (the producer of the hot path's input)
 struct TraceNode {

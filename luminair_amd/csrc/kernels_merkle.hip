@@ -858,6 +858,39 @@ LMN_D void chan_step_root_oods(uint32_t* scr, DevChannel* ch, uint32_t dg, uint3
   for (uint32_t k = tid + blockDim.x; k < copy_words; k += blockDim.x) copy_dst[k] = copy_src[k];
 }
 
+// Blake2s over the `total_words` words at W (LDS, zero-padded to whole 64-byte blocks) -> msg[0..8): the hash of a
+// message longer than one block (Channel::mix_felts: W = digest || values), on the first quad.  Called by all threads
+// behind a barrier that made W visible; no barrier at the end.
+LMN_D void qchan_hash_blocks(const uint32_t* W, uint32_t total_words, uint32_t* msg) {
+  const uint32_t tid = threadIdx.x;
+  const uint32_t n_blocks = (total_words + 15u) / 16u;
+#ifdef LMN_EMU
+  if (tid == 0u) {
+    uint32_t h[8];
+    b2_init(h);
+    for (uint32_t b = 0; b < n_blocks; ++b) {
+      const bool last = b + 1u == n_blocks;
+      b2_compress(h, W + 16u * b, last ? 4u * total_words : 64u * (b + 1u), last ? 0xffffffffu : 0u);
+    }
+    for (int k = 0; k < 8; ++k) msg[k] = h[k];
+  }
+#else
+  if (tid < 64u) {
+    const uint32_t q = tid & 3u;
+    uint32_t hl = q == 0 ? (0x6A09E667u ^ 0x01010020u) : q == 1 ? 0xBB67AE85u : q == 2 ? 0x3C6EF372u : 0xA54FF53Au;
+    uint32_t hh = q == 0 ? 0x510E527Fu : q == 1 ? 0x9B05688Cu : q == 2 ? 0x1F83D9ABu : 0x5BE0CD19u;
+    for (uint32_t b = 0; b < n_blocks; ++b) {
+      const bool last = b + 1u == n_blocks;
+      b2_quad_compress(W + 16u * b, q, hl, hh, last ? 4u * total_words : 64u * (b + 1u), last ? 0xffffffffu : 0u);
+    }
+    if (tid < 4u) {
+      msg[q] = hl;
+      msg[4u + q] = hh;
+    }
+  }
+#endif
+}
+
 // =============================================================================================
 // The step in front of the FRI quotient kernels (kernels.h QuotPrepPlan): mix_felts(sampled values), alpha = draw_felt(),
 // the quotient tables of every LDE size.  One workgroup; block-uniform control flow.
@@ -869,7 +902,7 @@ LMN_KERNEL k_quot_prepare(DevChannel* ch, const QuotPrepPlan* __restrict__ plan_
   LMN_SHARED uint32_t W[8 + 4 * QUOT_PREP_MAX_SAMPLES + 16];   // digest || values, zero-padded to whole blocks
   LMN_SHARED uint32_t scr[32];                                   // msg 16 | drawn words 8 | alpha 4
   LMN_SHARED QM31 sa[QUOT_MAX_ENTRIES], sb[QUOT_MAX_ENTRIES];
-  const uint32_t tid = threadIdx.x, q = tid & 3u;
+  const uint32_t tid = threadIdx.x;
   for (uint32_t k = tid; k < (uint32_t)QUOT_PREP_PLAN_WORDS; k += blockDim.x) sh_plan[k] = reinterpret_cast<const uint32_t*>(plan_g)[k];
   const uint32_t dgw = tid < 8u ? ch->digest[tid] : 0u;
   const uint32_t variant = ch->variant;
@@ -889,30 +922,7 @@ LMN_KERNEL k_quot_prepare(DevChannel* ch, const QuotPrepPlan* __restrict__ plan_
   __syncthreads();
   // ---- Channel::mix_felts: digest <- Blake2s(digest || values)
   uint32_t* msg = scr;
-#ifdef LMN_EMU
-  if (tid == 0u) {
-    uint32_t h[8];
-    b2_init(h);
-    for (uint32_t b = 0; b < n_blocks; ++b) {
-      const bool last = b + 1u == n_blocks;
-      b2_compress(h, W + 16u * b, last ? 4u * total_words : 64u * (b + 1u), last ? 0xffffffffu : 0u);
-    }
-    for (int k = 0; k < 8; ++k) msg[k] = h[k];
-  }
-#else
-  if (tid < 64u) {
-    uint32_t hl = q == 0 ? (0x6A09E667u ^ 0x01010020u) : q == 1 ? 0xBB67AE85u : q == 2 ? 0x3C6EF372u : 0xA54FF53Au;
-    uint32_t hh = q == 0 ? 0x510E527Fu : q == 1 ? 0x9B05688Cu : q == 2 ? 0x1F83D9ABu : 0x5BE0CD19u;
-    for (uint32_t b = 0; b < n_blocks; ++b) {
-      const bool last = b + 1u == n_blocks;
-      b2_quad_compress(W + 16u * b, q, hl, hh, last ? 4u * total_words : 64u * (b + 1u), last ? 0xffffffffu : 0u);
-    }
-    if (tid < 4u) {
-      msg[q] = hl;
-      msg[4u + q] = hh;
-    }
-  }
-#endif
+  qchan_hash_blocks(W, total_words, msg);
   __syncthreads();
   // ---- alpha = draw_felt(); the channel goes on into the FRI commit loop
   uint32_t n_sent = 0u, f[8];
@@ -1316,6 +1326,218 @@ void launch_grind_many(const PowWords* digests, const uint32_t* pending, uint32_
     LMN_LAUNCH(k_grind_many<false>, grid, dim3(POW_TPB), 0, s, digests, pending, base, mask, best);
   }
 #endif
+}
+
+// =============================================================================================
+// The close of the FRI transcript (kernels.h launch_fri_close / launch_fri_queries): one workgroup each, block-uniform
+// control flow, nothing whose length depends on the data - the host decides on first_bad and on a grind without a hit.
+// =============================================================================================
+constexpr uint32_t FRI_CLOSE_TPB = 1024;
+constexpr uint32_t FRI_CLOSE_PAIRS = (1u << (FRI_CLOSE_MAX_LOG - 1)) / FRI_CLOSE_TPB;   // butterflies per lane and pass
+static_assert(FRI_CLOSE_PAIRS * FRI_CLOSE_TPB * 2u == 1u << FRI_CLOSE_MAX_LOG, "a pass is held in registers across its barrier");
+
+// Line interpolation as run_fri_commit's host loop does it: a pass over chunks of 2^d values turns the neighbours
+// (2i, 2i+1) of every chunk into f0 = a + b (first half of the chunk) and f1 = (a - b) / x_i (second half); after log_n
+// passes value bit_reverse(j) is coefficient j times n.  A pass reads its pairs into registers, waits, and writes: in place.
+LMN_KERNEL k_fri_close(DevChannel* ch, const uint32_t* __restrict__ last, int log_n, int log_bound, FriCloseItw itw,
+                       uint32_t n_inv, uint32_t* scratch, uint32_t* __restrict__ coeffs, int pow_prefixed, uint32_t pow_bits,
+                       FriCloseState* st) {
+  LMN_SHARED uint32_t sh[4u << FRI_CLOSE_LDS_LOG];                        // the passes of a layer of up to 2^FRI_CLOSE_LDS_LOG values
+  LMN_SHARED uint32_t W[8 + (4 << FRI_CLOSE_MAX_BOUND_LOG) + 16];         // digest || coefficients, zero-padded to whole blocks
+  LMN_SHARED uint32_t scr[32];                                            // digest 8 (+ 8 unused) | the prefixed form's message 16
+  LMN_SHARED int sh_bad;
+  const uint32_t tid = threadIdx.x, q = tid & 3u;
+  const uint32_t n = 1u << log_n, bound = 1u << log_bound;
+  const uint32_t dgw = tid < 8u ? ch->digest[tid] : 0u;
+  uint32_t* buf = log_n <= FRI_CLOSE_LDS_LOG ? sh : scratch;               // coordinate k of value i at buf[k * n + i]
+  for (uint32_t k = tid; k < 4u * n; k += blockDim.x) buf[k] = last[k];
+  if (tid == 0u) sh_bad = 0x7fffffff;
+  __syncthreads();
+  for (int d = log_n; d >= 1; --d) {
+    const uint32_t half = 1u << (d - 1);
+    const uint32_t* __restrict__ tw = itw.p[d];
+    QM31 f0[FRI_CLOSE_PAIRS], f1[FRI_CLOSE_PAIRS];
+#pragma unroll
+    for (uint32_t k = 0; k < FRI_CLOSE_PAIRS; ++k) {
+      const uint32_t p = tid + k * FRI_CLOSE_TPB;   // pair i of chunk c: values c * 2^d + 2i, + 1
+      if (p < n / 2u) {
+        const uint32_t i = p & (half - 1u), at = 2u * p;
+        const QM31 a{buf[at], buf[n + at], buf[2u * n + at], buf[3u * n + at]};
+        const QM31 b{buf[at + 1u], buf[n + at + 1u], buf[2u * n + at + 1u], buf[3u * n + at + 1u]};
+        f0[k] = q_add(a, b);
+        f1[k] = q_mul_m(q_sub(a, b), tw[i]);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < FRI_CLOSE_PAIRS; ++k) {
+      const uint32_t p = tid + k * FRI_CLOSE_TPB;
+      if (p < n / 2u) {
+        const uint32_t i = p & (half - 1u), at = ((p >> (d - 1)) << d) + i;
+        buf[at] = f0[k].a;
+        buf[n + at] = f0[k].b;
+        buf[2u * n + at] = f0[k].c;
+        buf[3u * n + at] = f0[k].d;
+        buf[at + half] = f1[k].a;
+        buf[n + at + half] = f1[k].b;
+        buf[2u * n + at + half] = f1[k].c;
+        buf[3u * n + at + half] = f1[k].d;
+      }
+    }
+    __syncthreads();
+  }
+  // ---- coefficient j = value bit_reverse(j) / n; the degree check; W = digest || the first `bound` coefficients
+  const uint32_t total_words = 8u + 4u * bound, padded_words = (total_words + 15u) / 16u * 16u;
+  if (tid < 8u) W[tid] = dgw;
+  for (uint32_t k = total_words + tid; k < padded_words; k += blockDim.x) W[k] = 0u;
+  int bad = 0x7fffffff;
+  for (uint32_t j = tid; j < n; j += blockDim.x) {
+    const uint32_t at = log_n ? __brev(j) >> (32 - log_n) : 0u;
+    const QM31 c = q_mul_m(QM31{buf[at], buf[n + at], buf[2u * n + at], buf[3u * n + at]}, n_inv);
+    coeffs[4u * j] = c.a;
+    coeffs[4u * j + 1u] = c.b;
+    coeffs[4u * j + 2u] = c.c;
+    coeffs[4u * j + 3u] = c.d;
+    if (j < bound) {
+      W[8u + 4u * j] = c.a;
+      W[9u + 4u * j] = c.b;
+      W[10u + 4u * j] = c.c;
+      W[11u + 4u * j] = c.d;
+    } else if (!q_is_zero(c) && bad == 0x7fffffff) {
+      bad = (int)j;   // (a lane meets its indices in ascending order)
+    }
+  }
+  if (bad != 0x7fffffff) atomicMin(&sh_bad, bad);
+  __syncthreads();
+  // ---- Channel::mix_felts
+  uint32_t* msg = scr;
+  qchan_hash_blocks(W, total_words, msg);
+  __syncthreads();
+  if (tid < 8u) {
+    ch->digest[tid] = msg[tid];
+    st->digest_after_coeffs[tid] = msg[tid];
+  }
+  // ---- the words the grind hashes: the digest, or blake2s(0x12345678 || 12 zero bytes || digest || pow_bits) (52 bytes)
+  uint32_t* pre = scr + 16;
+  if (tid < 16u) pre[tid] = tid == 0u ? 0x12345678u : tid >= 4u && tid < 12u ? msg[tid - 4u] : tid == 12u ? pow_bits : 0u;
+  __syncthreads();
+  uint32_t lo = 0u, hi = 0u;
+  if (tid < 64u) b2_quad_parent(pre, q, lo, hi, 52u);
+  if (tid < 4u) {
+    st->pow.w[q] = pow_prefixed ? lo : msg[q];
+    st->pow.w[4u + q] = pow_prefixed ? hi : msg[4u + q];
+  }
+  if (tid == 0u) {
+    ch->n_sent = 0u;
+    st->best = ~0ull;
+    st->pending = 0u;
+    st->first_bad = sh_bad == 0x7fffffff ? 0xffffffffu : (uint32_t)sh_bad;
+  }
+}
+
+void launch_fri_close(DevChannel* ch, const uint32_t* last, int log_n, int log_bound, const FriCloseItw& itw, uint32_t n_inv,
+                      uint32_t* scratch, uint32_t* coeffs, bool pow_prefixed, uint32_t pow_bits, FriCloseState* st,
+                      lmn_stream_t s) {
+  if (!ch || !last || !coeffs || !st || log_n < 0 || log_n > FRI_CLOSE_MAX_LOG || log_bound < 0 || log_bound > log_n ||
+      log_bound > FRI_CLOSE_MAX_BOUND_LOG || (log_n > FRI_CLOSE_LDS_LOG && !scratch))
+    throw LmnError(-100, "fri_close: bad arguments");
+  for (int d = 1; d <= log_n; ++d)
+    if (!itw.p[d]) throw LmnError(-100, "fri_close: a twiddle table is missing");
+  LMN_LAUNCH(k_fri_close, dim3(1), dim3(FRI_CLOSE_TPB), 0, s, ch, last, log_n, log_bound, itw, n_inv, scratch, coeffs,
+             pow_prefixed ? 1 : 0, pow_bits, st);
+}
+
+// Every draw hashes digest || its own counter: draw k is the business of quad k alone, all of them at once.  Positions are
+// made distinct and ranked by counting (at most 1024 of them: two passes over LDS per lane).
+LMN_KERNEL k_fri_queries(DevChannel* ch, const FriCloseState* __restrict__ st, const uint32_t* __restrict__ coeffs,
+                         uint32_t n_coeff_words, int hashed, uint32_t n_queries, uint32_t pos_mask, uint32_t* __restrict__ out) {
+  static_assert(FRI_CLOSE_TPB == FRI_CLOSE_MAX_QUERIES, "one lane per position");
+  LMN_SHARED uint32_t msgs[FRI_CLOSE_MAX_QUERIES / 8u * 16u];   // one message per draw; afterwards the sorted positions
+  LMN_SHARED uint32_t pos[FRI_CLOSE_MAX_QUERIES], first[FRI_CLOSE_MAX_QUERIES];
+  LMN_SHARED uint32_t scr[32];                                   // digest || nonce | the digest behind the coefficients
+  const uint32_t tid = threadIdx.x, q = tid & 3u;
+  FriCloseHeader* hdr = reinterpret_cast<FriCloseHeader*>(out);
+  const unsigned long long nonce = st->best;
+  if (nonce == ~0ull) {   // block-uniform
+    if (tid == 0u) hdr->found = 0u;
+    return;
+  }
+  const uint32_t variant = ch->variant;
+  uint32_t* msg = scr;
+  if (tid < 8u) {
+    msg[tid] = ch->digest[tid];
+    scr[16u + tid] = msg[tid];
+  } else if (tid < 16u) {
+    msg[tid] = tid == 8u ? (uint32_t)nonce : tid == 9u ? (uint32_t)(nonce >> 32) : 0u;
+  }
+  // ---- Channel::mix_u64: blake2s(digest || nonce LE), or the KAT form's bare compression (h = digest, m = nonce, t = 0, no final flag)
+  if (hashed) {
+    qchan_mix(msg, 2u);
+  } else {
+    __syncthreads();
+    if (tid == 0u) {
+      uint32_t h[8], m[16];
+      for (int k = 0; k < 8; ++k) h[k] = msg[k];
+      for (int k = 0; k < 16; ++k) m[k] = k < 2 ? msg[8 + k] : 0u;
+      b2_compress(h, m, 0u, 0u);
+      for (int k = 0; k < 8; ++k) msg[k] = h[k];
+    }
+  }
+  __syncthreads();
+  // ---- draw_random_words, ceil(n_queries / 8) times
+  const uint32_t n_draws = (n_queries + 7u) / 8u;
+  for (uint32_t k = tid; k < n_draws * 16u; k += blockDim.x) msgs[k] = (k & 15u) < 8u ? msg[k & 15u] : (k & 15u) == 8u ? k >> 4 : 0u;
+  __syncthreads();
+  const uint32_t g = tid >> 2;
+  if (g < n_draws) {   // whole quads
+    uint32_t lo = 0u, hi = 0u;
+    b2_quad_parent(msgs + 16u * g, q, lo, hi, variant == 0u ? 64u : 37u);
+    if (8u * g + q < n_queries) pos[8u * g + q] = lo & pos_mask;
+    if (8u * g + 4u + q < n_queries) pos[8u * g + 4u + q] = hi & pos_mask;
+  }
+  __syncthreads();
+  // ---- ascending and distinct: a position counts at its first occurrence, its rank is the number of smaller ones that count
+  const uint32_t v = tid < n_queries ? pos[tid] : 0u;
+  uint32_t is_first = tid < n_queries ? 1u : 0u;
+  for (uint32_t j = 0; j < tid && j < n_queries; ++j) is_first &= pos[j] != v ? 1u : 0u;
+  first[tid] = is_first;
+  __syncthreads();
+  uint32_t rank = 0u, n_positions = 0u;
+  for (uint32_t j = 0; j < n_queries; ++j) {
+    n_positions += first[j];
+    rank += first[j] & (pos[j] < v ? 1u : 0u);
+  }
+  uint32_t* sorted = msgs;
+  if (is_first) sorted[rank] = v;
+  __syncthreads();
+  // ---- the result block
+  uint32_t* out_pos = out + sizeof(FriCloseHeader) / 4u;
+  uint32_t* out_coeffs = out_pos + n_queries;
+  if (tid < n_positions) out_pos[tid] = sorted[tid];
+  for (uint32_t k = tid; k < n_coeff_words; k += blockDim.x) out_coeffs[k] = coeffs[k];
+  if (tid < 8u) {
+    hdr->digest_after_coeffs[tid] = scr[16u + tid];
+    hdr->digest_after_nonce[tid] = msg[tid];
+    hdr->digest_end[tid] = msg[tid];   // (draws leave the digest alone)
+    ch->digest[tid] = msg[tid];
+  }
+  if (tid == 0u) {
+    ch->n_sent = n_draws;
+    hdr->found = 1u;
+    hdr->first_bad = st->first_bad;
+    hdr->n_positions = n_positions;
+    hdr->n_sent_end = n_draws;
+    hdr->nonce_lo = (uint32_t)nonce;
+    hdr->nonce_hi = (uint32_t)(nonce >> 32);
+  }
+}
+
+void launch_fri_queries(DevChannel* ch, const FriCloseState* st, const uint32_t* coeffs, uint32_t n_coeff_words,
+                        bool hashed, uint32_t n_queries, uint32_t pos_mask, uint32_t* out, lmn_stream_t s) {
+  if (!ch || !st || !coeffs || !out || n_queries < 1u || n_queries > FRI_CLOSE_MAX_QUERIES)
+    throw LmnError(-100, "fri_queries: bad arguments");
+  LMN_LAUNCH(k_fri_queries, dim3(1), dim3(FRI_CLOSE_TPB), 0, s, ch, st, coeffs, n_coeff_words, hashed ? 1 : 0, n_queries,
+             pos_mask, out);
 }
 
 }  // namespace lmn

@@ -527,6 +527,76 @@ void Context::col_fri_commit(const lmn_col* const* cols, uint32_t n, const uint8
   lmn_sync(stream_);
 }
 
+// ---- the close of the FRI transcript on a handle (lmn_col_fri_close): prove()'s own chain (phase_fri.cpp
+// enqueue_fri_close / finish_fri_close) on a caller-given last layer and start digest
+FriCloseOut::~FriCloseOut() {
+  free(r.coeffs);
+  free(r.positions);
+}
+lmn_fri_close_result FriCloseOut::release() {
+  lmn_fri_close_result o = r;
+  r = lmn_fri_close_result{};
+  return o;
+}
+
+void Context::col_fri_close(const lmn_col* last_layer, const uint8_t start_digest[32], uint32_t log_query_domain,
+                            FriCloseOut& out) {
+  const char* F = "fri_close: ";
+  auto refuse = [&](const std::string& what) { throw LmnError(LMN_ERR_INVALID_ARGUMENT, F + what); };
+  if (shard_.active) refuse("ctx is sharded (lmn_ctx_set_shard): the transcript is closed on an unsharded context only");
+  if (!last_layer) refuse("last_layer is null");
+  if (!start_digest) refuse("start_digest is null");
+  if (log_query_domain > 31) refuse("log_query_domain is " + u32s(log_query_domain) + ", at most 31");
+  const int last_log = (int)cfg.log_last_layer + (int)cfg.log_blowup;
+  if (last_layer->ncols != 4 || (int)last_layer->log_size != last_log)
+    refuse("last_layer has " + u32s(last_layer->ncols) + " columns of log size " + u32s(last_layer->log_size) +
+           ": the last layer is 4 coordinate columns of log size " + u32s(last_log) + " (log_last_layer + log_blowup)");
+  set_device();
+  ensure_twiddles(last_log + 1);
+  arena_.reserve(((size_t)8 << last_log) * 4 + (1u << 20));
+  begin_op();
+  reset_event_log();
+  Channel channel(cfg.protocol_variant);
+  Hash32 d0;
+  memcpy(d0.w, start_digest, 32);
+  channel.set_digest(d0);
+  DevChannel hc{};
+  memcpy(hc.digest, d0.w, 32);
+  hc.n_sent = 0;
+  hc.variant = (cfg.protocol_variant & LMN_PV_DRAW_CTR_U32) ? 1u : 0u;
+  FriClose fc;
+  try {
+    DevChannel* d_ch = (DevChannel*)stage_upload(&hc, sizeof hc);
+    enqueue_fri_close(fc, last_layer->d, d_ch, log_query_domain);
+    lmn_sync(stream_);
+    finish_fri_close(fc, channel, [&] {
+      const size_t n = (size_t)1 << last_log;
+      const uint32_t* raw = (const uint32_t*)stage_download(last_layer->d, 16 * n);
+      lmn_sync(stream_);
+      std::vector<QM31> v(n);
+      for (size_t i = 0; i < n; ++i) v[i] = QM31{raw[i], raw[n + i], raw[2 * n + i], raw[3 * n + i]};
+      return v;
+    }, false);
+  } catch (...) {
+    lmn_sync(stream_);   // launches in flight read tables in the staging memory the next op reuses
+    throw;
+  }
+  lmn_fri_close_result& o = out.r;
+  o.n_coeffs = (uint32_t)fc.coeffs.size();
+  o.first_bad = fc.first_bad;
+  o.n_positions = (uint32_t)fc.positions.size();
+  o.grind_rounds = (uint32_t)fc.grind_waits;
+  o.nonce = fc.nonce;
+  o.coeffs = malloc_words(4 * fc.coeffs.size());
+  memcpy(o.coeffs, fc.coeffs.data(), 16 * fc.coeffs.size());
+  o.positions = malloc_words(fc.positions.size());
+  memcpy(o.positions, fc.positions.data(), 4 * fc.positions.size());
+  memcpy(o.digest_after_coeffs, fc.digest_after_coeffs.w, 32);
+  memcpy(o.digest_after_nonce, fc.digest_after_nonce.w, 32);
+  memcpy(o.digest_end, fc.digest_after_nonce.w, 32);   // (draws leave the digest alone)
+  o.n_sent_end = fc.n_sent_end;
+}
+
 void Context::col_accumulate(lmn_col* dst, const lmn_col* src) {
   set_device();
   if (dst->ncols != src->ncols || dst->log_size != src->log_size)
@@ -904,6 +974,17 @@ int lmn_col_fri_commit(lmn_ctx* ctx, const lmn_col* const* cols, uint32_t n, con
     if (!result) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "fri_commit: result is null");
     lmn::FriCommitOut o;
     ctx->impl->col_fri_commit(cols, n, start_digest, o);
+    *result = o.release();
+  });
+}
+int lmn_col_fri_close(lmn_ctx* ctx, const lmn_col* last_layer, const uint8_t start_digest[32], uint32_t log_query_domain,
+                      lmn_fri_close_result* result) {
+  if (result) *result = lmn_fri_close_result{};
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  return guard2(ctx, [&] {
+    if (!result) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "fri_close: result is null");
+    lmn::FriCloseOut o;
+    ctx->impl->col_fri_close(last_layer, start_digest, log_query_domain, o);
     *result = o.release();
   });
 }

@@ -4,8 +4,7 @@
 
 namespace lmn {
 
-// the words one nonce is hashed with: the channel's digest, or its prefixed digest in the prefixed form
-static PowWords pow_words_of(const Channel& ch, uint32_t pow_bits, bool& kat) {
+PowWords pow_words_of(const Channel& ch, uint32_t pow_bits, bool& kat) {
   const bool prefixed = (ch.flags() & LMN_PV_POW_PREFIXED) != 0;
   kat = !prefixed && !(ch.flags() & LMN_PV_MIX_U64_HASHED);
   PowWords w;
@@ -18,29 +17,39 @@ static PowWords pow_words_of(const Channel& ch, uint32_t pow_bits, bool& kat) {
 // until one holds a passing nonce; its minimum is the host loop's answer (Channel::grind).  The window grows with
 // pow_bits (about two expected hits per window) up to pow_window_log_, the cap that keeps one launch well under a
 // millisecond (2^24 nonces: 0.24 ms measured), so that other contexts' launches interleave.
-//
-// Launches queued per host wait, here and in grind_many's rounds: one behind the launch that found a nonce returns at
-// once (every block sees the smaller nonce at its start), so the queue costs a few us of launches and saves waits while
-// nothing has been found.  (grind_many on 64 digests at pow_bits 20: 4 is within the spread of 8, 16 is 5 - 8 % slower.)
-constexpr int POW_WINDOWS_PER_WAIT = 8;
+// (POW_WINDOWS_PER_WAIT launches per host wait: kernels.h)
+
+int Context::grind_window_log(uint32_t pow_bits) const {
+  return std::min(pow_window_log_, std::max(POW_MIN_WINDOW_LOG, (int)pow_bits + 1));
+}
 
 uint64_t Context::device_grind(const Channel& ch, uint32_t pow_bits) {
   bool kat;
   const PowWords w = pow_words_of(ch, pow_bits, kat);
+#ifndef LMN_BATCH
+  ++counters_[0];   // (the lock-step build counts in grind_many, where its grinds go)
+#endif
+  return device_grind_from(w, kat, pow_bits, 0);
+}
+
+uint64_t Context::device_grind_from(const PowWords& w, bool kat, uint32_t pow_bits, uint64_t base) {
 #ifdef LMN_BATCH
   // lock-step members must issue identical sequences, and this loop's length depends on the digest: the members grind
-  // together, in one collective (grind_many below); a thread outside any batch is a group of one
+  // together, in one collective (grind_many below); a thread outside any batch is a group of one.  (From nonce 0 on
+  // whatever `base` says: the rounds are the collective's.)
+  (void)base;
   return grind_many(&w, 1, kat, pow_bits)[0];
 #else
   if (!pow_best_) pow_best_ = (unsigned long long*)lmn_dev_malloc(sizeof(unsigned long long));
   unsigned long long* found = (unsigned long long*)pin_alloc(sizeof(unsigned long long));
-  const int wlog = std::min(pow_window_log_, std::max(POW_MIN_WINDOW_LOG, (int)pow_bits + 1));
+  const int wlog = grind_window_log(pow_bits);
   lmn_memset(pow_best_, 0xff, sizeof(unsigned long long), stream_);
-  for (uint64_t base = 0;;) {
+  for (;;) {
     for (int k = 0; k < POW_WINDOWS_PER_WAIT; ++k, base += 1ull << wlog)
       launch_pow_grind(w, kat, base, wlog, pow_bits, pow_best_, stream_);
     lmn_d2h(found, pow_best_, sizeof(unsigned long long), stream_);
     lmn_sync(stream_);
+    ++counters_[1];
     if (*found != ~0ull) return *found;
   }
 #endif
@@ -108,6 +117,7 @@ uint64_t Context::grind_rounds(const PowWords* w, uint32_t n, bool kat, uint32_t
     pow_d2h(h_best, d_best, n * sizeof(u64), stream_);
     pow_wait(stream_);
     ++waits;
+    ++counters_[1];
     uint32_t kept = 0;   // (the table just uploaded is read by launches that have finished: it may be rewritten)
     for (uint32_t i = 0; i < n_pending; ++i)
       if (h_best[h_pend[i]] == ~0ull) h_pend[kept++] = h_pend[i];
@@ -145,6 +155,7 @@ uint64_t Context::grind_collective(void* arg, const BatchCollectiveItem* items, 
 std::vector<uint64_t> Context::grind_many(const PowWords* w, uint32_t n, bool kat, uint32_t pow_bits) {
   std::vector<uint64_t> nonces(n);
   if (n == 0) return nonces;
+  ++counters_[0];
 #ifdef LMN_BATCH
   GrindJob job{this, kat, pow_bits};
   batch_collective(&Context::grind_collective, &job, w, n, nonces.data(), stream_);
@@ -159,22 +170,28 @@ uint64_t Context::grind(const Channel& ch, uint32_t pow_bits) {
   return ch.grind(pow_bits);
 }
 
+std::vector<uint32_t> draw_query_positions(Channel& channel, uint32_t n_queries, uint32_t log_domain) {
+  std::set<uint32_t> qs;
+  uint64_t cnt = 0;
+  const uint32_t mask = (uint32_t)((1ull << log_domain) - 1u);
+  while (cnt < n_queries) {
+    Hash32 r = channel.draw_random_words();
+    for (int i = 0; i < 8 && cnt < n_queries; ++i, ++cnt) qs.insert(r.w[i] & mask);
+  }
+  return std::vector<uint32_t>(qs.begin(), qs.end());
+}
+
 void Context::run_queries(ProofRun& r) {
   LMN_RUN_ALIASES(r);
   // ---- proof of work + queries
-  proof.proof_of_work = grind(channel, cfg.pow_bits);
-  channel.mix_u64(proof.proof_of_work);
   const int ls0 = quots[0].log;
-  queries.clear();
-  {
-    std::set<uint32_t> qs;
-    uint64_t cnt = 0;
-    const uint32_t mask = (1u << ls0) - 1u;
-    while (cnt < cfg.n_queries) {
-      Hash32 r = channel.draw_random_words();
-      for (int i = 0; i < 8 && cnt < cfg.n_queries; ++i, ++cnt) qs.insert(r.w[i] & mask);
-    }
-    queries.assign(qs.begin(), qs.end());
+  if (r.close.on) {   // closed on the device, replayed by run_fri_commit
+    proof.proof_of_work = r.close.nonce;
+    queries = r.close.positions;
+  } else {
+    proof.proof_of_work = grind(channel, cfg.pow_bits);
+    channel.mix_u64(proof.proof_of_work);
+    queries = draw_query_positions(channel, cfg.n_queries, (uint32_t)ls0);
   }
   pos_by_log.clear();
   for (int ls : sizes) pos_by_log[ls] = fold_positions(queries, ls0 - ls);

@@ -265,6 +265,7 @@ void Context::fri_commit_layers(ProofRun& r) {
     if (n_roots > fp.max_layers || layer_log != fp.last_size_log || layer != fp.d_last)
       throw LmnError(LMN_ERR_INTERNAL, "FRI: the layer plan does not match the layers committed");
     last_log = layer_log;
+    if (r.close.on) enqueue_fri_close(r.close, fp.d_last, d_ch, (uint32_t)ls0);   // its results arrive with this wait
     // roots | alphas | last layer: one block, one download
     if (!h_out) h_out = (const uint32_t*)stage_download(fp.d_out, fp.out_bytes);
     const uint32_t* h_roots = h_out;
@@ -295,45 +296,149 @@ void Context::fri_commit_layers(ProofRun& r) {
   hm.mark("fri synced+replayed");
 }
 
+// The last layer's polynomial on the host: the line interpolation of its evaluation (bit-reversed over
+// LineDomain(half_odds(last_log))), all 2^last_log coefficients
+std::vector<QM31> interpolate_last_layer(const std::vector<QM31>& last_vals, int last_log) {
+  std::vector<std::vector<QM31>> chunks{last_vals};
+  int dlog = last_log;
+  // x-coordinates of the current line domain in bit-reversed order
+  auto line_xs = [&](int lg) {
+    std::vector<uint32_t> xs(1u << lg);
+    uint32_t init = 1u << (31 - (lg + 2)), step = lg >= 1 ? (1u << (31 - lg)) : 0u;
+    for (uint32_t i = 0; i < (1u << lg); ++i) xs[i] = pt_of_index(init + bit_reverse(i, lg) * step).x;
+    return xs;
+  };
+  while (dlog > 0) {
+    std::vector<uint32_t> xs = line_xs(dlog);
+    std::vector<std::vector<QM31>> nc;
+    for (auto& ch : chunks) {
+      std::vector<QM31> f0, f1;
+      for (size_t i = 0; i < ch.size() / 2; ++i) {
+        QM31 a = ch[2 * i], b = ch[2 * i + 1];
+        f0.push_back(q_add(a, b));
+        f1.push_back(q_mul_m(q_sub(a, b), m_inv(xs[2 * i])));
+      }
+      nc.push_back(f0);
+      nc.push_back(f1);
+    }
+    chunks.swap(nc);
+    // after halving, the remaining domain is the doubled line domain
+    dlog -= 1;
+  }
+  uint32_t n = 1u << last_log;
+  uint32_t ninv = m_inv(n % P31);
+  std::vector<QM31> coeffs(n);
+  for (uint32_t idx = 0; idx < n; ++idx) {
+    uint32_t j = 0;
+    for (int k = 0; k < last_log; ++k) j |= ((idx >> (last_log - 1 - k)) & 1u) << k;
+    coeffs[j] = q_mul_m(chunks[idx][0], ninv);
+  }
+  return coeffs;
+}
+
+// ---- the close of the transcript on the device (kernels.h launch_fri_close): enqueued behind whatever produces the last
+// layer, so that its results arrive with the same wait
+void Context::enqueue_fri_close(FriClose& fc, const uint32_t* d_last, DevChannel* d_ch, uint32_t log_query_domain) {
+  const bool prefixed = (cfg.protocol_variant & LMN_PV_POW_PREFIXED) != 0;
+  const bool hashed = (cfg.protocol_variant & LMN_PV_MIX_U64_HASHED) != 0;
+  fc.log_n = (int)cfg.log_last_layer + (int)cfg.log_blowup;
+  fc.n_queries = cfg.n_queries;
+  fc.log_query_domain = log_query_domain;
+  fc.kat = !prefixed && !hashed;
+  fc.window_log = grind_window_log(cfg.pow_bits);
+  if (fc.log_n > FRI_CLOSE_MAX_LOG || fc.log_n + 1 > tw_max_log_ || log_query_domain > 31)
+    throw LmnError(LMN_ERR_INTERNAL, "FRI close: a last layer or a query domain the chain was not built for");
+  const uint32_t n = 1u << fc.log_n, bound = 1u << cfg.log_last_layer;
+  FriCloseItw itw{};
+  for (int d = 1; d <= fc.log_n; ++d) itw.p[d] = itwX_[d + 1];
+  fc.d_state = (FriCloseState*)arena_.alloc_words(sizeof(FriCloseState) / 4);
+  uint32_t* d_coeffs = arena_.alloc_words(4ull * n);
+  uint32_t* scratch = fc.log_n > FRI_CLOSE_LDS_LOG ? arena_.alloc_words(4ull * n) : nullptr;
+  uint32_t* block = (uint32_t*)result_block(sizeof(FriCloseHeader) + 4ull * (fc.n_queries + 4ull * bound));
+  fc.h_block = block;
+  launch_fri_close(d_ch, d_last, fc.log_n, (int)cfg.log_last_layer, itw, m_inv(n % P31), scratch, d_coeffs, prefixed,
+                   cfg.pow_bits, fc.d_state, stream_);
+  // the grind's first round (device_grind's), on the words k_fri_close left: one digest, its one pending entry
+  for (int k = 0; k < POW_WINDOWS_PER_WAIT; ++k)
+    launch_grind_many(&fc.d_state->pow, &fc.d_state->pending, 1u, fc.kat, (uint64_t)k << fc.window_log, fc.window_log,
+                      cfg.pow_bits, &fc.d_state->best, stream_);
+  launch_fri_queries(d_ch, fc.d_state, d_coeffs, 4u * bound, hashed, fc.n_queries, (uint32_t)((1ull << log_query_domain) - 1u),
+                     block, stream_);
+  ++counters_[0];
+  fc.on = true;
+}
+
+// Behind the wait: the host replays mix_felts, the nonce's check, mix_u64 and the query draw on its own channel and
+// compares.  No nonce in the queued windows (found == 0): the kernels behind the grind did nothing - the host interpolates
+// `last_vals()` itself, goes on with device_grind's rounds where the queue ended, and mixes and draws as it always did.
+void Context::finish_fri_close(FriClose& fc, Channel& channel, const std::function<std::vector<QM31>()>& last_vals,
+                               bool refuse_bad_degree) {
+  const FriCloseHeader& h = *reinterpret_cast<const FriCloseHeader*>(fc.h_block);
+  const uint32_t bound = 1u << cfg.log_last_layer;
+  auto diverged = [] { throw LmnError(LMN_ERR_INTERNAL, "device/host transcript divergence in the FRI close"); };
+  fc.found = h.found == 1u;
+  if (fc.found) {
+    const uint32_t* cw = fc.h_block + sizeof(FriCloseHeader) / 4 + fc.n_queries;
+    fc.coeffs.resize(bound);
+    for (uint32_t j = 0; j < bound; ++j) fc.coeffs[j] = QM31{cw[4 * j], cw[4 * j + 1], cw[4 * j + 2], cw[4 * j + 3]};
+    fc.first_bad = h.first_bad;
+  } else {
+    std::vector<QM31> all = interpolate_last_layer(last_vals(), fc.log_n);
+    fc.first_bad = 0xffffffffu;
+    for (uint32_t j = (uint32_t)all.size(); j-- > bound;)
+      if (!q_is_zero(all[j])) fc.first_bad = j;
+    all.resize(bound);
+    fc.coeffs.swap(all);
+  }
+  if (refuse_bad_degree && fc.first_bad != 0xffffffffu) throw LmnError(LMN_ERR_INTERNAL, "FRI: invalid last-layer degree");
+  channel.mix_felts(fc.coeffs);
+  fc.digest_after_coeffs = channel.digest();
+  if (fc.found) {
+    if (memcmp(fc.digest_after_coeffs.w, h.digest_after_coeffs, 32) != 0) diverged();
+    fc.nonce = (uint64_t)h.nonce_hi << 32 | h.nonce_lo;
+    if (!channel.verify_pow_nonce(cfg.pow_bits, fc.nonce)) diverged();
+  } else {
+    bool kat;
+    const PowWords w = pow_words_of(channel, cfg.pow_bits, kat);
+    const uint64_t waits = counters_[1];
+    fc.nonce = device_grind_from(w, kat, cfg.pow_bits, (uint64_t)POW_WINDOWS_PER_WAIT << fc.window_log);
+    fc.grind_waits = counters_[1] - waits;
+  }
+  channel.mix_u64(fc.nonce);
+  fc.digest_after_nonce = channel.digest();
+  fc.positions = draw_query_positions(channel, fc.n_queries, fc.log_query_domain);
+  fc.n_sent_end = channel.n_sent();
+  if (fc.found) {
+    const uint32_t* pw = fc.h_block + sizeof(FriCloseHeader) / 4;
+    if (memcmp(fc.digest_after_nonce.w, h.digest_end, 32) != 0 || h.n_sent_end != fc.n_sent_end ||
+        h.n_positions != fc.positions.size() || memcmp(pw, fc.positions.data(), fc.positions.size() * 4) != 0)
+      diverged();
+  }
+}
+
 void Context::run_fri_commit(ProofRun& r) {
+  // LMN_DEVICE_FRI_CLOSE=1 (docs/SWITCHES.md): the transcript's close joins the layer loop's launches wherever the proof
+  // would otherwise wait a third time, for a device grind.  Off by default: the wait it saves did not show in a solo
+  // proof's latency ("Proof of work").  The lock-step build keeps the grind a collective of its members.
+#ifndef LMN_BATCH
+  r.close.on = !shard_.active && r.quot_dev && (int)cfg.pow_bits >= pow_device_min_bits_ && env_set("LMN_DEVICE_FRI_CLOSE");
+#endif
   fri_commit_layers(r);
   LMN_RUN_ALIASES(r);
+  if (r.close.on) {
+    FriClose& fc = r.close;
+    ++counters_[2];
+    finish_fri_close(fc, channel, [&] { return last_vals; }, true);
+    if (!fc.found) ++counters_[3];
+    proof.last_layer_coeffs = fc.coeffs;
+    proof.last_layer_log_size = cfg.log_last_layer;
+    hm.mark("last layer (device close)");
+    return;
+  }
   // last layer: interpolate the line evaluation (bit-reversed over LineDomain(half_odds(last_log)))
   {
-    std::vector<std::vector<QM31>> chunks{last_vals};
-    int dlog = last_log;
-    // x-coordinates of the current line domain in bit-reversed order
-    auto line_xs = [&](int lg) {
-      std::vector<uint32_t> xs(1u << lg);
-      uint32_t init = 1u << (31 - (lg + 2)), step = lg >= 1 ? (1u << (31 - lg)) : 0u;
-      for (uint32_t i = 0; i < (1u << lg); ++i) xs[i] = pt_of_index(init + bit_reverse(i, lg) * step).x;
-      return xs;
-    };
-    while (dlog > 0) {
-      std::vector<uint32_t> xs = line_xs(dlog);
-      std::vector<std::vector<QM31>> nc;
-      for (auto& ch : chunks) {
-        std::vector<QM31> f0, f1;
-        for (size_t i = 0; i < ch.size() / 2; ++i) {
-          QM31 a = ch[2 * i], b = ch[2 * i + 1];
-          f0.push_back(q_add(a, b));
-          f1.push_back(q_mul_m(q_sub(a, b), m_inv(xs[2 * i])));
-        }
-        nc.push_back(f0);
-        nc.push_back(f1);
-      }
-      chunks.swap(nc);
-      // after halving, the remaining domain is the doubled line domain
-      dlog -= 1;
-    }
+    std::vector<QM31> coeffs = interpolate_last_layer(last_vals, last_log);
     uint32_t n = 1u << last_log;
-    uint32_t ninv = m_inv(n % P31);
-    std::vector<QM31> coeffs(n);
-    for (uint32_t idx = 0; idx < n; ++idx) {
-      uint32_t j = 0;
-      for (int k = 0; k < last_log; ++k) j |= ((idx >> (last_log - 1 - k)) & 1u) << k;
-      coeffs[j] = q_mul_m(chunks[idx][0], ninv);
-    }
     uint32_t bound = 1u << cfg.log_last_layer;
     for (uint32_t j = bound; j < n; ++j)
       if (!q_is_zero(coeffs[j])) throw LmnError(LMN_ERR_INTERNAL, "FRI: invalid last-layer degree");

@@ -28,6 +28,27 @@ struct FriLayer {
   DevMerkle merkle;
 };
 
+// The close of the FRI transcript as a device chain (phase_fri.cpp enqueue_fri_close / finish_fri_close): what was
+// enqueued, and - after the wait and the host's replay - what it found.  prove() and lmn_col_fri_close share it.
+struct FriClose {
+  bool on = false;
+  int log_n = 0;                        // the last layer: 2^log_n values (log_last_layer + log_blowup)
+  uint32_t n_queries = 0, log_query_domain = 0;
+  bool kat = false;                     // the form the grind examines (k_grind_many<KAT>)
+  int window_log = 0;                   // device_grind's window: POW_WINDOWS_PER_WAIT of them are queued
+  FriCloseState* d_state = nullptr;
+  const uint32_t* h_block = nullptr;    // page-locked result block (FriCloseHeader | positions | coefficients)
+  // results
+  bool found = false;                   // a nonce lay in the queued windows
+  std::vector<QM31> coeffs;             // the first 2^log_last_layer
+  uint32_t first_bad = 0xffffffffu;
+  uint64_t nonce = 0;
+  uint64_t grind_waits = 0;             // host waits spent grinding behind the chain's own wait (the fallback)
+  std::vector<uint32_t> positions;
+  Hash32 digest_after_coeffs{}, digest_after_nonce{};
+  uint32_t n_sent_end = 0;
+};
+
 struct ProofRun {
   explicit ProofRun(uint32_t protocol_flags) : channel(protocol_flags) {}
   // inputs (borrowed)
@@ -107,12 +128,20 @@ struct ProofRun {
   } fri;
   std::vector<QM31> last_vals;
   int last_log = 0;
+  FriClose close;   // on: the transcript is closed on the device, in front of the FRI wait
   std::vector<uint32_t> queries;
   std::map<int, std::vector<uint32_t>> pos_by_log;
   bool sharded_log(int lg) const { return sh && lg > fri_T; }
   ProofRun(const ProofRun&) = delete;
   ProofRun& operator=(const ProofRun&) = delete;
 };
+
+// shared by the host's and the device's close of the transcript (phase_fri.cpp, phase_decommit.cpp)
+std::vector<QM31> interpolate_last_layer(const std::vector<QM31>& last_vals, int last_log);
+// the words one nonce is hashed with: the channel's digest, or its prefixed digest in the prefixed form
+PowWords pow_words_of(const Channel& ch, uint32_t pow_bits, bool& kat);
+// Queries::generate: n_queries positions, 8 per draw_random_words, masked to log_domain bits; ascending and distinct
+std::vector<uint32_t> draw_query_positions(Channel& channel, uint32_t n_queries, uint32_t log_domain);
 
 // the four coordinate columns of a secure column as tree columns
 inline void secure_columns(const uint32_t* vals, int lg, bool s, int g, std::vector<ColRef>& out) {

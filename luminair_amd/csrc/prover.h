@@ -156,6 +156,13 @@ struct FriCommitOut {
   lmn_fri_commit_result release();
 };
 
+// what lmn_col_fri_close hands to its caller (lmn_fri_close_result)
+struct FriCloseOut {
+  lmn_fri_close_result r{};
+  ~FriCloseOut();
+  lmn_fri_close_result release();
+};
+
 // the caller-facing limits of one accumulate_quotients call (level2.cpp): LMN_ERR_INVALID_ARGUMENT past them
 void check_quotient_limits(const uint32_t* sample_point, uint32_t nsamples);
 
@@ -236,6 +243,7 @@ class Prepared {
 
 struct StageTimer;
 
+struct FriClose;   // the device chain that closes the FRI transcript (prove_run.h)
 struct ProofRun;   // state of one proof across the phases of Context::prove (prove_run.h)
 
 class Context {
@@ -303,6 +311,9 @@ class Context {
   void col_gather(const lmn_col* c, const uint32_t* positions, uint32_t n, uint32_t* host_out);
   // FriProver::commit without the last layer's interpolation: prove()'s layer loop (fri_commit_layers) on column handles
   void col_fri_commit(const lmn_col* const* cols, uint32_t n, const uint8_t start_digest[32], FriCommitOut& out);
+  // what FriProver::commit and the query phase do behind the layer loop, as one device chain (enqueue_fri_close): the last
+  // layer's polynomial and degree check, mix_felts, the grind, mix_u64, Queries::generate
+  void col_fri_close(const lmn_col* last_layer, const uint8_t start_digest[32], uint32_t log_query_domain, FriCloseOut& out);
   void col_accumulate(lmn_col* dst, const lmn_col* src);
   lmn_col* col_accumulate_quotients(const lmn_col* const* cols, uint32_t n, const uint32_t* sample_col,
                                     const uint32_t* sample_point, const uint32_t* sample_values, uint32_t nsamples,
@@ -362,6 +373,9 @@ class Context {
   void trace_check(const lmn_table* tables, size_t n_tables, const lmn_settings* settings, lmn_trace_report& report);
 
   int device() const { return device_; }
+  // lmn_ctx_counter - 7: device grinds started, 8: host waits inside grind rounds, 9: proofs whose transcript was closed on
+  // the device, 10: those among them that fell back to the host's grind rounds; 0 for any other number
+  uint64_t counter(int which) const { return which >= 7 && which <= 10 ? counters_[which - 7] : 0; }
   lmn_config cfg;
   lmn_timings timings{};
   bool profiling = false;  // record HIP events around stages/kernels (lmn_set_profiling)
@@ -385,6 +399,12 @@ class Context {
   void run_quotients(ProofRun& r);
   void run_fri_commit(ProofRun& r);
   void fri_commit_layers(ProofRun& r);   // phase_fri.cpp: the layer loop, shared with col_fri_commit
+  // phase_fri.cpp, shared with col_fri_close: the chain k_fri_close | grind windows | k_fri_queries behind what produces
+  // `d_last` and leaves `d_ch` behind the last alpha; after the next wait, the host's replay on `channel` and its
+  // cross-check.  `last_vals`: the last layer on the host, fetched only if no nonce lay in the queued windows.
+  void enqueue_fri_close(FriClose& fc, const uint32_t* d_last, DevChannel* d_ch, uint32_t log_query_domain);
+  void finish_fri_close(FriClose& fc, Channel& channel, const std::function<std::vector<QM31>()>& last_vals,
+                        bool refuse_bad_degree);
   void run_queries(ProofRun& r);
   void run_decommit(ProofRun& r);
   std::vector<uint8_t> run_finish(ProofRun& r);
@@ -504,6 +524,10 @@ class Context {
   unsigned long long* pow_best_ = nullptr;   // device: the smallest passing nonce found so far (allocated on first use)
   uint64_t grind(const Channel& ch, uint32_t pow_bits);          // the proof's path: device or host by pow_device_min_bits_
   uint64_t device_grind(const Channel& ch, uint32_t pow_bits);
+  // device_grind's rounds from nonce `base` on (every nonce below it has been examined and fails)
+  uint64_t device_grind_from(const PowWords& w, bool kat, uint32_t pow_bits, uint64_t base);
+  int grind_window_log(uint32_t pow_bits) const;   // the window of device_grind's launches
+  uint64_t counters_[4] = {0, 0, 0, 0};            // counter()
   // grind_many's rounds; its tables (digests | best | pending, device and page-locked host) grow on demand
   uint64_t grind_rounds(const PowWords* w, uint32_t n, bool kat, uint32_t pow_bits, uint64_t* nonces);
   char *pow_many_dev_ = nullptr, *pow_many_host_ = nullptr;
