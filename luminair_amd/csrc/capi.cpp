@@ -83,9 +83,8 @@ uint32_t lmn_kind_columns(uint32_t kind) {
 int lmn_kind_padding_row(uint32_t kind, uint32_t* out) {
   const lmn::ComponentSpec* s = lmn::component_spec((int)kind);
   if (!s || !out) return LMN_ERR_INVALID_ARGUMENT;
-  for (int c = 0; c < s->n_cols; ++c) out[c] = 0u;
-  if (s->is_last_col >= 0) out[s->is_last_col] = 1u;
-  for (int k = 0; k < s->n_pad; ++k) out[s->pad_col[k]] = s->pad_val[k];
+  const lmn::PadRow pad = lmn::pad_row_of(*s);
+  for (int c = 0; c < s->n_cols; ++c) out[c] = pad.v[c];
   return LMN_OK;
 }
 

@@ -62,6 +62,15 @@ struct QPt {
 inline QPt qpt_add_m(QPt a, Pt b) {  // secure point + base point
   return {q_sub(q_mul_m(a.x, b.x), q_mul_m(a.y, b.y)), q_add(q_mul_m(a.x, b.y), q_mul_m(a.y, b.x))};
 }
+// secure field elements and points as the C boundary passes them: 4 words, 8 words (x, then y)
+inline QM31 q_words(const uint32_t* w) { return QM31{w[0], w[1], w[2], w[3]}; }
+inline QPt qpt_words(const uint32_t* w) { return {q_words(w), q_words(w + 4)}; }
+inline void store_words(uint32_t out[4], QM31 q) {
+  out[0] = q.a;
+  out[1] = q.b;
+  out[2] = q.c;
+  out[3] = q.d;
+}
 
 // ------------------------------------------------------------------------------------ channel
 inline Hash32 b2_hash_bytes(const uint8_t* data, size_t n) {

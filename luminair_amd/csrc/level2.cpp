@@ -154,13 +154,9 @@ void Context::col_eval_at_point(const lmn_col* co, uint32_t column, const uint32
   if (column >= co->ncols) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "eval_at_point: column index out of range");
   arena_.reserve(8u << 20);
   begin_op();
-  QPt p{{pt[0], pt[1], pt[2], pt[3]}, {pt[4], pt[5], pt[6], pt[7]}};
-  std::vector<QM31> r = eval_at_points({{co->d + ((uint64_t)column << co->log_size), (int)co->log_size, 0}}, {p},
+  std::vector<QM31> r = eval_at_points({{co->d + ((uint64_t)column << co->log_size), (int)co->log_size, 0}}, {qpt_words(pt)},
                                        (int)co->log_size);
-  out[0] = r[0].a;
-  out[1] = r[0].b;
-  out[2] = r[0].c;
-  out[3] = r[0].d;
+  store_words(out, r[0]);
 }
 
 // frees a tree handle (and its device slab) when the op that fills it throws
@@ -618,6 +614,17 @@ void check_quotient_limits(const uint32_t* sample_point, uint32_t nsamples) {
   }
 }
 
+QuotientSamples parse_quotient_samples(uint32_t ncols, const uint32_t* sample_col, const uint32_t* sample_point,
+                                       const uint32_t* sample_values, uint32_t nsamples, const uint32_t* points_xy, uint32_t npoints) {
+  QuotientSamples s{std::vector<QPt>(npoints), std::vector<std::vector<std::pair<int, QM31>>>(ncols)};
+  for (uint32_t p = 0; p < npoints; ++p) s.points[p] = qpt_words(points_xy + 8 * p);
+  for (uint32_t i = 0; i < nsamples; ++i) {
+    if (sample_col[i] >= ncols || sample_point[i] >= npoints) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "bad sample index");
+    s.of_col[sample_col[i]].push_back({(int)sample_point[i], q_words(sample_values + 4 * i)});
+  }
+  return s;
+}
+
 lmn_col* Context::col_accumulate_quotients(const lmn_col* const* cols, uint32_t n, const uint32_t* sample_col,
                                            const uint32_t* sample_point, const uint32_t* sample_values, uint32_t nsamples,
                                            const uint32_t* points_xy, uint32_t npoints, const uint32_t alpha[4]) {
@@ -635,23 +642,13 @@ lmn_col* Context::col_accumulate_quotients(const lmn_col* const* cols, uint32_t 
   check_canonical(points_xy, 8ull * npoints, "accumulate_quotients: point");
   check_canonical(sample_values, 4ull * nsamples, "accumulate_quotients: sample value");
   check_canonical(alpha, 4, "accumulate_quotients: alpha");
-  std::vector<QPt> pts(npoints);
-  for (uint32_t p = 0; p < npoints; ++p) {
-    const uint32_t* w = points_xy + 8 * p;
-    pts[p] = {{w[0], w[1], w[2], w[3]}, {w[4], w[5], w[6], w[7]}};
-  }
-  std::vector<std::vector<std::pair<int, QM31>>> smp(ncols);
-  for (uint32_t i = 0; i < nsamples; ++i) {
-    if (sample_col[i] >= ncols || sample_point[i] >= npoints) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "bad sample index");
-    const uint32_t* v = sample_values + 4 * i;
-    smp[sample_col[i]].push_back({(int)sample_point[i], QM31{v[0], v[1], v[2], v[3]}});
-  }
+  const QuotientSamples smp = parse_quotient_samples(ncols, sample_col, sample_point, sample_values, nsamples, points_xy, npoints);
   ensure_twiddles((int)log_size);
   arena_.reserve(8u << 20);
   begin_op();
   lmn_col* out = new_col(4, log_size);
   try {
-    QuotientArgs a = make_quotient_args((int)log_size, d_cols, smp, pts, QM31{alpha[0], alpha[1], alpha[2], alpha[3]}, false);
+    QuotientArgs a = make_quotient_args((int)log_size, d_cols, smp.of_col, smp.points, q_words(alpha), false);
     a.out = out->d;
     launch_quotients(a, stream_);
     lmn_sync(stream_);  // the (pointer, coefficient) table lives in the arena, which the next op resets
@@ -672,7 +669,7 @@ lmn_col* Context::col_fold_line(const lmn_col* src, const uint32_t alpha[4]) {
   ensure_twiddles((int)src->log_size + 1);
   arena_.reserve(8u << 20);
   begin_op();
-  std::vector<QM31> av{QM31{alpha[0], alpha[1], alpha[2], alpha[3]}};
+  std::vector<QM31> av{q_words(alpha)};
   QM31* d_alpha = upload_vec(av);
   ColGuard out(new_col(4, src->log_size - 1));
   launch_fold_line(out.c->d, src->d, 1u << src->log_size, itwX_[src->log_size + 1], d_alpha, stream_);
@@ -688,7 +685,7 @@ void Context::col_fold_circle_into_line(lmn_col* dst, const lmn_col* src, const 
   ensure_twiddles((int)src->log_size);
   arena_.reserve(8u << 20);
   begin_op();
-  std::vector<QM31> av{QM31{alpha[0], alpha[1], alpha[2], alpha[3]}};
+  std::vector<QM31> av{q_words(alpha)};
   QM31* d_alpha = upload_vec(av);
   launch_fold_circle_into_line(dst->d, src->d, 1u << src->log_size, itwY_[src->log_size], d_alpha, 1, stream_);
   lmn_sync(stream_);
@@ -705,10 +702,7 @@ lmn_col* Context::col_decompose(const lmn_col* f, uint32_t lambda_out[4]) {
   launch_decompose(f->d, (int)f->log_size, g->d, d_lambda, scratch, stream_);
   const QM31* l = (const QM31*)stage_download(d_lambda, sizeof(QM31));
   lmn_sync(stream_);
-  lambda_out[0] = l->a;
-  lambda_out[1] = l->b;
-  lambda_out[2] = l->c;
-  lambda_out[3] = l->d;
+  store_words(lambda_out, *l);
   return gg.release();
 }
 
@@ -752,8 +746,6 @@ static const ComponentSpec* spec_or_throw(uint32_t kind, const char* what) {
   if (!sp) throw LmnError(LMN_ERR_INVALID_ARGUMENT, std::string(what) + ": unknown component kind");
   return sp;
 }
-static QM31 q_words(const uint32_t* w) { return QM31{w[0], w[1], w[2], w[3]}; }
-
 lmn_col* Context::col_logup(uint32_t kind, const lmn_col* main, const lmn_col* pre, const uint32_t* elems,
                             uint32_t claimed_out[4]) {
   set_device();
@@ -791,10 +783,7 @@ lmn_col* Context::col_logup(uint32_t kind, const lmn_col* main, const lmn_col* p
                     m_inv((uint32_t)(n % P31)));
   const QM31* cs = (const QM31*)stage_download(d_cs, 2 * sizeof(QM31));
   lmn_sync(stream_);
-  claimed_out[0] = cs[0].a;
-  claimed_out[1] = cs[0].b;
-  claimed_out[2] = cs[0].c;
-  claimed_out[3] = cs[0].d;
+  store_words(claimed_out, cs[0]);
   return out.release();
 }
 

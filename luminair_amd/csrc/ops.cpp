@@ -106,12 +106,8 @@ void Context::op_eval_at_point(const uint32_t* coeffs, uint32_t log_size, const 
   begin_op();
   uint32_t* d = arena_.alloc_words(1ull << log_size);
   lmn_h2d(d, coeffs, 4ull << log_size, stream_);
-  QPt p{{pt[0], pt[1], pt[2], pt[3]}, {pt[4], pt[5], pt[6], pt[7]}};
-  std::vector<QM31> r = eval_at_points({{d, (int)log_size, 0}}, {p}, (int)log_size);
-  out[0] = r[0].a;
-  out[1] = r[0].b;
-  out[2] = r[0].c;
-  out[3] = r[0].d;
+  std::vector<QM31> r = eval_at_points({{d, (int)log_size, 0}}, {qpt_words(pt)}, (int)log_size);
+  store_words(out, r[0]);
 }
 
 // QuotientOps::accumulate_quotients for the columns of one LDE size
@@ -131,18 +127,8 @@ void Context::op_accumulate_quotients(uint32_t log_size, const uint32_t* const* 
     lmn_h2d(d, cols[c], L * 4, stream_);
     d_cols[c] = d;
   }
-  std::vector<QPt> pts(npoints);
-  for (uint32_t p = 0; p < npoints; ++p) {
-    const uint32_t* w = points_xy + 8 * p;
-    pts[p] = {{w[0], w[1], w[2], w[3]}, {w[4], w[5], w[6], w[7]}};
-  }
-  std::vector<std::vector<std::pair<int, QM31>>> smp(ncols);
-  for (uint32_t i = 0; i < nsamples; ++i) {
-    if (sample_col[i] >= ncols || sample_point[i] >= npoints) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "bad sample index");
-    const uint32_t* v = sample_values + 4 * i;
-    smp[sample_col[i]].push_back({(int)sample_point[i], QM31{v[0], v[1], v[2], v[3]}});
-  }
-  QuotientArgs a = make_quotient_args((int)log_size, d_cols, smp, pts, QM31{alpha[0], alpha[1], alpha[2], alpha[3]});
+  const QuotientSamples smp = parse_quotient_samples(ncols, sample_col, sample_point, sample_values, nsamples, points_xy, npoints);
+  QuotientArgs a = make_quotient_args((int)log_size, d_cols, smp.of_col, smp.points, q_words(alpha));
   launch_quotients(a, stream_);
   lmn_d2h(out, a.out, 16 * L, stream_);
   lmn_sync(stream_);
@@ -159,7 +145,7 @@ void Context::op_fold(int circle, uint32_t* dst, const uint32_t* src, uint32_t l
   uint32_t* d_src = arena_.alloc_words(4 * L);
   uint32_t* d_dst = arena_.alloc_words(2 * L);
   lmn_h2d(d_src, src, 16 * L, stream_);
-  std::vector<QM31> av{QM31{alpha[0], alpha[1], alpha[2], alpha[3]}};
+  std::vector<QM31> av{q_words(alpha)};
   QM31* d_alpha = upload_vec(av);
   if (circle) {
     lmn_h2d(d_dst, dst, 8 * L, stream_);

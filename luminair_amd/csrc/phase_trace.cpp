@@ -22,23 +22,19 @@ void Context::run_preprocessed(ProofRun& r) {
     // read-only with every other proof that uses it.  Nothing is checked on the host, uploaded, transformed or hashed, and
     // the host does not wait: the root is known.
     const Prepared& pp = *r.prepared;
-    uint32_t present = 0;
-    for (auto& ti : infos) {
-      if (ti.spec->kind == LMN_KIND_SIN_LOOKUP) present |= LMN_LOOKUP_SIN;
-      if (ti.spec->kind == LMN_KIND_EXP2_LOOKUP) present |= LMN_LOOKUP_EXP2;
-      if (ti.spec->kind == LMN_KIND_LOG2_LOOKUP) present |= LMN_LOOKUP_LOG2;
-      if (ti.spec->kind == LMN_KIND_RANGE_CHECK_LOOKUP) present |= LMN_LOOKUP_RANGE_CHECK;
-    }
+    const uint32_t present = lookups_present(infos);
     if (present & ~pp.lookups)
       throw LmnError(LMN_ERR_INVALID_ARGUMENT, "the pie holds a lookup table the settings were not prepared for");
     if (pp.lookups & ~present)
       throw LmnError(LMN_ERR_INVALID_ARGUMENT, "the settings were prepared for a lookup whose table is not in the pie");
-    for (auto& ci : inst)
-      for (int k = 0; k < ci.spec->n_pre; ++k)
-        if (ci.log_size != pp.log_of_pre[ci.spec->pre_id[k]])
-          throw LmnError(LMN_ERR_INVALID_ARGUMENT, ci.spec->pre_id[k] == PRE_RANGE_CHECK
-                                                       ? "RangeCheckLookup table must have exactly 256 rows"
-                                                       : "lookup table rows must match the LUT column size");
+    lmn_lut sized[3] = {};   // the prepared LUTs as lut_for_table reads them: their sizes (the columns are the object's)
+    Luts luts;
+    for (int k = 0; k < 3; ++k)
+      if (pp.log_of_pre[2 * k] >= 0) {
+        sized[k].log_size = (uint32_t)pp.log_of_pre[2 * k];
+        luts.of[k] = &sized[k];
+      }
+    for (size_t t = 0; t < inst.size(); ++t) lut_for_table(t, *inst[t].spec, inst[t].log_size, luts, Refusal{});
     // (the same components of the same sizes: the same tree-0 order as the prepared object's)
     const std::vector<int> logs = assign_preprocessed(inst);
     if (logs.size() != pp.tree.cols.size()) throw LmnError(LMN_ERR_INTERNAL, "prepared settings: tree-0 layout differs");
@@ -49,46 +45,24 @@ void Context::run_preprocessed(ProofRun& r) {
     return;
   }
   {
-    uint32_t present = 0;
-    const lmn_lut* lut_of[3] = {nullptr, nullptr, nullptr};
-    for (auto& ti : infos) {
-      if (ti.spec->kind == LMN_KIND_SIN_LOOKUP) present |= LMN_LOOKUP_SIN;
-      if (ti.spec->kind == LMN_KIND_EXP2_LOOKUP) present |= LMN_LOOKUP_EXP2;
-      if (ti.spec->kind == LMN_KIND_LOG2_LOOKUP) present |= LMN_LOOKUP_LOG2;
-      if (ti.spec->kind == LMN_KIND_RANGE_CHECK_LOOKUP) present |= LMN_LOOKUP_RANGE_CHECK;
-    }
-    if (settings && (settings->has_lookups & ~present))
-      throw LmnError(LMN_ERR_INVALID_ARGUMENT, "settings announce a lookup whose table is not in the pie");
-    if (settings && settings->n_luts) {
-      if (!settings->luts) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "null luts pointer");
-      for (uint32_t i = 0; i < settings->n_luts; ++i) {
-        const lmn_lut& l = settings->luts[i];
-        if (l.kind > LMN_LUT_LOG2 || !l.col0 || !l.col1 || lut_of[l.kind])
-          throw LmnError(LMN_ERR_INVALID_ARGUMENT, "bad or duplicate LUT in settings");
-        lut_of[l.kind] = &l;
-      }
-    }
+    const Luts luts = luts_for_pie(settings, infos);
     std::vector<int> logs = assign_preprocessed(inst);
     tree0.cols.resize(logs.size());
     pre_evals.resize(logs.size(), nullptr);
-    for (auto& ci : inst) {
+    for (size_t t = 0; t < inst.size(); ++t) {
+      Instance& ci = inst[t];
       const ComponentSpec* sp = ci.spec;
+      const lmn_lut* l = lut_for_table(t, *sp, ci.log_size, luts, Refusal{});
       for (int k = 0; k < sp->n_pre; ++k) {
         const uint64_t n = 1ull << ci.log_size;
         uint32_t* evals;
         if (sp->pre_id[k] == PRE_RANGE_CHECK) {
-          if (ci.log_size != 8) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "RangeCheckLookup table must have exactly 256 rows");
           std::vector<uint32_t> lut(n);
           for (uint32_t r = 0; r < n; ++r) lut[r] = r;
           evals = upload_vec(lut);
         } else {
-          const lmn_lut* l = lut_of[sp->pre_id[k] / 2];
-          if (!l) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "lookup table present but settings carry no LUT columns for it");
-          if ((int)l->log_size != ci.log_size)
-            throw LmnError(LMN_ERR_INVALID_ARGUMENT, "lookup table rows must match the LUT column size");
           const uint32_t* src = (sp->pre_id[k] & 1) ? l->col1 : l->col0;
-          for (uint64_t r = 0; r < n; ++r)
-            if (src[r] >= P31) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "LUT value is not a canonical M31");
+          if (first_noncanonical(src, n) < n) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "LUT value is not a canonical M31");
           evals = arena_.alloc_words(n);
           lmn_h2d(evals, src, n * 4, stream_);
         }
@@ -134,36 +108,21 @@ void Context::build_prepared(Prepared& out, const lmn_settings* settings, uint32
   out.log_blowup = cfg.log_blowup;
   if (lookups & ~(LMN_LOOKUP_SIN | LMN_LOOKUP_EXP2 | LMN_LOOKUP_LOG2 | LMN_LOOKUP_RANGE_CHECK))
     throw LmnError(LMN_ERR_INVALID_ARGUMENT, "lmn_settings_prepare: unknown bits in `lookups`");
-  const lmn_lut* lut_of[3] = {nullptr, nullptr, nullptr};
-  if (settings && settings->n_luts) {
-    if (!settings->luts) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "null luts pointer");
-    for (uint32_t i = 0; i < settings->n_luts; ++i) {
-      const lmn_lut& l = settings->luts[i];
-      if (l.kind > LMN_LUT_LOG2 || !l.col0 || !l.col1 || lut_of[l.kind])
-        throw LmnError(LMN_ERR_INVALID_ARGUMENT, "bad or duplicate LUT in settings (unknown kind, null column, or a kind given twice)");
-      // the bounds run_setup puts on the lookup table that will have the LUT's size
-      if (l.log_size < 4 || l.log_size > 26 || (int)l.log_size + lb + 2 > MAX_LOG - 2)
-        throw LmnError(LMN_ERR_INVALID_ARGUMENT, "LUT log_size " + std::to_string(l.log_size) +
-                                                     " is outside what the prover takes (at least 4, and at most what a trace table may have)");
-      lut_of[l.kind] = &l;
-    }
-  }
-  static const int kLookupKind[3] = {LMN_KIND_SIN_LOOKUP, LMN_KIND_EXP2_LOOKUP, LMN_KIND_LOG2_LOOKUP};
+  const Luts luts = parse_luts(settings);
+  for (const lmn_lut* l : luts.of)
+    // the bounds scan_tables puts on the lookup table that will have the LUT's size
+    if (l && (l->log_size < 4 || l->log_size > 26 || (int)l->log_size + lb + 2 > MAX_LOG - 2))
+      throw LmnError(LMN_ERR_INVALID_ARGUMENT, "LUT log_size " + std::to_string(l->log_size) +
+                                                   " is outside what the prover takes (at least 4, and at most what a trace table may have)");
   static const char* const kLookupName[3] = {"sin", "exp2", "log2"};
-  std::vector<Instance> inst;   // the lookup components of the pies to come, in gen_trace order (ascending kind)
-  for (int k = 0; k < 3; ++k) {
-    if (!(lookups & (1u << k))) continue;
-    if (!lut_of[k])
-      throw LmnError(LMN_ERR_INVALID_ARGUMENT, std::string("lookups announce ") + kLookupName[k] + " but the settings carry no LUT columns for it");
+  std::vector<Instance> inst;   // the lookup components of the pies to come, in the order of a pie's tables (ascending kind)
+  for (int k = 0; k < 4; ++k) {
+    if (!(lookups & kLookupKinds[k].bit)) continue;
     Instance ci{};
-    ci.spec = component_spec(kLookupKind[k]);
-    ci.log_size = (int)lut_of[k]->log_size;
-    inst.push_back(ci);
-  }
-  if (lookups & LMN_LOOKUP_RANGE_CHECK) {
-    Instance ci{};
-    ci.spec = component_spec(LMN_KIND_RANGE_CHECK_LOOKUP);
-    ci.log_size = 8;
+    ci.spec = component_spec(kLookupKinds[k].kind);
+    // the rows its table will have - the LUT's, the range check's 256 - so of the table's rules only the LUT's presence can fail
+    ci.log_size = k < 3 && luts.of[k] ? (int)luts.of[k]->log_size : 8;
+    lut_for_table(inst.size(), *ci.spec, ci.log_size, luts, Refusal{});
     inst.push_back(ci);
   }
   const std::vector<int> logs = assign_preprocessed(inst);
@@ -195,7 +154,7 @@ void Context::build_prepared(Prepared& out, const lmn_settings* settings, uint32
         pc.range_check = evals;
         pc.range_n = (uint32_t)n;
       } else {
-        const lmn_lut* l = lut_of[id / 2];
+        const lmn_lut* l = luts.of[id / 2];
         lmn_h2d(evals, (id & 1) ? l->col1 : l->col0, n * 4, stream_);
         pc_col[pc.n_luts] = id;
         pc.lut[pc.n_luts] = evals;
@@ -260,9 +219,7 @@ void Context::run_main_trace(ProofRun& r) {
         if (up1 > up0) lmn_h2d(stg, ti.rows + up0 * ti.spec->n_cols, (up1 - up0) * ti.spec->n_cols * 4, stream_);
         d_rows = stg - up0 * ti.spec->n_cols;   // indexed by table row: only rows [up0, up1) are ever read
       }
-      PadRow pad{};
-      if (ti.spec->is_last_col >= 0) pad.v[ti.spec->is_last_col] = 1u;
-      for (int k = 0; k < ti.spec->n_pad; ++k) pad.v[ti.spec->pad_col[k]] = ti.spec->pad_val[k];
+      const PadRow pad = pad_row_of(*ti.spec);
       inst[t].rows_dev = d_rows;
       inst[t].rows_n = ti.n_rows;
       inst[t].pad = pad;

@@ -8,6 +8,101 @@
 
 namespace lmn {
 
+// ------------------------------------------------------------------------------------ the prover's input rules
+void Refusal::operator()(size_t t, int code, const std::string& why) const {
+  if (!named) throw LmnError(code, why);
+  throw LmnError(code, "table " + std::to_string(t) + " (kind " + std::to_string(named[t].kind) + "): " + why);
+}
+
+int scan_tables(const lmn_table* tables, size_t n_tables, const lmn_config& cfg, bool sharded, int device, lmn_stream_t stream,
+                const Refusal& refuse, std::vector<TableInfo>& infos) {
+  const int n_slots = claim_slots(cfg.protocol_variant), lb = (int)cfg.log_blowup;
+  int max_log = 0, prev_kind = -1;
+  for (size_t t = 0; t < n_tables; ++t) {
+    const lmn_table& tb = tables[t];
+    const ComponentSpec* sp = component_spec((int)tb.kind);
+    if (!sp) refuse(t, LMN_ERR_INVALID_ARGUMENT, "unsupported component kind " + std::to_string(tb.kind));
+    if ((int)tb.kind >= n_slots) refuse(t, LMN_ERR_INVALID_ARGUMENT, "component kind has no claim slot in this protocol variant");
+    if ((int)tb.kind <= prev_kind)
+      refuse(t, LMN_ERR_INVALID_ARGUMENT, "tables must be in gen_trace order (ascending kind, no duplicates)");
+    prev_kind = (int)tb.kind;
+    if (tb.n_rows == 0) refuse(t, LMN_ERR_EMPTY_TRACE, "TraceError::EmptyTrace");
+    if (!tb.rows) refuse(t, LMN_ERR_INVALID_ARGUMENT, "null rows pointer");
+    if (tb.n_rows > (1ull << 26)) refuse(t, LMN_ERR_INVALID_ARGUMENT, "trace table has more than 2^26 rows");
+    const int ls = padded_log(tb.n_rows);
+    if (ls + lb + 2 > MAX_LOG - 2) refuse(t, LMN_ERR_INVALID_ARGUMENT, "trace too large");
+    // A column of 2^(ls + lb) evaluations joins the FRI line layer of 2^(ls + lb - 1); stwo's commit loop ends at the
+    // last layer of 2^(log_last_layer + lb) values and asserts that every column has been consumed by then: a table
+    // of 2^log_last_layer rows or fewer cannot be proved under this PcsConfig (the reference panics)
+    if (ls <= (int)cfg.log_last_layer)
+      refuse(t, LMN_ERR_INVALID_ARGUMENT, "a table needs more than 2^log_last_layer rows (after padding)");
+    const bool cols = (tb.flags & LMN_TABLE_COLS_ON_DEVICE) != 0;
+    if (cols) {
+      if (tb.flags & LMN_TABLE_ROWS_ON_DEVICE)
+        refuse(t, LMN_ERR_INVALID_ARGUMENT, "a table is LMN_TABLE_ROWS_ON_DEVICE or LMN_TABLE_COLS_ON_DEVICE, not both");
+#ifdef LMN_BATCH
+      refuse(t, LMN_ERR_INVALID_ARGUMENT, "LMN_TABLE_COLS_ON_DEVICE (row sinks) is not supported by the batch library");
+#else
+      if (sharded)
+        refuse(t, LMN_ERR_INVALID_ARGUMENT, "LMN_TABLE_COLS_ON_DEVICE (row sinks) is not supported on a sharded context");
+      try {
+        rows_sink_attach(tb, device, stream);   // the stream waits for the sink's finish event; the host does not
+      } catch (const LmnError& e) {
+        refuse(t, e.code, e.what());
+      }
+#endif
+    }
+    infos.push_back({sp, tb.n_rows, ls, tb.rows, (tb.flags & LMN_TABLE_ROWS_ON_DEVICE) != 0, cols});
+    max_log = std::max(max_log, ls);
+  }
+  return max_log;
+}
+
+uint32_t lookups_present(const std::vector<TableInfo>& infos) {
+  uint32_t present = 0;
+  for (const TableInfo& ti : infos)
+    for (const LookupKind& lk : kLookupKinds)
+      if (ti.spec->kind == lk.kind) present |= lk.bit;
+  return present;
+}
+
+Luts parse_luts(const lmn_settings* settings) {
+  Luts luts;
+  if (!settings || !settings->n_luts) return luts;
+  require_luts_pointer(*settings);
+  for (uint32_t i = 0; i < settings->n_luts; ++i) {
+    const lmn_lut& l = settings->luts[i];
+    if (l.kind > LMN_LUT_LOG2 || !l.col0 || !l.col1 || luts.of[l.kind])
+      throw LmnError(LMN_ERR_INVALID_ARGUMENT, "bad or duplicate LUT in settings (unknown kind, null column, or a kind given twice)");
+    luts.of[l.kind] = &l;
+  }
+  return luts;
+}
+
+Luts luts_for_pie(const lmn_settings* settings, const std::vector<TableInfo>& infos) {
+  if (settings && (settings->has_lookups & ~lookups_present(infos)))
+    throw LmnError(LMN_ERR_INVALID_ARGUMENT, "settings announce a lookup whose table is not in the pie");
+  return parse_luts(settings);
+}
+
+const lmn_lut* lut_for_table(size_t t, const ComponentSpec& spec, int log_size, const Luts& luts, const Refusal& refuse) {
+  if (spec.n_pre == 0) return nullptr;
+  if (spec.pre_id[0] == PRE_RANGE_CHECK) {
+    if (log_size != 8) refuse(t, LMN_ERR_INVALID_ARGUMENT, "RangeCheckLookup table must have exactly 256 rows");
+    return nullptr;
+  }
+  const lmn_lut* l = luts.of[spec.pre_id[0] / 2];
+  if (!l) refuse(t, LMN_ERR_INVALID_ARGUMENT, "lookup table present but settings carry no LUT columns for it");
+  if ((int)l->log_size != log_size) refuse(t, LMN_ERR_INVALID_ARGUMENT, "lookup table rows must match the LUT column size");
+  return l;
+}
+
+uint64_t first_noncanonical(const uint32_t* words, uint64_t n) {
+  uint64_t i = 0;
+  while (i < n && words[i] < P31) ++i;
+  return i;
+}
+
 #ifdef LMN_BATCH
 void Context::prepare_for(const lmn_table* tables, size_t n_tables) {
   LMN_HIP_CHECK(hipSetDevice(device_));
@@ -15,9 +110,7 @@ void Context::prepare_for(const lmn_table* tables, size_t n_tables) {
   int max_log = 0;
   for (size_t t = 0; t < n_tables; ++t) {
     if (tables[t].n_rows == 0 || tables[t].n_rows > (1ull << 26)) return;
-    int ls = 4;
-    while ((1ull << ls) < tables[t].n_rows) ++ls;
-    max_log = std::max(max_log, ls);
+    max_log = std::max(max_log, padded_log(tables[t].n_rows));
   }
   const int max_lde = max_log + 1 + (int)cfg.log_blowup;
   if (max_lde > MAX_LOG - 2) return;
@@ -103,54 +196,18 @@ std::vector<uint8_t> Context::prove(const lmn_table* tables, size_t n_tables, co
 
 void Context::run_setup(ProofRun& r) {
   LMN_RUN_ALIASES(r);
-  const lmn_table* tables = r.tables;
-  const size_t n_tables = r.n_tables;
-  // ---- validate + size
-  int max_log = 0;
-  int prev_kind = -1;
+  // ---- validate (the input rules above), then size the arena
+  const int max_log = scan_tables(r.tables, r.n_tables, cfg, shard_.active, device_, stream_, Refusal{}, infos);
   size_t words = 0;
   // a sharded context holds only its row block of every LDE / Merkle layer / large FRI layer
   const int size_g = shard_.active ? shard_.g : 0;
   auto row_split = [&](uint64_t w) { return size_g ? (w >> size_g) + 8192 : w; };
-  for (size_t t = 0; t < n_tables; ++t) {
-    const lmn_table& tb = tables[t];
-    const ComponentSpec* sp = component_spec((int)tb.kind);
-    if (!sp) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "unsupported component kind " + std::to_string(tb.kind));
-    if ((int)tb.kind >= n_slots)
-      throw LmnError(LMN_ERR_INVALID_ARGUMENT, "component kind has no claim slot in this protocol variant");
-    if ((int)tb.kind <= prev_kind)
-      throw LmnError(LMN_ERR_INVALID_ARGUMENT, "tables must be in gen_trace order (ascending kind, no duplicates)");
-    prev_kind = (int)tb.kind;
-    if (tb.n_rows == 0) throw LmnError(LMN_ERR_EMPTY_TRACE, "TraceError::EmptyTrace");
-    if (!tb.rows) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "null rows pointer");
-    if (tb.n_rows > (1ull << 26)) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "trace table has more than 2^26 rows");
-    uint64_t size = 16;
-    while (size < tb.n_rows) size <<= 1;
-    int ls = 0;
-    while ((1ull << ls) < size) ++ls;
-    if (ls + lb + 2 > MAX_LOG - 2) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "trace too large");
-    // A column of 2^(ls + lb) evaluations joins the FRI line layer of 2^(ls + lb - 1); stwo's commit loop ends at the
-    // last layer of 2^(log_last_layer + lb) values and asserts that every column has been consumed by then: a table
-    // of 2^log_last_layer rows or fewer cannot be proved under this PcsConfig (the reference panics)
-    if (ls <= (int)cfg.log_last_layer)
-      throw LmnError(LMN_ERR_INVALID_ARGUMENT, "a table needs more than 2^log_last_layer rows (after padding)");
-    infos.push_back({sp, tb.n_rows, ls, tb.rows, (tb.flags & LMN_TABLE_ROWS_ON_DEVICE) != 0});
-    if (tb.flags & LMN_TABLE_COLS_ON_DEVICE) {
-      if (tb.flags & LMN_TABLE_ROWS_ON_DEVICE)
-        throw LmnError(LMN_ERR_INVALID_ARGUMENT, "a table is LMN_TABLE_ROWS_ON_DEVICE or LMN_TABLE_COLS_ON_DEVICE, not both");
-#ifdef LMN_BATCH
-      throw LmnError(LMN_ERR_INVALID_ARGUMENT, "LMN_TABLE_COLS_ON_DEVICE (row sinks) is not supported by the batch library");
-#else
-      if (shard_.active)
-        throw LmnError(LMN_ERR_INVALID_ARGUMENT, "LMN_TABLE_COLS_ON_DEVICE (row sinks) is not supported on a sharded context");
-      rows_sink_attach(tb, device_, stream_);   // the proof's stream waits for the sink's finish event; the host does not
-      infos.back().cols_on_device = true;
-#endif
-    }
-    max_log = std::max(max_log, ls);
+  for (const TableInfo& ti : infos) {
+    const ComponentSpec* sp = ti.spec;
+    const int ls = ti.log_size;
     uint64_t cells = (uint64_t)(sp->n_cols + 4 * sp->n_rel) << ls;
     words += cells * 2 + row_split(cells << lb);               // evals + coeffs + lde (this rank's row block)
-    if (!infos.back().on_device && !infos.back().cols_on_device) words += tb.n_rows * sp->n_cols;  // staging
+    if (!ti.on_device && !ti.cols_on_device) words += ti.n_rows * sp->n_cols;  // staging
     if (!r.prepared) words += (uint64_t)sp->n_pre * ((2ull << ls) + row_split(2ull << ls));  // preprocessed columns: evals + coeffs + lde
     words += (4ull << ls) * 2;                                 // logup temps
     words += (4ull << (ls + 1)) * 3;                           // per-size composition scratch

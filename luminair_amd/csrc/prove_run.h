@@ -14,6 +14,36 @@ struct TableInfo {
   bool on_device;
   bool cols_on_device = false;   // LMN_TABLE_COLS_ON_DEVICE: `rows` = a finished row sink's padded columns, 2^log_size apart
 };
+
+// ---- The prover's input rules: which pie and which settings it takes.  Stated once (bodies in prove.cpp) for lmn_prove
+// (run_setup, run_preprocessed), lmn_trace_check and lmn_settings_prepare (build_prepared).
+// How a broken rule is answered: lmn_prove throws the rule's text as it is, lmn_trace_check names the table in front of it
+// ("table T (kind K): ").  Only ever called on the refusing path: nothing is built where a pie is accepted.
+struct Refusal {
+  const lmn_table* named = nullptr;   // the pie whose tables the text names; null: the bare text
+  [[noreturn]] void operator()(size_t t, int code, const std::string& why) const;
+};
+// log size of the padded table: the smallest power of two >= n_rows, and at least 2^4
+inline int padded_log(uint64_t n_rows) {
+  int ls = 4;
+  while ((1ull << ls) < n_rows) ++ls;
+  return ls;
+}
+// The rules on the tables, in table order; a row-sink table's columns are attached to `stream` (rows_sink_attach) when the
+// table has passed, before the next one is looked at.  Fills `infos`, returns the largest log size.
+int scan_tables(const lmn_table* tables, size_t n_tables, const lmn_config& cfg, bool sharded, int device, lmn_stream_t stream,
+                const Refusal& refuse, std::vector<TableInfo>& infos);
+uint32_t lookups_present(const std::vector<TableInfo>& infos);   // LMN_LOOKUP_* bits of the lookup tables in the pie
+struct Luts {
+  const lmn_lut* of[3] = {nullptr, nullptr, nullptr};   // by LMN_LUT_* kind
+};
+Luts parse_luts(const lmn_settings* settings);           // no null pointer, unknown kind, null column or kind given twice
+Luts luts_for_pie(const lmn_settings* settings, const std::vector<TableInfo>& infos);   // and no lookup announced without its table
+// the rules on one lookup table's size: 256 rows for the range check, the rows of its LUT (which the settings must carry)
+// otherwise.  Returns that LUT; null for the range check and for a component without preprocessed columns.
+const lmn_lut* lut_for_table(size_t t, const ComponentSpec& spec, int log_size, const Luts& luts, const Refusal& refuse);
+uint64_t first_noncanonical(const uint32_t* words, uint64_t n);   // index of the first word >= 2^31 - 1; n: all are canonical
+
 // one FRI quotient column (the columns of one LDE size accumulated)
 struct Quot {
   int log;

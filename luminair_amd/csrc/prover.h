@@ -16,6 +16,27 @@ namespace lmn {
 
 // kSpecs[kind] (constraints.h); nullptr for an unknown kind
 const ComponentSpec* component_spec(int kind);
+// The lookup components and the LMN_LOOKUP_* bit that announces each: the LUT-backed ones first, in LMN_LUT_* order (entry k
+// reads the LUT of kind k and has bit 1 << k), then the 8-bit range check, whose column the library generates.
+struct LookupKind {
+  int kind;
+  uint32_t bit;
+};
+constexpr LookupKind kLookupKinds[4] = {{LMN_KIND_SIN_LOOKUP, LMN_LOOKUP_SIN},
+                                        {LMN_KIND_EXP2_LOOKUP, LMN_LOOKUP_EXP2},
+                                        {LMN_KIND_LOG2_LOOKUP, LMN_LOOKUP_LOG2},
+                                        {LMN_KIND_RANGE_CHECK_LOOKUP, LMN_LOOKUP_RANGE_CHECK}};
+// settings that count LUTs point to them: the one rule on the LUT list that the prover and the verifier share
+inline void require_luts_pointer(const lmn_settings& s) {
+  if (s.n_luts && !s.luts) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "null luts pointer");
+}
+// the row a component's table is padded with: is_last = 1 and the spec's padding values, zero elsewhere
+inline PadRow pad_row_of(const ComponentSpec& sp) {
+  PadRow pad{};
+  if (sp.is_last_col >= 0) pad.v[sp.is_last_col] = 1u;
+  for (int k = 0; k < sp.n_pad; ++k) pad.v[sp.pad_col[k]] = sp.pad_val[k];
+  return pad;
+}
 // relation element sets drawn after the main commitment (components/mod.rs:227-235, lookups/mod.rs:44-51)
 struct RelElems {
   QM31 z[N_ELEMS], alpha[N_ELEMS];
@@ -165,6 +186,14 @@ struct FriCloseOut {
 
 // the caller-facing limits of one accumulate_quotients call (level2.cpp): LMN_ERR_INVALID_ARGUMENT past them
 void check_quotient_limits(const uint32_t* sample_point, uint32_t nsamples);
+// the sample points and each column's (point, value) list of such a call, as make_quotient_args takes them;
+// LMN_ERR_INVALID_ARGUMENT for a sample that names a column or a point the call does not have
+struct QuotientSamples {
+  std::vector<QPt> points;
+  std::vector<std::vector<std::pair<int, QM31>>> of_col;
+};
+QuotientSamples parse_quotient_samples(uint32_t ncols, const uint32_t* sample_col, const uint32_t* sample_point,
+                                       const uint32_t* sample_values, uint32_t nsamples, const uint32_t* points_xy, uint32_t npoints);
 
 // A trace table that a HOST producer fills chunk by chunk while it works (lmn_rows_*, trace_gen.cpp): column-major in
 // HBM from the first push on, so that what is left between the last row and the proof is one chunk's transfer, the padding

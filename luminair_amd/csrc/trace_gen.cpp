@@ -1,6 +1,6 @@
 // The step before the path: `process_trace` of the reference's operators on device-resident tensors
 // (crates/graph/src/op/prim.rs), filling trace-table rows in HBM.  Host side of the lmn_trace_* entry points.
-#include "prover_internal.h"
+#include "prove_run.h"
 
 #include <algorithm>
 
@@ -387,86 +387,17 @@ void Context::trace_check(const lmn_table* tables, size_t n_tables, const lmn_se
   LMN_HIP_CHECK(hipSetDevice(device_));
 #endif
   if (!tables || n_tables == 0) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "no trace tables");
-  // ---- the rules of lmn_prove's setup (prove.cpp run_setup, phase_trace.cpp run_preprocessed), in its order and with its
-  // codes; the text names the table
-  struct Info {
-    const ComponentSpec* spec;
-    int log_size;
-    bool on_device, cols;
-  };
-  std::vector<Info> infos;
-  const int n_slots = claim_slots(cfg.protocol_variant), lb = (int)cfg.log_blowup;
-  int prev_kind = -1;
-  auto refuse = [&](size_t t, int code, const std::string& why) {
-    throw LmnError(code, "table " + std::to_string(t) + " (kind " + std::to_string(tables[t].kind) + "): " + why);
-  };
+  // ---- lmn_prove's input rules (prove_run.h): the same calls in the same order, so the same rule is named with the
+  // same code; the text names the table
+  const Refusal refuse{tables};
+  std::vector<TableInfo> infos;
+  scan_tables(tables, n_tables, cfg, shard_.active, device_, stream_, refuse, infos);
+  const Luts luts = luts_for_pie(settings, infos);
   for (size_t t = 0; t < n_tables; ++t) {
-    const lmn_table& tb = tables[t];
-    const ComponentSpec* sp = component_spec((int)tb.kind);
-    if (!sp) refuse(t, LMN_ERR_INVALID_ARGUMENT, "unsupported component kind");
-    if ((int)tb.kind >= n_slots) refuse(t, LMN_ERR_INVALID_ARGUMENT, "component kind has no claim slot in this protocol variant");
-    if ((int)tb.kind <= prev_kind)
-      refuse(t, LMN_ERR_INVALID_ARGUMENT, "tables must be in gen_trace order (ascending kind, no duplicates)");
-    prev_kind = (int)tb.kind;
-    if (tb.n_rows == 0) refuse(t, LMN_ERR_EMPTY_TRACE, "TraceError::EmptyTrace");
-    if (!tb.rows) refuse(t, LMN_ERR_INVALID_ARGUMENT, "null rows pointer");
-    if (tb.n_rows > (1ull << 26)) refuse(t, LMN_ERR_INVALID_ARGUMENT, "trace table has more than 2^26 rows");
-    int ls = 4;
-    while ((1ull << ls) < tb.n_rows) ++ls;
-    if (ls + lb + 2 > MAX_LOG - 2) refuse(t, LMN_ERR_INVALID_ARGUMENT, "trace too large");
-    if (ls <= (int)cfg.log_last_layer)
-      refuse(t, LMN_ERR_INVALID_ARGUMENT, "a table needs more than 2^log_last_layer rows (after padding)");
-    const bool cols = (tb.flags & LMN_TABLE_COLS_ON_DEVICE) != 0;
-    if (cols) {
-      if (tb.flags & LMN_TABLE_ROWS_ON_DEVICE)
-        refuse(t, LMN_ERR_INVALID_ARGUMENT, "a table is LMN_TABLE_ROWS_ON_DEVICE or LMN_TABLE_COLS_ON_DEVICE, not both");
-#ifdef LMN_BATCH
-      refuse(t, LMN_ERR_INVALID_ARGUMENT, "LMN_TABLE_COLS_ON_DEVICE (row sinks) is not supported by the batch library");
-#else
-      if (shard_.active)
-        refuse(t, LMN_ERR_INVALID_ARGUMENT, "LMN_TABLE_COLS_ON_DEVICE (row sinks) is not supported on a sharded context");
-      try {
-        rows_sink_attach(tb, device_, stream_);   // this stream waits for the sink's finish event; the host does not
-      } catch (const LmnError& e) {
-        refuse(t, e.code, e.what());
-      }
-#endif
-    }
-    infos.push_back({sp, ls, (tb.flags & LMN_TABLE_ROWS_ON_DEVICE) != 0, cols});
-  }
-  const lmn_lut* lut_of[3] = {nullptr, nullptr, nullptr};
-  {
-    uint32_t present = 0;
-    for (auto& ti : infos) {
-      if (ti.spec->kind == LMN_KIND_SIN_LOOKUP) present |= LMN_LOOKUP_SIN;
-      if (ti.spec->kind == LMN_KIND_EXP2_LOOKUP) present |= LMN_LOOKUP_EXP2;
-      if (ti.spec->kind == LMN_KIND_LOG2_LOOKUP) present |= LMN_LOOKUP_LOG2;
-      if (ti.spec->kind == LMN_KIND_RANGE_CHECK_LOOKUP) present |= LMN_LOOKUP_RANGE_CHECK;
-    }
-    if (settings && (settings->has_lookups & ~present))
-      throw LmnError(LMN_ERR_INVALID_ARGUMENT, "settings announce a lookup whose table is not in the pie");
-    if (settings && settings->n_luts) {
-      if (!settings->luts) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "null luts pointer");
-      for (uint32_t i = 0; i < settings->n_luts; ++i) {
-        const lmn_lut& l = settings->luts[i];
-        if (l.kind > LMN_LUT_LOG2 || !l.col0 || !l.col1 || lut_of[l.kind])
-          throw LmnError(LMN_ERR_INVALID_ARGUMENT, "bad or duplicate LUT in settings");
-        lut_of[l.kind] = &l;
-      }
-    }
-    for (size_t t = 0; t < n_tables; ++t) {
-      const ComponentSpec* sp = infos[t].spec;
-      if (sp->n_pre == 0) continue;
-      if (sp->pre_id[0] == PRE_RANGE_CHECK) {
-        if (infos[t].log_size != 8) refuse(t, LMN_ERR_INVALID_ARGUMENT, "RangeCheckLookup table must have exactly 256 rows");
-        continue;
-      }
-      const lmn_lut* l = lut_of[sp->pre_id[0] / 2];
-      if (!l) refuse(t, LMN_ERR_INVALID_ARGUMENT, "lookup table present but settings carry no LUT columns for it");
-      if ((int)l->log_size != infos[t].log_size) refuse(t, LMN_ERR_INVALID_ARGUMENT, "lookup table rows must match the LUT column size");
-      for (uint64_t r = 0; r < (1ull << l->log_size); ++r)
-        if (l->col0[r] >= P31 || l->col1[r] >= P31) refuse(t, LMN_ERR_INVALID_ARGUMENT, "LUT value is not a canonical M31");
-    }
+    const lmn_lut* l = lut_for_table(t, *infos[t].spec, infos[t].log_size, luts, refuse);
+    const uint64_t n = 1ull << infos[t].log_size;
+    if (l && (first_noncanonical(l->col0, n) < n || first_noncanonical(l->col1, n) < n))
+      refuse(t, LMN_ERR_INVALID_ARGUMENT, "LUT value is not a canonical M31");
   }
 
   // ---- scratch: the counters, one tuple table per element set the pie uses, device copies of host rows and LUT columns
@@ -506,7 +437,7 @@ void Context::trace_check(const lmn_table* tables, size_t n_tables, const lmn_se
     tb.n_rows = tables[t].n_rows;
     tb.stride = 1ull << infos[t].log_size;
     tb.table = (uint32_t)t;
-    if (infos[t].on_device || infos[t].cols) {
+    if (infos[t].on_device || infos[t].cols_on_device) {
       tb.data = tables[t].rows;
     } else {
       const size_t bytes = (size_t)tb.n_rows * sp->n_cols * 4;
@@ -518,7 +449,7 @@ void Context::trace_check(const lmn_table* tables, size_t n_tables, const lmn_se
       const int k = sp->pre_id[0] / 2;
       for (int h = 0; h < 2; ++h) {
         uint32_t* d = (uint32_t*)scratch.get((size_t)tb.n_rows * 4, "a LUT column");
-        lmn_h2d(d, h ? lut_of[k]->col1 : lut_of[k]->col0, (size_t)tb.n_rows * 4, stream_);
+        lmn_h2d(d, h ? luts.of[k]->col1 : luts.of[k]->col0, (size_t)tb.n_rows * 4, stream_);
         d_lut[k][h] = d;
       }
       tb.pre0 = d_lut[k][0];
@@ -534,7 +465,7 @@ void Context::trace_check(const lmn_table* tables, size_t n_tables, const lmn_se
       tb.rel_neg[j] = sp->rel_neg[j];
       tb.rel_pre[j] = sp->rel_pre[j];
     }
-    launch_trace_check(sp->kind, infos[t].cols, tb, out, stream_);
+    launch_trace_check(sp->kind, infos[t].cols_on_device, tb, out, stream_);
   }
   TcFound* d_found = (TcFound*)(d_ctrl + off_found);
   for (int e = 0; e < N_ELEMS; ++e)
@@ -618,10 +549,8 @@ RowSink::RowSink(int device, uint32_t kind, uint64_t capacity_rows)
   if (!spec_) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "row sink: unsupported component kind " + std::to_string(kind));
   if (spec_->n_cols > CHUNK_MAX_COLS) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "row sink: component has too many columns");
   if (cap_ == 0 || cap_ > (1ull << 26)) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "row sink: capacity must be 1 .. 2^26 rows");
-  stride_ = 16;
-  while (stride_ < cap_) stride_ <<= 1;
-  if (spec_->is_last_col >= 0) pad_.v[spec_->is_last_col] = 1u;
-  for (int k = 0; k < spec_->n_pad; ++k) pad_.v[spec_->pad_col[k]] = spec_->pad_val[k];
+  stride_ = 1ull << padded_log(cap_);
+  pad_ = pad_row_of(*spec_);
   lmn_set_device(device_);
   try {
     cols_ = (uint32_t*)lmn_dev_malloc((size_t)spec_->n_cols * stride_ * 4);
@@ -711,8 +640,7 @@ void RowSink::finish(lmn_table* table_out) {
   if (state_ != FILLING)
     throw LmnError(LMN_ERR_INVALID_ARGUMENT, "row sink: finished already (lmn_rows_reset starts the next table)");
   if (count_ == 0) throw LmnError(LMN_ERR_EMPTY_TRACE, "TraceError::EmptyTrace");
-  uint64_t size = 16;   // as lmn_prove derives log_size from n_rows
-  while (size < count_) size <<= 1;
+  const uint64_t size = 1ull << padded_log(count_);   // as lmn_prove derives log_size from n_rows
   lmn_set_device(device_);
   if (size > count_) launch_rows_chunk(nullptr, count_, size - count_, spec_->n_cols, cols_, stride_, pad_, bad_, stream_);
   // a sink opened for more rows than came: columns `size` apart, as the proof's phases index them.  stride_ >= 2 * size,

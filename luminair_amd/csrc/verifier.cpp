@@ -328,11 +328,9 @@ void verify_proof(const uint8_t* data, size_t len, const lmn_config& expect, con
   if (settings) {
     // verifier.rs:47-57 derives the preprocessed column sizes from `settings.lookups`; here they follow from the
     // claim (a LUT column has its lookup component's size), so the settings must describe the same layout
-    static const int kLookupKind[3] = {LMN_KIND_SIN_LOOKUP, LMN_KIND_EXP2_LOOKUP, LMN_KIND_LOG2_LOOKUP};
     uint32_t present = 0;
-    for (int k = 0; k < 3; ++k)
-      if (kLookupKind[k] < n_slots && p.claim[kLookupKind[k]] >= 0) present |= 1u << k;
-    if (LMN_KIND_RANGE_CHECK_LOOKUP < n_slots && p.claim[LMN_KIND_RANGE_CHECK_LOOKUP] >= 0) present |= LMN_LOOKUP_RANGE_CHECK;
+    for (const LookupKind& lk : kLookupKinds)
+      if (lk.kind < n_slots && p.claim[lk.kind] >= 0) present |= lk.bit;
     // The sin / exp2 / log2 LUTs are named by the settings and must match exactly; the 8-bit range-check LUT is
     // generated by the library whenever LessThan is present, so settings may or may not announce it (the
     // pre-expanded `lookups` form does not) - it only must not be announced when the claim lacks it.
@@ -340,11 +338,11 @@ void verify_proof(const uint8_t* data, size_t len, const lmn_config& expect, con
     if (settings->has_lookups & ~present) fail("settings announce a lookup the proof's claim lacks");
     if (settings->has_lookups && (settings->has_lookups & lut_bits) != (present & lut_bits))
       fail("settings.lookups do not match the proof's claim");
-    if (settings->n_luts && !settings->luts) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "null luts pointer");
+    require_luts_pointer(*settings);
     for (uint32_t i = 0; i < settings->n_luts; ++i) {
       const lmn_lut& l = settings->luts[i];
       if (l.kind > LMN_LUT_LOG2) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "bad LUT kind in settings");
-      const int kind = kLookupKind[l.kind];
+      const int kind = kLookupKinds[l.kind].kind;
       if (kind >= n_slots || p.claim[kind] != (int)l.log_size) fail("settings LUT size does not match the proof's claim");
     }
   }

@@ -440,6 +440,108 @@ def check_refusals(lib):
         assert ("table %d " % table) in text, (name, text)
         assert ctx.check_trace(good).ok, name                            # the context is usable afterwards
     assert_clean(ctx.check_trace(act, luts), "the lookup pie itself")
+    check_refusals_rule_by_rule(lib)
+
+
+def _raw_codes(ctx, arr, n, settings):
+    """(code, text) of lmn_trace_check and of lmn_prove on structs made by hand"""
+    L = ctx.lib.lib
+    rep = backend.LmnTraceReport()
+    code = L.lmn_trace_check(ctx.handle, arr, n, C.byref(settings), C.byref(rep))
+    text = L.lmn_last_error(ctx.handle).decode() if code else ""
+    out, out_len = C.POINTER(C.c_uint8)(), C.c_size_t()
+    pcode = L.lmn_prove(ctx.handle, arr, n, C.byref(settings), C.byref(out), C.byref(out_len))
+    ptext = L.lmn_last_error(ctx.handle).decode() if pcode else ""
+    if pcode == 0:
+        L.lmn_free(out)
+    return (code, text), (pcode, ptext)
+
+
+def _prepare_code(ctx, settings, lookups):
+    """the code lmn_settings_prepare answers the same lmn_settings with (tests/prepared_checks.py _raw_prepare)"""
+    L = ctx.lib.lib
+    h = C.c_void_p()
+    rc = L.lmn_settings_prepare(0, C.byref(ctx.config), C.byref(settings), lookups, C.byref(h))
+    if rc == 0:
+        L.lmn_prepared_destroy(h)
+    return rc
+
+
+def check_refusals_rule_by_rule(lib):
+    """One case per rule of the prover's input checks that `check_refusals` above does not reach: the same non-zero code from
+    lmn_trace_check and lmn_prove, the table named where the rule belongs to one, a context that checks a good pie
+    afterwards.  The smallest shapes that reach each rule: 16- to 32-row tables, the 256-row range check, 16-row LUTs."""
+    kat, pinned = ctx_for(lib, KAT), ctx_for(lib, PINNED)
+    cfg = lib.default_config()
+    cfg.protocol_variant = PINNED
+    cfg.log_last_layer = 4
+    last4 = backend.Context(0, cfg, lib)
+    good = pie(syn.chain_graph(20))                                      # Add, Mul, Recip: 20 rows each, padded to 32
+    rows16 = syn.config2_add_only(16, 3)[0][1]
+    lt = pie(syn.less_than_graph(19))
+    rc_at = [k for k, _, _ in lt].index(air.KIND_RANGE_CHECK_LOOKUP)
+    act, luts = syn.activation_graph(5, names=("sin",), ranges={"sin": (-7, 7)})
+    act = pie(act)
+    sin_at = [k for k, _, _ in act].index(air.KIND_SIN_LOOKUP)
+    assert len(luts["sin"][0]) == 16 and len(lt[rc_at][1]) == 256
+    assert kat.check_trace(good).ok and last4.check_trace(good).ok and pinned.check_trace(act, luts).ok
+
+    def first_bad(c0, c1):
+        c0 = c0.copy()
+        c0[0] = P
+        return {"sin": (c0, c1)}
+
+    def last_bad(c0, c1):
+        c1 = c1.copy()
+        c1[-1] = P
+        return {"sin": (c0, c1)}
+
+    col = np.arange(16, dtype=np.uint32)
+    p = col.ctypes.data
+
+    def with_luts(*luts_c):
+        def change(arr, st, keep):
+            keep.append((backend.LmnLut * len(luts_c))(*luts_c))
+            st.luts, st.n_luts = keep[-1], len(luts_c)
+        return change
+
+    def null_luts(arr, st, keep):
+        st.luts, st.n_luts = C.POINTER(backend.LmnLut)(), 1
+
+    # (name, context, tables, luts, change of the marshalled structs, table the text names, lookups for lmn_settings_prepare)
+    cases = [("no claim slot under the KAT variant", kat, [good[0], (air.KIND_EXP2, good[1][1], 20)], None, None, 1, None),
+             ("2^26 + 1 rows", pinned, [(0, rows16, (1 << 26) + 1)], None, None, 0, None),
+             ("2^25 + 1 rows", pinned, [(0, rows16, (1 << 25) + 1)], None, None, 0, None),
+             ("no more than 2^log_last_layer rows", last4, [(0, rows16, 16)] + good[1:], None, None, 0, None),
+             ("both *_ON_DEVICE flags", pinned, good, None,
+              lambda arr, st, keep: setattr(arr[1], "flags", backend.TABLE_ROWS_ON_DEVICE | backend.TABLE_COLS_ON_DEVICE), 1, None),
+             ("null rows", pinned, good, None, lambda arr, st, keep: setattr(arr[2], "rows", None), 2, None),
+             ("a lookup announced without its table", pinned, good, None,
+              lambda arr, st, keep: setattr(st, "has_lookups", backend.LOOKUP_SIN), None, None),
+             ("null luts with n_luts > 0", pinned, good, None, null_luts, None, backend.LOOKUP_SIN),
+             ("unknown LUT kind", pinned, good, None, with_luts(backend.LmnLut(3, 4, p, p)), None, backend.LOOKUP_SIN),
+             ("null LUT column", pinned, good, None, with_luts(backend.LmnLut(0, 4, p, None)), None, backend.LOOKUP_SIN),
+             ("duplicate LUT", pinned, good, None, with_luts(backend.LmnLut(0, 4, p, p), backend.LmnLut(0, 4, p, p)), None,
+              backend.LOOKUP_SIN),
+             ("RangeCheckLookup of 16 rows", pinned, [(k, r[:16], 16) if i == rc_at else (k, r, n) for i, (k, r, n) in enumerate(lt)],
+              None, None, rc_at, None),
+             ("first LUT word 2^31 - 1", pinned, act, first_bad(*luts["sin"]), None, sin_at, None),
+             ("last LUT word 2^31 - 1", pinned, act, last_bad(*luts["sin"]), None, sin_at, None)]
+    try:
+        for name, ctx, tables, lut_dict, change, table, lookups in cases:
+            arr, n, settings, keep = ctx._marshal_tables(tables, lut_dict)
+            if change:
+                change(arr, settings, keep)
+            (code, text), (pcode, ptext) = _raw_codes(ctx, arr, n, settings)
+            assert code == pcode and code != 0, (name, code, text, pcode, ptext)
+            assert text and ptext, name
+            if table is not None:
+                assert ("table %d " % table) in text, (name, text)
+            if lookups is not None:
+                assert _prepare_code(ctx, settings, lookups) == code, name
+            assert ctx.check_trace(good).ok, name                        # the context is usable afterwards
+    finally:
+        last4.close()
 
 
 # ------------------------------------------------------------------------------------------------ 8: hot keys
