@@ -358,15 +358,16 @@ k_fft_fx(uint32_t* data, uint64_t col_stride, const uint32_t* src, uint64_t src_
 }
 
 // k_fft_interp_extend (kernels_fft.hip) with a fixed tile: layers [12, n) of the inverse transform on 2^n points, then the
-// same layers of both halves of the forward transform onto 2^(n+1) points from the coefficient tile kept in LDS.
-template <int RBITS>
-LMN_KERNEL LMN_BOUNDS((FxShape<RBITS, 4, false>::NT))
-k_fft_interp_extend_fx(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, uint64_t lde_stride, TwD itw, TwD tw,
-                       uint32_t scale_log) {
+// same layers of NH aligned blocks of the forward transform from the coefficient tile kept in LDS.  NH = 2: both halves of
+// the 2^(n+1)-point domain.  NH = 4: the four quarters of the 2^(n+2)-point domain (the composition polynomial built from
+// half of its evaluation domain, phase_composition.cpp: its 2^n coefficients are extended by two bits, both top layers
+// being copies); the inverse layers then use the first half of each table of the 2^(n+1)-point domain.
+template <int RBITS, int NH>
+LMN_D void fx_interp_extend_tile(uint32_t* sm, uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, uint64_t lde_stride,
+                                 const TwD& itw, const TwD& tw, uint32_t scale_log) {
   using S = FxShape<RBITS, 4, false>;
   constexpr int LO = 12;
-  LMN_DYN_SMEM(uint32_t, sm);
-  uint32_t* A = sm;                       // the coefficient tile, kept for both halves
+  uint32_t* A = sm;                       // the coefficient tile, kept for every block
   uint32_t* B = sm + S::LDS_WORDS;        // exchange buffer of the stages
   uint32_t tile = blockIdx.x;
   if ((gridDim.x & 7u) == 0u) tile = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
@@ -375,8 +376,25 @@ k_fft_interp_extend_fx(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, u
   uint32_t* ccol = coeffs + (uint64_t)blockIdx.y * coeff_stride + base;
   uint32_t* lcol = lde + (uint64_t)blockIdx.y * lde_stride + base;
   fx_steps<S, true, 0, true, true, true>(B, B, ccol, ccol, LO, 0u, itw.l, scale_log, A, threadIdx.x);
-  for (uint32_t h = 0; h < 2; ++h)
+#pragma unroll
+  for (uint32_t h = 0; h < (uint32_t)NH; ++h)
     fx_steps<S, false, 0, false, true, false>(A, B, lcol + h * n_words, nullptr, LO, h, tw.l, 0u, nullptr, threadIdx.x);
+}
+
+template <int RBITS>
+LMN_KERNEL LMN_BOUNDS((FxShape<RBITS, 4, false>::NT))
+k_fft_interp_extend_fx(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, uint64_t lde_stride, TwD itw, TwD tw,
+                       uint32_t scale_log) {
+  LMN_DYN_SMEM(uint32_t, sm);
+  fx_interp_extend_tile<RBITS, 2>(sm, coeffs, coeff_stride, lde, lde_stride, itw, tw, scale_log);
+}
+
+template <int RBITS>
+LMN_KERNEL LMN_BOUNDS((FxShape<RBITS, 4, false>::NT))
+k_fft_interp_quarters_fx(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, uint64_t lde_stride, TwD itw, TwD tw,
+                         uint32_t scale_log) {
+  LMN_DYN_SMEM(uint32_t, sm);
+  fx_interp_extend_tile<RBITS, 4>(sm, coeffs, coeff_stride, lde, lde_stride, itw, tw, scale_log);
 }
 
 // =============================================================================================
@@ -541,30 +559,44 @@ bool launch_fft_fixed_pass(bool inverse, uint32_t* data, uint64_t col_stride, co
                                       xcd_swizzle, zero_extended_top, s);
 }
 
-template <int RBITS>
+template <int RBITS, int NH>
 static void launch_ie(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, uint64_t lde_stride, const TwPtrs& itw,
                       const TwPtrs& tw_ext, uint32_t scale_log, int ncols, lmn_stream_t s) {
   using S = FxShape<RBITS, 4, false>;
   const size_t smem = (size_t)8 * S::LDS_WORDS;
+  if constexpr (NH == 2) {
 #if !defined(LMN_EMU) && !defined(LMN_BATCH)
-  if (smem > 64 * 1024) allow_big_lds((const void*)k_fft_interp_extend_fx<RBITS>, 160 * 1024);
+    if (smem > 64 * 1024) allow_big_lds((const void*)k_fft_interp_extend_fx<RBITS>, 160 * 1024);
 #endif
-  LMN_LAUNCH((k_fft_interp_extend_fx<RBITS>), dim3(1u << (12 - 4), (unsigned)ncols), dim3(S::NT), smem, s, coeffs, coeff_stride,
-             lde, lde_stride, doubled(itw), doubled(tw_ext), scale_log);
+    LMN_LAUNCH((k_fft_interp_extend_fx<RBITS>), dim3(1u << (12 - 4), (unsigned)ncols), dim3(S::NT), smem, s, coeffs,
+               coeff_stride, lde, lde_stride, doubled(itw), doubled(tw_ext), scale_log);
+  } else {
+#if !defined(LMN_EMU) && !defined(LMN_BATCH)
+    if (smem > 64 * 1024) allow_big_lds((const void*)k_fft_interp_quarters_fx<RBITS>, 160 * 1024);
+#endif
+    LMN_LAUNCH((k_fft_interp_quarters_fx<RBITS>), dim3(1u << (12 - 4), (unsigned)ncols), dim3(S::NT), smem, s, coeffs,
+               coeff_stride, lde, lde_stride, doubled(itw), doubled(tw_ext), scale_log);
+  }
 }
 
 bool launch_interp_extend_fixed(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, uint64_t lde_stride, int log_n,
-                                const TwPtrs& itw, const TwPtrs& tw_ext, int ncols, lmn_stream_t s) {
+                                const TwPtrs& itw, const TwPtrs& tw_ext, int ncols, int n_ext, lmn_stream_t s) {
   static const bool off = env_set("LMN_NO_FFT_FIXED");
-  if (off || !itw.d[0] || !tw_ext.d[0]) return false;
+  if (off || !itw.d[0] || !tw_ext.d[0] || (n_ext != 2 && n_ext != 4)) return false;
   const uint32_t scale_log = (uint32_t)((31 - (log_n % 31)) % 31);   // 2^-log_n = 2^(31 - log_n mod 31)
+#define LMN_IE_CASE(RB)                                                                                        \
+  case RB:                                                                                                     \
+    if (n_ext == 2) launch_ie<RB, 2>(coeffs, coeff_stride, lde, lde_stride, itw, tw_ext, scale_log, ncols, s); \
+    else launch_ie<RB, 4>(coeffs, coeff_stride, lde, lde_stride, itw, tw_ext, scale_log, ncols, s);            \
+    return true
   switch (log_n - 12) {
-    case 6: launch_ie<6>(coeffs, coeff_stride, lde, lde_stride, itw, tw_ext, scale_log, ncols, s); return true;
-    case 7: launch_ie<7>(coeffs, coeff_stride, lde, lde_stride, itw, tw_ext, scale_log, ncols, s); return true;
-    case 8: launch_ie<8>(coeffs, coeff_stride, lde, lde_stride, itw, tw_ext, scale_log, ncols, s); return true;
-    case 9: launch_ie<9>(coeffs, coeff_stride, lde, lde_stride, itw, tw_ext, scale_log, ncols, s); return true;
+    LMN_IE_CASE(6);
+    LMN_IE_CASE(7);
+    LMN_IE_CASE(8);
+    LMN_IE_CASE(9);
     default: return false;
   }
+#undef LMN_IE_CASE
 }
 
 }  // namespace lmn

@@ -59,6 +59,16 @@ int launch_fft(uint32_t* dst, uint64_t dst_stride, const uint32_t* src, uint64_t
 bool fft_interp_extend_supported(int log_n);
 int launch_interp_extend(uint32_t* coeffs, uint64_t coeff_stride, const uint32_t* evals, uint64_t evals_stride, uint32_t* lde,
                          uint64_t lde_stride, int ncols, int log_n, const TwPtrs& itw, const TwPtrs& tw_ext, lmn_stream_t s);
+// The same for a polynomial of 2^log_half coefficients given by its evaluations on storage rows [0, 2^log_half) of the
+// 2^(log_half + 1)-point domain (itw_full: that domain's inverse tables), extended onto the 2^(log_half + 2)-point domain
+// (tw_ext): the inverse low pass and the strided pass that writes four quarters (2 launches); launch_interp_extend_half_finish
+// is the forward low pass (1 launch).  Between the two, element 0 of the coefficients can still be changed: add the change to
+// the words at multiples of 2^12 of each quarter.  Sizes: fft_interp_extend_supported(log_half).
+int launch_interp_extend_half(uint32_t* coeffs, uint64_t coeff_stride, const uint32_t* evals, uint64_t evals_stride,
+                              uint32_t* lde, uint64_t lde_stride, int ncols, int log_half, const TwPtrs& itw_full,
+                              const TwPtrs& tw_ext, lmn_stream_t s);
+int launch_interp_extend_half_finish(uint32_t* lde, uint64_t lde_stride, int ncols, int log_half, const TwPtrs& tw_ext,
+                                     lmn_stream_t s);
 // The same from the table's AoS rows (transpose fused into the inverse low pass; launch_transpose_pad's padding and
 // canonical-word check included).  false: not applicable to this size / build (transpose first, then launch_interp_extend).
 struct PadRow;
@@ -522,6 +532,40 @@ struct CompositionArgs {
 void launch_composition(const CompositionArgs& a, lmn_stream_t s);
 // out (4 x n) += in (4 x n)
 void launch_secure_add(uint32_t* out, const uint32_t* in, uint64_t n_words, lmn_stream_t s);
+// the first n words of ncols columns: out[c * out_stride + i] += in[c * in_stride + i]
+void launch_add_cols(uint32_t* out, uint64_t out_stride, const uint32_t* in, uint64_t in_stride, uint64_t n, int ncols,
+                     lmn_stream_t s);
+
+// ---- a7: the composition polynomial from half of its evaluation domain (phase_composition.cpp).
+// The quotient p has N + 1 coefficients on its 2N-point domain (N = 2^log_half): [lo_0 .. lo_{N-1}, c].  The top layer's
+// basis function is +w on storage rows [0, N) and -w on [N, 2N), so g = the N-coefficient polynomial that agrees with p on
+// the first half differs from p by the constant 2wc on the second half: one evaluation of p there (the probe, row N) gives c.
+struct ProbeMaps {
+  uint32_t m[MAX_LOG];   // y, x, pi(x), pi^2(x), ... of the probe's domain point
+};
+constexpr int PROBE_CHUNK_LOG = 12;
+inline uint32_t probe_dot_blocks(int log_n) { return log_n > PROBE_CHUNK_LOG ? 1u << (log_n - PROBE_CHUNK_LOG) : 1u; }
+// partial[c * probe_dot_blocks(log_n) + b] = the share of run b of 2^PROBE_CHUNK_LOG coefficients in (column c)(point), 4 columns;
+// tail_out != nullptr: tail_out[c] = the word behind column c's 2^log_n coefficients (where the probe row's evaluation lies)
+void launch_probe_dot(const uint32_t* coeffs, uint64_t stride, int log_n, const ProbeMaps& pm, uint32_t* partial,
+                      uint32_t* tail_out, lmn_stream_t s);
+struct CompHalfFix {
+  uint32_t* coeffs;            // 4 columns, 2^(log_half + 1) words each: g in the lower half
+  uint64_t coeff_stride;
+  uint32_t* lde;               // 4 columns of 4 quarters behind the strided pass, or nullptr (a size that is folded into a larger one)
+  uint64_t lde_stride;
+  int log_half;
+  const uint32_t* part_g;      // launch_probe_dot of g: 4 x n_g
+  uint32_t n_g;
+  const uint32_t* part_f;      // ... of the smaller sizes' polynomial folded into this one (n_f = 0: none)
+  uint32_t n_f;
+  const uint32_t* probe;       // 4 words: this size's constraint quotients at the probe row (launch_probe_dot's tail_out)
+  const uint32_t* w_top;       // top-layer table of the 2N-point domain: w = w_top[0]
+  const uint32_t* w_ext;       // layer log_half of the 4N-point domain: the quarters' twiddles w_ext[0], w_ext[1]
+};
+// c = (g(probe) - (p(probe) - folded(probe))) / 2w per column; coefficient 0 -= wc, coefficient N = c, the rest of the upper
+// half = 0; every word at a multiple of 2^12 of quarter h of the LDE += c * ((-1)^h w_ext[h >> 1] - w)
+void launch_comp_half_fix(const CompHalfFix& f, lmn_stream_t s);
 
 // ---- a9: OODS evaluation of coefficient columns
 struct EvalJob {

@@ -279,7 +279,7 @@ LMN_KERNEL k_fft_staged(uint32_t* data, uint64_t col_stride, const uint32_t* src
 // ---------------------------------------------------------------------------------------------
 LMN_KERNEL k_fft_interp_extend(uint32_t* coeffs, uint64_t coeff_stride, const uint32_t* src, uint64_t src_stride,
                                uint32_t* lde, uint64_t lde_stride, FftStagePlan pl, TwPtrs itw, TwPtrs tw, uint32_t scale,
-                               int ncols, int cpb) {
+                               int ncols, int cpb, uint32_t n_ext) {
   LMN_DYN_SMEM(uint32_t, sm);
   const uint32_t tile_elems = 1u << (pl.hi - pl.lo + pl.cb);
   uint32_t* A = sm;                                   // the coefficient tile (kept for the second half)
@@ -301,8 +301,9 @@ LMN_KERNEL k_fft_interp_extend(uint32_t* coeffs, uint64_t coeff_stride, const ui
                                tg ? A : nullptr);
       __syncthreads();
     }
-    // forward layers [lo, n) of half h of the 2^(n+1)-point transform: stages descending, first one reads A
-    for (uint32_t h = 0; h < 2; ++h) {
+    // forward layers [lo, n) of half h of the 2^(n+1)-point transform (n_ext = 2; n_ext = 4: of quarter h of the
+    // 2^(n+2)-point one, launch_interp_extend_half): stages descending, first one reads A
+    for (uint32_t h = 0; h < n_ext; ++h) {
       for (int k = 0; k < pl.nst; ++k) {
         const int s = pl.nst - 1 - k;
         const bool tg = k == pl.nst - 1;
@@ -416,10 +417,9 @@ bool fft_interp_extend_supported(int log_n) {
   static const bool off = env_set("LMN_NO_FFT_FUSION");
   return !off && log_n > FFT_LOW_BITS && log_n - FFT_LOW_BITS <= FFT_HIGH_BITS - 1;
 }
-// the fused strided pass on coefficients that have been through the inverse low pass, then the forward low pass
-static void interp_extend_tail(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, uint64_t lde_stride, int ncols, int log_n,
-                               const TwPtrs& itw, const TwPtrs& tw_ext, lmn_stream_t s) {
-  const FftPass low{0, FFT_LOW_BITS, 0};
+// the fused strided pass on coefficients that have been through the inverse low pass: n_ext blocks of 2^log_n evaluations
+static void interp_extend_strided(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, uint64_t lde_stride, int ncols,
+                                  int log_n, const TwPtrs& itw, const TwPtrs& tw_ext, uint32_t n_ext, lmn_stream_t s) {
   FftStagePlan pl{};
   pl.lo = FFT_LOW_BITS;
   pl.hi = log_n;
@@ -434,9 +434,15 @@ static void interp_extend_tail(uint32_t* coeffs, uint64_t coeff_stride, uint32_t
 #if !defined(LMN_EMU) && !defined(LMN_BATCH)
   if (smem > 64 * 1024) allow_big_lds((const void*)k_fft_interp_extend, 160 * 1024);
 #endif
-  if (!launch_interp_extend_fixed(coeffs, coeff_stride, lde, lde_stride, log_n, itw, tw_ext, ncols, s))
+  if (!launch_interp_extend_fixed(coeffs, coeff_stride, lde, lde_stride, log_n, itw, tw_ext, ncols, (int)n_ext, s))
     LMN_LAUNCH(k_fft_interp_extend, dim3(tiles, (unsigned)((ncols + cpb - 1) / cpb)), dim3(threads), smem, s, coeffs,
-               coeff_stride, coeffs, coeff_stride, lde, lde_stride, pl, itw, tw_ext, inv_pow2(log_n), ncols, cpb);
+               coeff_stride, coeffs, coeff_stride, lde, lde_stride, pl, itw, tw_ext, inv_pow2(log_n), ncols, cpb, n_ext);
+}
+// ... then the forward low pass
+static void interp_extend_tail(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, uint64_t lde_stride, int ncols, int log_n,
+                               const TwPtrs& itw, const TwPtrs& tw_ext, lmn_stream_t s) {
+  const FftPass low{0, FFT_LOW_BITS, 0};
+  interp_extend_strided(coeffs, coeff_stride, lde, lde_stride, ncols, log_n, itw, tw_ext, 2u, s);
   launch_staged_pass<false>(lde, lde_stride, lde, lde_stride, 2ull << log_n, low, log_n + 1, tw_ext, 1u, ncols, s);
 }
 
@@ -447,6 +453,29 @@ int launch_interp_extend(uint32_t* coeffs, uint64_t coeff_stride, const uint32_t
   launch_staged_pass<true>(coeffs, coeff_stride, evals, evals_stride, 1ull << log_n, low, log_n, itw, 1u, ncols, s);
   interp_extend_tail(coeffs, coeff_stride, lde, lde_stride, ncols, log_n, itw, tw_ext, s);
   return 3;
+}
+
+// A polynomial of 2^log_half coefficients from its evaluations on the FIRST HALF of the 2^(log_half + 1)-point domain
+// (storage rows [0, 2^log_half): block 0, where the top layer's basis function is constant), extended onto the
+// 2^(log_half + 2)-point domain.  The inverse transform of that block without its top layer is the 2^log_half-point inverse
+// run on the first half of every table of itw_full = the 2^(log_half + 1)-point domain; the coefficient vector extended by
+// two bits makes both top forward layers copies, so the strided pass writes four quarters (twiddle rows 0..3 of tw_ext = the
+// 2^(log_half + 2)-point domain).  The caller may change element 0 of the coefficients between the two calls by adding its
+// change to the words of each quarter at multiples of 2^12 (where element 0 has spread to after the strided layers).
+int launch_interp_extend_half(uint32_t* coeffs, uint64_t coeff_stride, const uint32_t* evals, uint64_t evals_stride,
+                              uint32_t* lde, uint64_t lde_stride, int ncols, int log_half, const TwPtrs& itw_full,
+                              const TwPtrs& tw_ext, lmn_stream_t s) {
+  if (!fft_interp_extend_supported(log_half)) throw LmnError(-100, "interp_extend_half: unsupported size");
+  const FftPass low{0, FFT_LOW_BITS, 0};
+  launch_staged_pass<true>(coeffs, coeff_stride, evals, evals_stride, 1ull << log_half, low, log_half, itw_full, 1u, ncols, s);
+  interp_extend_strided(coeffs, coeff_stride, lde, lde_stride, ncols, log_half, itw_full, tw_ext, 4u, s);
+  return 2;
+}
+int launch_interp_extend_half_finish(uint32_t* lde, uint64_t lde_stride, int ncols, int log_half, const TwPtrs& tw_ext,
+                                     lmn_stream_t s) {
+  const FftPass low{0, FFT_LOW_BITS, 0};
+  launch_staged_pass<false>(lde, lde_stride, lde, lde_stride, 4ull << log_half, low, log_half + 2, tw_ext, 1u, ncols, s);
+  return 1;
 }
 
 // launch_interp_extend whose evaluations are still the table's AoS ROWS: the transpose happens inside the inverse low pass

@@ -147,6 +147,101 @@ void launch_secure_add(uint32_t* out, const uint32_t* in, uint64_t n_words, lmn_
   LMN_LAUNCH(k_secure_add, dim3(cdiv(n_words, TPB)), dim3(TPB), 0, s, out, in, n_words);
 }
 
+LMN_KERNEL k_add_cols(uint32_t* __restrict__ out, uint64_t out_stride, const uint32_t* __restrict__ in, uint64_t in_stride,
+                      uint64_t n) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t* o = out + (uint64_t)blockIdx.y * out_stride + i;
+  *o = m_add(*o, in[(uint64_t)blockIdx.y * in_stride + i]);
+}
+void launch_add_cols(uint32_t* out, uint64_t out_stride, const uint32_t* in, uint64_t in_stride, uint64_t n, int ncols,
+                     lmn_stream_t s) {
+  LMN_LAUNCH(k_add_cols, dim3(cdiv(n, TPB), (unsigned)ncols), dim3(TPB), 0, s, out, out_stride, in, in_stride, n);
+}
+
+// ---- the composition polynomial from half of its evaluation domain (kernels.h CompHalfFix)
+// prod_k m[k0 + k]^(bit k of v), k < nbits
+LMN_D uint32_t probe_basis(const ProbeMaps& pm, uint32_t v, int k0, int nbits) {
+  uint32_t acc = 1u;
+  for (int k = 0; k < nbits; ++k)
+    if ((v >> k) & 1u) acc = m_mul(acc, pm.m[k0 + k]);
+  return acc;
+}
+// sum of the block's values (every lane calls; valid in every lane)
+LMN_D uint32_t probe_block_sum(uint32_t* red, uint32_t v) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int st = TPB / 2; st > 0; st >>= 1) {
+    if ((int)threadIdx.x < st) red[threadIdx.x] = m_add(red[threadIdx.x], red[threadIdx.x + st]);
+    __syncthreads();
+  }
+  const uint32_t r = red[0];
+  __syncthreads();
+  return r;
+}
+// An M31 point's basis value of coefficient j factors over the bits of j: lane bits [0, 8) once per lane, bits [8, 12) per
+// coefficient of the lane, bits [12, log_n) once per block.
+LMN_KERNEL k_probe_dot(const uint32_t* __restrict__ coeffs, uint64_t stride, int log_n, ProbeMaps pm,
+                       uint32_t* __restrict__ partial, uint32_t* __restrict__ tail_out) {
+  LMN_SHARED uint32_t red[TPB];
+  const uint32_t* __restrict__ col = coeffs + (uint64_t)blockIdx.y * stride;
+  const uint64_t n = 1ull << log_n;
+  const uint64_t j0 = (uint64_t)blockIdx.x << PROBE_CHUNK_LOG;
+  const int lane_bits = log_n < 8 ? log_n : 8;
+  const int mid_bits = log_n < PROBE_CHUNK_LOG ? (log_n > 8 ? log_n - 8 : 0) : PROBE_CHUNK_LOG - 8;
+  uint32_t acc = 0u;
+  for (uint32_t i = 0; i < (1u << mid_bits); ++i) {
+    const uint64_t j = j0 + ((uint64_t)i << 8) + threadIdx.x;
+    if (threadIdx.x < (1u << lane_bits) && j < n) acc = m_add(acc, m_mul(col[j], probe_basis(pm, i, 8, mid_bits)));
+  }
+  acc = m_mul(acc, probe_basis(pm, threadIdx.x, 0, lane_bits));
+  if (log_n > PROBE_CHUNK_LOG) acc = m_mul(acc, probe_basis(pm, blockIdx.x, PROBE_CHUNK_LOG, log_n - PROBE_CHUNK_LOG));
+  const uint32_t sum = probe_block_sum(red, acc);
+  if (threadIdx.x == 0) {
+    partial[(uint64_t)blockIdx.y * gridDim.x + blockIdx.x] = sum;
+    if (tail_out && blockIdx.x == 0) tail_out[blockIdx.y] = col[n];
+  }
+}
+void launch_probe_dot(const uint32_t* coeffs, uint64_t stride, int log_n, const ProbeMaps& pm, uint32_t* partial,
+                      uint32_t* tail_out, lmn_stream_t s) {
+  if (log_n < 0 || log_n >= MAX_LOG) throw LmnError(-100, "probe_dot: bad size");
+  LMN_LAUNCH(k_probe_dot, dim3(probe_dot_blocks(log_n), 4), dim3(TPB), 0, s, coeffs, stride, log_n, pm, partial, tail_out);
+}
+
+LMN_KERNEL k_comp_half_fix(CompHalfFix f) {
+  LMN_SHARED uint32_t red[TPB];
+  const uint32_t c4 = blockIdx.y;
+  uint32_t acc = 0u;
+  for (uint32_t k = threadIdx.x; k < f.n_g; k += blockDim.x) acc = m_add(acc, f.part_g[(uint64_t)c4 * f.n_g + k]);
+  for (uint32_t k = threadIdx.x; k < f.n_f; k += blockDim.x) acc = m_sub(acc, f.part_f[(uint64_t)c4 * f.n_f + k]);
+  // g(probe) - p(probe), p = this size's quotients + the folded polynomial: every lane gets the sum
+  const uint32_t diff = m_sub(probe_block_sum(red, acc), f.probe[c4]);
+  const uint32_t w = f.w_top[0];
+  const uint32_t c = m_mul(diff, m_inv(m_add(w, w)));
+  const uint64_t N = 1ull << f.log_half;
+  uint32_t* __restrict__ col = f.coeffs + (uint64_t)c4 * f.coeff_stride;
+  const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, gstep = (uint64_t)gridDim.x * blockDim.x;
+  if (gid == 0) col[0] = m_sub(col[0], m_mul(w, c));
+  for (uint64_t i = gid; i < N; i += gstep) col[N + i] = i == 0 ? c : 0u;
+  if (f.lde) {
+    uint32_t* __restrict__ l = f.lde + (uint64_t)c4 * f.lde_stride;
+    const uint64_t per = N >> 12;   // words of a quarter that element 0 has spread to
+    for (uint64_t i = gid; i < 4 * per; i += gstep) {
+      const uint32_t h = (uint32_t)(i / per);
+      const uint32_t we = f.w_ext[h >> 1];
+      const uint32_t kappa = m_sub((h & 1u) ? m_neg(we) : we, w);
+      uint32_t* p = l + (uint64_t)h * N + ((i % per) << 12);
+      *p = m_add(*p, m_mul(c, kappa));
+    }
+  }
+}
+void launch_comp_half_fix(const CompHalfFix& f, lmn_stream_t s) {
+  if (f.log_half < 0 || (f.lde && f.log_half < 12)) throw LmnError(-100, "comp_half_fix: bad size");
+  const uint64_t N = 1ull << f.log_half;
+  const unsigned gx = (unsigned)std::min<uint64_t>(std::max<uint64_t>(N / (4 * TPB), 1), 256);
+  LMN_LAUNCH(k_comp_half_fix, dim3(gx, 4), dim3(TPB), 0, s, f);
+}
+
 // =============================================================================================
 // a9  eval_at_point: sum_j coeff_j * basis_j(point), basis factored as lo-table x hi-table
 // =============================================================================================

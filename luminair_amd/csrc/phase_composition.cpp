@@ -21,6 +21,17 @@ void Context::run_composition(ProofRun& r) {
     StageTimer st(this, log, stream_, C_COMPOSITION);
     std::map<int, uint32_t*> sub;  // eval log -> 4 x 2^e accumulation buffer
     const int sg = shard_.active ? shard_.g : 0;
+    // Every component's quotient has degree at most its trace size N (max_constraint_log_degree_bound = log_size + 1, then the
+    // division by the trace domain's vanishing polynomial): N + 1 coefficients on the 2N-point evaluation domain.  Storage rows
+    // [0, N) and ONE row of the second half (the probe, row N) determine them (kernels.h CompHalfFix; docs/HISTORY.md), so
+    // that is all that is evaluated and interpolated.  Unsharded proofs at blow-up 2 whose largest size has the fused
+    // transform; LMN_COMP_FULL_DOMAIN=1 keeps the whole domain (A/B runs, tests).
+#ifdef LMN_BATCH
+    const bool half = false;
+#else
+    const bool half = !shard_.active && lb == 1 && fft_interp_extend_supported(comp_log - 1) &&
+                      env_int("LMN_COMP_FULL_DOMAIN", 0) == 0;
+#endif
     int k0 = 0;
     for (auto& ci : inst) {
       int e = ci.log_size + 1;
@@ -117,6 +128,8 @@ void Context::run_composition(ProofRun& r) {
         for (int k = 0; k < ci.log_size - 1; ++k) x = m_sub(m_dbl(m_sqr(x)), 1u);
         a.zinv[b] = m_inv(x);
       }
+      // rows [0, E/2) and the probe, row E/2: one contiguous block (its evaluation lands where coefficient N will be)
+      if (half) a.n_rows = (uint32_t)(E / 2) + 1;
       launch_composition(a, stream_);
     }
     // sharded: every rank evaluated its row block of each per-size accumulator; make them whole everywhere (the
@@ -131,6 +144,68 @@ void Context::run_composition(ProofRun& r) {
       int e = kv.first;
       uint64_t E = 1ull << e;
       uint32_t* vals = kv.second;
+      if (half) {
+        // vals: the evaluations on rows [0, E/2) of each column and the probe row's at E/2
+        const int lh = e - 1;
+        const uint64_t N = E / 2;
+        const Pt pp = domain_point(e, (uint32_t)N);
+        ProbeMaps pm{};
+        pm.m[0] = pp.y;
+        pm.m[1] = pp.x;
+        for (int k = 2; k < e; ++k) pm.m[k] = m_sub(m_dbl(m_sqr(pm.m[k - 1])), 1u);
+        CompHalfFix f{};
+        if (cur) {
+          // the smaller sizes' polynomial on this size's first half, and its value at the probe (it has at most N coefficients,
+          // but the two halves of the domain differ in every layer's twiddles: its value at row N is not its value at row 0)
+          uint32_t* ext = arena_.alloc_words(4 * N);
+          uint32_t* part = arena_.alloc_words(4 * (size_t)probe_dot_blocks(cur_log));
+          StageTimer t(this, log, stream_, C_FFT);
+          timings.fft_launches += launch_fft_block(ext, N, cur, 1ull << cur_log, cur_log, 4, e, 1, 0, tw(e), stream_);
+          timings.fft_bytes += 4ull * (4ull << cur_log) + 4ull * 4ull * N;
+          timings.fft_butterflies += 4ull * (N / 2) * (uint64_t)lh;
+          launch_add_cols(vals, E, ext, N, N, 4, stream_);
+          launch_probe_dot(cur, 1ull << cur_log, cur_log, pm, part, nullptr, stream_);
+          f.part_f = part;
+          f.n_f = probe_dot_blocks(cur_log);
+        }
+        uint32_t* lde = nullptr;
+        {
+          StageTimer t(this, log, stream_, C_FFT);
+          timings.fft_bytes += 4ull * 8ull * N;
+          timings.fft_butterflies += 4ull * (N / 2) * (uint64_t)lh;
+          if (e == comp_log) {
+            lde = arena_.alloc_words(4 * 4 * N);
+            timings.fft_launches += launch_interp_extend_half(vals, E, vals, E, lde, 4 * N, 4, lh, itw(e), tw(e + 1), stream_);
+            timings.fft_bytes += 4ull * 20ull * N;                        // the extension: 4N read + 16N written
+            timings.fft_butterflies += 4ull * 2ull * N * (uint64_t)lh;    // four quarters of N/2 * lh (both top layers are copies)
+          } else {
+            if (lh >= 1) timings.fft_launches += launch_ifft(vals, E, vals, E, 4, lh, itw(e), stream_);
+          }
+        }
+        uint32_t* part_g = arena_.alloc_words(4 * (size_t)probe_dot_blocks(lh) + 4);
+        uint32_t* probe = part_g + 4 * (size_t)probe_dot_blocks(lh);
+        launch_probe_dot(vals, E, lh, pm, part_g, probe, stream_);
+        f.coeffs = vals;
+        f.coeff_stride = E;
+        f.lde = lde;
+        f.lde_stride = 4 * N;
+        f.log_half = lh;
+        f.part_g = part_g;
+        f.n_g = probe_dot_blocks(lh);
+        f.probe = probe;
+        f.w_top = tw(e).l[e - 1];
+        f.w_ext = tw(e + 1).l[e - 1];
+        launch_comp_half_fix(f, stream_);
+        if (lde) {
+          StageTimer t(this, log, stream_, C_FFT);
+          timings.fft_launches += launch_interp_extend_half_finish(lde, 4 * N, 4, lh, tw(e + 1), stream_);
+          comp_out.lde = lde;
+          comp_out.stride = 4 * N;
+        }
+        cur = vals;
+        cur_log = e;
+        continue;
+      }
       if (cur) {
         uint32_t* ext = arena_.alloc_words(4 * E);
         StageTimer t(this, log, stream_, C_FFT);
