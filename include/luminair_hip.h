@@ -897,10 +897,66 @@ struct lmn_fri_close_result {
 typedef struct lmn_fri_close_result lmn_fri_close_result;
 int lmn_col_fri_close(lmn_ctx* ctx, const lmn_col* last_layer, const uint8_t start_digest[32],
                       uint32_t log_query_domain /* 0..31 */, lmn_fri_close_result* result);
+/* Query positions in device memory: at most 1024 ascending distinct positions < 2^log_domain (log_domain <= 31).  A
+ * handle is what lmn_open_queries reads; it is made from host positions (lmn_positions_from_cpu: LMN_ERR_INVALID_ARGUMENT
+ * with a text naming the argument for a null pointer with n > 0, n > 1024, log_domain > 31, a position out of range or
+ * not strictly above its predecessor) or left behind by lmn_col_fri_close_keep, behind the same single wait as the
+ * close itself.  lmn_positions_to_cpu writes the positions to `host` (room for 1024 words) and their number
+ * to *n_out.  lmn_positions_free waits for the context's stream first; a null handle is ignored. */
+typedef struct lmn_positions lmn_positions;
+int lmn_positions_from_cpu(lmn_ctx* ctx, const uint32_t* positions, uint32_t n, uint32_t log_domain, lmn_positions** out);
+int lmn_positions_to_cpu(lmn_ctx* ctx, const lmn_positions* positions, uint32_t* host, uint32_t* n_out);
+uint32_t lmn_positions_log_domain(const lmn_positions* positions);
+void lmn_positions_free(lmn_ctx* ctx, lmn_positions* positions);
+/* lmn_col_fri_close with the positions kept on the device as well: the same chain behind the same single wait (one
+ * implementation behind both entry points), with one copy queued behind k_fri_queries that moves the positions from the
+ * chain's page-locked result block - where k_fri_queries writes them for the host - into a new handle of log_domain =
+ * log_query_domain: they cross the link once more, in front of the wait, and no host code touches them.  When the nonce lay beyond the queued windows
+ * the handle is filled from the host's positions.  On any error *positions_out is NULL and the result zeroed. */
+int lmn_col_fri_close_keep(lmn_ctx* ctx, const lmn_col* last_layer, const uint8_t start_digest[32],
+                           uint32_t log_query_domain, lmn_fri_close_result* result, lmn_positions** positions_out);
+/* Opens up to 64 trees at the positions of a handle with ONE plan launch (k_open_plan, one workgroup per item, followed
+ * by a one-workgroup offset step), ONE fetch launch, one transfer and one wait: MerkleProver::decommit's walk and FRI's
+ * pair expansion run on the device, no walk runs on the host, and the host need not know the positions at all.
+ * An item is a tree with the handles it was committed from (`cols`, as for lmn_tree_decommit).  Its groups are, for every
+ * log size at which the tree has columns, fold_positions(positions, log_domain - log size): without flags its three
+ * Merkle outputs equal lmn_tree_decommit's for those groups.  LMN_OPEN_FRI_PAIRS (a FRI layer's tree: 4 coordinate
+ * columns at each of its sizes) first expands every group to sibling pairs - position p contributes 2 floor(p / 2) and
+ * 2 floor(p / 2) + 1, FriProver::decommit's rule at fold step 1 - and fri_witness receives 4 words (a, b, c, d) per
+ * pair member that is no position itself, sizes descending, members ascending.  out: n_items results, every pointer
+ * from malloc and released with lmn_free, NULL with count 0 where empty.  Zero positions or zero items: LMN_OK, empty
+ * outputs, nothing launched.
+ * LMN_ERR_INVALID_ARGUMENT with a text naming the argument, all outputs zeroed, nothing launched, context and handles
+ * usable: a null pointer where a count is non-zero, more than 64 items, a tree larger than 2^log_domain, columns that
+ * differ from what the tree was committed from, LMN_OPEN_FRI_PAIRS (or an unknown flag) on a tree that does not have
+ * exactly 4 columns at each of its sizes or has columns of log size 0, an upper bound of the opening (computed from the
+ * number of positions, before they are looked at) above the 12 MiB one call carries, a sharded context. */
+#define LMN_OPEN_FRI_PAIRS 1u
+struct lmn_open_item {
+  const lmn_tree* tree;
+  const lmn_col* const* cols;
+  uint32_t n_cols;
+  uint32_t flags;
+};
+typedef struct lmn_open_item lmn_open_item;
+struct lmn_opening {
+  uint32_t* queried_values;
+  uint8_t* hash_witness;     /* 32 bytes per hash */
+  uint32_t* column_witness;
+  uint32_t* fri_witness;
+  uint64_t n_values, n_hashes, n_column_words, n_fri_words;
+};
+typedef struct lmn_opening lmn_opening;
+int lmn_open_queries(lmn_ctx* ctx, const lmn_positions* positions, const lmn_open_item* items, uint32_t n_items,
+                     lmn_opening* out /* n_items */);
 /* Counters of a context since its creation, in lmn_batch_counter's numbering where it applies - 7: proof-of-work grinds
  * started on the device, 8: host waits spent inside grind rounds, 9: proofs whose transcript was closed on the device
  * (lmn_prove under LMN_DEVICE_FRI_CLOSE=1 at pow_bits >= LMN_POW_DEVICE_MIN_BITS, unsharded), 10: those among them whose nonce
- * lay beyond the queued windows (the host went on grinding).  Any other number, or a null context: 0. */
+ * lay beyond the queued windows (the host went on grinding), 11: proofs whose openings were planned on the device
+ * (LMN_DEVICE_DECOMMIT=1 where 9 counts), 12: those among them that fell back to the host plan (no nonce in the queued
+ * windows).  Diagnostic only, outside lmn_batch_counter's numbering and not part of what a binding needs - 13: k_open_plan
+ * launches made for lmn_open_queries (counted where the launch is made), 14: its k_open_fetch launches, 15: its host
+ * waits.  Any other number, or a null context: 0. */
 uint64_t lmn_ctx_counter(const lmn_ctx* ctx, int which);
 int lmn_col_accumulate(lmn_ctx* ctx, lmn_col* dst, const lmn_col* src);     /* AccumulationOps::accumulate: dst += src (same shape) */
 /* FieldOps<BaseField>::batch_inverse and FieldOps<SecureField>::batch_inverse on whole columns, on the device.

@@ -237,8 +237,38 @@ class FriClose:
     n_sent_end: int
 
 
+class LmnOpenItem(C.Structure):
+    """`lmn_open_item`"""
+    _fields_ = [("tree", C.c_void_p), ("cols", C.POINTER(C.c_void_p)), ("n_cols", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class LmnOpening(C.Structure):
+    """`lmn_opening`"""
+    _fields_ = [("queried_values", C.c_void_p), ("hash_witness", C.c_void_p), ("column_witness", C.c_void_p),
+                ("fri_witness", C.c_void_p), ("n_values", C.c_uint64), ("n_hashes", C.c_uint64),
+                ("n_column_words", C.c_uint64), ("n_fri_words", C.c_uint64)]
+
+
+OPEN_FRI_PAIRS = 1          # LMN_OPEN_FRI_PAIRS
+OPEN_MAX_POSITIONS = 1024
+OPEN_MAX_ITEMS = 64
+
+
+@dataclass
+class Opening:
+    """One item of `Context.open_queries`: the three outputs of `Tree.decommit`, and - under OPEN_FRI_PAIRS - the FRI
+    witness, one (a, b, c, d) per pair member that is no position itself."""
+    queried_values: np.ndarray
+    hash_witness: List[bytes]
+    column_witness: np.ndarray
+    fri_witness: List[Tuple[int, int, int, int]]
+
+
 # lmn_ctx_counter
 COUNTER_GRINDS, COUNTER_GRIND_WAITS, COUNTER_DEVICE_CLOSES, COUNTER_DEVICE_CLOSE_FALLBACKS = 7, 8, 9, 10
+COUNTER_DEVICE_OPENINGS, COUNTER_DEVICE_OPENING_FALLBACKS = 11, 12
+# diagnostic only (the tests' evidence of one plan launch, one fetch launch and one wait per lmn_open_queries call)
+COUNTER_OPEN_PLAN_LAUNCHES, COUNTER_OPEN_FETCH_LAUNCHES, COUNTER_OPEN_WAITS = 13, 14, 15
 
 API_VERSION = 6   # LMN_API_VERSION of include/luminair_hip.h
 
@@ -261,7 +291,9 @@ EXPORTS = ["lmn_abi_version", "lmn_kind_padding_row", "lmn_strerror", "lmn_last_
            "lmn_eval_elementwise_v", "lmn_eval_reduce", "lmn_eval_reduce_split", "lmn_eval_lut_ranges", "lmn_tensor_range",
            "lmn_trace_many_elementwise_v", "lmn_trace_many_contiguous", "lmn_trace_many_reduce", "lmn_trace_many_lut_ranges",
            "lmn_settings_prepare", "lmn_prepared_root", "lmn_prepared_lookups", "lmn_prepared_destroy", "lmn_prove_prepared",
-           "lmn_prove_submit_prepared", "lmn_batch_prove_prepared"]
+           "lmn_prove_submit_prepared", "lmn_batch_prove_prepared",
+           "lmn_positions_from_cpu", "lmn_positions_to_cpu", "lmn_positions_log_domain", "lmn_positions_free",
+           "lmn_col_fri_close_keep", "lmn_open_queries"]
 TRACE_MANY_MAX = 1024   # LMN_TRACE_MANY_MAX
 
 
@@ -388,6 +420,14 @@ class Library:
         lib.lmn_col_gather.argtypes = [VP, VP, VP, U32, VP]
         lib.lmn_col_fri_commit.argtypes = [VP, C.POINTER(VP), U32, VP, C.POINTER(LmnFriCommitResult)]
         lib.lmn_col_fri_close.argtypes = [VP, VP, VP, U32, C.POINTER(LmnFriCloseResult)]
+        lib.lmn_col_fri_close_keep.argtypes = [VP, VP, VP, U32, C.POINTER(LmnFriCloseResult), C.POINTER(VP)]
+        lib.lmn_positions_from_cpu.argtypes = [VP, VP, U32, U32, C.POINTER(VP)]
+        lib.lmn_positions_to_cpu.argtypes = [VP, VP, VP, C.POINTER(U32)]
+        lib.lmn_positions_log_domain.argtypes = [VP]
+        lib.lmn_positions_log_domain.restype = U32
+        lib.lmn_positions_free.argtypes = [VP, VP]
+        lib.lmn_positions_free.restype = None
+        lib.lmn_open_queries.argtypes = [VP, VP, C.POINTER(LmnOpenItem), U32, C.POINTER(LmnOpening)]
         lib.lmn_ctx_counter.argtypes = [VP, C.c_int]
         lib.lmn_ctx_counter.restype = C.c_uint64
         lib.lmn_tree_free.argtypes = [VP, VP]
@@ -868,6 +908,30 @@ class Tree:
             self.handle = None
 
 
+class Positions:
+    """`lmn_positions`: up to 1024 ascending distinct query positions of a domain of 2^log_domain rows, in device memory -
+    what `Context.open_queries` reads.  Made by `Context.positions_from_cpu` or left behind by
+    `Context.fri_close(..., keep=True)`."""
+
+    def __init__(self, ctx: "Context", handle):
+        self.ctx, self.handle = ctx, handle
+
+    @property
+    def log_domain(self) -> int:
+        return int(self.ctx.lib.lib.lmn_positions_log_domain(self.handle))
+
+    def to_cpu(self) -> List[int]:
+        buf = np.zeros(OPEN_MAX_POSITIONS, dtype=np.uint32)
+        n = C.c_uint32()
+        self.ctx._check(self.ctx.lib.lib.lmn_positions_to_cpu(self.ctx.handle, self.handle, buf.ctypes.data, C.byref(n)))
+        return [int(v) for v in buf[:n.value]]
+
+    def free(self):
+        if self.handle:
+            self.ctx.lib.lib.lmn_positions_free(self.ctx.handle, self.handle)
+            self.handle = None
+
+
 class PreparedSettings:
     """`lmn_prepared`: a circuit's preprocessed tree (tree 0) - LUT and range-check columns, coefficients, low-degree
     extension, Merkle layers, root - built once on the device and shared read-only by every proof that names it with
@@ -1047,25 +1111,74 @@ class Context:
                 if p:
                     L.lmn_free(p)
 
-    def fri_close(self, col: Col, start_digest: bytes, log_query_domain: int) -> FriClose:
+    def positions_from_cpu(self, positions, log_domain: int) -> Positions:
+        """`lmn_positions_from_cpu`: at most 1024 strictly ascending positions < 2^log_domain"""
+        pos = np.ascontiguousarray(positions, dtype=np.uint32).reshape(-1)
+        out = C.c_void_p()
+        self._check(self.lib.lib.lmn_positions_from_cpu(self.handle, pos.ctypes.data if len(pos) else None, len(pos),
+                                                        log_domain, C.byref(out)))
+        return Positions(self, out)
+
+    def open_queries(self, positions: Positions, items) -> List[Opening]:
+        """`lmn_open_queries`: opens every item - (tree, the handles it was committed from[, flags]) - at `positions`
+        with one plan launch, one fetch launch, one transfer and one wait; the walk that decides what an opening needs
+        runs on the device."""
+        L = self.lib.lib
+        n = len(items)
+        c_items = (LmnOpenItem * max(n, 1))()
+        keep = []
+        for k, it in enumerate(items):
+            tree, cols = it[0], it[1]
+            arr = (C.c_void_p * max(len(cols), 1))(*[c.handle for c in cols])
+            keep.append(arr)
+            c_items[k] = LmnOpenItem(tree.handle, arr, len(cols), int(it[2]) if len(it) > 2 else 0)
+        res = (LmnOpening * max(n, 1))()
+        try:
+            self._check(L.lmn_open_queries(self.handle, positions.handle, c_items, n, res))
+
+            def words(p, cnt):
+                return np.frombuffer(C.string_at(p, 4 * cnt), dtype=np.uint32).copy() if cnt else np.zeros(0, dtype=np.uint32)
+            out = []
+            for k in range(n):
+                r = res[k]
+                raw = C.string_at(r.hash_witness, 32 * r.n_hashes) if r.n_hashes else b""
+                fri = words(r.fri_witness, int(r.n_fri_words)).reshape(-1, 4)
+                out.append(Opening(words(r.queried_values, int(r.n_values)),
+                                   [raw[32 * i:32 * i + 32] for i in range(int(r.n_hashes))],
+                                   words(r.column_witness, int(r.n_column_words)), [tuple(int(v) for v in q) for q in fri]))
+            return out
+        finally:
+            for k in range(n):
+                for name in ("queried_values", "hash_witness", "column_witness", "fri_witness"):
+                    p = getattr(res[k], name)
+                    if p:
+                        L.lmn_free(p)
+
+    def fri_close(self, col: Col, start_digest: bytes, log_query_domain: int, keep: bool = False):
         """`lmn_col_fri_close`: what stands between FRI's layer loop and the decommitment, on the device - the last layer's
         polynomial (`col`: 4 coordinate columns of 2^(log_last_layer + log_blowup) rows) and its degree check, mix_felts
         from the channel digest `start_digest`, the grind, mix_u64 and the query positions of a domain of
-        2^log_query_domain rows."""
+        2^log_query_domain rows.  keep=True (`lmn_col_fri_close_keep`): -> (FriClose, Positions) - the positions also stay
+        on the device, in a handle `open_queries` reads."""
         L = self.lib.lib
         if len(start_digest) != 32:
             raise ValueError("start_digest is 32 bytes")
         dig = (C.c_uint8 * 32)(*start_digest)
         res = LmnFriCloseResult()
+        kept = C.c_void_p()
         try:
-            self._check(L.lmn_col_fri_close(self.handle, col.handle, dig, log_query_domain, C.byref(res)))
+            if keep:
+                self._check(L.lmn_col_fri_close_keep(self.handle, col.handle, dig, log_query_domain, C.byref(res), C.byref(kept)))
+            else:
+                self._check(L.lmn_col_fri_close(self.handle, col.handle, dig, log_query_domain, C.byref(res)))
             nc, npos = int(res.n_coeffs), int(res.n_positions)
             coeffs = np.frombuffer(C.string_at(res.coeffs, 16 * nc), dtype=np.uint32).reshape(nc, 4)
             positions = np.frombuffer(C.string_at(res.positions, 4 * npos), dtype=np.uint32) if npos else []
-            return FriClose([tuple(int(v) for v in c) for c in coeffs],
-                            None if res.first_bad == 0xffffffff else int(res.first_bad), int(res.nonce), int(res.grind_rounds),
-                            [int(v) for v in positions], bytes(res.digest_after_coeffs), bytes(res.digest_after_nonce),
-                            bytes(res.digest_end), int(res.n_sent_end))
+            out = FriClose([tuple(int(v) for v in c) for c in coeffs],
+                           None if res.first_bad == 0xffffffff else int(res.first_bad), int(res.nonce), int(res.grind_rounds),
+                           [int(v) for v in positions], bytes(res.digest_after_coeffs), bytes(res.digest_after_nonce),
+                           bytes(res.digest_end), int(res.n_sent_end))
+            return (out, Positions(self, kept)) if keep else out
         finally:
             for name in ("coeffs", "positions"):
                 p = getattr(res, name)

@@ -307,6 +307,69 @@ void launch_tree_decommit(const uint32_t* const* src, const DecommitEntry* plan,
 void launch_col_gather(const uint32_t* cols, uint32_t log_size, uint32_t ncols, const uint32_t* positions, uint32_t n,
                        uint32_t* out, lmn_stream_t s);
 
+// ---- openings planned on the device (lmn_open_queries): MerkleProver::decommit's walk and FRI's pair expansion, restated
+// as a kernel that reads the query positions where they were born - in device memory - so that no host walk stands
+// between the positions and the fetch.  Three launches behind each other, no wait in between:
+//   k_open_plan     one workgroup per item (a tree to open): walks the layers, writes the item's four counts and its
+//                   entries (OpenEntry) into the item's region of the plan table
+//   k_open_offsets  one workgroup: the items' counts -> compact word offsets in the proof's order (per item: FRI
+//                   witness, queried values, hash witness, column witness; items in launch order)
+//   k_open_fetch    one lane per entry over the host's upper bound; an item's entry count is read from device memory
+//                   and surplus workgroups return at once
+constexpr uint32_t OPEN_MAX_POSITIONS = 1024;   // = FRI_CLOSE_MAX_QUERIES
+constexpr uint32_t OPEN_MAX_NODES = 2048;       // a layer's node set: the positions, pair-expanded
+constexpr uint32_t OPEN_MAX_ITEMS = 64;
+constexpr uint32_t OPEN_MAX_LOG = 31;
+constexpr uint32_t OPEN_FRI_PAIRS = 1u;         // = LMN_OPEN_FRI_PAIRS
+constexpr uint32_t OPEN_EMPTY = 1u << 31;       // an item without a tree (a proof's tree 0 without lookups): four empty lists
+constexpr uint32_t OPEN_STORED = 0xffu;         // OpenItemDesc::cut_of_layer: the layer lies in memory
+enum { OPEN_LIST_FRI = 0, OPEN_LIST_QUERIED = 1, OPEN_LIST_HASH = 2, OPEN_LIST_WITNESS = 3 };
+// what the host knows of an item before the positions exist
+struct OpenItemDesc {
+  uint32_t max_log, flags;
+  uint32_t layer_src0;   // pointer-table index of layer 0; layer l is layer_src0 + l
+  uint32_t col_src0;     // pointer-table index of the first column, columns in tree order (size descending)
+  uint32_t ent_off, ent_cap;           // the item's region of the plan table, in entries
+  uint32_t job_off, job_cap;           // its region of the recompute table (hashes of layers a fused launch never stored)
+  uint32_t ncols[OPEN_MAX_LOG + 1];    // columns per log size
+  uint8_t cut_of_layer[OPEN_MAX_LOG + 1];   // OPEN_STORED, or the index of the layer's MerkleCut in the launch's cut table
+};
+// what the device writes per item: count[list] in words (hashes: in hashes), then - by k_open_offsets - base[list], the
+// word offset of the list in the output
+struct OpenItemHeader {
+  uint32_t count[4];
+  uint32_t n_entries, overflow, n_jobs, pad;
+  uint32_t base[4];
+  uint32_t pad2[4];
+};
+struct OpenHeader {        // in front of the items' headers; the output's first bytes
+  uint32_t overflow;       // an item's plan exceeded its region or the node set, or the lists exceed out_cap_words
+  uint32_t total_words, n_positions, pad;
+};
+struct OpenEntry {
+  uint32_t src;   // index into the pointer table
+  uint32_t idx;   // node (hash entries: 8 words at 8 * idx) or row
+  uint32_t dst;   // word offset inside the item's list
+  uint32_t list;  // OPEN_LIST_*
+};
+// *count = the number of positions (clamped to OPEN_MAX_POSITIONS), positions = ascending and distinct; found (may be null):
+// the plan is made only if *found == 1 (FriCloseHeader::found: without a nonce k_fri_queries wrote no positions).
+// A hash of a layer that is not stored goes to `jobs` instead of `entries`: src = the cut's index, idx = the node,
+// list = OPEN_LIST_HASH | depth << 8 (levels above the cut's start level), fetched by launch_open_recompute from `cuts`
+// (MerkleRecompute templates: node, depth and dst_off unused).  *n_launched (may be null) counts the launches made.
+void launch_open_plan(const uint32_t* count, const uint32_t* positions, const uint32_t* found, uint32_t log_domain,
+                      const OpenItemDesc* items, uint32_t n_items, OpenItemHeader* headers, OpenEntry* entries, OpenEntry* jobs,
+                      lmn_stream_t s, uint64_t* n_launched = nullptr);
+void launch_open_offsets(const uint32_t* count, OpenHeader* header, OpenItemHeader* headers, uint32_t n_items,
+                         uint32_t out_cap_words, lmn_stream_t s);
+void launch_open_fetch(const uint32_t* const* src, uint32_t n_src, const OpenItemDesc* items, uint32_t n_items, uint32_t max_cap,
+                       OpenHeader* header, const OpenItemHeader* headers, const OpenEntry* entries, uint32_t* out,
+                       lmn_stream_t s, uint64_t* n_launched = nullptr);
+struct MerkleRecompute;
+void launch_open_recompute(const MerkleRecompute* cuts, uint32_t n_cuts, const OpenItemDesc* items, uint32_t n_items,
+                           uint32_t max_job_cap, OpenHeader* header, const OpenItemHeader* headers, const OpenEntry* jobs,
+                           uint32_t* out, lmn_stream_t s);
+
 // ---- proof-of-work grind (GrindOps on the device): one launch examines the nonces [base, base + 2^window_log) and
 // lowers *best (device, u64) to the smallest of them that passes, if it is below what *best holds.  A block whose nonces
 // all lie above *best at its start returns at once, so launches queued behind the one that found a nonce cost nothing

@@ -1107,6 +1107,32 @@ void launch_fri_tail(DevChannel* ch, const FriTailLayer* layers, int n_layers, i
 // =============================================================================================
 // gather
 // =============================================================================================
+// A tree node its fused launch kept in registers only, recomputed from the launch's start level: lane q of a quad hashes
+// start node (node << depth) + q, the quad reduces the 2^depth hashes pairwise; h of every lane of the quad = the node's
+// hash.  Every lane of the workgroup calls it together (every quad does the same: block-uniform control flow).
+LMN_D void merkle_recompute_node(const MerkleRecompute& j, uint32_t node, int depth, uint32_t (&h)[8]) {
+  const uint32_t q = threadIdx.x & 3u;
+  const uint32_t i0 = (node << depth) + (q & ((1u << depth) - 1u));
+  if (j.below) {
+    uint32_t mb[16];
+    merkle_load_below(j.below, j.below_ncols, j.size, i0, mb);
+    merkle_hash_below(j.sg, j.ncols, j.size, j.below_ncols, i0, mb, h);
+  } else {
+    merkle_hash_start(j.prev, j.sg, j.ncols, j.size, i0, h);
+  }
+  for (int s = 0; s < depth; ++s) {
+    const bool hi = ((q >> s) & 1u) != 0u;
+    uint32_t m[16];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const uint32_t other = lmn_shfl_xor(h[k], 1 << s);
+      m[k] = hi ? other : h[k];
+      m[8 + k] = hi ? h[k] : other;
+    }
+    b2_compress_fresh(h, m, 64u);
+  }
+}
+
 LMN_KERNEL k_gather(const uint32_t* __restrict__ arena, const uint32_t* __restrict__ shared,
                     const GatherEntry* __restrict__ entries, uint32_t n, const MerkleRecompute* __restrict__ jobs,
                     uint32_t n_jobs, uint32_t* __restrict__ out) {
@@ -1120,30 +1146,9 @@ LMN_KERNEL k_gather(const uint32_t* __restrict__ arena, const uint32_t* __restri
   }
   e -= n;
   if (e >= n_jobs) return;
-  // A tree node the fused launch kept in registers only: lane q of a quad hashes start node (node << depth) + q, the
-  // quad reduces the 2^depth hashes pairwise (every quad of the block does the same; block-uniform control flow).
   const MerkleRecompute j = jobs[e];
-  const uint32_t q = threadIdx.x & 3u;
   uint32_t h[8];
-  const uint32_t i0 = (j.node << j.depth) + (q & ((1u << j.depth) - 1u));
-  if (j.below) {
-    uint32_t mb[16];
-    merkle_load_below(j.below, j.below_ncols, j.size, i0, mb);
-    merkle_hash_below(j.sg, j.ncols, j.size, j.below_ncols, i0, mb, h);
-  } else {
-    merkle_hash_start(j.prev, j.sg, j.ncols, j.size, i0, h);
-  }
-  for (int s = 0; s < j.depth; ++s) {
-    const bool hi = ((q >> s) & 1u) != 0u;
-    uint32_t m[16];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const uint32_t other = lmn_shfl_xor(h[k], 1 << s);
-      m[k] = hi ? other : h[k];
-      m[8 + k] = hi ? h[k] : other;
-    }
-    b2_compress_fresh(h, m, 64u);
-  }
+  merkle_recompute_node(j, j.node, j.depth, h);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) out[j.dst_off + k] = h[k];
@@ -1201,6 +1206,374 @@ void launch_col_gather(const uint32_t* cols, uint32_t log_size, uint32_t ncols, 
   if (n == 0) return;
   LMN_LAUNCH(k_col_gather, dim3((n + DECOMMIT_TPB - 1) / DECOMMIT_TPB), dim3(DECOMMIT_TPB), 0, s, cols, log_size, ncols,
              positions, n, out);
+}
+
+// =============================================================================================
+// Openings planned on the device (kernels.h launch_open_plan / launch_open_offsets / launch_open_fetch).
+//
+// k_open_plan restates plan_opening (level2.cpp) / plan_merkle_decommit and plan_fri_witness (decommit.cpp) for one item
+// per workgroup.  Every set it handles - the positions, a size's group, a layer's node set - is a sorted array of
+// distinct values in LDS, so the sequential merge becomes counting: an element's place in a merged or compacted array is
+// the number of elements in front of it, found by a block-wide exclusive scan over flags (open_scan) or a binary search
+// (open_lb).  Per layer, from the leaves up:
+//   A    = the parents of the previous node set, each with the mask of its children that were in it
+//   G    = the layer's group: the positions folded to this size, pair-expanded under OPEN_FRI_PAIRS (then each pair member
+//          that is no position gives 4 FRI witness entries)
+//   cur  = A merged with G; a node of G is queried, a child outside the mask is a hash to fetch
+// and a scan over cur's (hashes, queried) counts gives every entry its place in its list.  An entry carries its
+// destination, so the order of the plan table itself is free and lanes write it without atomics.
+// Nothing here trusts the positions: they are masked to the domain, every LDS index is checked against OPEN_MAX_NODES,
+// every table index against the item's region, and k_open_fetch checks an entry's destination against the list it names.
+// Control flow around every barrier depends on counts the whole workgroup holds alike.
+// =============================================================================================
+constexpr uint32_t OPEN_TPB = 256;
+constexpr uint32_t OPEN_EPT = OPEN_MAX_NODES / OPEN_TPB;   // elements a lane owns: [tid * OPEN_EPT, (tid + 1) * OPEN_EPT)
+constexpr uint32_t OPEN_GROUPS = 16;                       // the scan's second level: groups of OPEN_TPB / OPEN_GROUPS lane totals
+static_assert(OPEN_EPT * OPEN_TPB == OPEN_MAX_NODES && OPEN_TPB % OPEN_GROUPS == 0, "a lane owns whole elements");
+
+// exclusive scan of v[0 .. n) in place (n <= OPEN_MAX_NODES), returns the total; every lane of the block calls it
+LMN_D uint32_t open_scan(uint32_t* v, uint32_t n, uint32_t* tot, uint32_t* grp) {
+  const uint32_t tid = threadIdx.x, i0 = tid * OPEN_EPT;
+  constexpr uint32_t PER = OPEN_TPB / OPEN_GROUPS;
+  __syncthreads();
+  uint32_t sum = 0u;
+  for (uint32_t i = i0; i < i0 + OPEN_EPT && i < n; ++i) {
+    const uint32_t t = v[i];
+    v[i] = sum;
+    sum += t;
+  }
+  tot[tid] = sum;
+  __syncthreads();
+  if (tid < OPEN_GROUPS) {
+    uint32_t acc = 0u;
+    for (uint32_t k = tid * PER; k < (tid + 1u) * PER; ++k) {
+      const uint32_t t = tot[k];
+      tot[k] = acc;
+      acc += t;
+    }
+    grp[tid] = acc;
+  }
+  __syncthreads();
+  uint32_t off = tot[tid], total = 0u;
+  for (uint32_t g = 0; g < OPEN_GROUPS; ++g) {
+    const uint32_t x = grp[g];
+    off += g < tid / PER ? x : 0u;
+    total += x;
+  }
+  for (uint32_t i = i0; i < i0 + OPEN_EPT && i < n; ++i) v[i] += off;
+  __syncthreads();
+  return total;
+}
+// number of elements of the ascending a[0 .. n) below x (ends for any content)
+LMN_D uint32_t open_lb(const uint32_t* a, uint32_t n, uint32_t x) {
+  uint32_t lo = 0u, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (a[mid] < x)
+      lo = mid + 1u;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+LMN_KERNEL k_open_plan(const uint32_t* __restrict__ count, const uint32_t* __restrict__ positions,
+                       const uint32_t* __restrict__ found, uint32_t log_domain, const OpenItemDesc* __restrict__ items,
+                       OpenItemHeader* __restrict__ headers, OpenEntry* __restrict__ entries, OpenEntry* __restrict__ jobs) {
+  LMN_SHARED uint32_t s_pos[OPEN_MAX_POSITIONS];
+  LMN_SHARED uint32_t s_set[2][OPEN_MAX_NODES];   // the previous and the current node set, swapped per layer
+  LMN_SHARED uint32_t s_a[OPEN_MAX_NODES], s_g[OPEN_MAX_NODES], s_scan[OPEN_MAX_NODES];
+  LMN_SHARED uint8_t s_amask[OPEN_MAX_NODES];     // A: bit b = child 2 * node + b was in the previous set
+  LMN_SHARED uint8_t s_gin[OPEN_MAX_NODES];       // pair-expanded G: the member is a position itself
+  LMN_SHARED uint8_t s_cflag[OPEN_MAX_NODES];     // cur: the child mask | 4 = queried
+  LMN_SHARED uint32_t s_tot[OPEN_TPB], s_grp[OPEN_GROUPS];
+  const uint32_t tid = threadIdx.x, i0 = tid * OPEN_EPT;
+  const OpenItemDesc* it = items + blockIdx.x;
+  const uint32_t max_log = it->max_log, layer_src0 = it->layer_src0, col_src0 = it->col_src0, cap = it->ent_cap;
+  const bool pairs = (it->flags & OPEN_FRI_PAIRS) != 0u;
+  OpenEntry* ent = entries + it->ent_off;
+  OpenEntry* job = jobs + it->job_off;
+  const uint32_t job_cap = it->job_cap;
+  // (block-uniform: no positions without a nonce, and none for an item without a tree)
+  const bool idle = (found && *found != 1u) || (it->flags & OPEN_EMPTY) != 0u;
+  const uint32_t n = idle ? 0u : *count < OPEN_MAX_POSITIONS ? *count : OPEN_MAX_POSITIONS;
+  bool overflow = !idle && (log_domain > OPEN_MAX_LOG || max_log > log_domain);
+  const uint32_t dmask = overflow ? 0u : (uint32_t)((1ull << log_domain) - 1u);
+  for (uint32_t i = tid; i < n; i += OPEN_TPB) s_pos[i] = positions[i] & dmask;
+  __syncthreads();   // (the only barrier a lane's own elements do not cover: s_pos is loaded strided)
+  uint32_t cnt[4] = {0u, 0u, 0u, 0u};
+  uint32_t ne = 0u, nj = 0u, first_col = 0u, np = 0u;
+  uint32_t* prev = s_set[0];
+  uint32_t* cur = s_set[1];
+  for (int log = idle ? -1 : (int)max_log; log >= 0 && !overflow; --log) {
+    const uint32_t nc = it->ncols[log], shift = log_domain - (uint32_t)log;
+    const uint32_t lmask = (uint32_t)((1ull << log) - 1u), cmask = (uint32_t)((2ull << log) - 1u);
+    const bool have_prev = log < (int)max_log;
+    // ---- A: the parents of the previous set
+    uint32_t na = 0u;
+    if (np) {
+      for (uint32_t i = i0; i < i0 + OPEN_EPT && i < np; ++i) s_scan[i] = i == 0u || (prev[i] >> 1) != (prev[i - 1u] >> 1) ? 1u : 0u;
+      na = open_scan(s_scan, np, s_tot, s_grp);
+      for (uint32_t i = i0; i < i0 + OPEN_EPT && i < np; ++i) {
+        const uint32_t v = prev[i];
+        if (i != 0u && (v >> 1) == (prev[i - 1u] >> 1)) continue;
+        uint32_t m = 1u << (v & 1u);
+        if (i + 1u < np && (prev[i + 1u] >> 1) == (v >> 1)) m |= 1u << (prev[i + 1u] & 1u);
+        s_a[s_scan[i]] = v >> 1;   // (its rank among at most np first-of-pair elements)
+        s_amask[s_scan[i]] = (uint8_t)m;
+      }
+    }
+    // ---- G: the positions folded to this size; F (the plain fold) is kept in `cur` while the pairs are made
+    uint32_t ng = 0u;
+    if (nc && n) {
+      if (pairs && nc != 4u) {
+        overflow = true;
+        break;
+      }
+      for (uint32_t i = i0; i < i0 + OPEN_EPT && i < n; ++i)
+        s_scan[i] = i == 0u || (s_pos[i] >> shift) != (s_pos[i - 1u] >> shift) ? 1u : 0u;
+      const uint32_t nf = open_scan(s_scan, n, s_tot, s_grp);
+      uint32_t* F = pairs ? cur : s_g;
+      for (uint32_t i = i0; i < i0 + OPEN_EPT && i < n; ++i)
+        if (i == 0u || (s_pos[i] >> shift) != (s_pos[i - 1u] >> shift)) F[s_scan[i]] = s_pos[i] >> shift;
+      ng = nf;
+      if (pairs) {
+        __syncthreads();
+        for (uint32_t i = i0; i < i0 + OPEN_EPT && i < nf; ++i) s_scan[i] = i == 0u || (F[i] >> 1) != (F[i - 1u] >> 1) ? 1u : 0u;
+        const uint32_t n_pairs = open_scan(s_scan, nf, s_tot, s_grp);
+        for (uint32_t i = i0; i < i0 + OPEN_EPT && i < nf; ++i) {
+          const uint32_t v = F[i];
+          if (i != 0u && (v >> 1) == (F[i - 1u] >> 1)) continue;
+          const uint32_t k = 2u * s_scan[i];   // n_pairs <= nf <= 1024: k + 1 < OPEN_MAX_NODES
+          const bool both = i + 1u < nf && (F[i + 1u] >> 1) == (v >> 1);
+          s_g[k] = v & ~1u;
+          s_g[k + 1u] = v | 1u;
+          s_gin[k] = (v & 1u) == 0u ? 1u : 0u;
+          s_gin[k + 1u] = (v & 1u) != 0u || both ? 1u : 0u;
+        }
+        ng = 2u * n_pairs;
+        // the FRI witness of this size: 4 coordinate words per member that is no position, members ascending
+        const uint32_t n_fri = ng >= nf ? ng - nf : 0u;
+        if (ne + 4u * n_fri > cap) {
+          overflow = true;
+          break;
+        }
+        __syncthreads();
+        for (uint32_t e = i0; e < i0 + OPEN_EPT && e < ng; ++e) {
+          if (s_gin[e]) continue;
+          const uint32_t at = e - open_lb(F, nf, s_g[e]);   // members in front of it that are no positions either
+          if (at >= n_fri) continue;
+          for (uint32_t k = 0; k < 4u; ++k)
+            ent[ne + 4u * at + k] = OpenEntry{col_src0 + first_col + k, s_g[e] & lmask, cnt[OPEN_LIST_FRI] + 4u * at + k, OPEN_LIST_FRI};
+        }
+        cnt[OPEN_LIST_FRI] += 4u * n_fri;
+        ne += 4u * n_fri;
+      }
+    }
+    // ---- cur = A merged with G
+    __syncthreads();
+    uint32_t ncur;
+    if (ng == 0u || na == 0u) {
+      ncur = ng ? ng : na;
+      for (uint32_t i = i0; i < i0 + OPEN_EPT && i < ncur; ++i) {
+        cur[i] = ng ? s_g[i] : s_a[i];
+        s_cflag[i] = ng ? (uint8_t)4u : s_amask[i];
+      }
+    } else {
+      for (uint32_t i = i0; i < i0 + OPEN_EPT && i < na; ++i) {
+        const uint32_t lb = open_lb(s_g, ng, s_a[i]);
+        s_scan[i] = lb < ng && s_g[lb] == s_a[i] ? 1u : 0u;
+      }
+      const uint32_t n_both = open_scan(s_scan, na, s_tot, s_grp);   // s_scan[i]: nodes of A below A[i] that are in G as well
+      ncur = na + ng - n_both;
+      if (ncur > OPEN_MAX_NODES) {
+        overflow = true;
+        break;
+      }
+      for (uint32_t i = i0; i < i0 + OPEN_EPT && i < na; ++i) {
+        const uint32_t a = s_a[i], lb = open_lb(s_g, ng, a);
+        const bool in_g = lb < ng && s_g[lb] == a;
+        const uint32_t r = i + lb - s_scan[i];
+        if (r < ncur) {
+          cur[r] = a;
+          s_cflag[r] = (uint8_t)(s_amask[i] | (in_g ? 4u : 0u));
+        }
+      }
+      for (uint32_t j = i0; j < i0 + OPEN_EPT && j < ng; ++j) {
+        const uint32_t g = s_g[j], lb = open_lb(s_a, na, g);
+        if (lb < na && s_a[lb] == g) continue;
+        const uint32_t r = j + lb - (lb < na ? s_scan[lb] : n_both);
+        if (r < ncur) {
+          cur[r] = g;
+          s_cflag[r] = (uint8_t)4u;
+        }
+      }
+    }
+    // ---- the layer's entries: per node the hashes of its children outside the mask, then its column values
+    __syncthreads();
+    for (uint32_t i = i0; i < i0 + OPEN_EPT && i < ncur; ++i) {
+      const uint32_t f = s_cflag[i];
+      const uint32_t hc = have_prev ? 2u - (f & 1u) - ((f >> 1) & 1u) : 0u;
+      s_scan[i] = hc | ((f >> 2) & 1u) << 16;
+    }
+    const uint32_t both_tot = open_scan(s_scan, ncur, s_tot, s_grp);
+    const uint32_t nh = both_tot & 0xffffu, nq = both_tot >> 16, nw = ncur - nq;
+    // the children's layer was kept in registers by its launch: their hashes are recompute jobs
+    const uint32_t cut = have_prev ? it->cut_of_layer[log + 1] : OPEN_STORED;
+    const uint32_t nh_ent = cut == OPEN_STORED ? nh : 0u, nh_job = nh - nh_ent;
+    if (ne + nh_ent + ncur * nc > cap || nj + nh_job > job_cap) {
+      overflow = true;
+      break;
+    }
+    for (uint32_t i = i0; i < i0 + OPEN_EPT && i < ncur; ++i) {
+      const uint32_t f = s_cflag[i], node = cur[i] & lmask;
+      const uint32_t qp = s_scan[i] >> 16, wp = i - qp;
+      uint32_t hp = s_scan[i] & 0xffffu, slot = ne + (cut == OPEN_STORED ? hp : 0u) + i * nc;
+      if (have_prev) {
+        for (uint32_t b = 0; b < 2u; ++b)
+          if (!((f >> b) & 1u)) {
+            const uint32_t child = (2u * node + b) & cmask, dst = (cnt[OPEN_LIST_HASH] + hp) * 8u;
+            if (cut == OPEN_STORED)
+              ent[slot++] = OpenEntry{layer_src0 + (uint32_t)log + 1u, child, dst, OPEN_LIST_HASH};
+            else
+              job[nj + hp] = OpenEntry{cut, child, dst, OPEN_LIST_HASH | ((uint32_t)log + 1u) << 8};   // (| the children's layer)
+            ++hp;
+          }
+      }
+      const bool q = (f & 4u) != 0u;
+      const uint32_t dst0 = q ? cnt[OPEN_LIST_QUERIED] + qp * nc : cnt[OPEN_LIST_WITNESS] + wp * nc;
+      for (uint32_t c = 0; c < nc; ++c)
+        ent[slot++] = OpenEntry{col_src0 + first_col + c, node, dst0 + c, q ? (uint32_t)OPEN_LIST_QUERIED : (uint32_t)OPEN_LIST_WITNESS};
+    }
+    cnt[OPEN_LIST_HASH] += nh;
+    cnt[OPEN_LIST_QUERIED] += nq * nc;
+    cnt[OPEN_LIST_WITNESS] += nw * nc;
+    ne += nh_ent + ncur * nc;
+    nj += nh_job;
+    first_col += nc;
+    uint32_t* t = prev;
+    prev = cur;
+    cur = t;
+    np = ncur;
+  }
+  if (tid == 0u) {
+    OpenItemHeader* h = headers + blockIdx.x;
+    for (int k = 0; k < 4; ++k) h->count[k] = overflow ? 0u : cnt[k];
+    h->n_entries = overflow ? 0u : ne;
+    h->n_jobs = overflow ? 0u : nj;
+    h->overflow = overflow ? 1u : 0u;
+  }
+}
+
+// (one lane: at most 64 items x 4 lists, a few hundred cycles behind the planner - not worth a scan)
+LMN_KERNEL k_open_offsets(const uint32_t* __restrict__ count, OpenHeader* header, OpenItemHeader* headers, uint32_t n_items,
+                          uint32_t out_cap_words) {
+  if (threadIdx.x != 0u) return;
+  uint64_t at = 0u;
+  uint32_t overflow = 0u;
+  for (uint32_t k = 0; k < n_items; ++k) {
+    OpenItemHeader* h = headers + k;
+    overflow |= h->overflow;
+    for (int l = 0; l < 4; ++l) {
+      h->base[l] = (uint32_t)(at < out_cap_words ? at : out_cap_words);
+      at += (uint64_t)h->count[l] * (l == OPEN_LIST_HASH ? 8u : 1u);
+    }
+  }
+  if (at > out_cap_words) overflow = 1u;
+  header->overflow = overflow;
+  header->total_words = overflow ? 0u : (uint32_t)at;
+  header->n_positions = *count < OPEN_MAX_POSITIONS ? *count : OPEN_MAX_POSITIONS;
+}
+
+// (an entry that fails a check below can only come from a defect of the planner: it raises the header's overflow word - a
+// plain vector store of 1, whoever else stores it - and the host refuses the whole opening instead of reading stale words)
+LMN_KERNEL k_open_fetch(const uint32_t* const* __restrict__ src, uint32_t n_src, const OpenItemDesc* __restrict__ items,
+                        OpenHeader* header, const OpenItemHeader* __restrict__ headers,
+                        const OpenEntry* __restrict__ entries, uint32_t* __restrict__ out) {
+  const uint32_t item = blockIdx.y, t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (header->overflow) return;
+  const OpenItemHeader* h = headers + item;
+  if (t >= h->n_entries || t >= items[item].ent_cap) return;   // the launch covers the host's upper bound
+  const OpenEntry e = entries[items[item].ent_off + t];
+  if (e.list > 3u || e.src >= n_src) {
+    header->overflow = 1u;
+    return;
+  }
+  const bool hash = e.list == OPEN_LIST_HASH;
+  if ((uint64_t)e.dst + (hash ? 8u : 1u) > (uint64_t)h->count[e.list] * (hash ? 8u : 1u)) {
+    header->overflow = 1u;
+    return;
+  }
+  const uint32_t* p = src[e.src];
+  uint32_t* o = out + h->base[e.list] + e.dst;   // (word-aligned only: the lists are compact)
+  if (hash) {
+    const uint4* hp = reinterpret_cast<const uint4*>(p) + (uint64_t)e.idx * 2;
+    const uint4 a = hp[0], b = hp[1];
+    o[0] = a.x, o[1] = a.y, o[2] = a.z, o[3] = a.w;
+    o[4] = b.x, o[5] = b.y, o[6] = b.z, o[7] = b.w;
+  } else {
+    *o = p[e.idx];
+  }
+}
+
+// A hash of a layer its fused launch never stored (k_gather's second form): one workgroup per job over the host's upper
+// bound; lane q of a quad hashes start node (node << depth) + q, the quad reduces pairwise, every quad does the same.
+LMN_KERNEL k_open_recompute(const MerkleRecompute* __restrict__ cuts, uint32_t n_cuts, const OpenItemDesc* __restrict__ items,
+                            OpenHeader* header, const OpenItemHeader* __restrict__ headers,
+                            const OpenEntry* __restrict__ jobs, uint32_t* __restrict__ out) {
+  const uint32_t item = blockIdx.y, t = blockIdx.x;
+  if (header->overflow) return;   // (block-uniform, as every return below)
+  const OpenItemHeader* h = headers + item;
+  if (t >= h->n_jobs || t >= items[item].job_cap) return;
+  const OpenEntry e = jobs[items[item].job_off + t];
+  if (e.src >= n_cuts || (uint64_t)e.dst + 8u > (uint64_t)h->count[OPEN_LIST_HASH] * 8u) {
+    if (threadIdx.x == 0u) header->overflow = 1u;
+    return;
+  }
+  const MerkleRecompute j = cuts[e.src];
+  int start_log = 0;
+  while ((1u << start_log) < j.size && start_log < 31) ++start_log;
+  const int depth = start_log - (int)(e.list >> 8);
+  if (depth < 0 || depth > 2) {
+    if (threadIdx.x == 0u) header->overflow = 1u;
+    return;
+  }
+  const uint32_t node = e.idx & ((1u << (start_log - depth)) - 1u);
+  uint32_t hh[8];
+  merkle_recompute_node(j, node, depth, hh);
+  if (threadIdx.x == 0) {
+    uint32_t* o = out + h->base[OPEN_LIST_HASH] + e.dst;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = hh[k];
+  }
+}
+
+void launch_open_plan(const uint32_t* count, const uint32_t* positions, const uint32_t* found, uint32_t log_domain,
+                      const OpenItemDesc* items, uint32_t n_items, OpenItemHeader* headers, OpenEntry* entries, OpenEntry* jobs,
+                      lmn_stream_t s, uint64_t* n_launched) {
+  if (!count || !positions || !items || !headers || !entries || !jobs || n_items == 0 || n_items > OPEN_MAX_ITEMS ||
+      log_domain > OPEN_MAX_LOG)
+    throw LmnError(-100, "open_plan: bad arguments");
+  LMN_LAUNCH(k_open_plan, dim3(n_items), dim3(OPEN_TPB), 0, s, count, positions, found, log_domain, items, headers, entries, jobs);
+  if (n_launched) ++*n_launched;
+}
+void launch_open_offsets(const uint32_t* count, OpenHeader* header, OpenItemHeader* headers, uint32_t n_items,
+                         uint32_t out_cap_words, lmn_stream_t s) {
+  LMN_LAUNCH(k_open_offsets, dim3(1), dim3(1), 0, s, count, header, headers, n_items, out_cap_words);
+}
+void launch_open_recompute(const MerkleRecompute* cuts, uint32_t n_cuts, const OpenItemDesc* items, uint32_t n_items,
+                           uint32_t max_job_cap, OpenHeader* header, const OpenItemHeader* headers, const OpenEntry* jobs,
+                           uint32_t* out, lmn_stream_t s) {
+  if (max_job_cap == 0 || n_items == 0) return;
+  LMN_LAUNCH(k_open_recompute, dim3(max_job_cap, n_items), dim3(64), 0, s, cuts, n_cuts, items, header, headers, jobs, out);
+}
+void launch_open_fetch(const uint32_t* const* src, uint32_t n_src, const OpenItemDesc* items, uint32_t n_items,
+                       uint32_t max_cap, OpenHeader* header, const OpenItemHeader* headers, const OpenEntry* entries,
+                       uint32_t* out, lmn_stream_t s, uint64_t* n_launched) {
+  if (max_cap == 0 || n_items == 0) return;
+  if (n_launched) ++*n_launched;
+  LMN_LAUNCH(k_open_fetch, dim3((max_cap + OPEN_TPB - 1) / OPEN_TPB, n_items), dim3(OPEN_TPB), 0, s, src, n_src, items,
+             header, headers, entries, out);
 }
 
 // =============================================================================================

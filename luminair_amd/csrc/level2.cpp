@@ -21,6 +21,12 @@ struct lmn_tree {
   std::vector<uint32_t> ncols_of_log;  // [log]: how many columns of 2^log rows it was committed from (lmn_tree_decommit)
 };
 
+struct lmn_positions {
+  uint32_t* d;          // word 0: their number; words 1 .. 1024: the positions (k_open_plan's input)
+  uint32_t log_domain;
+  uint32_t n;           // what the host knows of their number: an upper bound for sizing, exact once a wait has passed
+};
+
 namespace lmn {
 
 constexpr uint32_t COL_MAX_LOG = 27;  // 2^26-row traces have 2^27-row LDEs
@@ -401,6 +407,205 @@ void Context::col_gather(const lmn_col* c, const uint32_t* positions, uint32_t n
   memcpy(host_out, got, out_bytes);
 }
 
+// ---- query positions on the device, and openings planned there (lmn_positions_*, lmn_open_queries)
+static lmn_positions* new_positions(uint32_t log_domain, uint32_t n) {
+  lmn_positions* p = new lmn_positions{nullptr, log_domain, n};
+  try {
+    p->d = (uint32_t*)lmn_dev_malloc((1 + OPEN_MAX_POSITIONS) * 4);
+  } catch (const LmnError& e) {
+    delete p;
+    throw LmnError(LMN_ERR_OUT_OF_MEMORY, std::string("positions allocation failed: ") + e.what());
+  }
+  return p;
+}
+
+lmn_positions* Context::positions_from_cpu(const uint32_t* positions, uint32_t n, uint32_t log_domain) {
+  const char* F = "positions_from_cpu: ";
+  auto refuse = [&](const std::string& what) { throw LmnError(LMN_ERR_INVALID_ARGUMENT, F + what); };
+  if (log_domain > OPEN_MAX_LOG) refuse("log_domain is " + u32s(log_domain) + ", at most " + u32s(OPEN_MAX_LOG));
+  if (n > OPEN_MAX_POSITIONS) refuse("n is " + u32s(n) + ", at most " + u32s(OPEN_MAX_POSITIONS) + " positions");
+  if (n && !positions) refuse("positions is null with n = " + u32s(n));
+  for (uint32_t i = 0; i < n; ++i) {
+    if (positions[i] >> log_domain)
+      refuse("positions[" + u32s(i) + "] = " + u32s(positions[i]) + " is out of range for log_domain " + u32s(log_domain));
+    if (i && positions[i] <= positions[i - 1])
+      refuse("positions is not strictly ascending at index " + u32s(i) + " (" + u32s(positions[i - 1]) + " then " +
+             u32s(positions[i]) + ")");
+  }
+  set_device();
+  lmn_positions* p = new_positions(log_domain, n);
+  begin_op();
+  uint32_t* h = (uint32_t*)pin_alloc((1 + (size_t)n) * 4);
+  h[0] = n;
+  if (n) memcpy(h + 1, positions, (size_t)n * 4);
+  lmn_h2d(p->d, h, (1 + (size_t)n) * 4, stream_);
+  lmn_sync(stream_);   // the staging memory is the next op's
+  return p;
+}
+void Context::positions_to_cpu(const lmn_positions* p, uint32_t* host, uint32_t* n_out) {
+  set_device();
+  begin_op();
+  const uint32_t* got = (const uint32_t*)stage_download(p->d, (1 + OPEN_MAX_POSITIONS) * 4);
+  lmn_sync(stream_);
+  const uint32_t n = std::min(got[0], OPEN_MAX_POSITIONS);
+  if (n) memcpy(host, got + 1, (size_t)n * 4);
+  *n_out = n;
+}
+void Context::positions_free(lmn_positions* p) {
+  if (!p) return;
+  set_device();
+  lmn_sync(stream_);
+  lmn_dev_free(p->d);
+  delete p;
+}
+
+// What an item's plan and output can hold at most, from the NUMBER of positions alone (k_open_plan checks both): with m
+// nodes per layer at most - the positions, doubled by the pair expansion - a layer of 2^log nodes opens min(2^log, m) of
+// them, each with its column values and at most both children's hashes; a size's pairs have at most as many members
+// that are no positions as there are pairs.
+OpenBound open_bound(int max_log, const std::vector<uint32_t>& ncols_of_log, uint32_t n_positions, bool pairs) {
+  OpenBound b;
+  const uint64_t m = pairs ? 2ull * n_positions : n_positions;
+  for (int log = max_log; log >= 0; --log) {
+    const uint64_t nodes = std::min<uint64_t>(1ull << log, m);
+    const uint64_t hashes = log < max_log ? 2 * nodes : 0;
+    const uint64_t fri = pairs && ncols_of_log[log] ? 4 * std::min<uint64_t>(std::max<uint64_t>(1ull << log, 2) / 2, n_positions) : 0;
+    b.entries += nodes * ncols_of_log[log] + hashes + fri;
+    b.words += nodes * ncols_of_log[log] + 8 * hashes + fri;
+  }
+  return b;
+}
+
+void Context::open_queries(const lmn_positions* p, const lmn_open_item* items, uint32_t n_items, lmn_opening* out) {
+  const char* F = "open_queries: ";
+  auto refuse = [&](const std::string& what) { throw LmnError(LMN_ERR_INVALID_ARGUMENT, F + what); };
+  if (shard_.active) refuse("ctx is sharded (lmn_ctx_set_shard): openings are planned on an unsharded context only");
+  if (!p) refuse("positions is null");
+  if (n_items > OPEN_MAX_ITEMS) refuse("n_items is " + u32s(n_items) + ", at most " + u32s(OPEN_MAX_ITEMS));
+  if (n_items && !items) refuse("items is null with n_items = " + u32s(n_items));
+  if (n_items && !out) refuse("out is null with n_items = " + u32s(n_items));
+  // the items: their columns as at commit time (tree_decommit's rule), the pointer table, the bounds
+  std::vector<const uint32_t*> ptrs;
+  std::vector<OpenItemDesc> descs(n_items);
+  uint64_t total_entries = 0, total_words = 0, max_cap = 0;
+  std::vector<ColRef> sorted;
+  for (uint32_t k = 0; k < n_items; ++k) {
+    const lmn_open_item& it = items[k];
+    const std::string I = "items[" + u32s(k) + "]";
+    if (!it.tree) refuse(I + ".tree is null");
+    if (it.n_cols && !it.cols) refuse(I + ".cols is null with n_cols = " + u32s(it.n_cols));
+    if (it.flags & ~LMN_OPEN_FRI_PAIRS) refuse(I + ".flags = " + u32s(it.flags) + " holds an unknown flag");
+    const lmn_tree* t = it.tree;
+    const int max_log = t->max_log;
+    if (max_log > (int)p->log_domain)
+      refuse(I + ".tree has log size " + u32s(max_log) + ", larger than the positions' log_domain " + u32s(p->log_domain));
+    sorted.clear();
+    std::vector<uint32_t> have(max_log + 1, 0u);
+    for (uint32_t c = 0; c < it.n_cols; ++c) {
+      const lmn_col* col = it.cols[c];
+      if (!col) refuse(I + ".cols[" + u32s(c) + "] is null");
+      if ((int)col->log_size > max_log)
+        refuse(I + ".cols[" + u32s(c) + "] has log size " + u32s(col->log_size) + ", the tree's is " + u32s(max_log));
+      for (uint32_t j = 0; j < col->ncols; ++j) sorted.push_back({col->d + ((uint64_t)j << col->log_size), (int)col->log_size, false});
+      have[col->log_size] += col->ncols;
+    }
+    const bool pairs = (it.flags & LMN_OPEN_FRI_PAIRS) != 0;
+    for (int log = max_log; log >= 0; --log) {
+      if (have[log] != t->ncols_of_log[log])
+        refuse(I + ".cols holds " + u32s(have[log]) + " columns of log size " + u32s(log) + ", the tree was committed from " +
+               u32s(t->ncols_of_log[log]));
+      if (pairs && have[log] != 0 && (have[log] != 4 || log == 0))
+        refuse(I + ".flags: LMN_OPEN_FRI_PAIRS needs exactly 4 columns at each of the tree's sizes and none of log size 0; it has " +
+               u32s(have[log]) + " of log size " + u32s(log));
+    }
+    std::stable_sort(sorted.begin(), sorted.end(), [](auto& a, auto& b) { return a.log > b.log; });
+    OpenItemDesc& d = descs[k];
+    d = OpenItemDesc{};
+    d.max_log = (uint32_t)max_log;
+    d.flags = it.flags;
+    d.layer_src0 = (uint32_t)ptrs.size();
+    for (int l = 0; l <= max_log; ++l) ptrs.push_back(t->layers[l]);
+    d.col_src0 = (uint32_t)ptrs.size();
+    for (auto& c : sorted) ptrs.push_back(c.ptr);
+    for (int l = 0; l <= max_log; ++l) d.ncols[l] = t->ncols_of_log[l];
+    memset(d.cut_of_layer, (int)OPEN_STORED, sizeof d.cut_of_layer);   // a level-2 tree keeps every layer
+    const OpenBound b = open_bound(max_log, t->ncols_of_log, p->n, pairs);
+    d.ent_off = (uint32_t)total_entries;
+    d.ent_cap = (uint32_t)std::min<uint64_t>(b.entries, 0xffffffffu);
+    total_entries += b.entries;
+    total_words += b.words;
+    max_cap = std::max(max_cap, b.entries);
+    if (total_words * 4 > OPENING_MAX_BYTES || total_entries * sizeof(OpenEntry) > 4 * OPENING_MAX_BYTES)
+      refuse("items: the upper bound of the opening (" + u32s(total_words * 4) + " bytes up to " + I + ", for " + u32s(p->n) +
+             " positions) exceeds the " + u32s(OPENING_MAX_BYTES) + " bytes one call carries");
+  }
+  if (n_items == 0 || p->n == 0) return;   // (out is zeroed by the caller)
+  const size_t head_bytes = sizeof(OpenHeader) + n_items * sizeof(OpenItemHeader);
+  const size_t table_bytes = ptrs.size() * sizeof(void*) + n_items * sizeof(OpenItemDesc);
+  const size_t out_bytes = head_bytes + total_words * 4;
+  set_device();
+  arena_.reserve(std::max<size_t>(8u << 20, table_bytes + out_bytes + total_entries * sizeof(OpenEntry) + (1u << 20)));
+  begin_op();
+  // pointer table and descriptors: ONE transfer; nothing in them depends on the positions
+  char* h_tab = (char*)pin_alloc(table_bytes);
+  memcpy(h_tab, ptrs.data(), ptrs.size() * sizeof(void*));
+  memcpy(h_tab + ptrs.size() * sizeof(void*), descs.data(), n_items * sizeof(OpenItemDesc));
+  char* d_tab = (char*)arena_.alloc_bytes(table_bytes);
+  lmn_h2d(d_tab, h_tab, table_bytes, stream_);
+  const uint32_t* const* d_ptrs = (const uint32_t* const*)d_tab;
+  const OpenItemDesc* d_items = (const OpenItemDesc*)(d_tab + ptrs.size() * sizeof(void*));
+  char* d_out = (char*)arena_.alloc_bytes(out_bytes);   // header | item headers | the lists
+  OpenHeader* d_head = (OpenHeader*)d_out;
+  OpenItemHeader* d_heads = (OpenItemHeader*)(d_out + sizeof(OpenHeader));
+  OpenEntry* d_ent = (OpenEntry*)arena_.alloc_bytes(std::max<size_t>(total_entries, 1) * sizeof(OpenEntry));
+  // (the wrappers count the launches they make: open_counters_)
+  launch_open_plan(p->d, p->d + 1, nullptr, p->log_domain, d_items, n_items, d_heads, d_ent, d_ent, stream_, &open_counters_[0]);
+  launch_open_offsets(p->d, d_head, d_heads, n_items, (uint32_t)total_words, stream_);
+  launch_open_fetch(d_ptrs, (uint32_t)ptrs.size(), d_items, n_items, (uint32_t)max_cap, d_head, d_heads, d_ent,
+                    (uint32_t*)(d_out + head_bytes), stream_, &open_counters_[1]);
+  const char* got = (const char*)stage_download(d_out, out_bytes);
+  lmn_sync(stream_);
+  ++open_counters_[2];
+  const OpenHeader& head = *(const OpenHeader*)got;
+  const OpenItemHeader* heads = (const OpenItemHeader*)(got + sizeof(OpenHeader));
+  const uint32_t* words = (const uint32_t*)(got + head_bytes);
+  if (head.overflow) throw LmnError(LMN_ERR_INTERNAL, "open_queries: the device plan exceeded the bounds it was launched with");
+  std::vector<lmn_opening> res(n_items, lmn_opening{});
+  auto release = [&] {
+    for (auto& o : res) {
+      free(o.queried_values);
+      free(o.hash_witness);
+      free(o.column_witness);
+      free(o.fri_witness);
+    }
+  };
+  try {
+    for (uint32_t k = 0; k < n_items; ++k) {
+      const OpenItemHeader& h = heads[k];
+      uint64_t end = 0;
+      for (int l = 0; l < 4; ++l) end = std::max<uint64_t>(end, (uint64_t)h.base[l] + (uint64_t)h.count[l] * (l == OPEN_LIST_HASH ? 8 : 1));
+      if (end > total_words) throw LmnError(LMN_ERR_INTERNAL, "open_queries: the device plan's counts exceed the result block");
+      lmn_opening& o = res[k];
+      o.n_fri_words = h.count[OPEN_LIST_FRI];
+      o.n_values = h.count[OPEN_LIST_QUERIED];
+      o.n_hashes = h.count[OPEN_LIST_HASH];
+      o.n_column_words = h.count[OPEN_LIST_WITNESS];
+      o.fri_witness = malloc_words(o.n_fri_words);
+      o.queried_values = malloc_words(o.n_values);
+      o.hash_witness = (uint8_t*)malloc_words(o.n_hashes * 8);
+      o.column_witness = malloc_words(o.n_column_words);
+      if (o.n_fri_words) memcpy(o.fri_witness, words + h.base[OPEN_LIST_FRI], o.n_fri_words * 4);
+      if (o.n_values) memcpy(o.queried_values, words + h.base[OPEN_LIST_QUERIED], o.n_values * 4);
+      if (o.n_hashes) memcpy(o.hash_witness, words + h.base[OPEN_LIST_HASH], o.n_hashes * 32);
+      if (o.n_column_words) memcpy(o.column_witness, words + h.base[OPEN_LIST_WITNESS], o.n_column_words * 4);
+    }
+  } catch (...) {
+    release();
+    throw;
+  }
+  memcpy(out, res.data(), n_items * sizeof(lmn_opening));
+}
+
 // ---- the FRI commit loop on handles (lmn_col_fri_commit): prove()'s own layer loop (phase_fri.cpp fri_commit_layers) on
 // caller-given quotient columns, then everything it left in device memory brought to the host
 FriCommitOut::~FriCommitOut() {
@@ -536,7 +741,7 @@ lmn_fri_close_result FriCloseOut::release() {
 }
 
 void Context::col_fri_close(const lmn_col* last_layer, const uint8_t start_digest[32], uint32_t log_query_domain,
-                            FriCloseOut& out) {
+                            FriCloseOut& out, lmn_positions** keep) {
   const char* F = "fri_close: ";
   auto refuse = [&](const std::string& what) { throw LmnError(LMN_ERR_INVALID_ARGUMENT, F + what); };
   if (shard_.active) refuse("ctx is sharded (lmn_ctx_set_shard): the transcript is closed on an unsharded context only");
@@ -561,9 +766,15 @@ void Context::col_fri_close(const lmn_col* last_layer, const uint8_t start_diges
   hc.n_sent = 0;
   hc.variant = (cfg.protocol_variant & LMN_PV_DRAW_CTR_U32) ? 1u : 0u;
   FriClose fc;
+  lmn_positions* kept = keep ? new_positions(log_query_domain, 0) : nullptr;
   try {
     DevChannel* d_ch = (DevChannel*)stage_upload(&hc, sizeof hc);
     enqueue_fri_close(fc, last_layer->d, d_ch, log_query_domain);
+    if (kept) {   // behind k_fri_queries, in front of the wait: the block's count and positions into the handle
+      const FriCloseHeader* h = reinterpret_cast<const FriCloseHeader*>(fc.h_block);
+      lmn_h2d(kept->d, &h->n_positions, 4, stream_);
+      lmn_h2d(kept->d + 1, fc.h_block + sizeof(FriCloseHeader) / 4, (size_t)fc.n_queries * 4, stream_);
+    }
     lmn_sync(stream_);
     finish_fri_close(fc, channel, [&] {
       const size_t n = (size_t)1 << last_log;
@@ -573,10 +784,25 @@ void Context::col_fri_close(const lmn_col* last_layer, const uint8_t start_diges
       for (size_t i = 0; i < n; ++i) v[i] = QM31{raw[i], raw[n + i], raw[2 * n + i], raw[3 * n + i]};
       return v;
     }, false);
+    if (kept) {
+      kept->n = (uint32_t)fc.positions.size();
+      if (!fc.found) {   // nothing behind the grind ran: the host's positions
+        uint32_t* h = (uint32_t*)pin_alloc((1 + fc.positions.size()) * 4);
+        h[0] = kept->n;
+        if (kept->n) memcpy(h + 1, fc.positions.data(), fc.positions.size() * 4);
+        lmn_h2d(kept->d, h, (1 + fc.positions.size()) * 4, stream_);
+        lmn_sync(stream_);
+      }
+    }
   } catch (...) {
     lmn_sync(stream_);   // launches in flight read tables in the staging memory the next op reuses
+    if (kept) {
+      lmn_dev_free(kept->d);
+      delete kept;
+    }
     throw;
   }
+  if (keep) *keep = kept;
   lmn_fri_close_result& o = out.r;
   o.n_coeffs = (uint32_t)fc.coeffs.size();
   o.first_bad = fc.first_bad;
@@ -976,6 +1202,50 @@ int lmn_col_fri_close(lmn_ctx* ctx, const lmn_col* last_layer, const uint8_t sta
     ctx->impl->col_fri_close(last_layer, start_digest, log_query_domain, o);
     *result = o.release();
   });
+}
+int lmn_col_fri_close_keep(lmn_ctx* ctx, const lmn_col* last_layer, const uint8_t start_digest[32], uint32_t log_query_domain,
+                           lmn_fri_close_result* result, lmn_positions** positions_out) {
+  if (result) *result = lmn_fri_close_result{};
+  if (positions_out) *positions_out = nullptr;
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  return guard2(ctx, [&] {
+    if (!result) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "fri_close: result is null");
+    if (!positions_out) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "fri_close: positions_out is null");
+    lmn::FriCloseOut o;
+    lmn_positions* kept = nullptr;
+    ctx->impl->col_fri_close(last_layer, start_digest, log_query_domain, o, &kept);
+    *result = o.release();
+    *positions_out = kept;
+  });
+}
+int lmn_positions_from_cpu(lmn_ctx* ctx, const uint32_t* positions, uint32_t n, uint32_t log_domain, lmn_positions** out) {
+  if (out) *out = nullptr;
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  return guard2(ctx, [&] {
+    if (!out) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "positions_from_cpu: out is null");
+    *out = ctx->impl->positions_from_cpu(positions, n, log_domain);
+  });
+}
+int lmn_positions_to_cpu(lmn_ctx* ctx, const lmn_positions* positions, uint32_t* host, uint32_t* n_out) {
+  if (n_out) *n_out = 0;
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  return guard2(ctx, [&] {
+    if (!positions) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "positions_to_cpu: positions is null");
+    if (!host) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "positions_to_cpu: host is null");
+    if (!n_out) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "positions_to_cpu: n_out is null");
+    ctx->impl->positions_to_cpu(positions, host, n_out);
+  });
+}
+uint32_t lmn_positions_log_domain(const lmn_positions* positions) { return positions ? positions->log_domain : 0; }
+void lmn_positions_free(lmn_ctx* ctx, lmn_positions* positions) {
+  if (ctx && positions) guard2(ctx, [&] { ctx->impl->positions_free(positions); });
+}
+int lmn_open_queries(lmn_ctx* ctx, const lmn_positions* positions, const lmn_open_item* items, uint32_t n_items,
+                     lmn_opening* out) {
+  if (out)
+    for (uint32_t k = 0; k < n_items; ++k) out[k] = lmn_opening{};
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  return guard2(ctx, [&] { ctx->impl->open_queries(positions, items, n_items, out); });
 }
 void lmn_tree_free(lmn_ctx* ctx, lmn_tree* tree) {
   if (ctx && tree) guard2(ctx, [&] { ctx->impl->tree_free(tree); });

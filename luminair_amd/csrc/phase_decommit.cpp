@@ -2,6 +2,8 @@
 // through one planned gather launch; assembles the proof container.
 #include "prove_run.h"
 
+#include <array>
+
 namespace lmn {
 
 PowWords pow_words_of(const Channel& ch, uint32_t pow_bits, bool& kat) {
@@ -199,111 +201,282 @@ void Context::run_queries(ProofRun& r) {
   hm.mark("pow+queries");
 }
 
+// LMN_DEVICE_DECOMMIT=1 (docs/SWITCHES.md; effective where the close runs on the device): the openings of every tree
+// [first FRI tree, inner layers..., trees 0..3] planned by k_open_plan from the positions k_fri_queries left in the result
+// block, fetched into a page-locked block sized from n_queries - all queued behind k_fri_queries, in front of the FRI wait.
+// The descriptor table depends on nothing the device has yet to compute: layer and column pointers (arena, or the prepared
+// slab: absolute pointers serve both), columns per size, and the MerkleCut of every layer its launch never stored.
+void Context::enqueue_device_decommit(ProofRun& r) {
+  LMN_RUN_ALIASES(r);
+  const FriClose& fc = r.close;
+  struct Item {
+    const DevMerkle* m;
+    std::vector<ColRef> cols;
+    bool pairs;
+  };
+  std::vector<Item> its;
+  its.push_back({&first_merkle, first_cols, true});
+  for (auto& fl : inner) {
+    Item it{&fl.merkle, {}, true};
+    secure_columns(fl.vals, fl.log, fl.sharded, g, it.cols);
+    its.push_back(std::move(it));
+  }
+  for (auto* t : trees) {
+    Item it{&t->merkle, {}, false};
+    for (auto& c : t->cols) it.cols.push_back({c.lde, c.log_size + lb, c.sharded});
+    std::stable_sort(it.cols.begin(), it.cols.end(), [](auto& a, auto& b) { return a.log > b.log; });
+    its.push_back(std::move(it));
+  }
+  if (its.size() > OPEN_MAX_ITEMS) return;   // (more FRI layers than a launch takes: the host plans)
+  const uint32_t n_items = (uint32_t)its.size(), nq = fc.n_queries;
+  std::vector<const uint32_t*> ptrs;
+  std::vector<OpenItemDesc> descs(n_items);
+  std::vector<MerkleRecompute> cuts;
+  uint64_t total_entries = 0, total_jobs = 0, total_words = 0, max_cap = 0, max_job_cap = 0;
+  for (uint32_t k = 0; k < n_items; ++k) {
+    const DevMerkle& m = *its[k].m;
+    OpenItemDesc& d = descs[k];
+    d = OpenItemDesc{};
+    memset(d.cut_of_layer, (int)OPEN_STORED, sizeof d.cut_of_layer);
+    d.ent_off = (uint32_t)total_entries;
+    d.job_off = (uint32_t)total_jobs;
+    if (m.max_log < 0) {
+      d.flags = OPEN_EMPTY;
+      continue;
+    }
+    if (m.max_log > (int)OPEN_MAX_LOG) throw LmnError(LMN_ERR_INTERNAL, "device decommit: a tree larger than the planner takes");
+    d.max_log = (uint32_t)m.max_log;
+    d.flags = its[k].pairs ? OPEN_FRI_PAIRS : 0u;
+    std::vector<uint32_t> ncols_of_log(m.max_log + 1, 0u);
+    for (auto& c : its[k].cols) {
+      if (c.log < 0 || c.log > m.max_log) throw LmnError(LMN_ERR_INTERNAL, "device decommit: a column larger than its tree");
+      ++ncols_of_log[c.log];
+    }
+    d.layer_src0 = (uint32_t)ptrs.size();
+    const uint64_t mm = its[k].pairs ? 2ull * nq : nq;
+    uint64_t job_cap = 0;
+    for (int l = 0; l <= m.max_log; ++l) {
+      d.ncols[l] = ncols_of_log[l];
+      ptrs.push_back(m.layers[l]);
+      if (m.layers[l] || l == 0) continue;   // (an opening reads the children's hashes: layers 1 .. max_log)
+      const MerkleCut* cut = nullptr;   // node_ref's rule (decommit.cpp)
+      for (auto& c : m.cuts)
+        if (l <= c.start_log && l > c.start_log - c.depth) {
+          cut = &c;
+          break;
+        }
+      if (!cut) throw LmnError(LMN_ERR_INTERNAL, "merkle: layer without storage");
+      if (cuts.size() >= OPEN_STORED) return;   // (the host plans)
+      d.cut_of_layer[l] = (uint8_t)cuts.size();
+      cuts.push_back({cut->prev, cut->sg, cut->ncols, 1u << cut->start_log, cut->below, cut->below_ncols, 0u, 0, 0u});
+      if (l >= 1) job_cap += 2 * std::min<uint64_t>(1ull << (l - 1), mm);
+    }
+    d.col_src0 = (uint32_t)ptrs.size();
+    for (auto& c : its[k].cols) ptrs.push_back(c.ptr);
+    const OpenBound b = open_bound(m.max_log, ncols_of_log, nq, its[k].pairs);
+    d.ent_cap = (uint32_t)b.entries;
+    d.job_cap = (uint32_t)job_cap;
+    total_entries += b.entries;
+    total_jobs += job_cap;
+    total_words += b.words;
+    max_cap = std::max(max_cap, b.entries);
+    max_job_cap = std::max(max_job_cap, job_cap);
+  }
+  // What the plan takes beside the proof's own buffers: tables, headers and both entry tables in the arena, the tables'
+  // staging, the headers' copy and the lists in page-locked memory.  Where either does not have it, the host plans.
+  const size_t head_bytes = sizeof(OpenHeader) + n_items * sizeof(OpenItemHeader);
+  const size_t ptr_bytes = ptrs.size() * sizeof(void*), desc_bytes = n_items * sizeof(OpenItemDesc);
+  const size_t table_bytes = ptr_bytes + desc_bytes + (cuts.size() + 1) * sizeof(MerkleRecompute);
+  const size_t ent_bytes = (total_entries + 1) * sizeof(OpenEntry), job_bytes = (total_jobs + 1) * sizeof(OpenEntry);
+  // (room is left for what the proof still stages behind this point: the FRI results' download, and - should the grind
+  // fall back - the host plan's own entry table and result block, which the same bound covers)
+  const size_t slack = 1u << 20;
+  const size_t arena_need = table_bytes + head_bytes + ent_bytes + job_bytes + slack;
+  const size_t pin_need = table_bytes + head_bytes + 2 * (total_words * 4) + total_entries * sizeof(GatherEntry) + r.fri.out_bytes + slack;
+  if (total_words > 0xffffffffull || total_entries > 0xffffffffull || arena_need > arena_.capacity() - arena_.used() ||
+      pin_need > pin_cap_ - pin_off_)
+    return;
+  char* h_tab = (char*)pin_alloc(table_bytes);
+  memcpy(h_tab, ptrs.data(), ptr_bytes);
+  memcpy(h_tab + ptr_bytes, descs.data(), desc_bytes);
+  if (!cuts.empty()) memcpy(h_tab + ptr_bytes + desc_bytes, cuts.data(), cuts.size() * sizeof(MerkleRecompute));
+  char* d_tab = (char*)arena_.alloc_bytes(table_bytes);
+  lmn_h2d(d_tab, h_tab, table_bytes, stream_);
+  const uint32_t* const* d_ptrs = (const uint32_t* const*)d_tab;
+  const OpenItemDesc* d_items = (const OpenItemDesc*)(d_tab + ptr_bytes);
+  const MerkleRecompute* d_cuts = (const MerkleRecompute*)(d_tab + ptr_bytes + desc_bytes);
+  OpenEntry* d_ent = (OpenEntry*)arena_.alloc_bytes(ent_bytes);
+  OpenEntry* d_job = (OpenEntry*)arena_.alloc_bytes(job_bytes);
+  // The headers stay in device memory, where every lane of the fetch reads them, and come back with one copy behind the
+  // last launch; the lists are written straight to page-locked memory: nothing to download behind them.
+  char* d_head = (char*)arena_.alloc_bytes(head_bytes);
+  OpenHeader* head = (OpenHeader*)d_head;
+  OpenItemHeader* heads = (OpenItemHeader*)(d_head + sizeof(OpenHeader));
+  char* block = (char*)result_block(head_bytes + total_words * 4);
+  uint32_t* out = (uint32_t*)(block + head_bytes);
+  const FriCloseHeader* fh = reinterpret_cast<const FriCloseHeader*>(fc.h_block);
+  launch_open_plan(&fh->n_positions, fc.h_block + sizeof(FriCloseHeader) / 4, &fh->found, fc.log_query_domain, d_items, n_items,
+                   heads, d_ent, d_job, stream_);
+  launch_open_offsets(&fh->n_positions, head, heads, n_items, (uint32_t)total_words, stream_);
+  launch_open_fetch(d_ptrs, (uint32_t)ptrs.size(), d_items, n_items, (uint32_t)max_cap, head, heads, d_ent, out, stream_);
+  launch_open_recompute(d_cuts, (uint32_t)cuts.size(), d_items, n_items, (uint32_t)max_job_cap, head, heads, d_job, out, stream_);
+  lmn_d2h(block, d_head, head_bytes, stream_);
+  r.open.on = true;
+  r.open.n_items = n_items;
+  r.open.h_block = block;
+  r.open.head_bytes = head_bytes;
+  r.open.cap_words = total_words;
+  ++dev_open_counters_[0];
+}
+
+// The host's plan: MerkleProver::decommit's walk for every tree (decommit.cpp), one gather launch, one wait.  Fills cnt per
+// plan [first, inner..., tree0..3] - words of FRI witness, queried words, hashes, column witness words - and returns the
+// gathered words in that order (`merged` keeps them alive for a sharded proof).
+const uint32_t* Context::plan_and_gather_on_host(ProofRun& r, std::vector<std::array<size_t, 4>>& cnt, std::vector<uint32_t>& merged) {
+  LMN_RUN_ALIASES(r);
+  typedef DecommitPlan Plan;
+  const uint32_t* gathered = nullptr;
+  if (!host_scratch) host_scratch = new HostScratch();
+  HostScratch& hs = *static_cast<HostScratch*>(host_scratch);
+  hs.used = 0;
+  hs.jobs.clear();
+  hs.plans.reserve(inner.size() + 5);  // plans are handed out by reference: no reallocation while planning
+  std::vector<Plan>& plans = hs.plans;  // [first, inner..., tree0..3]
+  {
+    Plan& p = hs.next();
+    std::map<int, std::vector<uint32_t>> dec;
+    for (size_t qk = 0; qk < quots.size(); ++qk) {
+      const ColRef(&c4)[4] = *reinterpret_cast<const ColRef(*)[4]>(&first_cols[4 * qk]);
+      plan_fri_witness(c4, g, pos_by_log[quots[qk].log], dec[quots[qk].log], p.fri_wit);
+    }
+    std::vector<Ref> dummy;
+    plan_merkle_decommit(first_merkle, first_cols, g, dec, dummy, p.hash_wit, p.col_wit, hs.jobs);
+  }
+  std::vector<uint32_t> lq = fold_positions(queries, 1);
+  for (auto& fl : inner) {
+    Plan& p = hs.next();
+    std::map<int, std::vector<uint32_t>> dec;
+    std::vector<ColRef>& lc = hs.cols;
+    lc.clear();
+    secure_columns(fl.vals, fl.log, fl.sharded, g, lc);
+    const ColRef(&c4)[4] = *reinterpret_cast<const ColRef(*)[4]>(lc.data());
+    plan_fri_witness(c4, g, lq, dec[fl.log], p.fri_wit);
+    std::vector<Ref> dummy;
+    plan_merkle_decommit(fl.merkle, lc, g, dec, dummy, p.hash_wit, p.col_wit, hs.jobs);
+    lq = fold_positions(lq, 1);
+  }
+  for (auto* t : trees) {
+    Plan& p = hs.next();
+    std::vector<ColRef>& sorted = hs.cols;
+    sorted.clear();
+    std::map<int, std::vector<uint32_t>> qmap;
+    sorted.reserve(t->cols.size());
+    for (auto& c : t->cols) {
+      sorted.push_back({c.lde, c.log_size + lb, c.sharded});
+      if (!qmap.count(c.log_size + lb)) qmap[c.log_size + lb] = pos_by_log[c.log_size + lb];
+    }
+    std::stable_sort(sorted.begin(), sorted.end(), [](auto& a, auto& b) { return a.log > b.log; });
+    plan_merkle_decommit(t->merkle, sorted, g, qmap, p.queried, p.hash_wit, p.col_wit, hs.jobs);
+  }
+  // Every rank plans the same list; it fetches the runs it holds into its own slot of the output buffer, the
+  // slots are all-gathered (a few KB per rank) and each run is then read from its owner's slot.
+  std::vector<GatherEntry>& entries = hs.entries;
+  entries.clear();
+  std::vector<std::pair<int, uint32_t>>& runs = hs.runs;  // (owner, len) in output order
+  runs.clear();
+  uint32_t out_words = 0;
+  const Prepared* const shared = r.prepared;
+  auto add_refs = [&](const std::vector<Ref>& refs) {
+    for (auto& r : refs) {
+      if (r.job >= 0)
+        hs.jobs[r.job].dst_off = out_words;   // unsharded proofs only: one output slot
+      else if (shared && shared->holds(r.ptr))   // the prepared tree 0 lies outside the arena: its own base
+        entries.push_back({GATHER_SHARED | shared->word_offset(r.ptr), r.len, out_words});
+      else if (r.owner < 0 || r.owner == (int)shard_.rank)
+        entries.push_back({arena_.word_offset(r.ptr), r.len, out_words});
+      if (sh) runs.push_back({r.owner, r.len});
+      out_words += r.len;
+    }
+  };
+  for (size_t k = 0; k < hs.used; ++k) {
+    Plan& p = plans[k];
+    add_refs(p.fri_wit);
+    add_refs(p.queried);
+    add_refs(p.hash_wit);
+    add_refs(p.col_wit);
+  }
+  if (out_words) {
+    const uint32_t slots = sh ? shard_.world : 1u, mine = sh ? shard_.rank : 0u;
+    for (auto& e : entries) e.dst_off += mine * out_words;
+    // the entry table is read once, one entry per lane: the kernel takes it straight from pinned host memory
+    GatherEntry* d_e = (GatherEntry*)pin_alloc((entries.size() + 1) * sizeof(GatherEntry));
+    if (!entries.empty()) memcpy(d_e, entries.data(), entries.size() * sizeof(GatherEntry));
+    if (!hs.jobs.empty() && sh) throw LmnError(LMN_ERR_INTERNAL, "sharded proofs keep whole trees");
+    MerkleRecompute* d_j = (MerkleRecompute*)pin_alloc((hs.jobs.size() + 1) * sizeof(MerkleRecompute));
+    if (!hs.jobs.empty()) memcpy(d_j, hs.jobs.data(), hs.jobs.size() * sizeof(MerkleRecompute));   // (memcpy from a null vector: UB even for 0 bytes)
+    // an unsharded proof's gather writes straight to page-locked memory: nothing to download behind it
+    uint32_t* d_o = sh ? arena_.alloc_words((size_t)slots * out_words) : (uint32_t*)result_block((size_t)out_words * 4);
+    hm.mark("decommit planned");
+    if (hm.on) fprintf(stderr, "[host] decommit: %zu runs gathered, %zu tree nodes recomputed\n", entries.size(), hs.jobs.size());
+    launch_gather(arena_.base_words(), shared ? shared->base_words() : nullptr, d_e, (uint32_t)entries.size(), d_j, (uint32_t)hs.jobs.size(), d_o, stream_);
+    if (sh) gather_columns(d_o, 0, 1, out_words);
+    gathered = sh ? (const uint32_t*)stage_download(d_o, (size_t)slots * out_words * 4) : d_o;
+    lmn_sync(stream_);
+    hm.mark("gathered");
+    if (sh) {
+      merged.resize(out_words);
+      uint32_t at = 0;
+      for (auto& r : runs) {
+        const uint32_t slot = r.first < 0 ? mine : (uint32_t)r.first;
+        memcpy(&merged[at], gathered + (size_t)slot * out_words + at, (size_t)r.second * 4);
+        at += r.second;
+      }
+      gathered = merged.data();
+    }
+  }
+  for (size_t k = 0; k < hs.used; ++k)
+    cnt.push_back({plans[k].fri_wit.size(), plans[k].queried.size(), plans[k].hash_wit.size(), plans[k].col_wit.size()});
+  return gathered;
+}
+
 void Context::run_decommit(ProofRun& r) {
   LMN_RUN_ALIASES(r);
   // ---- decommitment: plan device references, gather once, distribute
   {
     StageTimer st(this, log, stream_, C_DECOMMIT);
-    typedef DecommitPlan Plan;
-    if (!host_scratch) host_scratch = new HostScratch();
-    HostScratch& hs = *static_cast<HostScratch*>(host_scratch);
-    hs.used = 0;
-    hs.jobs.clear();
-    hs.plans.reserve(inner.size() + 5);  // plans are handed out by reference: no reallocation while planning
-    std::vector<Plan>& plans = hs.plans;  // [first, inner..., tree0..3]
-    {
-      Plan& p = hs.next();
-      std::map<int, std::vector<uint32_t>> dec;
-      for (size_t qk = 0; qk < quots.size(); ++qk) {
-        const ColRef(&c4)[4] = *reinterpret_cast<const ColRef(*)[4]>(&first_cols[4 * qk]);
-        plan_fri_witness(c4, g, pos_by_log[quots[qk].log], dec[quots[qk].log], p.fri_wit);
-      }
-      std::vector<Ref> dummy;
-      plan_merkle_decommit(first_merkle, first_cols, g, dec, dummy, p.hash_wit, p.col_wit, hs.jobs);
-    }
-    std::vector<uint32_t> lq = fold_positions(queries, 1);
-    for (auto& fl : inner) {
-      Plan& p = hs.next();
-      std::map<int, std::vector<uint32_t>> dec;
-      std::vector<ColRef>& lc = hs.cols;
-      lc.clear();
-      secure_columns(fl.vals, fl.log, fl.sharded, g, lc);
-      const ColRef(&c4)[4] = *reinterpret_cast<const ColRef(*)[4]>(lc.data());
-      plan_fri_witness(c4, g, lq, dec[fl.log], p.fri_wit);
-      std::vector<Ref> dummy;
-      plan_merkle_decommit(fl.merkle, lc, g, dec, dummy, p.hash_wit, p.col_wit, hs.jobs);
-      lq = fold_positions(lq, 1);
-    }
-    for (auto* t : trees) {
-      Plan& p = hs.next();
-      std::vector<ColRef>& sorted = hs.cols;
-      sorted.clear();
-      std::map<int, std::vector<uint32_t>> qmap;
-      sorted.reserve(t->cols.size());
-      for (auto& c : t->cols) {
-        sorted.push_back({c.lde, c.log_size + lb, c.sharded});
-        if (!qmap.count(c.log_size + lb)) qmap[c.log_size + lb] = pos_by_log[c.log_size + lb];
-      }
-      std::stable_sort(sorted.begin(), sorted.end(), [](auto& a, auto& b) { return a.log > b.log; });
-      plan_merkle_decommit(t->merkle, sorted, g, qmap, p.queried, p.hash_wit, p.col_wit, hs.jobs);
-    }
-    // Every rank plans the same list; it fetches the runs it holds into its own slot of the output buffer, the
-    // slots are all-gathered (a few KB per rank) and each run is then read from its owner's slot.
-    std::vector<GatherEntry>& entries = hs.entries;
-    entries.clear();
-    std::vector<std::pair<int, uint32_t>>& runs = hs.runs;  // (owner, len) in output order
-    runs.clear();
-    uint32_t out_words = 0;
-    const Prepared* const shared = r.prepared;
-    auto add_refs = [&](const std::vector<Ref>& refs) {
-      for (auto& r : refs) {
-        if (r.job >= 0)
-          hs.jobs[r.job].dst_off = out_words;   // unsharded proofs only: one output slot
-        else if (shared && shared->holds(r.ptr))   // the prepared tree 0 lies outside the arena: its own base
-          entries.push_back({GATHER_SHARED | shared->word_offset(r.ptr), r.len, out_words});
-        else if (r.owner < 0 || r.owner == (int)shard_.rank)
-          entries.push_back({arena_.word_offset(r.ptr), r.len, out_words});
-        if (sh) runs.push_back({r.owner, r.len});
-        out_words += r.len;
-      }
-    };
-    for (size_t k = 0; k < hs.used; ++k) {
-      Plan& p = plans[k];
-      add_refs(p.fri_wit);
-      add_refs(p.queried);
-      add_refs(p.hash_wit);
-      add_refs(p.col_wit);
-    }
+    // per plan [first, inner..., tree0..3]: words of FRI witness, queried words, hashes, column witness words
+    std::vector<std::array<size_t, 4>> cnt;
     const uint32_t* gathered = nullptr;
     std::vector<uint32_t> merged;
-    if (out_words) {
-      const uint32_t slots = sh ? shard_.world : 1u, mine = sh ? shard_.rank : 0u;
-      for (auto& e : entries) e.dst_off += mine * out_words;
-      // the entry table is read once, one entry per lane: the kernel takes it straight from pinned host memory
-      GatherEntry* d_e = (GatherEntry*)pin_alloc((entries.size() + 1) * sizeof(GatherEntry));
-      if (!entries.empty()) memcpy(d_e, entries.data(), entries.size() * sizeof(GatherEntry));
-      if (!hs.jobs.empty() && sh) throw LmnError(LMN_ERR_INTERNAL, "sharded proofs keep whole trees");
-      MerkleRecompute* d_j = (MerkleRecompute*)pin_alloc((hs.jobs.size() + 1) * sizeof(MerkleRecompute));
-      if (!hs.jobs.empty()) memcpy(d_j, hs.jobs.data(), hs.jobs.size() * sizeof(MerkleRecompute));   // (memcpy from a null vector: UB even for 0 bytes)
-      // an unsharded proof's gather writes straight to page-locked memory: nothing to download behind it
-      uint32_t* d_o = sh ? arena_.alloc_words((size_t)slots * out_words) : (uint32_t*)result_block((size_t)out_words * 4);
-      hm.mark("decommit planned");
-      if (hm.on) fprintf(stderr, "[host] decommit: %zu runs gathered, %zu tree nodes recomputed\n", entries.size(), hs.jobs.size());
-      launch_gather(arena_.base_words(), shared ? shared->base_words() : nullptr, d_e, (uint32_t)entries.size(), d_j, (uint32_t)hs.jobs.size(), d_o, stream_);
-      if (sh) gather_columns(d_o, 0, 1, out_words);
-      gathered = sh ? (const uint32_t*)stage_download(d_o, (size_t)slots * out_words * 4) : d_o;
-      lmn_sync(stream_);
-      hm.mark("gathered");
-      if (sh) {
-        merged.resize(out_words);
-        uint32_t at = 0;
-        for (auto& r : runs) {
-          const uint32_t slot = r.first < 0 ? mine : (uint32_t)r.first;
-          memcpy(&merged[at], gathered + (size_t)slot * out_words + at, (size_t)r.second * 4);
-          at += r.second;
+    // planned and fetched on the device, in front of the wait that has passed (enqueue_device_decommit) - unless the queued
+    // grind windows held no nonce: then nothing behind the grind ran, and the host plans as it always did
+    const bool dev_plan = r.open.on && r.close.found;
+    if (r.open.on && !r.close.found) ++dev_open_counters_[1];
+    if (dev_plan) {
+      const OpenHeader& head = *(const OpenHeader*)r.open.h_block;
+      const OpenItemHeader* heads = (const OpenItemHeader*)(r.open.h_block + sizeof(OpenHeader));
+      if (head.overflow || r.open.n_items != inner.size() + 5)
+        throw LmnError(LMN_ERR_INTERNAL, "device decommit: the plan exceeded the bounds it was launched with");
+      uint64_t at = 0, n_entries = 0, n_jobs = 0;
+      for (uint32_t k = 0; k < r.open.n_items; ++k) {
+        const OpenItemHeader& h = heads[k];
+        for (int l = 0; l < 4; ++l) {
+          if (h.base[l] != at) throw LmnError(LMN_ERR_INTERNAL, "device decommit: the lists are not compact");
+          at += (uint64_t)h.count[l] * (l == OPEN_LIST_HASH ? 8 : 1);
         }
-        gathered = merged.data();
+        if (h.count[OPEN_LIST_FRI] % 4) throw LmnError(LMN_ERR_INTERNAL, "device decommit: a partial FRI witness");
+        cnt.push_back({h.count[OPEN_LIST_FRI], h.count[OPEN_LIST_QUERIED], h.count[OPEN_LIST_HASH], h.count[OPEN_LIST_WITNESS]});
+        n_entries += h.n_entries;
+        n_jobs += h.n_jobs;
       }
+      if (at > r.open.cap_words) throw LmnError(LMN_ERR_INTERNAL, "device decommit: the counts exceed the result block");
+      gathered = (const uint32_t*)(r.open.h_block + r.open.head_bytes);
+      hm.mark("decommit sliced (device plan)");
+      if (hm.on)
+        fprintf(stderr, "[host] decommit: device plan, %llu entries fetched, %llu tree nodes recomputed\n",
+                (unsigned long long)n_entries, (unsigned long long)n_jobs);
+    } else {
+      gathered = plan_and_gather_on_host(r, cnt, merged);
     }
     size_t g = 0;
     // (runs behind the proof's last wait: whole runs are copied, not words)
@@ -325,23 +498,23 @@ void Context::run_decommit(ProofRun& r) {
     };
     size_t pi = 0;
     auto fill_layer = [&](FriLayerProof& lp, const Hash32& root) {
-      Plan& p = plans[pi++];
-      lp.fri_witness = take_q(p.fri_wit.size());
-      skip(p.queried.size());
-      lp.decommitment.hash_witness = take_hashes(p.hash_wit.size());
-      lp.decommitment.column_witness = take_u32(p.col_wit.size());
+      const std::array<size_t, 4>& p = cnt[pi++];
+      lp.fri_witness = take_q(p[0]);
+      skip(p[1]);
+      lp.decommitment.hash_witness = take_hashes(p[2]);
+      lp.decommitment.column_witness = take_u32(p[3]);
       lp.commitment = root;
     };
     fill_layer(proof.first_layer, first_merkle.root);
     proof.inner_layers.resize(inner.size());
     for (size_t i = 0; i < inner.size(); ++i) fill_layer(proof.inner_layers[i], inner[i].merkle.root);
     for (int t = 0; t < 4; ++t) {
-      Plan& p = plans[pi++];
-      skip(p.fri_wit.size());
-      proof.queried_values.push_back(take_u32(p.queried.size()));
+      const std::array<size_t, 4>& p = cnt[pi++];
+      skip(p[0]);
+      proof.queried_values.push_back(take_u32(p[1]));
       Decommitment d;
-      d.hash_witness = take_hashes(p.hash_wit.size());
-      d.column_witness = take_u32(p.col_wit.size());
+      d.hash_witness = take_hashes(p[2]);
+      d.column_witness = take_u32(p[3]);
       proof.decommitments.push_back(d);
     }
   }

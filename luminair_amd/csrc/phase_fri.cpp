@@ -266,6 +266,7 @@ void Context::fri_commit_layers(ProofRun& r) {
       throw LmnError(LMN_ERR_INTERNAL, "FRI: the layer plan does not match the layers committed");
     last_log = layer_log;
     if (r.close.on) enqueue_fri_close(r.close, fp.d_last, d_ch, (uint32_t)ls0);   // its results arrive with this wait
+    if (r.close.on && env_set("LMN_DEVICE_DECOMMIT")) enqueue_device_decommit(r);   // and so do the openings
     // roots | alphas | last layer: one block, one download
     if (!h_out) h_out = (const uint32_t*)stage_download(fp.d_out, fp.out_bytes);
     const uint32_t* h_roots = h_out;

@@ -79,6 +79,16 @@ struct FriClose {
   uint32_t n_sent_end = 0;
 };
 
+// The openings planned and fetched on the device behind k_fri_queries (phase_decommit.cpp enqueue_device_decommit,
+// LMN_DEVICE_DECOMMIT=1): what was queued; the page-locked block holds OpenHeader | item headers | the lists.
+struct DevOpen {
+  bool on = false;
+  uint32_t n_items = 0;
+  const char* h_block = nullptr;
+  size_t head_bytes = 0;
+  uint64_t cap_words = 0;
+};
+
 struct ProofRun {
   explicit ProofRun(uint32_t protocol_flags) : channel(protocol_flags) {}
   // inputs (borrowed)
@@ -159,6 +169,7 @@ struct ProofRun {
   std::vector<QM31> last_vals;
   int last_log = 0;
   FriClose close;   // on: the transcript is closed on the device, in front of the FRI wait
+  DevOpen open;     // on: the openings are planned and fetched there as well
   std::vector<uint32_t> queries;
   std::map<int, std::vector<uint32_t>> pos_by_log;
   bool sharded_log(int lg) const { return sh && lg > fri_T; }

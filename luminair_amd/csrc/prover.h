@@ -8,6 +8,8 @@
 #include <vector>
 
 #include "../../include/luminair_hip.h"
+
+#include <array>
 #include "constraints.h"
 #include "host.h"
 #include "kernels.h"
@@ -342,7 +344,14 @@ class Context {
   void col_fri_commit(const lmn_col* const* cols, uint32_t n, const uint8_t start_digest[32], FriCommitOut& out);
   // what FriProver::commit and the query phase do behind the layer loop, as one device chain (enqueue_fri_close): the last
   // layer's polynomial and degree check, mix_felts, the grind, mix_u64, Queries::generate
-  void col_fri_close(const lmn_col* last_layer, const uint8_t start_digest[32], uint32_t log_query_domain, FriCloseOut& out);
+  // keep != nullptr (lmn_col_fri_close_keep): the positions also stay on the device, in a new handle
+  void col_fri_close(const lmn_col* last_layer, const uint8_t start_digest[32], uint32_t log_query_domain, FriCloseOut& out,
+                     lmn_positions** keep = nullptr);
+  // query positions on the device and the openings planned there (lmn_positions_*, lmn_open_queries; kernels.h k_open_plan)
+  lmn_positions* positions_from_cpu(const uint32_t* positions, uint32_t n, uint32_t log_domain);
+  void positions_to_cpu(const lmn_positions* p, uint32_t* host, uint32_t* n_out);
+  void positions_free(lmn_positions* p);
+  void open_queries(const lmn_positions* p, const lmn_open_item* items, uint32_t n_items, lmn_opening* out);
   void col_accumulate(lmn_col* dst, const lmn_col* src);
   lmn_col* col_accumulate_quotients(const lmn_col* const* cols, uint32_t n, const uint32_t* sample_col,
                                     const uint32_t* sample_point, const uint32_t* sample_values, uint32_t nsamples,
@@ -404,7 +413,14 @@ class Context {
   int device() const { return device_; }
   // lmn_ctx_counter - 7: device grinds started, 8: host waits inside grind rounds, 9: proofs whose transcript was closed on
   // the device, 10: those among them that fell back to the host's grind rounds; 0 for any other number
-  uint64_t counter(int which) const { return which >= 7 && which <= 10 ? counters_[which - 7] : 0; }
+  // 11, 12: proofs opened by the device plan, fallbacks among them; 13, 14, 15 (diagnostic): plan launches, fetch launches
+  // and host waits of open_queries
+  uint64_t counter(int which) const {
+    return which >= 7 && which <= 10    ? counters_[which - 7]
+           : which >= 11 && which <= 12 ? dev_open_counters_[which - 11]
+           : which >= 13 && which <= 15 ? open_counters_[which - 13]
+                                        : 0;
+  }
   lmn_config cfg;
   lmn_timings timings{};
   bool profiling = false;  // record HIP events around stages/kernels (lmn_set_profiling)
@@ -436,6 +452,8 @@ class Context {
                         bool refuse_bad_degree);
   void run_queries(ProofRun& r);
   void run_decommit(ProofRun& r);
+  void enqueue_device_decommit(ProofRun& r);   // behind enqueue_fri_close, in front of the FRI wait
+  const uint32_t* plan_and_gather_on_host(ProofRun& r, std::vector<std::array<size_t, 4>>& cnt, std::vector<uint32_t>& merged);
   std::vector<uint8_t> run_finish(ProofRun& r);
 
   void ensure_twiddles(int max_domain_log);
@@ -557,6 +575,8 @@ class Context {
   uint64_t device_grind_from(const PowWords& w, bool kat, uint32_t pow_bits, uint64_t base);
   int grind_window_log(uint32_t pow_bits) const;   // the window of device_grind's launches
   uint64_t counters_[4] = {0, 0, 0, 0};            // counter()
+  uint64_t open_counters_[3] = {0, 0, 0};          // counter() 13 .. 15
+  uint64_t dev_open_counters_[2] = {0, 0};         // counter() 11, 12: proofs opened by the device plan, fallbacks among them
   // grind_many's rounds; its tables (digests | best | pending, device and page-locked host) grow on demand
   uint64_t grind_rounds(const PowWords* w, uint32_t n, bool kat, uint32_t pow_bits, uint64_t* nonces);
   char *pow_many_dev_ = nullptr, *pow_many_host_ = nullptr;

@@ -104,6 +104,11 @@ struct HostScratch {
   }
 };
 
+// upper bounds of one item of a device plan (kernels.h k_open_plan), from the number of positions alone (level2.cpp)
+struct OpenBound {
+  uint64_t entries = 0, words = 0;
+};
+OpenBound open_bound(int max_log, const std::vector<uint32_t>& ncols_of_log, uint32_t n_positions, bool pairs);
 void release_host_scratch(void* p);
 void plan_merkle_decommit(const DevMerkle& m, const std::vector<ColRef>& cols_sorted, int g,
                           const std::map<int, std::vector<uint32_t>>& queries, std::vector<Ref>& queried,

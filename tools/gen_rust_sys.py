@@ -85,6 +85,10 @@ def parse(headers):
                     k += 1
                 ctype = " ".join(toks[:k])
                 dmap = {a: b for a, b in defines}
+                if "const" in toks[k:] and "," not in toks[k:] and re.match(r"\w+$", toks[-1]):
+                    # one declarator with a const pointer level (`const lmn_col* const* cols`): the type is all but the name
+                    fields.append((toks[-1], ("data", " ".join(toks[:-1]), [])))
+                    continue
                 for item in " ".join(toks[k:]).split(","):
                     item = item.replace(" ", "")
                     stars = item.count("*")
