@@ -574,7 +574,7 @@ int lmn_tensor_range(lmn_ctx* ctx, const int32_t* buf_dev, uint64_t n, int32_t* 
  *    are serialised by the sink.
  *  - lmn_rows_finish writes the padding rows (lmn_kind_padding_row; rows [count, 2^log_size), log_size as lmn_prove
  *    derives it from n_rows: the next power of two, at least 16 rows), waits ONCE, and returns LMN_ERR_INVALID_ARGUMENT
- *    if any pushed word was >= 2^31 - 1, LMN_ERR_EMPTY_TRACE if no row was pushed.  If 2^log_size is smaller than the
+ *    if any pushed word was >= 2^31 - 1 (or a device producer refused an element, lmn_rows_append_* below), LMN_ERR_EMPTY_TRACE if no row was pushed.  If 2^log_size is smaller than the
  *    column stride chosen at open, the columns are compacted so that table_out->rows has stride 2^log_size.  After an
  *    error the sink can be reset and the context is usable.  Pushing or finishing again without lmn_rows_reset is
  *    LMN_ERR_INVALID_ARGUMENT.
@@ -598,6 +598,54 @@ int lmn_rows_finish(lmn_rows* rows, lmn_table* table_out); /* pad, verdict on no
 uint64_t lmn_rows_count(const lmn_rows* rows);
 int lmn_rows_reset(lmn_rows* rows);                        /* same capacity, zero rows: the next proof's table */
 void lmn_rows_close(lmn_rows* rows);
+
+/* ---- Device producers that fill a row sink (lmn_rows_append_*): the four single producers - lmn_trace_elementwise_v (and
+ * lmn_trace_less_than), lmn_trace_contiguous, lmn_trace_sum_reduce / _max_reduce, lmn_trace_lut_ranges, of which every other
+ * single form is a special case - writing the node's rows straight into a sink's COLUMNS.  A pie built this way reaches
+ * lmn_prove as LMN_TABLE_COLS_ON_DEVICE tables: no array-of-structs rows in HBM, and no transpose launch in front of the
+ * proof.  The arguments are those of the single forms, with the sink in place of rows_dev / row_offset and a refused-element
+ * counter behind them (lmn_rows_append_elementwise_v takes LessThan too: range_check_mult_dev is its 256-word table, ignored
+ * for every other kind).
+ *
+ * The contract:
+ *  - Rows: exactly the rows the corresponding lmn_trace_* call writes - n, max(in_size, out_size), front * dim * back and n of
+ *    them - appended at the sink's current row count, in table order, as prim.rs appends.  There is no row_offset.
+ *    lmn_rows_count has grown by that number when the call returns.  The values follow the producers' contract
+ *    (lmn_trace_elementwise): out_dev receives what the row form writes, 0 for a refused element, and a refused element adds
+ *    nothing to a multiplicity table.
+ *  - Refused before any launch, with LMN_ERR_INVALID_ARGUMENT and a text in lmn_last_error(ctx) that names the argument, the
+ *    sink keeping its count and content: a null sink; a sink whose kind is not the producer's (LMN_KIND_CONTIGUOUS for
+ *    lmn_rows_append_contiguous, LMN_KIND_SUM_REDUCE / LMN_KIND_MAX_REDUCE for lmn_rows_append_reduce); a sink that is not
+ *    filling (finished, or failed, without lmn_rows_reset); more rows than capacity - count; a context on another device
+ *    than the sink's.  Each single form's own argument errors keep their own codes (n == 0: LMN_ERR_EMPTY_TRACE; a view whose
+ *    shape product is not n: LMN_ERR_INVALID_ARGUMENT; ...).  libluminair_hip_batch.so exports the four entry points, and -
+ *    as no sink can exist there - they refuse in the same way.
+ *  - No call waits for the device.  An element outside the producers' contract - a LUT input outside every range included,
+ *    as in lmn_trace_many_lut_ranges and lmn_eval_lut_ranges - is a refused element: its row carries the non-canonical word
+ *    2^31 - 1 in the output-value column, the sink's verdict word is set, and *refused_dev (a uint32 device word, may be
+ *    NULL, never reset by a call) grows by one.  lmn_rows_finish of such a sink returns LMN_ERR_INVALID_ARGUMENT.
+ *  - A call takes the context's lock, as every lmn_trace_* call does, and then the sink's - always in that order.  The other
+ *    lmn_rows_* calls still never take a context's lock.
+ *  - Stream order: the launch runs on the context's stream, ordered with the tensors it reads and writes, and the sink
+ *    records an event on that stream behind each append.  lmn_rows_sync, lmn_rows_finish, lmn_rows_reset and lmn_rows_close
+ *    make the sink's own stream wait for that event before they do anything else, so lmn_rows_sync after appends means the
+ *    producers have finished (operand tensors may be freed).  lmn_rows_reset records an event behind the clearing of the
+ *    verdict word, and the next append makes the context's stream wait for it: a failed table followed by a clean one can
+ *    neither lose nor inherit the verdict.
+ *  - Host pushes and device appends may be mixed in one sink, in any order: they write disjoint rows, and the finish waits
+ *    for both.
+ *  - lmn_rows_finish is unchanged in shape - padding rows, compaction when 2^log_size is below the stride chosen at open, one
+ *    wait, the verdict - and table_out is the same LMN_TABLE_COLS_ON_DEVICE table, accepted wherever such tables are. */
+int lmn_rows_append_elementwise_v(lmn_ctx* ctx, lmn_rows* rows, uint32_t kind, const int32_t* lhs_dev, const lmn_view* lhs_view,
+                                  const int32_t* rhs_dev, const lmn_view* rhs_view, uint64_t n, const lmn_node_info* info,
+                                  uint32_t* range_check_mult_dev /* LessThan only */, int32_t* out_dev, uint32_t* refused_dev);
+int lmn_rows_append_contiguous(lmn_ctx* ctx, lmn_rows* rows, const int32_t* input_dev, uint64_t in_size, const lmn_view* view,
+                               uint64_t out_size, const lmn_node_info* info, int32_t* out_dev, uint32_t* refused_dev);
+int lmn_rows_append_reduce(lmn_ctx* ctx, lmn_rows* rows, uint32_t is_max, const int32_t* input_dev, uint64_t front, uint64_t dim,
+                           uint64_t back, const lmn_node_info* info, int32_t* out_dev, uint32_t* refused_dev);
+int lmn_rows_append_lut_ranges(lmn_ctx* ctx, lmn_rows* rows, uint32_t kind, const int32_t* input_dev, const lmn_view* view,
+                               uint64_t n, const lmn_node_info* info, const uint32_t* lut_col1_dev, const lmn_range* ranges,
+                               uint32_t n_ranges, uint32_t* mult_dev, int32_t* out_dev, uint32_t* refused_dev);
 
 /* ---- lmn_trace_check: which rows and which logup tuples break a trace.  lmn_prove answers a bad trace once, at the end of
  * a whole proof, with LMN_ERR_CONSTRAINTS - no table, no row, no constraint - and a trace whose logup relations do not

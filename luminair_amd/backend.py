@@ -288,6 +288,7 @@ EXPORTS = ["lmn_abi_version", "lmn_kind_padding_row", "lmn_strerror", "lmn_last_
            "lmn_col_decompose", "lmn_col_batch_inverse", "lmn_col_batch_inverse_secure", "lmn_col_logup", "lmn_col_composition", "lmn_kind_constraints", "lmn_kind_relations", "lmn_ctx_set_shard", "lmn_rccl_unique_id", "lmn_ctx_set_shard_rccl", "lmn_ctx_clear_shard",
            "lmn_rows_open", "lmn_rows_push", "lmn_rows_push_pinned", "lmn_rows_sync", "lmn_rows_finish", "lmn_rows_count",
            "lmn_rows_reset", "lmn_rows_close", "lmn_trace_check",
+           "lmn_rows_append_elementwise_v", "lmn_rows_append_contiguous", "lmn_rows_append_reduce", "lmn_rows_append_lut_ranges",
            "lmn_eval_elementwise_v", "lmn_eval_reduce", "lmn_eval_reduce_split", "lmn_eval_lut_ranges", "lmn_tensor_range",
            "lmn_trace_many_elementwise_v", "lmn_trace_many_contiguous", "lmn_trace_many_reduce", "lmn_trace_many_lut_ranges",
            "lmn_settings_prepare", "lmn_prepared_root", "lmn_prepared_lookups", "lmn_prepared_destroy", "lmn_prove_prepared",
@@ -459,6 +460,16 @@ class Library:
         lib.lmn_rows_reset.argtypes = [C.c_void_p]
         lib.lmn_rows_close.argtypes = [C.c_void_p]
         lib.lmn_rows_close.restype = None
+        lib.lmn_rows_append_elementwise_v.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(LmnView),
+                                                      C.c_void_p, C.POINTER(LmnView), C.c_uint64, C.POINTER(LmnNodeInfo),
+                                                      C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.lmn_rows_append_contiguous.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(LmnView),
+                                                   C.c_uint64, C.POINTER(LmnNodeInfo), C.c_void_p, C.c_void_p]
+        lib.lmn_rows_append_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64,
+                                               C.c_uint64, C.POINTER(LmnNodeInfo), C.c_void_p, C.c_void_p]
+        lib.lmn_rows_append_lut_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(LmnView),
+                                                   C.c_uint64, C.POINTER(LmnNodeInfo), C.c_void_p, C.POINTER(LmnRange),
+                                                   C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.lmn_trace_check.argtypes = [C.c_void_p, C.POINTER(LmnTable), C.c_size_t, C.POINTER(LmnSettings),
                                         C.POINTER(LmnTraceReport)]
         lib.lmn_trace_elementwise_v.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(LmnView), C.c_void_p,
@@ -1311,17 +1322,27 @@ class Context:
                           input_ids, num_consumers: int, is_final_output: bool = False, input_mults=(-1, -1),
                           rows: Optional[DeviceBuffer] = None, row_offset: int = 0,
                           lhs_view: Optional[LmnView] = None, rhs_view: Optional[LmnView] = None,
-                          out: Optional[DeviceBuffer] = None):
+                          out: Optional[DeviceBuffer] = None, sink: Optional["RowSink"] = None,
+                          refused: Optional[DeviceBuffer] = None):
         """`process_trace` of one Add / Mul / Recip node on device tensors (int32 Fixed<12> values).
-        Returns (rows DeviceBuffer, out DeviceBuffer)."""
+        Returns (rows DeviceBuffer, out DeviceBuffer).
+        sink= (every `trace_*` method takes it): the node's rows are appended to that `RowSink`'s columns at its current
+        row count instead (`lmn_rows_append_*`; `rows` / `row_offset` are not used, and the sink is returned in place of the
+        rows buffer); `refused` is then a uint32 counter on the device that grows by the refused elements.  Nothing waits."""
         ncols = self.lib.kind_columns(kind)
-        if rows is None:
+        if rows is None and sink is None:
             rows = self.alloc((row_offset + n) * ncols * 4)
         out = out or self.alloc(n * 4)
         ids = list(input_ids) + [0] * (2 - len(input_ids))
         mults = list(input_mults) + [0] * (2 - len(input_mults))
         info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(*ids), num_consumers, 1 if is_final_output else 0,
                            (C.c_int32 * 2)(*mults))
+        if sink is not None:
+            self._check(self.lib.lib.lmn_rows_append_elementwise_v(
+                self.handle, sink.handle, kind, lhs.ptr, C.byref(lhs_view) if lhs_view is not None else None,
+                rhs.ptr if rhs is not None else None, C.byref(rhs_view) if rhs_view is not None else None, n,
+                C.byref(info), None, out.ptr, refused.ptr if refused is not None else None))
+            return sink, out
         if lhs_view is None and rhs_view is None:
             self._check(self.lib.lib.lmn_trace_elementwise(self.handle, kind, lhs.ptr, rhs.ptr if rhs is not None else None,
                                                            n, C.byref(info), rows.ptr, row_offset, out.ptr))
@@ -1335,14 +1356,20 @@ class Context:
     def trace_contiguous(self, inp: DeviceBuffer, in_size: int, out_size: int, node_id: int, input_id: int,
                          num_consumers: int, is_final_output: bool = False, input_mult: int = -1,
                          view: Optional[LmnView] = None, rows: Optional[DeviceBuffer] = None, row_offset: int = 0,
-                         out: Optional[DeviceBuffer] = None):
+                         out: Optional[DeviceBuffer] = None, sink: Optional["RowSink"] = None,
+                         refused: Optional[DeviceBuffer] = None):
         """`LuminairContiguous::process_trace` in the reference's row rule: max(in_size, out_size) rows."""
         n_rows = max(in_size, out_size)
-        if rows is None:
+        if rows is None and sink is None:
             rows = self.alloc((row_offset + n_rows) * 11 * 4)
         out = out or self.alloc(out_size * 4)
         info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(input_id, 0), num_consumers, 1 if is_final_output else 0,
                            (C.c_int32 * 2)(input_mult, 0))
+        if sink is not None:
+            self._check(self.lib.lib.lmn_rows_append_contiguous(
+                self.handle, sink.handle, inp.ptr, in_size, C.byref(view) if view is not None else None, out_size,
+                C.byref(info), out.ptr, refused.ptr if refused is not None else None))
+            return sink, out
         self._check(self.lib.lib.lmn_trace_contiguous(self.handle, inp.ptr, in_size, C.byref(view) if view is not None else None,
                                                       out_size, C.byref(info), rows.ptr, row_offset, out.ptr))
         return rows, out
@@ -1351,15 +1378,24 @@ class Context:
                   lut_col1: DeviceBuffer, lo: int = 0, lut_len: int = 0, mult: DeviceBuffer = None,
                   is_final_output: bool = False, input_mult: int = -1, view: Optional[LmnView] = None,
                   rows: Optional[DeviceBuffer] = None, row_offset: int = 0, out: Optional[DeviceBuffer] = None,
-                  ranges: Optional[Sequence[Tuple[int, int]]] = None):
+                  ranges: Optional[Sequence[Tuple[int, int]]] = None, sink: Optional["RowSink"] = None,
+                  refused: Optional[DeviceBuffer] = None):
         """`process_trace` of a Sin / Exp2 / Log2 node; `mult` (the lookup component's table) is updated in place.
-        The LUT enumerates either the single range lo .. lo + lut_len - 1 or `ranges` (ascending, disjoint)."""
-        if rows is None:
+        The LUT enumerates either the single range lo .. lo + lut_len - 1 or `ranges` (ascending, disjoint).
+        With sink= an input outside every range is a refused element (marked, counted), not an error of the call."""
+        if rows is None and sink is None:
             rows = self.alloc((row_offset + n) * 12 * 4)
         out = out or self.alloc(n * 4)
         info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(input_id, 0), num_consumers, 1 if is_final_output else 0,
                            (C.c_int32 * 2)(input_mult, 0))
         vp = C.byref(view) if view is not None else None
+        if sink is not None:
+            rg = ranges if ranges is not None else [(lo, lo + lut_len - 1)]
+            arr = (LmnRange * max(len(rg), 1))(*[LmnRange(int(a), int(b)) for a, b in rg])
+            self._check(self.lib.lib.lmn_rows_append_lut_ranges(
+                self.handle, sink.handle, kind, inp.ptr, vp, n, C.byref(info), lut_col1.ptr, arr, len(rg), mult.ptr, out.ptr,
+                refused.ptr if refused is not None else None))
+            return sink, out
         if ranges is None:
             self._check(self.lib.lib.lmn_trace_lut(self.handle, kind, inp.ptr, vp, n, C.byref(info), lut_col1.ptr, lo,
                                                    lut_len, mult.ptr, rows.ptr, row_offset, out.ptr))
@@ -1372,15 +1408,21 @@ class Context:
     def trace_sum_reduce(self, inp: DeviceBuffer, front: int, dim: int, back: int, node_id: int, input_id: int,
                          num_consumers: int, is_final_output: bool = False, input_mult: int = -1,
                          rows: Optional[DeviceBuffer] = None, row_offset: int = 0, maximum: bool = False,
-                         out: Optional[DeviceBuffer] = None):
+                         out: Optional[DeviceBuffer] = None, sink: Optional["RowSink"] = None,
+                         refused: Optional[DeviceBuffer] = None):
         """`LuminairSumReduce::process_trace` (or MaxReduce with maximum=True) on a contiguous
         (front, dim, back) int32 device tensor."""
         n_rows, n_out = front * dim * back, front * back
-        if rows is None:
+        if rows is None and sink is None:
             rows = self.alloc((row_offset + n_rows) * (15 if maximum else 14) * 4)
         out = out or self.alloc(n_out * 4)
         info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(input_id, 0), num_consumers, 1 if is_final_output else 0,
                            (C.c_int32 * 2)(input_mult, 0))
+        if sink is not None:
+            self._check(self.lib.lib.lmn_rows_append_reduce(
+                self.handle, sink.handle, 1 if maximum else 0, inp.ptr, front, dim, back, C.byref(info), out.ptr,
+                refused.ptr if refused is not None else None))
+            return sink, out
         fn = self.lib.lib.lmn_trace_max_reduce if maximum else self.lib.lib.lmn_trace_sum_reduce
         self._check(fn(self.handle, inp.ptr, front, dim, back, C.byref(info), rows.ptr, row_offset, out.ptr))
         return rows, out
@@ -1389,13 +1431,20 @@ class Context:
                         range_check_mult: DeviceBuffer, is_final_output: bool = False, input_mults=(-1, -1),
                         rows: Optional[DeviceBuffer] = None, row_offset: int = 0,
                         lhs_view: Optional[LmnView] = None, rhs_view: Optional[LmnView] = None,
-                        out: Optional[DeviceBuffer] = None):
+                        out: Optional[DeviceBuffer] = None, sink: Optional["RowSink"] = None,
+                        refused: Optional[DeviceBuffer] = None):
         """`LuminairLessThan::process_trace`; `range_check_mult` (256 words) is the RangeCheckLookup table."""
-        if rows is None:
+        if rows is None and sink is None:
             rows = self.alloc((row_offset + n) * 22 * 4)
         out = out or self.alloc(n * 4)
         info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(*input_ids), num_consumers, 1 if is_final_output else 0,
                            (C.c_int32 * 2)(*input_mults))
+        if sink is not None:
+            self._check(self.lib.lib.lmn_rows_append_elementwise_v(
+                self.handle, sink.handle, 13, lhs.ptr, C.byref(lhs_view) if lhs_view is not None else None,
+                rhs.ptr, C.byref(rhs_view) if rhs_view is not None else None, n, C.byref(info), range_check_mult.ptr,
+                out.ptr, refused.ptr if refused is not None else None))
+            return sink, out
         self._check(self.lib.lib.lmn_trace_less_than(
             self.handle, lhs.ptr, C.byref(lhs_view) if lhs_view is not None else None, rhs.ptr,
             C.byref(rhs_view) if rhs_view is not None else None, n, C.byref(info), range_check_mult.ptr, rows.ptr,
@@ -1550,7 +1599,8 @@ class Context:
         return arr, n, settings, keep
 
     def row_sink(self, kind: int, capacity_rows: int) -> RowSink:
-        """`lmn_rows_open`: a table of `kind` to be filled with up to `capacity_rows` host rows while they are produced."""
+        """`lmn_rows_open`: a table of `kind` to be filled with up to `capacity_rows` rows while they are produced - host
+        rows (`push`), or a device producer's (the `sink=` argument of the `trace_*` methods)."""
         return RowSink(self, kind, capacity_rows)
 
     def prove_tables(self, tables: Sequence[Tuple[int, object, int]], luts=None,

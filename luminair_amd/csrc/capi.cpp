@@ -412,6 +412,57 @@ int lmn_rows_reset(lmn_rows* rows) {
 }
 void lmn_rows_close(lmn_rows* rows) { delete rows; }
 
+// ---- device producers that fill a sink (trace_gen.cpp Context::rows_append_*).  These do take the context's lock - the
+// launch runs on its stream, as every lmn_trace_* launch does - and the sink's behind it.  Null pointers are refused where
+// the single forms refuse them, with the argument's name in lmn_last_error(ctx).
+}  // extern "C"
+namespace {
+template <class F>
+int rows_append(lmn_ctx* ctx, lmn_rows* rows, const char* call, const char* null_arg /* the first null argument, if any */, F&& f) {
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  const std::string name = std::string(call) + ": ";
+#ifdef LMN_BATCH
+  (void)rows; (void)null_arg; (void)f;
+  return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, (name + "rows: row sinks are not part of the batch library (use libluminair_hip.so)").c_str());
+#else
+  if (!rows) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, (name + "null rows").c_str());
+  if (null_arg) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, (name + "null " + null_arg).c_str());
+  return guard(ctx, [&] { f(rows->sink); });
+#endif
+}
+}  // namespace
+extern "C" {
+int lmn_rows_append_elementwise_v(lmn_ctx* ctx, lmn_rows* rows, uint32_t kind, const int32_t* lhs_dev, const lmn_view* lhs_view,
+                                  const int32_t* rhs_dev, const lmn_view* rhs_view, uint64_t n, const lmn_node_info* info,
+                                  uint32_t* range_check_mult_dev, int32_t* out_dev, uint32_t* refused_dev) {
+  return rows_append(ctx, rows, "lmn_rows_append_elementwise_v", !lhs_dev ? "lhs_dev" : !info ? "info" : nullptr, [&](lmn::RowSink& sink) {
+    ctx->impl->rows_append_elementwise(sink, kind, lhs_dev, lhs_view, rhs_dev, rhs_view, n, *info, range_check_mult_dev, out_dev,
+                                       refused_dev);
+  });
+}
+int lmn_rows_append_contiguous(lmn_ctx* ctx, lmn_rows* rows, const int32_t* input_dev, uint64_t in_size, const lmn_view* view,
+                               uint64_t out_size, const lmn_node_info* info, int32_t* out_dev, uint32_t* refused_dev) {
+  return rows_append(ctx, rows, "lmn_rows_append_contiguous", !input_dev ? "input_dev" : !info ? "info" : nullptr, [&](lmn::RowSink& sink) {
+    ctx->impl->rows_append_contiguous(sink, input_dev, in_size, view, out_size, *info, out_dev, refused_dev);
+  });
+}
+int lmn_rows_append_reduce(lmn_ctx* ctx, lmn_rows* rows, uint32_t is_max, const int32_t* input_dev, uint64_t front, uint64_t dim,
+                           uint64_t back, const lmn_node_info* info, int32_t* out_dev, uint32_t* refused_dev) {
+  return rows_append(ctx, rows, "lmn_rows_append_reduce", !input_dev ? "input_dev" : !info ? "info" : nullptr, [&](lmn::RowSink& sink) {
+    ctx->impl->rows_append_reduce(sink, is_max != 0, input_dev, front, dim, back, *info, out_dev, refused_dev);
+  });
+}
+int lmn_rows_append_lut_ranges(lmn_ctx* ctx, lmn_rows* rows, uint32_t kind, const int32_t* input_dev, const lmn_view* view,
+                               uint64_t n, const lmn_node_info* info, const uint32_t* lut_col1_dev, const lmn_range* ranges,
+                               uint32_t n_ranges, uint32_t* mult_dev, int32_t* out_dev, uint32_t* refused_dev) {
+  return rows_append(ctx, rows, "lmn_rows_append_lut_ranges",
+                     !input_dev ? "input_dev" : !info ? "info" : !lut_col1_dev ? "lut_col1_dev" : !mult_dev ? "mult_dev" : nullptr,
+                     [&](lmn::RowSink& sink) {
+                       ctx->impl->rows_append_lut(sink, kind, input_dev, view, n, *info, lut_col1_dev, ranges, n_ranges, mult_dev,
+                                                  out_dev, refused_dev);
+                     });
+}
+
 int lmn_upload(lmn_ctx* ctx, const void* host, size_t bytes, void** device_out) {
   if (!ctx || !host || !device_out) return LMN_ERR_INVALID_ARGUMENT;
   return guard(ctx, [&] { *device_out = ctx->impl->upload(host, bytes); });

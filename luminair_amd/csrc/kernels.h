@@ -470,6 +470,21 @@ void launch_trace_lut(const int32_t* input, const TraceView& view, uint64_t n, c
 void launch_trace_reduce(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back,
                          const TraceNode& nd, uint32_t* rows, int32_t* out, lmn_stream_t s);
 
+// ---- the column forms (lmn_rows_append_*): the same row rules with the rows stored into a row sink's columns - word c of
+// the node's row r goes to cols[c * col_stride + r], so `cols` is column 0 at the node's FIRST TABLE ROW (the sink's row
+// count, any value: no alignment is asked of it).  One dword per lane per column, no LDS tile (the reduce kernels keep the
+// LDS of their scan).  A refused element is marked as in the row forms, sets *bad_word (the sink's verdict word) to 1 and is
+// added to *refused (may be null); a LUT input outside every range is a refused element, as in the many-member forms.
+void launch_trace_elementwise_cols(int kind, const int32_t* lhs, const TraceView& lv, const int32_t* rhs, const TraceView& rv,
+                                   uint64_t n, const TraceNode& nd, uint32_t* cols, uint64_t col_stride, int32_t* out,
+                                   uint32_t* aux, uint32_t* bad_word, uint32_t* refused, lmn_stream_t s);
+void launch_trace_reduce_cols(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back,
+                              const TraceNode& nd, uint32_t* cols, uint64_t col_stride, int32_t* out, uint32_t* bad_word,
+                              uint32_t* refused, lmn_stream_t s);
+void launch_trace_lut_cols(const int32_t* input, const TraceView& view, uint64_t n, const TraceNode& nd,
+                           const uint32_t* lut_col1, const LutRanges& ranges, uint32_t* mult, uint32_t* cols,
+                           uint64_t col_stride, int32_t* out, uint32_t* bad_word, uint32_t* refused, lmn_stream_t s);
+
 // ---- the many-member forms (lmn_trace_many_*): one launch fills a node's rows for n_members pies, grid.y = the member.
 // Member m works on base + m * stride (`*_ms`: operands and outputs in elements, rows / aux / mult in WORDS here - the host
 // side converts row strides); an operand stride of 0 shares the operand, out_ms == 0 stores the shared output from member 0

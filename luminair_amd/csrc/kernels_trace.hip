@@ -229,21 +229,63 @@ LMN_D void trace_count_refused(bool bad, uint32_t* __restrict__ refused) {
   if (refused && c && (threadIdx.x & 63u) == 0u) atomicAdd(refused, c);
 }
 
+// Where a producer's rows go, and how a block's rows leave.  The ROW form (COLS false): `p` is the node's first row of an
+// array-of-structs table; a lane builds its row in the block's LDS tile and the block writes the tile out as one contiguous,
+// coalesced run of words.  The COLUMN form (a row sink's columns, lmn_rows_append_*): `p` is column 0 at the node's first
+// table row - any row, aligned to nothing - and word c of the node's row r goes to p[c * col_stride + r]: the row is built in
+// registers and stored column by column, one dword per lane per column (a 256-byte run per wave store), with no LDS tile.
+// A lane whose row carries the mark sets *bad, the sink's verdict word (the word k_rows_chunk sets for a pushed word >= P).
+struct TraceDst {
+  uint32_t* p;
+  uint64_t col_stride;   // column form only
+  uint32_t* bad;         // column form only
+};
+template <int NC, bool COLS, int ST = (NC | 1)>   // ST: the tile's row stride, odd: conflict-free column writes
+struct RowOut {   // the row form
+  uint32_t* tile;
+  uint32_t* t;    // this lane's row
+  LMN_D RowOut() {
+    LMN_SHARED uint32_t s_tile[TPB * ST];
+    tile = s_tile;
+    t = s_tile + threadIdx.x * ST;
+  }
+  // reached by all TPB lanes: the block holds rows [row0, min(row0 + TPB, n)) of the node's n rows
+  LMN_D void store(const TraceDst& d, uint64_t row0, uint64_t n, bool, bool) {
+    __syncthreads();
+    const uint64_t rows_here = n - row0 < (uint64_t)TPB ? n - row0 : (uint64_t)TPB;
+    const uint32_t words = (uint32_t)rows_here * NC;
+    uint32_t* dst = d.p + row0 * NC;
+    for (uint32_t w = threadIdx.x; w < words; w += TPB) dst[w] = tile[(w / NC) * ST + (w % NC)];
+  }
+};
+template <int NC, int ST>
+struct RowOut<NC, true, ST> {   // the column form
+  uint32_t t[NC];
+  LMN_D void store(const TraceDst& d, uint64_t row0, uint64_t n, bool on, bool bad) {
+    if (!on) return;
+    uint32_t* col = d.p + row0 + threadIdx.x;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) col[(uint64_t)c * d.col_stride] = t[c];
+    if (bad) *d.bad = 1u;
+  }
+};
+
 // The row rule of the elementwise kinds, stated once for k_trace_elementwise (one tensor per launch) and
 // k_trace_many_elementwise (blockIdx.y = the member): the pointers are the launch's own or the member's bases, blockIdx.x is
-// the tile of TPB rows in both.  MANY: the refused elements are counted in *refused (may be null).
-template <int KIND, bool MANY>
+// the tile of TPB rows in both.  MANY or COLS: the refused elements are counted in *refused (may be null).  COLS: the
+// column form of the single launch (k_sink_elementwise), see TraceDst.
+template <int KIND, bool MANY, bool COLS = false>
 LMN_D void trace_elementwise_rows(const int32_t* __restrict__ lhs, const TraceView& lv, const int32_t* __restrict__ rhs,
-                                  const TraceView& rv, uint64_t n, const TraceNode& nd, uint32_t* __restrict__ rows,
+                                  const TraceView& rv, uint64_t n, const TraceNode& nd, const TraceDst& dst,
                                   int32_t* __restrict__ out, uint32_t* __restrict__ aux, uint32_t* __restrict__ refused) {
+  static_assert(!(MANY && COLS), "the many-member forms keep rows only");
   constexpr int NC = trace_ncols(KIND);
-  constexpr int ST = NC | 1;  // odd LDS row stride: conflict-free column writes
-  LMN_SHARED uint32_t tile[TPB * ST];
+  RowOut<NC, COLS> ro;
   const uint64_t row0 = (uint64_t)blockIdx.x * TPB;
   const uint64_t r = row0 + threadIdx.x;
   bool bad = false;   // this lane's element is refused (its row carries the mark)
   if (r < n) {
-    uint32_t* t = tile + threadIdx.x * ST;
+    uint32_t* t = ro.t;
     const bool ref_contig = KIND == 16 && nd.phys_n != 0;
     const int64_t a = lhs[view_offset(lv, ref_contig ? r % nd.out_n : r)];
     const uint32_t idx = (uint32_t)r, last = r + 1 == (ref_contig ? nd.phys_n : n) ? 1u : 0u;
@@ -328,21 +370,25 @@ LMN_D void trace_elementwise_rows(const int32_t* __restrict__ lhs, const TraceVi
       }
       if (out) out[r] = (int32_t)e.out;
     }
-    if constexpr (MANY) bad = t[trace_mark_col(KIND)] == P31;
+    if constexpr (MANY || COLS) bad = t[trace_mark_col(KIND)] == P31;
   }
-  if constexpr (MANY) trace_count_refused(bad, refused);
-  __syncthreads();
-  const uint64_t rows_here = n - row0 < (uint64_t)TPB ? n - row0 : (uint64_t)TPB;
-  const uint32_t words = (uint32_t)rows_here * NC;
-  uint32_t* dst = rows + row0 * NC;
-  for (uint32_t w = threadIdx.x; w < words; w += TPB) dst[w] = tile[(w / NC) * ST + (w % NC)];
+  if constexpr (MANY || COLS) trace_count_refused(bad, refused);
+  ro.store(dst, row0, n, r < n, bad);
 }
 
 template <int KIND>
 LMN_KERNEL k_trace_elementwise(const int32_t* __restrict__ lhs, TraceView lv, const int32_t* __restrict__ rhs,
                                TraceView rv, uint64_t n, TraceNode nd, uint32_t* __restrict__ rows,
                                int32_t* __restrict__ out, uint32_t* __restrict__ aux) {
-  trace_elementwise_rows<KIND, false>(lhs, lv, rhs, rv, n, nd, rows, out, aux, nullptr);
+  trace_elementwise_rows<KIND, false>(lhs, lv, rhs, rv, n, nd, TraceDst{rows, 0, nullptr}, out, aux, nullptr);
+}
+// the column form: cols = column 0 at the node's first table row, columns col_stride words apart (TraceDst)
+template <int KIND>
+LMN_KERNEL k_sink_elementwise(const int32_t* __restrict__ lhs, TraceView lv, const int32_t* __restrict__ rhs,
+                                    TraceView rv, uint64_t n, TraceNode nd, uint32_t* __restrict__ cols, uint64_t col_stride,
+                                    int32_t* __restrict__ out, uint32_t* __restrict__ aux, uint32_t* __restrict__ bad_word,
+                                    uint32_t* __restrict__ refused) {
+  trace_elementwise_rows<KIND, false, true>(lhs, lv, rhs, rv, n, nd, TraceDst{cols, col_stride, bad_word}, out, aux, refused);
 }
 
 // Member m of a many-member launch works on base + m * member stride (blockIdx.y is uniform over the workgroup: the bases are
@@ -357,8 +403,8 @@ LMN_KERNEL k_trace_many_elementwise(const int32_t* __restrict__ lhs, TraceView l
                                     uint32_t* __restrict__ rows, uint64_t rows_ms, int32_t* __restrict__ out, uint64_t out_ms,
                                     uint32_t* __restrict__ aux, uint64_t aux_ms, uint32_t* __restrict__ refused) {
   const uint64_t m = blockIdx.y;
-  trace_elementwise_rows<KIND, true>(lhs + m * lhs_ms, lv, rhs ? rhs + m * rhs_ms : nullptr, rv, n, nd, rows + m * rows_ms,
-                                     many_out_base(out, out_ms, m), aux ? aux + m * aux_ms : nullptr,
+  trace_elementwise_rows<KIND, true>(lhs + m * lhs_ms, lv, rhs ? rhs + m * rhs_ms : nullptr, rv, n, nd,
+                                     TraceDst{rows + m * rows_ms, 0, nullptr}, many_out_base(out, out_ms, m), aux ? aux + m * aux_ms : nullptr,
                                      refused ? refused + m : nullptr);
 }
 
@@ -369,13 +415,15 @@ LMN_KERNEL k_trace_many_elementwise(const int32_t* __restrict__ lhs, TraceView l
 // MAX: MaxReduce rows (prim.rs:1591-1734): the running maximum starts at the group's first element, is_max marks
 // the rows whose input becomes the new maximum (strict comparison).
 // (the row rule once, for k_trace_reduce and k_trace_many_reduce: `input` is the launch's or the member's own tensor, so the
-// cooperative carry-in reads the member's own input)
-template <bool MAX, bool MANY>
+// cooperative carry-in reads the member's own input.  COLS: the column form - the scan keeps its LDS, the rows are not
+// staged)
+template <bool MAX, bool MANY, bool COLS = false>
 LMN_D void trace_reduce_rows(const int32_t* __restrict__ input, uint64_t dim, uint64_t back, uint64_t n_rows, uint64_t n_out,
-                             const TraceNode& nd, uint32_t* __restrict__ rows, int32_t* __restrict__ out,
+                             const TraceNode& nd, const TraceDst& dst, int32_t* __restrict__ out,
                              uint32_t* __restrict__ refused) {
+  static_assert(!(MANY && COLS), "the many-member forms keep rows only");
   constexpr int NC = MAX ? 15 : 14, ST = MAX ? 17 : 15;
-  LMN_SHARED uint32_t tile[TPB * ST];
+  RowOut<NC, COLS, ST> ro;
   LMN_SHARED int64_t scan[TPB];   // inclusive segmented scan of the block's inputs (segment = reduction group)
   LMN_SHARED uint32_t head[TPB];  // distance (in lanes) back to the segment's first lane inside this block
   const uint64_t row0 = (uint64_t)blockIdx.x * TPB;
@@ -434,7 +482,7 @@ LMN_D void trace_reduce_rows(const int32_t* __restrict__ input, uint64_t dim, ui
     // running values may leave the value range (exact words mod P); an input outside it, or a group result outside it
     // on the last step, marks the row's output-value column
     const bool ok = fixed_ok(v) && (!last_step || fixed_ok(next));
-    uint32_t* t = tile + threadIdx.x * ST;
+    uint32_t* t = ro.t;
     t[0] = nd.node_id; t[1] = nd.lhs_id; t[2] = (uint32_t)g; t[3] = g + 1 == n_out ? 1u : 0u;
     t[4] = nd.node_id; t[5] = nd.lhs_id; t[6] = (uint32_t)g + 1u;
     t[7] = fixed_to_m31(v); t[8] = !ok ? P31 : last_step ? fixed_to_m31(next) : 0u;
@@ -447,26 +495,28 @@ LMN_D void trace_reduce_rows(const int32_t* __restrict__ input, uint64_t dim, ui
     if (last_step && out) out[g] = ok ? (int32_t)next : 0;
     bad = !ok;
   }
-  if constexpr (MANY) trace_count_refused(bad, refused);
-  __syncthreads();
-  const uint64_t rows_here = n_rows - row0 < (uint64_t)TPB ? n_rows - row0 : (uint64_t)TPB;
-  const uint32_t words = (uint32_t)rows_here * NC;
-  uint32_t* dst = rows + row0 * NC;
-  for (uint32_t w = threadIdx.x; w < words; w += TPB) dst[w] = tile[(w / NC) * ST + (w % NC)];
+  if constexpr (MANY || COLS) trace_count_refused(bad, refused);
+  ro.store(dst, row0, n_rows, on, bad);
 }
 
 template <bool MAX>
 LMN_KERNEL k_trace_reduce(const int32_t* __restrict__ input, uint64_t dim, uint64_t back, uint64_t n_rows,
                           uint64_t n_out, TraceNode nd, uint32_t* __restrict__ rows, int32_t* __restrict__ out) {
-  trace_reduce_rows<MAX, false>(input, dim, back, n_rows, n_out, nd, rows, out, nullptr);
+  trace_reduce_rows<MAX, false>(input, dim, back, n_rows, n_out, nd, TraceDst{rows, 0, nullptr}, out, nullptr);
+}
+template <bool MAX>
+LMN_KERNEL k_sink_reduce(const int32_t* __restrict__ input, uint64_t dim, uint64_t back, uint64_t n_rows, uint64_t n_out,
+                               TraceNode nd, uint32_t* __restrict__ cols, uint64_t col_stride, int32_t* __restrict__ out,
+                               uint32_t* __restrict__ bad_word, uint32_t* __restrict__ refused) {
+  trace_reduce_rows<MAX, false, true>(input, dim, back, n_rows, n_out, nd, TraceDst{cols, col_stride, bad_word}, out, refused);
 }
 template <bool MAX>
 LMN_KERNEL k_trace_many_reduce(const int32_t* __restrict__ input, uint64_t in_ms, uint64_t dim, uint64_t back, uint64_t n_rows,
                                uint64_t n_out, TraceNode nd, uint32_t* __restrict__ rows, uint64_t rows_ms,
                                int32_t* __restrict__ out, uint64_t out_ms, uint32_t* __restrict__ refused) {
   const uint64_t m = blockIdx.y;
-  trace_reduce_rows<MAX, true>(input + m * in_ms, dim, back, n_rows, n_out, nd, rows + m * rows_ms, many_out_base(out, out_ms, m),
-                               refused ? refused + m : nullptr);
+  trace_reduce_rows<MAX, true>(input + m * in_ms, dim, back, n_rows, n_out, nd, TraceDst{rows + m * rows_ms, 0, nullptr},
+                               many_out_base(out, out_ms, m), refused ? refused + m : nullptr);
 }
 
 void launch_trace_reduce(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back,
@@ -476,6 +526,17 @@ void launch_trace_reduce(bool is_max, const int32_t* input, uint64_t front, uint
     LMN_LAUNCH(k_trace_reduce<true>, dim3(cdiv(n_rows, TPB)), dim3(TPB), 0, s, input, dim, back, n_rows, n_out, nd, rows, out);
   else
     LMN_LAUNCH(k_trace_reduce<false>, dim3(cdiv(n_rows, TPB)), dim3(TPB), 0, s, input, dim, back, n_rows, n_out, nd, rows, out);
+}
+
+void launch_trace_reduce_cols(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back,
+                              const TraceNode& nd, uint32_t* cols, uint64_t col_stride, int32_t* out, uint32_t* bad_word,
+                              uint32_t* refused, lmn_stream_t s) {
+  const uint64_t n_out = front * back, n_rows = n_out * dim;
+  const dim3 g(cdiv(n_rows, TPB)), b(TPB);
+  if (is_max)
+    LMN_LAUNCH(k_sink_reduce<true>, g, b, 0, s, input, dim, back, n_rows, n_out, nd, cols, col_stride, out, bad_word, refused);
+  else
+    LMN_LAUNCH(k_sink_reduce<false>, g, b, 0, s, input, dim, back, n_rows, n_out, nd, cols, col_stride, out, bad_word, refused);
 }
 
 void launch_trace_many_reduce(bool is_max, const int32_t* input, uint64_t in_ms, uint64_t front, uint64_t dim, uint64_t back,
@@ -504,6 +565,22 @@ void launch_trace_elementwise(int kind, const int32_t* lhs, const TraceView& lv,
     case 16: LMN_LAUNCH(k_trace_elementwise<16>, g, b, 0, s, lhs, lv, rhs, rv, n, nd, rows, out, aux); break;
     default: throw LmnError(-100, "trace_elementwise: unsupported kind");
   }
+}
+
+void launch_trace_elementwise_cols(int kind, const int32_t* lhs, const TraceView& lv, const int32_t* rhs, const TraceView& rv,
+                                   uint64_t n, const TraceNode& nd, uint32_t* cols, uint64_t col_stride, int32_t* out,
+                                   uint32_t* aux, uint32_t* bad_word, uint32_t* refused, lmn_stream_t s) {
+  const dim3 g(cdiv(n, TPB)), b(TPB);
+#define LMN_COLS_CASE(K)                                                                                                       \
+  case K:                                                                                                                      \
+    LMN_LAUNCH(k_sink_elementwise<K>, g, b, 0, s, lhs, lv, rhs, rv, n, nd, cols, col_stride, out, aux, bad_word, refused); \
+    break;
+  switch (kind) {
+    LMN_COLS_CASE(0) LMN_COLS_CASE(1) LMN_COLS_CASE(2) LMN_COLS_CASE(7) LMN_COLS_CASE(8) LMN_COLS_CASE(13) LMN_COLS_CASE(15)
+    LMN_COLS_CASE(16)
+    default: throw LmnError(-100, "trace_elementwise_cols: unsupported kind");
+  }
+#undef LMN_COLS_CASE
 }
 
 void launch_trace_many_elementwise(int kind, const int32_t* lhs, const TraceView& lv, uint64_t lhs_ms, const int32_t* rhs,
@@ -538,14 +615,15 @@ LMN_D int32_t lut_out_value(uint32_t ow) { return ow > (P31 >> 1) ? (int32_t)ow 
 // Sin / Exp2 / Log2 rows (sin/table.rs: node, input, idx, is_last, next_node, next_input, next_idx, input, out,
 // input_mult, out_mult, lookup_mult) with out read from the LUT's output column, plus the LUT multiplicities.
 // (the row rule once, for k_trace_lut and k_trace_many_lut.  An input outside every range: its row is marked; the single form
-// also raises *err_flag - the call fails - the many form counts it as a refused element in *refused)
-template <bool MANY>
+// also raises *err_flag - the call fails - the many form and the column form count it as a refused element in *refused)
+template <bool MANY, bool COLS = false>
 LMN_D void trace_lut_rows(const int32_t* __restrict__ input, const TraceView& view, uint64_t n, const TraceNode& nd,
                           const uint32_t* __restrict__ lut1, const LutRanges& rg, uint32_t* __restrict__ mult,
-                          uint32_t* __restrict__ rows, int32_t* __restrict__ out, uint32_t* __restrict__ err_flag,
+                          const TraceDst& dst, int32_t* __restrict__ out, uint32_t* __restrict__ err_flag,
                           uint32_t* __restrict__ refused) {
-  constexpr int NC = 12, ST = 13;
-  LMN_SHARED uint32_t tile[TPB * ST];
+  static_assert(!(MANY && COLS), "the many-member forms keep rows only");
+  constexpr int NC = 12;
+  RowOut<NC, COLS> ro;
   const uint64_t row0 = (uint64_t)blockIdx.x * TPB;
   const uint64_t r = row0 + threadIdx.x;
   bool bad = false;
@@ -555,29 +633,31 @@ LMN_D void trace_lut_rows(const int32_t* __restrict__ input, const TraceView& vi
     uint32_t ow = P31;  // an input outside every range
     if (li < 0) {
       bad = true;
-      if constexpr (!MANY) *err_flag = 1u;
+      if constexpr (!MANY && !COLS) *err_flag = 1u;
     } else {
       ow = lut1[li];
       atomicAdd(&mult[li], 1u);
     }
-    uint32_t* t = tile + threadIdx.x * ST;
+    uint32_t* t = ro.t;
     t[0] = nd.node_id; t[1] = nd.lhs_id; t[2] = (uint32_t)r; t[3] = r + 1 == n ? 1u : 0u;
     t[4] = nd.node_id; t[5] = nd.lhs_id; t[6] = (uint32_t)r + 1u;
     t[7] = fixed_to_m31(a); t[8] = ow; t[9] = nd.lhs_mult; t[10] = nd.out_mult; t[11] = 1u;
     if (out) out[r] = lut_out_value(ow);
   }
-  if constexpr (MANY) trace_count_refused(bad, refused);
-  __syncthreads();
-  const uint64_t rows_here = n - row0 < (uint64_t)TPB ? n - row0 : (uint64_t)TPB;
-  const uint32_t words = (uint32_t)rows_here * NC;
-  uint32_t* dst = rows + row0 * NC;
-  for (uint32_t w = threadIdx.x; w < words; w += TPB) dst[w] = tile[(w / NC) * ST + (w % NC)];
+  if constexpr (MANY || COLS) trace_count_refused(bad, refused);
+  ro.store(dst, row0, n, r < n, bad);
 }
 
 LMN_KERNEL k_trace_lut(const int32_t* __restrict__ input, TraceView view, uint64_t n, TraceNode nd,
                        const uint32_t* __restrict__ lut1, LutRanges rg, uint32_t* __restrict__ mult,
                        uint32_t* __restrict__ rows, int32_t* __restrict__ out, uint32_t* __restrict__ err_flag) {
-  trace_lut_rows<false>(input, view, n, nd, lut1, rg, mult, rows, out, err_flag, nullptr);
+  trace_lut_rows<false>(input, view, n, nd, lut1, rg, mult, TraceDst{rows, 0, nullptr}, out, err_flag, nullptr);
+}
+LMN_KERNEL k_sink_lut(const int32_t* __restrict__ input, TraceView view, uint64_t n, TraceNode nd,
+                            const uint32_t* __restrict__ lut1, LutRanges rg, uint32_t* __restrict__ mult,
+                            uint32_t* __restrict__ cols, uint64_t col_stride, int32_t* __restrict__ out,
+                            uint32_t* __restrict__ bad_word, uint32_t* __restrict__ refused) {
+  trace_lut_rows<false, true>(input, view, n, nd, lut1, rg, mult, TraceDst{cols, col_stride, bad_word}, out, nullptr, refused);
 }
 // lut1 is shared by all members; the multiplicity atomics go to the member's own table
 LMN_KERNEL k_trace_many_lut(const int32_t* __restrict__ input, TraceView view, uint64_t in_ms, uint64_t n, TraceNode nd,
@@ -585,7 +665,7 @@ LMN_KERNEL k_trace_many_lut(const int32_t* __restrict__ input, TraceView view, u
                             uint32_t* __restrict__ rows, uint64_t rows_ms, int32_t* __restrict__ out, uint64_t out_ms,
                             uint32_t* __restrict__ refused) {
   const uint64_t m = blockIdx.y;
-  trace_lut_rows<true>(input + m * in_ms, view, n, nd, lut1, rg, mult + m * mult_ms, rows + m * rows_ms,
+  trace_lut_rows<true>(input + m * in_ms, view, n, nd, lut1, rg, mult + m * mult_ms, TraceDst{rows + m * rows_ms, 0, nullptr},
                        many_out_base(out, out_ms, m), nullptr, refused ? refused + m : nullptr);
 }
 
@@ -594,6 +674,13 @@ void launch_trace_lut(const int32_t* input, const TraceView& view, uint64_t n, c
                       int32_t* out, uint32_t* err_flag, lmn_stream_t s) {
   LMN_LAUNCH(k_trace_lut, dim3(cdiv(n, TPB)), dim3(TPB), 0, s, input, view, n, nd, lut_col1, ranges, mult, rows, out,
              err_flag);
+}
+
+void launch_trace_lut_cols(const int32_t* input, const TraceView& view, uint64_t n, const TraceNode& nd,
+                           const uint32_t* lut_col1, const LutRanges& ranges, uint32_t* mult, uint32_t* cols,
+                           uint64_t col_stride, int32_t* out, uint32_t* bad_word, uint32_t* refused, lmn_stream_t s) {
+  LMN_LAUNCH(k_sink_lut, dim3(cdiv(n, TPB)), dim3(TPB), 0, s, input, view, n, nd, lut_col1, ranges, mult, cols, col_stride,
+             out, bad_word, refused);
 }
 
 void launch_trace_many_lut(const int32_t* input, const TraceView& view, uint64_t in_ms, uint64_t n, const TraceNode& nd,

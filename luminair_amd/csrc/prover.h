@@ -202,6 +202,12 @@ QuotientSamples parse_quotient_samples(uint32_t ncols, const uint32_t* sample_co
 // rows and one wait.  The columns come from lmn_dev_malloc, outside every context's per-proof arena; all device work runs
 // on the sink's own stream, so a proof on the context it was opened on overlaps with its filling.  Calls on one sink are
 // serialised by its own lock and never take the context's.
+// A DEVICE producer may fill it too (lmn_rows_append_*, Context::rows_append_*): the producer's column-form launch runs on
+// the context's stream and writes the node's rows straight into the columns at the sink's current row count.  Such a call
+// holds the context's lock and takes the sink's behind it - always in that order.  The two streams are tied by two events:
+// `appended_` (recorded on the producer's stream behind every append; sync, finish, reset and the destructor make the sink's
+// stream wait for it before anything else) and `cleared_` (recorded on the sink's stream behind the memset that clears
+// `bad_`, at open and at every reset; the next append makes the producer's stream wait for it).
 class RowSink {
  public:
   RowSink(int device, uint32_t kind, uint64_t capacity_rows);
@@ -214,6 +220,25 @@ class RowSink {
   void finish(lmn_table* table_out);
   void reset();
   uint64_t count() const;
+  // One device append, between the producer's argument checks and its launch.  The constructor takes the sink's lock and
+  // refuses (LMN_ERR_INVALID_ARGUMENT, text = `call`: `rows`: ...) a sink of another kind or device, one that is not filling,
+  // and more rows than capacity - count; then makes `producer` wait for the last clearing of `bad_`.  cols() / stride() /
+  // bad() are what the column-form launch takes.  done(): the launch is enqueued - records `appended_` behind it and adds the
+  // rows to the count.  Without done() the sink is as it was.
+  class Append {
+   public:
+    Append(RowSink& sink, const char* call, int device, lmn_stream_t producer, uint32_t kind, uint64_t n_rows);
+    uint32_t* cols() const { return sink_.cols_ + sink_.count_; }
+    uint64_t stride() const { return sink_.stride_; }
+    uint32_t* bad() const { return sink_.bad_; }
+    void done();
+
+   private:
+    RowSink& sink_;
+    std::lock_guard<std::mutex> lock_;
+    lmn_stream_t producer_;
+    uint64_t n_rows_;
+  };
 
  private:
   friend void rows_sink_attach(const lmn_table& tb, int device, lmn_stream_t proof_stream);
@@ -228,6 +253,11 @@ class RowSink {
   uint32_t* h_bad_ = nullptr;    // page-locked: its copy, read after finish's one wait
   lmn_stream_t stream_{};
   lmn_event_t done_{};           // recorded behind finish's last launch: what a proof's stream waits for
+  lmn_event_t appended_{};       // recorded on a producer's stream behind a device append (pending_: not yet waited for)
+  lmn_event_t cleared_{};        // recorded on stream_ behind every clearing of bad_
+  lmn_stream_t pending_on_{};    // the producer stream appended_ was last recorded on
+  bool pending_ = false;
+  void join_appends();           // stream_ waits for the pending appends (mu_ held)
   // Staging ring of lmn_rows_push (pageable rows), allocated by the first such push: SLOTS page-locked slots of SLOT_BYTES.
   // 4 MiB holds one of the 16 chunks of BASELINE config 2a (2^16 rows x 15 columns = 3.75 MiB) in ONE launch, and
   // is ~75 us of link time against ~400 us of the CPU copy that fills it: with 4 slots the copy never waits for the link.
@@ -382,6 +412,18 @@ class Context {
   void trace_lut(uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t n, const lmn_node_info& info,
                  const uint32_t* lut_col1, const lmn_range* ranges, uint32_t n_ranges, uint32_t* mult, uint32_t* rows,
                  uint64_t row_offset, int32_t* out);
+  // lmn_rows_append_* (trace_gen.cpp): the same four producers in their column form, appending the node's rows to a row
+  // sink at its current count; refused elements are counted in *refused (may be null) and fail the sink's finish.  No wait.
+  void rows_append_elementwise(RowSink& sink, uint32_t kind, const int32_t* lhs, const lmn_view* lv, const int32_t* rhs,
+                               const lmn_view* rv, uint64_t n, const lmn_node_info& info, uint32_t* rc_mult, int32_t* out,
+                               uint32_t* refused);
+  void rows_append_contiguous(RowSink& sink, const int32_t* input, uint64_t in_size, const lmn_view* view, uint64_t out_size,
+                              const lmn_node_info& info, int32_t* out, uint32_t* refused);
+  void rows_append_reduce(RowSink& sink, bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back,
+                          const lmn_node_info& info, int32_t* out, uint32_t* refused);
+  void rows_append_lut(RowSink& sink, uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t n,
+                       const lmn_node_info& info, const uint32_t* lut_col1, const lmn_range* ranges, uint32_t n_ranges,
+                       uint32_t* mult, int32_t* out, uint32_t* refused);
   // lmn_trace_many_* (trace_gen.cpp): the same producers for n_members pies of one shape, one launch per node; member m
   // works on base + m * member stride (`*_ms`: operands / outputs in elements, rows in rows of the kind, tables in words)
   void trace_many_elementwise(uint32_t kind, const int32_t* lhs, const lmn_view* lv, uint64_t lhs_ms, const int32_t* rhs,

@@ -344,6 +344,71 @@ void Context::trace_many_lut(uint32_t kind, const int32_t* input, const lmn_view
                         rows_ms * 12ull, out, out_ms, refused, stream_);
 }
 
+// ------------------------------------------------------------------------------------ lmn_rows_append_*
+// The four single producers in their column form: the node's rows go straight into a row sink's columns at its current row
+// count (no array-of-structs table, no transpose in front of the proof).  The single form's own argument rules come first,
+// then the sink's (RowSink::Append); nothing is launched before both hold, and no call waits.
+void Context::rows_append_elementwise(RowSink& sink, uint32_t kind, const int32_t* lhs, const lmn_view* lv, const int32_t* rhs,
+                                      const lmn_view* rv, uint64_t n, const lmn_node_info& info, uint32_t* rc_mult, int32_t* out,
+                                      uint32_t* refused) {
+  const char* call = "lmn_rows_append_elementwise_v";
+#ifndef LMN_EMU
+  LMN_HIP_CHECK(hipSetDevice(device_));
+#endif
+  many_rules(call, [&] { return check_elementwise(kind, rhs, rc_mult, n); });
+  const bool binary = elementwise_binary(kind);
+  const TraceView tlv = many_rules(call, [&] { return trace_view(lv, n); });
+  const TraceView trv = binary ? many_rules(call, [&] { return trace_view(rv, n); }) : TraceView{};
+  RowSink::Append ap(sink, call, device_, stream_, kind, n);
+  launch_trace_elementwise_cols((int)kind, lhs, tlv, binary ? rhs : nullptr, trv, n, trace_node(info), ap.cols(), ap.stride(), out,
+                                kind == LMN_KIND_LESS_THAN ? rc_mult : nullptr, ap.bad(), refused, stream_);
+  ap.done();
+}
+
+void Context::rows_append_contiguous(RowSink& sink, const int32_t* input, uint64_t in_size, const lmn_view* view,
+                                     uint64_t out_size, const lmn_node_info& info, int32_t* out, uint32_t* refused) {
+  const char* call = "lmn_rows_append_contiguous";
+#ifndef LMN_EMU
+  LMN_HIP_CHECK(hipSetDevice(device_));
+#endif
+  TraceNode nd = trace_node(info);
+  const TraceView tv = many_rules(call, [&] { return check_contiguous(in_size, view, out_size, nd); });
+  const uint64_t n = std::max(in_size, out_size);
+  RowSink::Append ap(sink, call, device_, stream_, LMN_KIND_CONTIGUOUS, n);
+  launch_trace_elementwise_cols(LMN_KIND_CONTIGUOUS, input, tv, nullptr, TraceView{}, n, nd, ap.cols(), ap.stride(), out, nullptr,
+                                ap.bad(), refused, stream_);
+  ap.done();
+}
+
+void Context::rows_append_reduce(RowSink& sink, bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back,
+                                 const lmn_node_info& info, int32_t* out, uint32_t* refused) {
+  const char* call = "lmn_rows_append_reduce";
+#ifndef LMN_EMU
+  LMN_HIP_CHECK(hipSetDevice(device_));
+#endif
+  many_rules(call, [&] { check_reduce_shape(front, dim, back); return 0; });
+  RowSink::Append ap(sink, call, device_, stream_, is_max ? LMN_KIND_MAX_REDUCE : LMN_KIND_SUM_REDUCE, front * dim * back);
+  launch_trace_reduce_cols(is_max, input, front, dim, back, trace_node(info), ap.cols(), ap.stride(), out, ap.bad(), refused,
+                           stream_);
+  ap.done();
+}
+
+void Context::rows_append_lut(RowSink& sink, uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t n,
+                              const lmn_node_info& info, const uint32_t* lut_col1, const lmn_range* ranges, uint32_t n_ranges,
+                              uint32_t* mult, int32_t* out, uint32_t* refused) {
+  const char* call = "lmn_rows_append_lut_ranges";
+#ifndef LMN_EMU
+  LMN_HIP_CHECK(hipSetDevice(device_));
+#endif
+  uint64_t lut_rows = 0;
+  const LutRanges rg = many_rules(call, [&] { return trace_lut_ranges(kind, n, ranges, n_ranges, lut_rows); });
+  const TraceView tv = many_rules(call, [&] { return trace_view(view, n); });
+  RowSink::Append ap(sink, call, device_, stream_, kind, n);
+  launch_trace_lut_cols(input, tv, n, trace_node(info), lut_col1, rg, mult, ap.cols(), ap.stride(), out, ap.bad(), refused,
+                        stream_);
+  ap.done();
+}
+
 // ------------------------------------------------------------------------------------ lmn_trace_check
 // lmn_prove answers a bad trace with ProverError(ConstraintsNotSatisfied) after the FRI loop (phase_oods.cpp) and proves an
 // unbalanced one all the same.  This pass names the rows and the tuples instead: one launch per table over the rows where
@@ -562,18 +627,24 @@ RowSink::RowSink(int device, uint32_t kind, uint64_t capacity_rows)
   h_bad_ = (uint32_t*)lmn_host_alloc_pinned(64);
   stream_ = lmn_stream_create();
   done_ = lmn_event_create_untimed();
+  appended_ = lmn_event_create_untimed();
+  cleared_ = lmn_event_create_untimed();
   for (auto& e : slot_done_) e = lmn_event_create_untimed();
   lmn_memset(bad_, 0, 4, stream_);
+  lmn_event_record(cleared_, stream_);   // a device append's stream waits for it: the memset is in front of the producer
 }
 
 RowSink::~RowSink() {
   forget();
   try {
     lmn_set_device(device_);
+    join_appends();   // a producer may still be writing the columns
     lmn_sync(stream_);
   } catch (...) {
   }
   lmn_event_destroy(done_);
+  lmn_event_destroy(appended_);
+  lmn_event_destroy(cleared_);
   for (auto e : slot_done_) lmn_event_destroy(e);
   lmn_stream_destroy(stream_);
   if (ring_) lmn_host_free_pinned(ring_);
@@ -629,9 +700,39 @@ void RowSink::push(const uint32_t* host_rows, uint64_t n, bool pinned) {
   }
 }
 
+void RowSink::join_appends() {
+  if (!pending_) return;
+  lmn_stream_wait_event(stream_, appended_);
+  pending_ = false;
+}
+
+RowSink::Append::Append(RowSink& sink, const char* call, int device, lmn_stream_t producer, uint32_t kind, uint64_t n_rows)
+    : sink_(sink), lock_(sink.mu_), producer_(producer), n_rows_(n_rows) {
+  auto refuse = [&](const std::string& why) { throw LmnError(LMN_ERR_INVALID_ARGUMENT, std::string(call) + ": rows: " + why); };
+  if ((uint32_t)sink.spec_->kind != kind)
+    refuse("the sink was opened for kind " + std::to_string(sink.spec_->kind) + ", the producer writes kind " + std::to_string(kind));
+  if (sink.device_ != device)
+    refuse("the sink lives on device " + std::to_string(sink.device_) + ", ctx on device " + std::to_string(device));
+  if (sink.state_ != FILLING) refuse("the sink is finished or has failed (lmn_rows_reset starts the next table)");
+  if (n_rows > sink.cap_ - sink.count_)
+    refuse("the node's " + std::to_string(n_rows) + " rows exceed the " + std::to_string(sink.cap_ - sink.count_) +
+           " left of the capacity the sink was opened with");
+  // appended_ is one event: appends from another stream than the last one's must not lose that one's record
+  if (sink.pending_ && sink.pending_on_ != producer) sink.join_appends();
+  lmn_stream_wait_event(producer, sink.cleared_);   // the verdict word is clear before a producer can set it
+}
+
+void RowSink::Append::done() {
+  lmn_event_record(sink_.appended_, producer_);
+  sink_.pending_ = true;
+  sink_.pending_on_ = producer_;
+  sink_.count_ += n_rows_;
+}
+
 void RowSink::sync() {
   std::lock_guard<std::mutex> lk(mu_);
   lmn_set_device(device_);
+  join_appends();
   lmn_sync(stream_);
 }
 
@@ -642,6 +743,7 @@ void RowSink::finish(lmn_table* table_out) {
   if (count_ == 0) throw LmnError(LMN_ERR_EMPTY_TRACE, "TraceError::EmptyTrace");
   const uint64_t size = 1ull << padded_log(count_);   // as lmn_prove derives log_size from n_rows
   lmn_set_device(device_);
+  join_appends();   // the compaction and the verdict below are behind every producer
   if (size > count_) launch_rows_chunk(nullptr, count_, size - count_, spec_->n_cols, cols_, stride_, pad_, bad_, stream_);
   // a sink opened for more rows than came: columns `size` apart, as the proof's phases index them.  stride_ >= 2 * size,
   // so column c's new place ends before its old one - and every later column's - begins
@@ -653,7 +755,9 @@ void RowSink::finish(lmn_table* table_out) {
   lmn_sync(stream_);   // the one wait: every pushed buffer is free, and the verdict is here
   if (*h_bad_) {
     state_ = FAILED;
-    throw LmnError(LMN_ERR_INVALID_ARGUMENT, "row sink: a pushed word is not a canonical M31 (>= 2^31-1)");
+    throw LmnError(LMN_ERR_INVALID_ARGUMENT,
+                   "row sink: a pushed word is not a canonical M31 (>= 2^31-1), or a device producer refused an element "
+                   "(lmn_rows_append_*: its row carries that mark)");
   }
   state_ = FINISHED;
   {
@@ -670,7 +774,9 @@ void RowSink::reset() {
   std::lock_guard<std::mutex> lk(mu_);
   forget();
   lmn_set_device(device_);
+  join_appends();                    // a producer of the table given up may still set the verdict word
   lmn_memset(bad_, 0, 4, stream_);   // ordered in front of the next table's chunks
+  lmn_event_record(cleared_, stream_);   // ... and, through this, in front of its device appends
   count_ = 0;
   state_ = FILLING;
 }

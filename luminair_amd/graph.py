@@ -45,6 +45,16 @@ class _SlabLease(backend.DeviceBuffer):
         self.ptr = 0
 
 
+class _SinkLease:
+    """A `gen_trace(columns=True)` sink among the call's buffers: `free()` closes it, like any other allocation of the call."""
+
+    def __init__(self, sink: "backend.RowSink"):
+        self.sink = sink
+
+    def free(self):
+        self.sink.close()
+
+
 def _lease_slab(ctx, need: int) -> _SlabLease:
     cached = getattr(ctx, "_graph_slab", None)
     if cached is not None and cached.nbytes >= need:
@@ -319,10 +329,22 @@ class DeviceGraph:
         t.is_output = True
         return t
 
-    def gen_trace(self):
+    def gen_trace(self, columns: bool = False, sinks: Optional[Dict[int, "backend.RowSink"]] = None):
         """Runs every node on the device.  Returns (tables, luts, buffers): tables = [(kind, rows DeviceBuffer,
         n_rows)] in `gen_trace` order (ascending kind) and luts = {name: (col0, col1)} for
-        Context.prove_tables(tables, luts); buffers = every device allocation made (free them after proving)."""
+        Context.prove_tables(tables, luts); buffers = every device allocation made (free them after proving).
+        columns=True: every operator table is a `RowSink` the producers fill column-major (`lmn_rows_append_*`), so the
+        proof starts without the transpose of those tables: the table entries are (kind, finished RowSink, n_rows) - the
+        lookup-multiplicity and range-check tables stay one-column device buffers - and `buffers` holds the sinks too, so
+        freeing it after the proof closes them.  All sinks are finished after the last node has been enqueued; a refused
+        element raises the dry run's ValueError.  sinks= the sinks of an earlier call - {kind: RowSink} as
+        `sinks_of(buffers)` returns them, or that call's `buffers` - are reset and reused instead of opened (a service
+        does not reallocate per pie); a sink that is closed or too small is replaced."""
+        if sinks is not None and not columns:
+            raise ValueError("gen_trace: sinks= needs columns=True")
+        if sinks is not None and not isinstance(sinks, dict):     # an earlier call's buffers, or any collection of sinks
+            sinks = {s.kind: s for s in (b.sink if isinstance(b, _SinkLease) else b for b in sinks)
+                     if isinstance(s, backend.RowSink)}
         ctx = self.ctx
         K = TraceTableKind
         self.release_dry_run()     # (its slab goes back to the context's cache: the lease below may take it)
@@ -371,7 +393,10 @@ class DeviceGraph:
                 luts_out[name] = (c0, c1)
         if int(K.LessThan) in total:
             stage(("rc",), np.zeros(256, dtype=np.uint32))
-        need = sum(al(total[k] * _NCOLS[k] * 4) for k in total) + sum(al(n.out.size * 4) for n in self.nodes) + cursor_h[0]
+        if columns:
+            stage(("refused",), np.zeros(1, dtype=np.uint32))
+        need = (0 if columns else sum(al(total[k] * _NCOLS[k] * 4) for k in total)) + \
+            sum(al(n.out.size * 4) for n in self.nodes) + cursor_h[0]
         slab = _lease_slab(ctx, need)
         cursor = [0]
 
@@ -384,9 +409,23 @@ class DeviceGraph:
         if staged is not None:
             ctx.upload_to(staged, np.concatenate(stage_parts))
         dev_of = lambda key: staged.view(*stage_off[key])
-        tables = {k: carve(total[k] * _NCOLS[k] * 4) for k in total}
-        offset = {k: 0 for k in total}
         bufs = [slab]
+        refused = None
+        if columns:
+            # one sink per operator table, of exactly the table's rows: the finish has nothing to compact
+            tables = {}
+            for k in total:
+                sink = (sinks or {}).get(k)
+                if sink is None or sink.capacity < total[k] or sink.handle is None:
+                    sink = ctx.row_sink(k, total[k])
+                else:
+                    sink.reset()
+                tables[k] = sink
+                bufs.append(_SinkLease(sink))
+            refused = dev_of(("refused",))
+        else:
+            tables = {k: carve(total[k] * _NCOLS[k] * 4) for k in total}
+        offset = {k: 0 for k in total}
         lut_dev, lut_tables = {}, {}
         for kind in sorted(total):
             if kind in _LUT_OF:
@@ -400,8 +439,11 @@ class DeviceGraph:
         for n in self.nodes:
             t = n.out
             t.member_stride = 0
-            common = dict(num_consumers=t.consumers, is_final_output=t.is_output, rows=tables[n.kind],
-                          row_offset=offset[n.kind], out=carve(t.size * 4))
+            common = dict(num_consumers=t.consumers, is_final_output=t.is_output, out=carve(t.size * 4))
+            if columns:
+                common.update(sink=tables[n.kind], refused=refused)
+            else:
+                common.update(rows=tables[n.kind], row_offset=offset[n.kind])
             if n.kind == int(K.Inputs):
                 src = dev_of(("in", t.node_id))
                 _, t.buf = ctx.trace_elementwise(n.kind, src, None, t.size, node_id=t.node_id, input_ids=(),
@@ -435,8 +477,33 @@ class DeviceGraph:
                     input_ids=tuple(i.base.node_id for i in ins), input_mults=tuple(-1 for _ in ins),
                     lhs_view=view_of(ins[0]), rhs_view=view_of(ins[1]) if len(ins) > 1 else None, **common)
             offset[n.kind] += rows_of(n)
+        if columns:
+            # every node is enqueued: the first finish waits for nearly all of the work, the others find it done.  A sink
+            # fails its finish exactly when a producer refused one of its elements; only then the counter is read
+            failed = False
+            for sink in tables.values():
+                try:
+                    sink.finish()
+                except backend.LuminairBackendError as e:
+                    if e.code != backend.ERR_INVALID_ARGUMENT:
+                        raise
+                    failed = True
+            if failed:
+                n_refused = int(ctx.download(refused)[0])
+                for b in bufs:
+                    if not (isinstance(b, _SinkLease) and sinks is not None and b.sink in sinks.values()):
+                        b.free()           # (the caller's own sinks stay open: the next call resets them)
+                raise ValueError("dry run: %d elements refused (a value outside [-(2^30-1), 2^30-1], Recip of a value <= 0, "
+                                 "Sqrt of a negative value, Rem outside lhs >= 0 and rhs > 0, or a LUT input outside its range)"
+                                 % n_refused)
         out = [(k, tables[k], total[k]) for k in tables] + [(k, b, n) for k, (b, n) in lut_tables.items()]
         return sorted(out, key=lambda e: e[0]), luts_out, bufs
+
+    @staticmethod
+    def sinks_of(buffers) -> Dict[int, "backend.RowSink"]:
+        """The sinks among what `gen_trace(columns=True)` returned as buffers, by kind: pass them as `sinks=` to the next
+        call - and then free only the other buffers of this one (closing a sink ends its reuse)."""
+        return {b.sink.kind: b.sink for b in buffers if isinstance(b, _SinkLease)}
 
     def gen_trace_many(self, n_members: int, feeds):
         """`gen_trace` for `n_members` pies of this graph at once - the producers in front of `BatchProver.prove_batch`:
