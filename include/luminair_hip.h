@@ -347,6 +347,40 @@ typedef struct lmn_verify_report {
 int lmn_verify_diagnose(const uint8_t* proof_bincode, size_t proof_len, const lmn_settings* settings,
                         const lmn_config* expected, lmn_verify_report* report);
 
+/* Verifies n proofs in one call: the front of lmn_verify_with_config (parse, config and shape checks, the settings
+ * cross-check, logup sum, transcript replay, OODS identity, last-layer shape, proof of work, query draw) runs on the host per
+ * proof, the back (the four trace-tree decommitments, the FRI quotients at the queried positions, the FRI layers: 77 % to
+ * 94 % of lmn_verify's time) on the device for all proofs that passed the front.
+ *  - Returns LMN_OK when every proof was judged, whatever the verdicts; otherwise the error that stopped the call (null
+ *    arguments with n > 0, a bad `expected`, a sharded context, out of memory, a device error), its text in
+ *    lmn_last_error(ctx).  n = 0 returns LMN_OK and touches nothing.  After LMN_OK, lmn_last_error(ctx) carries the text
+ *    of the first rejection in index order, if there was one.
+ *  - results[i].rc is what lmn_verify_with_config(proofs[i], lens[i], settings, expected) returns.
+ *  - stage 0: decided by the front; checks_failed holds the bit of the check that failed (a structural stop:
+ *    LMN_CHECK_SHAPE; bytes that do not parse: LMN_CHECK_PARSE).
+ *    stage 1: decided by the device stage; a rejection is LMN_ERR_VERIFICATION and checks_failed holds
+ *    lmn_verify_diagnose's TREE_DECOMMIT | FRI_DECOMMIT | FRI_FOLDS bits (nothing behind a failed tree decommitment is
+ *    looked at), or LMN_CHECK_SHAPE for a structural stop of that region (a witness list too short or too long, the
+ *    queried-values shape, a degenerate denominator).
+ *    stage 2: judged by the host's back half, with the same verdict - a proof the device stage does not take is never
+ *    refused: more than 128 distinct query positions, more than 8 column sizes or 36 trees, column sizes that no FRI
+ *    layer consumes, more than 4 MiB of lists and scratch, or a claim beyond the 4 different claims (kinds present and
+ *    their log sizes) that one call buckets.
+ *  - Proofs are staged in chunks of at most 256 proofs or 16 MiB: one transfer in, two launches per claim, one transfer
+ *    out and one host wait per chunk.
+ *  - Any unsharded context; in the batch library outside a batch.  The context's arena is not used.
+ *  - lmn_ctx_counter 16: proofs judged by the device stage, 17: stage-2 proofs, 18: verify launches, 19: host waits. */
+struct lmn_verify_result {
+  int32_t rc;             /* what lmn_verify_with_config returns for these bytes */
+  uint32_t checks_failed; /* LMN_CHECK_* bits */
+  uint32_t stage;         /* 0: decided on the host before the device stage, 1: decided by the device stage,
+                             2: judged entirely by the host verifier (fallback) */
+};
+typedef struct lmn_verify_result lmn_verify_result;
+int lmn_verify_many(lmn_ctx* ctx, const uint8_t* const* proofs, const size_t* lens, uint32_t n,
+                    const lmn_settings* settings, const lmn_config* expected /* NULL: PcsConfig::default(), variant 0 */,
+                    lmn_verify_result* results /* n */);
+
 /* Page-locked host memory for tables handed over as HOST buffers (`lmn_table.rows` without LMN_TABLE_ROWS_ON_DEVICE -
  * the reference's own calling convention: `prove(pie, settings)` takes the pie by value in host memory,
  * /root/reference/crates/prover/src/prover.rs:28-31,70).  Rows in ordinary pageable memory are copied through the
@@ -1004,7 +1038,8 @@ int lmn_open_queries(lmn_ctx* ctx, const lmn_positions* positions, const lmn_ope
  * (LMN_DEVICE_DECOMMIT=1 where 9 counts), 12: those among them that fell back to the host plan (no nonce in the queued
  * windows).  Diagnostic only, outside lmn_batch_counter's numbering and not part of what a binding needs - 13: k_open_plan
  * launches made for lmn_open_queries (counted where the launch is made), 14: its k_open_fetch launches, 15: its host
- * waits.  Any other number, or a null context: 0. */
+ * waits; 16 - 19: lmn_verify_many's proofs judged by the device stage, stage-2 proofs, launches and host waits.  Any
+ * other number, or a null context: 0. */
 uint64_t lmn_ctx_counter(const lmn_ctx* ctx, int which);
 int lmn_col_accumulate(lmn_ctx* ctx, lmn_col* dst, const lmn_col* src);     /* AccumulationOps::accumulate: dst += src (same shape) */
 /* FieldOps<BaseField>::batch_inverse and FieldOps<SecureField>::batch_inverse on whole columns, on the device.

@@ -9,7 +9,7 @@ from .pie import (CircuitSettings, ExecutionResources, Lookup, LookupLayout, Lum
                   Metadata, RangeCheckLookup, TraceTable, TraceTableKind)
 from .backend import RowSink, TraceReport
 from .graph import DeviceGraph
-from .prover import Prover, ProverPool, check_trace, prove, verify
+from .prover import Prover, ProverPool, check_trace, prove, verify, verify_many
 
 __all__ = ["Lookup", "LookupLayout", "RangeCheckLookup", "CircuitSettings", "ExecutionResources", "LuminairError", "LuminairPie", "LuminairProof", "Metadata",
-           "TraceTable", "TraceTableKind", "Prover", "ProverPool", "prove", "verify", "DeviceGraph", "RowSink", "TraceReport", "check_trace"]
+           "TraceTable", "TraceTableKind", "Prover", "ProverPool", "prove", "verify", "verify_many", "DeviceGraph", "RowSink", "TraceReport", "check_trace"]

@@ -254,6 +254,21 @@ OPEN_MAX_POSITIONS = 1024
 OPEN_MAX_ITEMS = 64
 
 
+class LmnVerifyResult(C.Structure):
+    """`lmn_verify_result`"""
+    _fields_ = [("rc", C.c_int32), ("checks_failed", C.c_uint32), ("stage", C.c_uint32)]
+
+
+@dataclass
+class VerifyResult:
+    """One proof of `Library.verify_many`: `code` is what `lmn_verify_with_config` returns for the proof, `checks_failed`
+    the LMN_CHECK_* bits, `stage` 0 (decided by the host front), 1 (by the device stage) or 2 (by the host verifier)."""
+    ok: bool
+    code: int
+    checks_failed: int
+    stage: int
+
+
 @dataclass
 class Opening:
     """One item of `Context.open_queries`: the three outputs of `Tree.decommit`, and - under OPEN_FRI_PAIRS - the FRI
@@ -269,6 +284,8 @@ COUNTER_GRINDS, COUNTER_GRIND_WAITS, COUNTER_DEVICE_CLOSES, COUNTER_DEVICE_CLOSE
 COUNTER_DEVICE_OPENINGS, COUNTER_DEVICE_OPENING_FALLBACKS = 11, 12
 # diagnostic only (the tests' evidence of one plan launch, one fetch launch and one wait per lmn_open_queries call)
 COUNTER_OPEN_PLAN_LAUNCHES, COUNTER_OPEN_FETCH_LAUNCHES, COUNTER_OPEN_WAITS = 13, 14, 15
+# lmn_verify_many: proofs judged by the device stage, stage-2 proofs, verify launches, host waits
+COUNTER_VERIFY_DEVICE, COUNTER_VERIFY_STAGE2, COUNTER_VERIFY_LAUNCHES, COUNTER_VERIFY_WAITS = 16, 17, 18, 19
 
 API_VERSION = 6   # LMN_API_VERSION of include/luminair_hip.h
 
@@ -294,7 +311,7 @@ EXPORTS = ["lmn_abi_version", "lmn_kind_padding_row", "lmn_strerror", "lmn_last_
            "lmn_settings_prepare", "lmn_prepared_root", "lmn_prepared_lookups", "lmn_prepared_destroy", "lmn_prove_prepared",
            "lmn_prove_submit_prepared", "lmn_batch_prove_prepared",
            "lmn_positions_from_cpu", "lmn_positions_to_cpu", "lmn_positions_log_domain", "lmn_positions_free",
-           "lmn_col_fri_close_keep", "lmn_open_queries"]
+           "lmn_col_fri_close_keep", "lmn_open_queries", "lmn_verify_many"]
 TRACE_MANY_MAX = 1024   # LMN_TRACE_MANY_MAX
 
 
@@ -429,6 +446,8 @@ class Library:
         lib.lmn_positions_free.argtypes = [VP, VP]
         lib.lmn_positions_free.restype = None
         lib.lmn_open_queries.argtypes = [VP, VP, C.POINTER(LmnOpenItem), U32, C.POINTER(LmnOpening)]
+        lib.lmn_verify_many.argtypes = [VP, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), U32, C.POINTER(LmnSettings),
+                                        C.POINTER(LmnConfig), C.POINTER(LmnVerifyResult)]
         lib.lmn_ctx_counter.argtypes = [VP, C.c_int]
         lib.lmn_ctx_counter.restype = C.c_uint64
         lib.lmn_tree_free.argtypes = [VP, VP]
@@ -582,6 +601,34 @@ class Library:
             msg = self.lib.lmn_last_error(None).decode() or self.lib.lmn_strerror(rc).decode()
             raise LuminairBackendError(rc, msg)
 
+    def verify_many(self, proofs: Sequence[bytes], variant: int = VARIANT_KAT, config: Optional[LmnConfig] = None,
+                    settings: Optional[LmnSettings] = None, ctx: Optional["Context"] = None) -> List["VerifyResult"]:
+        """`lmn_verify_many`: the verifier's front per proof on the host, its back for all of them on the device of `ctx`
+        (default: a context on device 0 that lives for this call).  One `VerifyResult` per proof, whatever the verdicts;
+        raises LuminairBackendError only when the call itself fails."""
+        proofs = [bytes(p) for p in proofs]
+        if not proofs:
+            return []
+        cfg = LmnConfig()
+        if config is not None:
+            C.memmove(C.byref(cfg), C.byref(config), C.sizeof(LmnConfig))
+        else:
+            self.lib.lmn_default_config(C.byref(cfg))
+            cfg.protocol_variant = variant
+        own = ctx is None
+        if own:
+            ctx = Context(0, library=self)
+        try:
+            n = len(proofs)
+            ptrs = (C.c_char_p * n)(*proofs)
+            lens = (C.c_size_t * n)(*[len(p) for p in proofs])
+            res = (LmnVerifyResult * n)()
+            sp = C.byref(settings) if settings is not None else None
+            ctx._check(self.lib.lmn_verify_many(ctx.handle, ptrs, lens, n, sp, C.byref(cfg), res))
+            return [VerifyResult(r.rc == LMN_OK, int(r.rc), int(r.checks_failed), int(r.stage)) for r in res]
+        finally:
+            if own:
+                ctx.close()
 
     def diagnose(self, proof: bytes, variant: int, config: Optional[LmnConfig] = None,
                  settings: Optional[LmnSettings] = None):

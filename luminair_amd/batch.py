@@ -37,6 +37,8 @@ class BatchProver:
             setattr(cfg, k, v)
         self.slots = slots
         self.config = cfg
+        self.device = device
+        self._verify_ctx = None
         self.handle = C.c_void_p()
         rc = lib.lmn_batch_create(device, C.byref(cfg), slots, C.byref(self.handle))
         if rc != 0:
@@ -64,10 +66,24 @@ class BatchProver:
         """`backend.PreparedSettings` made by THIS library and config, for `prove_batch(..., prepared=)`"""
         return backend.PreparedSettings(device, self.config, luts, lookups, self.lib)
 
-    def prove_batch(self, pies, luts=None, prepared: Optional["backend.PreparedSettings"] = None) -> List[bytes]:
+    def verify_proofs(self, proofs: Sequence[bytes]) -> None:
+        """`lmn_verify_many` of the batch library, outside any batch, under this prover's config: raises on the first
+        proof that is rejected."""
+        if self._verify_ctx is None:
+            self._verify_ctx = backend.Context(self.device, config=self.config, library=self.lib)
+        res = self.lib.verify_many(proofs, config=self.config, ctx=self._verify_ctx)
+        for i, r in enumerate(res):
+            if not r.ok:
+                raise LuminairBackendError(r.code, "proof %d of %d is rejected (checks_failed 0x%x, stage %d): %s"
+                                           % (i, len(res), r.checks_failed, r.stage,
+                                              self.lib.lib.lmn_last_error(self._verify_ctx.handle).decode()))
+
+    def prove_batch(self, pies, luts=None, prepared: Optional["backend.PreparedSettings"] = None,
+                    verify: bool = False) -> List[bytes]:
         """pies[i] = [(kind, rows, n_rows)] like `Context.prove_tables`; all pies must have the same kinds and row counts.
         Or what `marshal(pies, luts)` returned.  prepared: settings prepared once with the batch library (`prepare`) in
-        place of `luts` - `lmn_batch_prove_prepared`: no member handles a LUT, builds tree 0 or waits for its root."""
+        place of `luts` - `lmn_batch_prove_prepared`: no member handles a LUT, builds tree 0 or waits for its root.
+        verify: check the returned proofs with one `lmn_verify_many` call and raise on a rejection (off by default)."""
         if not (isinstance(pies, tuple) and len(pies) == 6 and pies[0] == "marshalled"):
             pies = self.marshal(pies, None if prepared is not None else luts)
         _, n, arrs, n_tables, settings, keep = pies
@@ -89,6 +105,8 @@ class BatchProver:
         if rc != 0:
             raise LuminairBackendError(rc, "lmn_batch_prove: %s (per pie: %s)"
                                        % ((lib.lmn_batch_last_error(self.handle) or b"").decode(), list(rcs)))
+        if verify:
+            self.verify_proofs(out)
         return out
 
     def counters(self):
@@ -100,6 +118,9 @@ class BatchProver:
                 "grinds": int(c(self.handle, 7)), "grind_rounds": int(c(self.handle, 8))}
 
     def close(self):
+        if getattr(self, "_verify_ctx", None) is not None:
+            self._verify_ctx.close()
+            self._verify_ctx = None
         if self.handle:
             self.lib.lib.lmn_batch_destroy(self.handle)
             self.handle = C.c_void_p()
@@ -140,9 +161,10 @@ class BatchPool:
         return self.groups[0].prepare(luts, lookups, device)
 
     def prove_many(self, pies: Sequence[Sequence[Tuple[int, object, int]]], luts=None,
-                   prepared: Optional["backend.PreparedSettings"] = None) -> List[bytes]:
+                   prepared: Optional["backend.PreparedSettings"] = None, verify: bool = False) -> List[bytes]:
         """all pies of identical shape (as in `BatchProver.prove_batch`); any number of them.  prepared: as in
-        `BatchProver.prove_batch` - every group reads the one prepared object."""
+        `BatchProver.prove_batch` - every group reads the one prepared object.  verify: check all returned proofs with one
+        `lmn_verify_many` call and raise on a rejection (off by default)."""
         import threading
         chunks = [(i, pies[i:i + self.slots]) for i in range(0, len(pies), self.slots)]
         out: List[Optional[bytes]] = [None] * len(pies)
@@ -169,6 +191,8 @@ class BatchPool:
             t.join()
         if errors:
             raise errors[0]
+        if verify and out:
+            self.groups[0].verify_proofs(out)
         return out
 
     def close(self):

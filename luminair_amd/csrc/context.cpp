@@ -101,6 +101,8 @@ Context::~Context() {
   if (pow_best_) lmn_dev_free(pow_best_);
   if (pow_many_dev_) lmn_dev_free(pow_many_dev_);
   if (pow_many_host_) lmn_host_free_pinned(pow_many_host_);
+  if (vm_dev_) lmn_dev_free(vm_dev_);
+  if (vm_host_) lmn_host_free_pinned(vm_host_);
   if (pin_base_) lmn_host_free_pinned(pin_base_);
 #ifndef LMN_EMU
   if (owns_stream_) (void)hipStreamDestroy(stream_);

@@ -370,6 +370,72 @@ void launch_open_recompute(const MerkleRecompute* cuts, uint32_t n_cuts, const O
                            uint32_t max_job_cap, OpenHeader* header, const OpenItemHeader* headers, const OpenEntry* jobs,
                            uint32_t* out, lmn_stream_t s);
 
+// ---- proofs verified in batches (lmn_verify_many; kernels_verify.h): the part of the verifier behind the query draw - the
+// four trace-tree decommitments, the FRI quotients at the queried positions, the FRI layers - for many proofs at once.
+// The host stages a chunk of proofs into ONE block of 32-bit words (verifier.cpp): per bucket (proofs of one claim) a
+// layout table, per proof a descriptor of offsets and lengths into the block.  Two launches per bucket:
+//   k_verify_values  one wave per proof: quotients, sibling pairs, folds, last layer; writes the FRI trees' leaf words
+//                    into the proof's scratch region of the block and the proof's values verdict
+//   k_verify_trees   one workgroup per (proof, tree): MerkleVerifier::verify; writes the tree's verdict
+// Every length a kernel uses is a descriptor field that the stager bounded against the block; no length is read from
+// proof content, and every counter is compared with its list's length before it becomes an address.
+constexpr uint32_t VM_MAX_POS = 128;     // distinct query positions of a proof the device stage takes
+constexpr uint32_t VM_MAX_SIZES = 8;     // distinct column sizes of a claim
+constexpr uint32_t VM_MAX_TREES = 36;    // 4 trace trees + the first FRI layer + the inner layers
+constexpr uint32_t VM_MAX_NODES = 2 * VM_MAX_POS;   // a level's node set: the positions, pair-expanded
+constexpr uint32_t VM_NONE = 0xffffffffu;
+// A verdict word is VM_DONE | failure bits: a word without the tag was never written (the host refuses it).
+constexpr uint32_t VM_DONE = 0x564d0000u, VM_DONE_MASK = 0xffff0000u;
+enum : uint32_t {
+  VM_FAIL_FOLDS = 1u,            // values: the last layer's polynomial does not reproduce a folded value
+  VM_FAIL_QUERIED_SHAPE = 2u,    // values: a queried value lies beyond its list
+  VM_FAIL_DENOMINATOR = 4u,      // values: degenerate quotient denominator
+  VM_FAIL_WITNESS_SHORT = 8u,    // values: a FRI witness ran out
+  VM_FAIL_WITNESS_LONG = 16u,    // values: a FRI witness has elements left over
+  VM_FAIL_POSITIONS = 32u,       // values: a layer's positions do not line up with the values folded so far
+  VM_FAIL_TREE = 1u,             // trees: the decommitment does not lead to the root (or a list ran out / has words left)
+};
+struct VmSpan {
+  uint32_t off, len;   // word offset in the chunk's block; len in the list's elements (words, hashes or QM31s)
+};
+struct VmProof {
+  VmSpan pos;                           // ascending distinct query positions in the largest domain
+  VmSpan queried[4];                    // words
+  VmSpan hash_wit[VM_MAX_TREES];        // hashes; trees 0-3, then the first FRI layer, then the inner layers
+  VmSpan col_wit[VM_MAX_TREES];         // words
+  VmSpan fri_wit[VM_MAX_TREES - 4];     // QM31s; layer 0 = the first layer
+  VmSpan leaves[VM_MAX_TREES - 4];      // scratch (words): the FRI tree's queried values, as long as the positions imply
+  VmSpan last;                          // QM31s: the last layer's coefficients
+  uint32_t roots;                       // n_trees x 8 words
+  uint32_t samples;                     // n_bcols x 4 words: the sampled values in the layout's batch-column order
+  uint32_t points, n_points;            // n_points x 8 words (x, y)
+  uint32_t alphas;                      // 4 words quot_alpha, then 4 words per FRI layer's fold alpha
+  uint32_t qbase[4][VM_MAX_SIZES];      // offset of a size's group inside queried[tree]
+  uint32_t verdict;                     // the proof's verdict words: [values, tree 0, tree 1, ...]
+};
+// one sampled column of a batch: queried value = queried[tree][qbase[tree][size] + query * ncol + j]
+struct VmBatchCol {
+  uint32_t tree, size, ncol, j;
+};
+struct VmBatch {
+  uint32_t point, col0, col1;   // batch columns [col0, col1), the k-th of which is sampled at samples[k]
+};
+// What proofs of one claim share; in the block it is followed by n_batches VmBatch and n_bcols VmBatchCol.
+struct VmLayout {
+  uint32_t n_sizes, top, n_inner, n_trees, n_batches, n_bcols;
+  uint32_t size_log[VM_MAX_SIZES];            // the LDE sizes, descending; size_log[0] == top
+  uint32_t size_batch0[VM_MAX_SIZES + 1];     // batches of size s: [size_batch0[s], size_batch0[s + 1])
+  uint32_t join_of_layer[VM_MAX_TREES];       // inner layer l: the size whose columns join behind its fold, or VM_NONE
+  uint32_t tree_max_log[VM_MAX_TREES];        // VM_NONE: a tree without columns
+  uint16_t tree_ncols[VM_MAX_TREES][32];      // columns per log size
+};
+// proofs: n_proofs descriptors; blk: the chunk's block (staged words | scratch | verdicts); tpb: 64, 128 or 256 lanes per
+// (proof, tree), from the largest number of distinct positions.  *n_launched (may be null) counts the launches made.
+void launch_verify_values(uint32_t* blk, uint32_t layout_off, uint32_t proofs_off, uint32_t n_proofs, lmn_stream_t s,
+                          uint64_t* n_launched = nullptr);
+void launch_verify_trees(uint32_t* blk, uint32_t layout_off, uint32_t proofs_off, uint32_t n_proofs, uint32_t n_trees,
+                         uint32_t tpb, lmn_stream_t s, uint64_t* n_launched = nullptr);
+
 // ---- proof-of-work grind (GrindOps on the device): one launch examines the nonces [base, base + 2^window_log) and
 // lowers *best (device, u64) to the smallest of them that passes, if it is below what *best holds.  A block whose nonces
 // all lie above *best at its start returns at once, so launches queued behind the one that found a nonce cost nothing

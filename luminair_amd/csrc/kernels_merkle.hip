@@ -1913,4 +1913,6 @@ void launch_fri_queries(DevChannel* ch, const FriCloseState* st, const uint32_t*
              pos_mask, out);
 }
 
+#include "kernels_verify.h"   // lmn_verify_many: k_verify_values, k_verify_trees
+
 }  // namespace lmn

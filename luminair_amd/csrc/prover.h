@@ -382,6 +382,9 @@ class Context {
   void positions_to_cpu(const lmn_positions* p, uint32_t* host, uint32_t* n_out);
   void positions_free(lmn_positions* p);
   void open_queries(const lmn_positions* p, const lmn_open_item* items, uint32_t n_items, lmn_opening* out);
+  // lmn_verify_many (verifier.cpp): results[i] for every proof; first_rejection = the text of the first rejection in index order
+  void verify_many(const uint8_t* const* proofs, const size_t* lens, uint32_t n, const lmn_settings* settings,
+                   const lmn_config& expect, lmn_verify_result* results, std::string& first_rejection);
   void col_accumulate(lmn_col* dst, const lmn_col* src);
   lmn_col* col_accumulate_quotients(const lmn_col* const* cols, uint32_t n, const uint32_t* sample_col,
                                     const uint32_t* sample_point, const uint32_t* sample_values, uint32_t nsamples,
@@ -456,11 +459,12 @@ class Context {
   // lmn_ctx_counter - 7: device grinds started, 8: host waits inside grind rounds, 9: proofs whose transcript was closed on
   // the device, 10: those among them that fell back to the host's grind rounds; 0 for any other number
   // 11, 12: proofs opened by the device plan, fallbacks among them; 13, 14, 15 (diagnostic): plan launches, fetch launches
-  // and host waits of open_queries
+  // and host waits of open_queries; 16 .. 19: verify_many's proofs judged by the device stage, stage-2 proofs, launches, waits
   uint64_t counter(int which) const {
     return which >= 7 && which <= 10    ? counters_[which - 7]
            : which >= 11 && which <= 12 ? dev_open_counters_[which - 11]
            : which >= 13 && which <= 15 ? open_counters_[which - 13]
+           : which >= 16 && which <= 19 ? verify_counters_[which - 16]
                                         : 0;
   }
   lmn_config cfg;
@@ -619,6 +623,10 @@ class Context {
   uint64_t counters_[4] = {0, 0, 0, 0};            // counter()
   uint64_t open_counters_[3] = {0, 0, 0};          // counter() 13 .. 15
   uint64_t dev_open_counters_[2] = {0, 0};         // counter() 11, 12: proofs opened by the device plan, fallbacks among them
+  uint64_t verify_counters_[4] = {0, 0, 0, 0};     // counter() 16 .. 19
+  // verify_many's block, page-locked (staged words | verdicts) and on the device; grown on demand, never the arena
+  char *vm_host_ = nullptr, *vm_dev_ = nullptr;
+  size_t vm_host_cap_ = 0, vm_dev_cap_ = 0;
   // grind_many's rounds; its tables (digests | best | pending, device and page-locked host) grow on demand
   uint64_t grind_rounds(const PowWords* w, uint32_t n, bool kat, uint32_t pow_bits, uint64_t* nonces);
   char *pow_many_dev_ = nullptr, *pow_many_host_ = nullptr;

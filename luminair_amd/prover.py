@@ -127,11 +127,8 @@ def check_trace(pie: LuminairPie, settings: Optional[CircuitSettings] = None) ->
     return _default.check(pie, settings)
 
 
-def verify(proof: LuminairProof, settings: Optional[CircuitSettings] = None,
-           protocol_variant: int = backend.VARIANT_KAT, library=None) -> None:
-    """Drop-in for the reference's `verify(proof, settings)` (crates/verifiers/rust/src/verifier.rs:21-143):
-    host-side check of a proof's bincode bytes; raises LuminairError(StwoVerifierError | InvalidLogUp | ...)."""
-    lib = library or backend.default_library()
+def _verifier_settings(settings: Optional[CircuitSettings]):
+    """(`lmn_settings` or None, what keeps its arrays alive) as the verifier reads them"""
     c_settings, keep = None, None
     if settings is not None and (settings.layouts or settings.lookups or settings.range_check):
         # what verifier.rs:47-57 reads from the settings: which lookups exist and how large their LUTs are
@@ -147,8 +144,31 @@ def verify(proof: LuminairProof, settings: Optional[CircuitSettings] = None,
             mask |= 8
         keep = (backend.LmnLut * max(len(luts), 1))(*luts)
         c_settings = backend.LmnSettings(mask, len(luts), keep)
+    return c_settings, keep
+
+
+def verify(proof: LuminairProof, settings: Optional[CircuitSettings] = None,
+           protocol_variant: int = backend.VARIANT_KAT, library=None) -> None:
+    """Drop-in for the reference's `verify(proof, settings)` (crates/verifiers/rust/src/verifier.rs:21-143):
+    host-side check of a proof's bincode bytes; raises LuminairError(StwoVerifierError | InvalidLogUp | ...)."""
+    lib = library or backend.default_library()
+    c_settings, keep = _verifier_settings(settings)
     try:
         lib.verify(proof.to_bincode() if isinstance(proof, LuminairProof) else bytes(proof), protocol_variant,
                    settings=c_settings)
+    except backend.LuminairBackendError as e:
+        raise LuminairError(_ERR_VARIANT.get(e.code, "Internal"), str(e), e.code) from e
+
+
+def verify_many(proofs, settings: Optional[CircuitSettings] = None, protocol_variant: int = backend.VARIANT_KAT,
+                library=None, ctx=None):
+    """`verify` for many proofs of one circuit in one call (`lmn_verify_many`): the transcript replay per proof on the
+    host, the decommitments and the FRI checks of all proofs on the GPU.  Returns one `backend.VerifyResult` per proof
+    (`ok`, `code`, `checks_failed`, `stage`), whatever the verdicts; raises only if the call itself fails."""
+    lib = library or backend.default_library()
+    c_settings, keep = _verifier_settings(settings)
+    raw = [p.to_bincode() if isinstance(p, LuminairProof) else bytes(p) for p in proofs]
+    try:
+        return lib.verify_many(raw, protocol_variant, settings=c_settings, ctx=ctx)
     except backend.LuminairBackendError as e:
         raise LuminairError(_ERR_VARIANT.get(e.code, "Internal"), str(e), e.code) from e
