@@ -1001,7 +1001,7 @@ int lmn_col_fri_close_keep(lmn_ctx* ctx, const lmn_col* last_layer, const uint8_
  * by a one-workgroup offset step), ONE fetch launch, one transfer and one wait: MerkleProver::decommit's walk and FRI's
  * pair expansion run on the device, no walk runs on the host, and the host need not know the positions at all.
  * An item is a tree with the handles it was committed from (`cols`, as for lmn_tree_decommit).  Its groups are, for every
- * log size at which the tree has columns, fold_positions(positions, log_domain - log size): without flags its three
+ * log size at which the tree has columns, fold_positions(positions, log_domain - log size) (csrc/openings.h): without flags its three
  * Merkle outputs equal lmn_tree_decommit's for those groups.  LMN_OPEN_FRI_PAIRS (a FRI layer's tree: 4 coordinate
  * columns at each of its sizes) first expands every group to sibling pairs - position p contributes 2 floor(p / 2) and
  * 2 floor(p / 2) + 1, FriProver::decommit's rule at fold step 1 - and fri_witness receives 4 words (a, b, c, d) per

@@ -44,6 +44,23 @@ namespace lmn {
 extern const char prepared_tag;
 // the shared object behind a caller's handle; refuses a null handle and one made by another library
 std::shared_ptr<const Prepared> prepared_ref(const lmn_prepared* p);
+// The exception in flight as an entry point reports it: its LMN_ERR_* code and its text.  (Inside a catch block only;
+// what is no std::exception passes through.)
+inline int current_exception_code(std::string& text) {
+  try {
+    throw;
+  } catch (const LmnError& e) {
+    text = e.what();
+    const int c = e.code;
+    return (c == -100 || (c <= -1 && c >= -10)) ? c : LMN_ERR_INTERNAL;
+  } catch (const std::bad_alloc&) {
+    text = "host allocation failed";
+    return LMN_ERR_OUT_OF_MEMORY;
+  } catch (const std::exception& e) {
+    text = e.what();
+    return LMN_ERR_INTERNAL;
+  }
+}
 template <typename F>
 int capi_guard(lmn_ctx* ctx, F&& f) {
   std::unique_lock<std::recursive_mutex> lock;
@@ -51,16 +68,9 @@ int capi_guard(lmn_ctx* ctx, F&& f) {
   try {
     f();
     return LMN_OK;
-  } catch (const LmnError& e) {
-    if (ctx) ctx->last_error = e.what();
-    int c = e.code;
-    return (c == -100 || (c <= -1 && c >= -10)) ? c : LMN_ERR_INTERNAL;
-  } catch (const std::bad_alloc&) {
-    if (ctx) ctx->last_error = "host allocation failed";
-    return LMN_ERR_OUT_OF_MEMORY;
-  } catch (const std::exception& e) {
-    if (ctx) ctx->last_error = e.what();
-    return LMN_ERR_INTERNAL;
+  } catch (...) {
+    std::string unheard;
+    return current_exception_code(ctx ? ctx->last_error : unheard);
   }
 }
 }  // namespace lmn

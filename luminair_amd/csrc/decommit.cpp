@@ -15,12 +15,10 @@ static Ref col_ref(const ColRef& c, uint64_t row, int g) {
 }
 static Ref node_ref(const DevMerkle& m, int layer, uint64_t node, std::vector<MerkleRecompute>& jobs) {
   if (!m.layers[layer]) {   // a level its launch kept in registers (MerkleCut)
-    for (auto& c : m.cuts)
-      if (layer <= c.start_log && layer > c.start_log - c.depth) {
-        jobs.push_back({c.prev, c.sg, c.ncols, 1u << c.start_log, c.below, c.below_ncols, (uint32_t)node, c.start_log - layer, 0u});
-        return {nullptr, 8, -1, (int)jobs.size() - 1};
-      }
-    throw LmnError(LMN_ERR_INTERNAL, "merkle: layer without storage");
+    const MerkleCut* c = cut_holding(m.cuts, layer);
+    if (!c) throw LmnError(LMN_ERR_INTERNAL, "merkle: layer without storage");
+    jobs.push_back({c->prev, c->sg, c->ncols, 1u << c->start_log, c->below, c->below_ncols, (uint32_t)node, c->start_log - layer, 0u});
+    return {nullptr, 8, -1, (int)jobs.size() - 1};
   }
   if (m.g == 0 || layer <= m.g) return {m.layers[layer] + node * 8, 8, -1};
   const int sh = layer - m.g;
@@ -29,58 +27,33 @@ static Ref node_ref(const DevMerkle& m, int layer, uint64_t node, std::vector<Me
 
 void release_host_scratch(void* p) { delete static_cast<HostScratch*>(p); }
 
-// MerkleProver::decommit: emits device references in output order
+// MerkleProver::decommit (openings.h walk_openings): emits device references in output order
 void plan_merkle_decommit(const DevMerkle& m, const std::vector<ColRef>& cols_sorted, int g,
                                  const std::map<int, std::vector<uint32_t>>& queries, std::vector<Ref>& queried,
                                  std::vector<Ref>& hash_wit, std::vector<Ref>& col_wit, std::vector<MerkleRecompute>& jobs) {
-  size_t pos = 0;
-  std::vector<uint32_t> last, total;
-  last.reserve(16);
-  total.reserve(16);
-  for (int log = m.max_log; log >= 0; --log) {
-    size_t start = pos;
-    while (pos < cols_sorted.size() && cols_sorted[pos].log == log) ++pos;
-    bool have_prev = log < m.max_log;
-    static const std::vector<uint32_t> kNone;
-    auto it = queries.find(log);
-    const std::vector<uint32_t>& colq = it != queries.end() ? it->second : kNone;
-    size_t pi = 0, ci = 0;
-    total.clear();
-    while (pi < last.size() || ci < colq.size()) {
-      uint32_t node;
-      if (pi < last.size() && ci < colq.size())
-        node = std::min(last[pi] / 2, colq[ci]);
-      else if (pi < last.size())
-        node = last[pi] / 2;
-      else
-        node = colq[ci];
-      if (have_prev) {
-        if (pi < last.size() && last[pi] == 2 * node)
-          ++pi;
-        else
-          hash_wit.push_back(node_ref(m, log + 1, 2ull * node, jobs));
-        if (pi < last.size() && last[pi] == 2 * node + 1)
-          ++pi;
-        else
-          hash_wit.push_back(node_ref(m, log + 1, 2ull * node + 1, jobs));
-      }
-      bool is_q = ci < colq.size() && colq[ci] == node;
-      if (is_q) ++ci;
-      for (size_t c = start; c < pos; ++c) (is_q ? queried : col_wit).push_back(col_ref(cols_sorted[c], node, g));
-      total.push_back(node);
+  if (m.max_log > (int)OPEN_MAX_LOG) throw LmnError(LMN_ERR_INTERNAL, "merkle: a tree larger than the planner takes");
+  uint32_t ncols_of_log[OPEN_MAX_LOG + 1] = {};
+  Positions queries_of_log[OPEN_MAX_LOG + 1];
+  for (const ColRef& c : cols_sorted) ++ncols_of_log[c.log];
+  for (auto& q : queries)
+    if (q.first >= 0 && q.first <= m.max_log) queries_of_log[q.first] = {q.second.data(), q.second.size()};
+  struct Plan {
+    const DevMerkle& m;
+    const std::vector<ColRef>& cols;
+    int g;
+    std::vector<Ref> &queried, &hash_wit, &col_wit;
+    std::vector<MerkleRecompute>& jobs;
+    bool child(int layer, uint32_t child, bool opened) {
+      if (!opened) hash_wit.push_back(node_ref(m, layer, child, jobs));
+      return true;
     }
-    last.swap(total);
-  }
-}
-
-std::vector<uint32_t> fold_positions(const std::vector<uint32_t>& p, int n) {
-  std::vector<uint32_t> out;
-  out.reserve(p.size());
-  for (auto v : p) {
-    uint32_t q = v >> n;
-    if (out.empty() || out.back() != q) out.push_back(q);
-  }
-  return out;
+    bool column(uint32_t col, uint32_t node, bool is_query) {
+      (is_query ? queried : col_wit).push_back(col_ref(cols[col], node, g));
+      return true;
+    }
+    bool node(int, uint32_t) { return true; }
+  };
+  walk_openings(m.max_log, ncols_of_log, queries_of_log, Plan{m, cols_sorted, g, queried, hash_wit, col_wit, jobs});
 }
 
 // compute_decommitment_positions_and_witness_evals with fold_step = 1; `cols` = the 4 coordinate columns
@@ -88,17 +61,12 @@ void plan_fri_witness(const ColRef (&cols)[4], int g, const std::vector<uint32_t
                              std::vector<uint32_t>& dec_pos, std::vector<Ref>& wit) {
   // (planning runs between the proof's last two waits: no allocation per pair)
   dec_pos.reserve(dec_pos.size() + 2 * qpos.size());
-  size_t i = 0;
-  while (i < qpos.size()) {
-    const uint32_t start = (qpos[i] >> 1) << 1;
-    bool have[2] = {false, false};   // which of the pair's two positions are queried (sorted, distinct positions)
-    while (i < qpos.size() && ((qpos[i] >> 1) << 1) == start) have[qpos[i++] - start] = true;
-    for (uint32_t pos = start; pos < start + 2; ++pos) {
-      dec_pos.push_back(pos);
-      if (have[pos - start]) continue;
+  for_each_pair_member(qpos, [&](uint32_t pos, bool is_query) {
+    dec_pos.push_back(pos);
+    if (!is_query)
       for (int k = 0; k < 4; ++k) wit.push_back(col_ref(cols[k], pos, g));
-    }
-  }
+    return true;
+  });
 }
 
 }  // namespace lmn

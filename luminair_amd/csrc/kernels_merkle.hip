@@ -1211,8 +1211,8 @@ void launch_col_gather(const uint32_t* cols, uint32_t log_size, uint32_t ncols, 
 // =============================================================================================
 // Openings planned on the device (kernels.h launch_open_plan / launch_open_offsets / launch_open_fetch).
 //
-// k_open_plan restates plan_opening (level2.cpp) / plan_merkle_decommit and plan_fri_witness (decommit.cpp) for one item
-// per workgroup.  Every set it handles - the positions, a size's group, a layer's node set - is a sorted array of
+// k_open_plan restates the host's opening rules (openings.h: walk_openings, for_each_pair_member) for one item per
+// workgroup.  Every set it handles - the positions, a size's group, a layer's node set - is a sorted array of
 // distinct values in LDS, so the sequential merge becomes counting: an element's place in a merged or compacted array is
 // the number of elements in front of it, found by a block-wide exclusive scan over flags (open_scan) or a binary search
 // (open_lb).  Per layer, from the leaves up:

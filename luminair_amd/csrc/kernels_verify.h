@@ -1,7 +1,7 @@
 // Kernels of lmn_verify_many (kernels.h "proofs verified in batches"); included by kernels_merkle.hip inside namespace lmn.
 //
-// The verifier's back half (verifier.cpp verify_back) restated for a device: what the host walks with std::map and
-// std::set is, for a proof that passed the front, a function of the sorted distinct query positions alone -
+// The verifier's back half (verifier.cpp verify_back, a visitor of openings.h's walk) restated for a device: what the host
+// walks is, for a proof that passed the front, a function of the sorted distinct query positions alone -
 //   the positions of a size        = the distinct values of position >> (top - log)
 //   a FRI layer's decommitment set = those, pair-expanded: 2k and 2k + 1 for every distinct k = position >> (top - log + 1)
 //   a tree level's node set        = the parents of the level below merged with the level's own queries
@@ -94,7 +94,7 @@ LMN_D uint32_t vm_or(uint32_t v, uint32_t* s_bad) {
   return r;
 }
 
-// One FRI layer at its queried positions fp[0 .. np) (verifier.cpp rebuild_pairs + the fold): the sibling pairs from the
+// One FRI layer at its queried positions fp[0 .. np) (openings.h for_each_pair_member + the fold): the sibling pairs from the
 // known values and the witness, both members' coordinate words to the layer's leaf list, the pairs' folds to out[0 ..
 // return).  wi / leaf_at: the places reached in the witness (QM31s) and the leaf list (words), advanced.
 LMN_D uint32_t vm_layer_pairs(const uint32_t* fp, uint32_t np, const QM31* known, const uint32_t* wit, uint32_t wit_len,
@@ -276,7 +276,7 @@ LMN_KERNEL k_verify_values(uint32_t* blk, uint32_t layout_off, uint32_t proofs_o
   if (lane == 0u) blk[d.verdict] = VM_DONE | all;
 }
 
-// One workgroup per (proof, tree): verifier.cpp merkle_verify from the deepest level to the root.
+// One workgroup per (proof, tree): openings.h walk_openings, as verifier.cpp replays it, from the deepest level to the root.
 LMN_KERNEL k_verify_trees(uint32_t* blk, uint32_t layout_off, uint32_t proofs_off, uint32_t n_proofs, uint32_t n_trees) {
   LMN_SHARED uint32_t s_pos[VM_MAX_POS], s_fp[VM_MAX_POS];
   LMN_SHARED uint32_t s_set[2][VM_MAX_NODES];        // the previous and the current level's nodes, ascending

@@ -242,48 +242,53 @@ constexpr size_t OPENING_MAX_BYTES = 12u << 20;   // of the plan and of the resu
 
 static std::string u32s(uint64_t v) { return std::to_string(v); }
 
-// MerkleProver::decommit's walk (stwo prover/vcs/prover.rs; the rule oracle/merkle.py restates): layer by layer from the
-// leaves up, the nodes to open are the parents of the layer below's nodes merged with this layer's own queries; a child
-// that is not itself opened goes to the hash witness, the layer's column values at a node to the queried values if the
-// node is a query and to the column witness otherwise.
+// MerkleProver::decommit's walk (openings.h walk_openings) as entries of the launch's plan.  The pointer table: layers
+// 0 .. max_log, then the columns in tree order.
+namespace {
 struct OpeningPlan {
   std::vector<DecommitEntry> hashes, values, witness;
-};
-static OpeningPlan plan_opening(int max_log, const std::vector<uint32_t>& ncols_of_log,
-                                const std::vector<const uint32_t*>& queries_of_log, const std::vector<uint32_t>& count_of_log) {
-  OpeningPlan pl;
-  const uint32_t col_src0 = (uint32_t)max_log + 1;   // the pointer table: layers 0 .. max_log, then the columns in tree order
-  uint32_t first_col = 0;                            // tree order = size descending: the columns of a layer are a run
-  std::vector<uint32_t> prev, cur;
-  for (int log = max_log; log >= 0; --log) {
-    const uint32_t ncols = ncols_of_log[log];
-    const uint32_t* q = queries_of_log[log];
-    const size_t nq = count_of_log[log];
-    const bool have_prev = log < max_log;
-    size_t pi = 0, ci = 0;
-    cur.clear();
-    while (pi < prev.size() || ci < nq) {
-      uint32_t node = 0xFFFFFFFFu;
-      if (pi < prev.size()) node = prev[pi] >> 1;
-      if (ci < nq) node = std::min(node, q[ci]);
-      if (have_prev) {
-        for (uint32_t child = 2 * node; child <= 2 * node + 1; ++child) {
-          if (pi < prev.size() && prev[pi] == child)
-            ++pi;
-          else
-            pl.hashes.push_back({(uint32_t)log + 1, child});
-        }
-      }
-      const bool queried = ci < nq && q[ci] == node;
-      if (queried) ++ci;
-      std::vector<DecommitEntry>& dst = queried ? pl.values : pl.witness;
-      for (uint32_t c = 0; c < ncols; ++c) dst.push_back({col_src0 + first_col + c, node});
-      cur.push_back(node);
-    }
-    first_col += ncols;
-    prev.swap(cur);
+  uint32_t col_src0;
+  bool child(int layer, uint32_t child, bool opened) {
+    if (!opened) hashes.push_back({(uint32_t)layer, child});
+    return true;
   }
+  bool column(uint32_t col, uint32_t node, bool queried) {
+    (queried ? values : witness).push_back({col_src0 + col, node});
+    return true;
+  }
+  bool node(int, uint32_t) { return true; }
+};
+}  // namespace
+static OpeningPlan plan_opening(int max_log, const std::vector<uint32_t>& ncols_of_log, const std::vector<Positions>& queries_of_log) {
+  OpeningPlan pl{{}, {}, {}, (uint32_t)max_log + 1};
+  walk_openings(max_log, ncols_of_log.data(), queries_of_log.data(), pl);
   return pl;
+}
+
+// The handles of an opening call must be the columns the tree was committed from: as many at each size.  -> the columns
+// in tree order.  `A` names the argument in the refusals; also(log, n): the caller's own rule for a size's n columns.
+template <class Refuse, class Also>
+static std::vector<ColRef> columns_as_committed(const lmn_tree* t, const lmn_col* const* cols, uint32_t n_cols, const std::string& A,
+                                                Refuse&& refuse, Also&& also) {
+  const int max_log = t->max_log;
+  std::vector<ColRef> sorted;
+  std::vector<uint32_t> have(max_log + 1, 0u);
+  for (uint32_t k = 0; k < n_cols; ++k) {
+    const lmn_col* c = cols[k];
+    if (!c) refuse(A + "[" + u32s(k) + "] is null");
+    if ((int)c->log_size > max_log)
+      refuse(A + "[" + u32s(k) + "] has log size " + u32s(c->log_size) + ", the tree's is " + u32s(max_log));
+    for (uint32_t j = 0; j < c->ncols; ++j) sorted.push_back({c->d + ((uint64_t)j << c->log_size), (int)c->log_size, false});
+    have[c->log_size] += c->ncols;
+  }
+  for (int log = max_log; log >= 0; --log) {
+    if (have[log] != t->ncols_of_log[log])
+      refuse(A + " holds " + u32s(have[log]) + " columns of log size " + u32s(log) + ", the tree was committed from " +
+             u32s(t->ncols_of_log[log]));
+    also(log, have[log]);
+  }
+  std::stable_sort(sorted.begin(), sorted.end(), [](auto& a, auto& b) { return a.log > b.log; });
+  return sorted;
 }
 
 static uint32_t* malloc_words(size_t n) {
@@ -300,26 +305,10 @@ void Context::tree_decommit(const lmn_tree* t, const lmn_col* const* cols, uint3
   if (n_cols && !cols) refuse("cols is null with n_cols = " + u32s(n_cols));
   if (n_groups && !query_logs) refuse("query_logs is null with n_groups = " + u32s(n_groups));
   if (n_groups && !query_counts) refuse("query_counts is null with n_groups = " + u32s(n_groups));
-  // the columns: same sizes, in tree order, as at commit time
   const int max_log = t->max_log;
-  std::vector<ColRef> sorted;
-  std::vector<uint32_t> have(max_log + 1, 0u);
-  for (uint32_t k = 0; k < n_cols; ++k) {
-    const lmn_col* c = cols[k];
-    if (!c) refuse("cols[" + u32s(k) + "] is null");
-    if ((int)c->log_size > max_log)
-      refuse("cols[" + u32s(k) + "] has log size " + u32s(c->log_size) + ", the tree's is " + u32s(max_log));
-    for (uint32_t j = 0; j < c->ncols; ++j) sorted.push_back({c->d + ((uint64_t)j << c->log_size), (int)c->log_size, false});
-    have[c->log_size] += c->ncols;
-  }
-  for (int log = max_log; log >= 0; --log)
-    if (have[log] != t->ncols_of_log[log])
-      refuse("cols holds " + u32s(have[log]) + " columns of log size " + u32s(log) + ", the tree was committed from " +
-             u32s(t->ncols_of_log[log]));
-  std::stable_sort(sorted.begin(), sorted.end(), [](auto& a, auto& b) { return a.log > b.log; });
+  const std::vector<ColRef> sorted = columns_as_committed(t, cols, n_cols, "cols", refuse, [](int, uint32_t) {});
   // the queries
-  std::vector<const uint32_t*> queries_of_log(max_log + 1, nullptr);
-  std::vector<uint32_t> count_of_log(max_log + 1, 0u);
+  std::vector<Positions> queries_of_log(max_log + 1);
   std::vector<bool> seen(max_log + 1, false);
   uint64_t at = 0;
   for (uint32_t g = 0; g < n_groups; ++g) {
@@ -336,11 +325,10 @@ void Context::tree_decommit(const lmn_tree* t, const lmn_col* const* cols, uint3
         refuse("queries: group " + u32s(g) + " is not strictly ascending at index " + u32s(i) + " (" + u32s(q[i - 1]) +
                " then " + u32s(q[i]) + ")");
     }
-    queries_of_log[log] = q;
-    count_of_log[log] = n;
+    queries_of_log[log] = {q, n};
     at += n;
   }
-  const OpeningPlan pl = plan_opening(max_log, t->ncols_of_log, queries_of_log, count_of_log);
+  const OpeningPlan pl = plan_opening(max_log, t->ncols_of_log, queries_of_log);
   const size_t nh = pl.hashes.size(), nv = pl.values.size(), nw = pl.witness.size();
   if (nh + nv + nw == 0) return;
   const size_t n_ptrs = (size_t)max_log + 1 + sorted.size();
@@ -459,21 +447,54 @@ void Context::positions_free(lmn_positions* p) {
   delete p;
 }
 
-// What an item's plan and output can hold at most, from the NUMBER of positions alone (k_open_plan checks both): with m
+// (prover_internal.h)  What an item's plan and output can hold at most follows from the NUMBER of positions alone (k_open_plan checks both): with m
 // nodes per layer at most - the positions, doubled by the pair expansion - a layer of 2^log nodes opens min(2^log, m) of
 // them, each with its column values and at most both children's hashes; a size's pairs have at most as many members
 // that are no positions as there are pairs.
-OpenBound open_bound(int max_log, const std::vector<uint32_t>& ncols_of_log, uint32_t n_positions, bool pairs) {
-  OpenBound b;
-  const uint64_t m = pairs ? 2ull * n_positions : n_positions;
-  for (int log = max_log; log >= 0; --log) {
-    const uint64_t nodes = std::min<uint64_t>(1ull << log, m);
-    const uint64_t hashes = log < max_log ? 2 * nodes : 0;
-    const uint64_t fri = pairs && ncols_of_log[log] ? 4 * std::min<uint64_t>(std::max<uint64_t>(1ull << log, 2) / 2, n_positions) : 0;
-    b.entries += nodes * ncols_of_log[log] + hashes + fri;
-    b.words += nodes * ncols_of_log[log] + 8 * hashes + fri;
+bool append_open_item(int max_log, uint32_t* const* layers, const std::vector<uint32_t>& ncols_of_log,
+                      const std::vector<ColRef>& cols_sorted, const std::vector<MerkleCut>* cuts, uint32_t n_positions,
+                      uint32_t flags, std::vector<const uint32_t*>& ptrs, std::vector<MerkleRecompute>& recompute,
+                      OpenItemDesc& d, OpenTotals& tot) {
+  d = OpenItemDesc{};
+  memset(d.cut_of_layer, (int)OPEN_STORED, sizeof d.cut_of_layer);
+  d.ent_off = (uint32_t)tot.entries;
+  d.job_off = (uint32_t)tot.jobs;
+  if (max_log < 0) {
+    d.flags = OPEN_EMPTY;
+    return true;
   }
-  return b;
+  d.max_log = (uint32_t)max_log;
+  d.flags = flags;
+  const bool pairs = (flags & OPEN_FRI_PAIRS) != 0;
+  const uint64_t m = pairs ? 2ull * n_positions : n_positions;
+  uint64_t entries = 0, words = 0, job_cap = 0;
+  d.layer_src0 = (uint32_t)ptrs.size();
+  for (int l = 0; l <= max_log; ++l) {
+    const uint64_t nodes = std::min<uint64_t>(1ull << l, m);
+    const uint64_t hashes = l < max_log ? 2 * nodes : 0;
+    const uint64_t fri = pairs && ncols_of_log[l] ? 4 * std::min<uint64_t>(std::max<uint64_t>(1ull << l, 2) / 2, n_positions) : 0;
+    entries += nodes * ncols_of_log[l] + hashes + fri;
+    words += nodes * ncols_of_log[l] + 8 * hashes + fri;
+    d.ncols[l] = ncols_of_log[l];
+    ptrs.push_back(layers[l]);
+    if (layers[l] || l == 0) continue;   // (an opening reads the children's hashes: layers 1 .. max_log)
+    const MerkleCut* cut = cuts ? cut_holding(*cuts, l) : nullptr;
+    if (!cut) throw LmnError(LMN_ERR_INTERNAL, "merkle: layer without storage");
+    if (recompute.size() >= OPEN_STORED) return false;
+    d.cut_of_layer[l] = (uint8_t)recompute.size();
+    recompute.push_back({cut->prev, cut->sg, cut->ncols, 1u << cut->start_log, cut->below, cut->below_ncols, 0u, 0, 0u});
+    job_cap += 2 * std::min<uint64_t>(1ull << (l - 1), m);
+  }
+  d.col_src0 = (uint32_t)ptrs.size();
+  for (auto& c : cols_sorted) ptrs.push_back(c.ptr);
+  d.ent_cap = (uint32_t)std::min<uint64_t>(entries, 0xffffffffu);
+  d.job_cap = (uint32_t)job_cap;
+  tot.entries += entries;
+  tot.jobs += job_cap;
+  tot.words += words;
+  tot.max_cap = std::max(tot.max_cap, entries);
+  tot.max_job_cap = std::max(tot.max_job_cap, job_cap);
+  return true;
 }
 
 void Context::open_queries(const lmn_positions* p, const lmn_open_item* items, uint32_t n_items, lmn_opening* out) {
@@ -484,11 +505,11 @@ void Context::open_queries(const lmn_positions* p, const lmn_open_item* items, u
   if (n_items > OPEN_MAX_ITEMS) refuse("n_items is " + u32s(n_items) + ", at most " + u32s(OPEN_MAX_ITEMS));
   if (n_items && !items) refuse("items is null with n_items = " + u32s(n_items));
   if (n_items && !out) refuse("out is null with n_items = " + u32s(n_items));
-  // the items: their columns as at commit time (tree_decommit's rule), the pointer table, the bounds
+  // the items: their columns as at commit time, the pointer table, the bounds
   std::vector<const uint32_t*> ptrs;
   std::vector<OpenItemDesc> descs(n_items);
-  uint64_t total_entries = 0, total_words = 0, max_cap = 0;
-  std::vector<ColRef> sorted;
+  std::vector<MerkleRecompute> none;   // a level-2 tree keeps every layer
+  OpenTotals tot;
   for (uint32_t k = 0; k < n_items; ++k) {
     const lmn_open_item& it = items[k];
     const std::string I = "items[" + u32s(k) + "]";
@@ -496,55 +517,25 @@ void Context::open_queries(const lmn_positions* p, const lmn_open_item* items, u
     if (it.n_cols && !it.cols) refuse(I + ".cols is null with n_cols = " + u32s(it.n_cols));
     if (it.flags & ~LMN_OPEN_FRI_PAIRS) refuse(I + ".flags = " + u32s(it.flags) + " holds an unknown flag");
     const lmn_tree* t = it.tree;
-    const int max_log = t->max_log;
-    if (max_log > (int)p->log_domain)
-      refuse(I + ".tree has log size " + u32s(max_log) + ", larger than the positions' log_domain " + u32s(p->log_domain));
-    sorted.clear();
-    std::vector<uint32_t> have(max_log + 1, 0u);
-    for (uint32_t c = 0; c < it.n_cols; ++c) {
-      const lmn_col* col = it.cols[c];
-      if (!col) refuse(I + ".cols[" + u32s(c) + "] is null");
-      if ((int)col->log_size > max_log)
-        refuse(I + ".cols[" + u32s(c) + "] has log size " + u32s(col->log_size) + ", the tree's is " + u32s(max_log));
-      for (uint32_t j = 0; j < col->ncols; ++j) sorted.push_back({col->d + ((uint64_t)j << col->log_size), (int)col->log_size, false});
-      have[col->log_size] += col->ncols;
-    }
+    if (t->max_log > (int)p->log_domain)
+      refuse(I + ".tree has log size " + u32s(t->max_log) + ", larger than the positions' log_domain " + u32s(p->log_domain));
     const bool pairs = (it.flags & LMN_OPEN_FRI_PAIRS) != 0;
-    for (int log = max_log; log >= 0; --log) {
-      if (have[log] != t->ncols_of_log[log])
-        refuse(I + ".cols holds " + u32s(have[log]) + " columns of log size " + u32s(log) + ", the tree was committed from " +
-               u32s(t->ncols_of_log[log]));
-      if (pairs && have[log] != 0 && (have[log] != 4 || log == 0))
+    const std::vector<ColRef> sorted = columns_as_committed(t, it.cols, it.n_cols, I + ".cols", refuse, [&](int log, uint32_t n) {
+      if (pairs && n != 0 && (n != 4 || log == 0))
         refuse(I + ".flags: LMN_OPEN_FRI_PAIRS needs exactly 4 columns at each of the tree's sizes and none of log size 0; it has " +
-               u32s(have[log]) + " of log size " + u32s(log));
-    }
-    std::stable_sort(sorted.begin(), sorted.end(), [](auto& a, auto& b) { return a.log > b.log; });
-    OpenItemDesc& d = descs[k];
-    d = OpenItemDesc{};
-    d.max_log = (uint32_t)max_log;
-    d.flags = it.flags;
-    d.layer_src0 = (uint32_t)ptrs.size();
-    for (int l = 0; l <= max_log; ++l) ptrs.push_back(t->layers[l]);
-    d.col_src0 = (uint32_t)ptrs.size();
-    for (auto& c : sorted) ptrs.push_back(c.ptr);
-    for (int l = 0; l <= max_log; ++l) d.ncols[l] = t->ncols_of_log[l];
-    memset(d.cut_of_layer, (int)OPEN_STORED, sizeof d.cut_of_layer);   // a level-2 tree keeps every layer
-    const OpenBound b = open_bound(max_log, t->ncols_of_log, p->n, pairs);
-    d.ent_off = (uint32_t)total_entries;
-    d.ent_cap = (uint32_t)std::min<uint64_t>(b.entries, 0xffffffffu);
-    total_entries += b.entries;
-    total_words += b.words;
-    max_cap = std::max(max_cap, b.entries);
-    if (total_words * 4 > OPENING_MAX_BYTES || total_entries * sizeof(OpenEntry) > 4 * OPENING_MAX_BYTES)
-      refuse("items: the upper bound of the opening (" + u32s(total_words * 4) + " bytes up to " + I + ", for " + u32s(p->n) +
+               u32s(n) + " of log size " + u32s(log));
+    });
+    append_open_item(t->max_log, t->layers.data(), t->ncols_of_log, sorted, nullptr, p->n, it.flags, ptrs, none, descs[k], tot);
+    if (tot.words * 4 > OPENING_MAX_BYTES || tot.entries * sizeof(OpenEntry) > 4 * OPENING_MAX_BYTES)
+      refuse("items: the upper bound of the opening (" + u32s(tot.words * 4) + " bytes up to " + I + ", for " + u32s(p->n) +
              " positions) exceeds the " + u32s(OPENING_MAX_BYTES) + " bytes one call carries");
   }
   if (n_items == 0 || p->n == 0) return;   // (out is zeroed by the caller)
   const size_t head_bytes = sizeof(OpenHeader) + n_items * sizeof(OpenItemHeader);
   const size_t table_bytes = ptrs.size() * sizeof(void*) + n_items * sizeof(OpenItemDesc);
-  const size_t out_bytes = head_bytes + total_words * 4;
+  const size_t out_bytes = head_bytes + tot.words * 4;
   set_device();
-  arena_.reserve(std::max<size_t>(8u << 20, table_bytes + out_bytes + total_entries * sizeof(OpenEntry) + (1u << 20)));
+  arena_.reserve(std::max<size_t>(8u << 20, table_bytes + out_bytes + tot.entries * sizeof(OpenEntry) + (1u << 20)));
   begin_op();
   // pointer table and descriptors: ONE transfer; nothing in them depends on the positions
   char* h_tab = (char*)pin_alloc(table_bytes);
@@ -557,11 +548,11 @@ void Context::open_queries(const lmn_positions* p, const lmn_open_item* items, u
   char* d_out = (char*)arena_.alloc_bytes(out_bytes);   // header | item headers | the lists
   OpenHeader* d_head = (OpenHeader*)d_out;
   OpenItemHeader* d_heads = (OpenItemHeader*)(d_out + sizeof(OpenHeader));
-  OpenEntry* d_ent = (OpenEntry*)arena_.alloc_bytes(std::max<size_t>(total_entries, 1) * sizeof(OpenEntry));
+  OpenEntry* d_ent = (OpenEntry*)arena_.alloc_bytes(std::max<size_t>(tot.entries, 1) * sizeof(OpenEntry));
   // (the wrappers count the launches they make: open_counters_)
   launch_open_plan(p->d, p->d + 1, nullptr, p->log_domain, d_items, n_items, d_heads, d_ent, d_ent, stream_, &open_counters_[0]);
-  launch_open_offsets(p->d, d_head, d_heads, n_items, (uint32_t)total_words, stream_);
-  launch_open_fetch(d_ptrs, (uint32_t)ptrs.size(), d_items, n_items, (uint32_t)max_cap, d_head, d_heads, d_ent,
+  launch_open_offsets(p->d, d_head, d_heads, n_items, (uint32_t)tot.words, stream_);
+  launch_open_fetch(d_ptrs, (uint32_t)ptrs.size(), d_items, n_items, (uint32_t)tot.max_cap, d_head, d_heads, d_ent,
                     (uint32_t*)(d_out + head_bytes), stream_, &open_counters_[1]);
   const char* got = (const char*)stage_download(d_out, out_bytes);
   lmn_sync(stream_);
@@ -584,7 +575,7 @@ void Context::open_queries(const lmn_positions* p, const lmn_open_item* items, u
       const OpenItemHeader& h = heads[k];
       uint64_t end = 0;
       for (int l = 0; l < 4; ++l) end = std::max<uint64_t>(end, (uint64_t)h.base[l] + (uint64_t)h.count[l] * (l == OPEN_LIST_HASH ? 8 : 1));
-      if (end > total_words) throw LmnError(LMN_ERR_INTERNAL, "open_queries: the device plan's counts exceed the result block");
+      if (end > tot.words) throw LmnError(LMN_ERR_INTERNAL, "open_queries: the device plan's counts exceed the result block");
       lmn_opening& o = res[k];
       o.n_fri_words = h.count[OPEN_LIST_FRI];
       o.n_values = h.count[OPEN_LIST_QUERIED];

@@ -172,17 +172,6 @@ uint64_t Context::grind(const Channel& ch, uint32_t pow_bits) {
   return ch.grind(pow_bits);
 }
 
-std::vector<uint32_t> draw_query_positions(Channel& channel, uint32_t n_queries, uint32_t log_domain) {
-  std::set<uint32_t> qs;
-  uint64_t cnt = 0;
-  const uint32_t mask = (uint32_t)((1ull << log_domain) - 1u);
-  while (cnt < n_queries) {
-    Hash32 r = channel.draw_random_words();
-    for (int i = 0; i < 8 && cnt < n_queries; ++i, ++cnt) qs.insert(r.w[i] & mask);
-  }
-  return std::vector<uint32_t>(qs.begin(), qs.end());
-}
-
 void Context::run_queries(ProofRun& r) {
   LMN_RUN_ALIASES(r);
   // ---- proof of work + queries
@@ -232,68 +221,31 @@ void Context::enqueue_device_decommit(ProofRun& r) {
   std::vector<const uint32_t*> ptrs;
   std::vector<OpenItemDesc> descs(n_items);
   std::vector<MerkleRecompute> cuts;
-  uint64_t total_entries = 0, total_jobs = 0, total_words = 0, max_cap = 0, max_job_cap = 0;
+  OpenTotals tot;
   for (uint32_t k = 0; k < n_items; ++k) {
     const DevMerkle& m = *its[k].m;
-    OpenItemDesc& d = descs[k];
-    d = OpenItemDesc{};
-    memset(d.cut_of_layer, (int)OPEN_STORED, sizeof d.cut_of_layer);
-    d.ent_off = (uint32_t)total_entries;
-    d.job_off = (uint32_t)total_jobs;
-    if (m.max_log < 0) {
-      d.flags = OPEN_EMPTY;
-      continue;
-    }
     if (m.max_log > (int)OPEN_MAX_LOG) throw LmnError(LMN_ERR_INTERNAL, "device decommit: a tree larger than the planner takes");
-    d.max_log = (uint32_t)m.max_log;
-    d.flags = its[k].pairs ? OPEN_FRI_PAIRS : 0u;
     std::vector<uint32_t> ncols_of_log(m.max_log + 1, 0u);
     for (auto& c : its[k].cols) {
       if (c.log < 0 || c.log > m.max_log) throw LmnError(LMN_ERR_INTERNAL, "device decommit: a column larger than its tree");
       ++ncols_of_log[c.log];
     }
-    d.layer_src0 = (uint32_t)ptrs.size();
-    const uint64_t mm = its[k].pairs ? 2ull * nq : nq;
-    uint64_t job_cap = 0;
-    for (int l = 0; l <= m.max_log; ++l) {
-      d.ncols[l] = ncols_of_log[l];
-      ptrs.push_back(m.layers[l]);
-      if (m.layers[l] || l == 0) continue;   // (an opening reads the children's hashes: layers 1 .. max_log)
-      const MerkleCut* cut = nullptr;   // node_ref's rule (decommit.cpp)
-      for (auto& c : m.cuts)
-        if (l <= c.start_log && l > c.start_log - c.depth) {
-          cut = &c;
-          break;
-        }
-      if (!cut) throw LmnError(LMN_ERR_INTERNAL, "merkle: layer without storage");
-      if (cuts.size() >= OPEN_STORED) return;   // (the host plans)
-      d.cut_of_layer[l] = (uint8_t)cuts.size();
-      cuts.push_back({cut->prev, cut->sg, cut->ncols, 1u << cut->start_log, cut->below, cut->below_ncols, 0u, 0, 0u});
-      if (l >= 1) job_cap += 2 * std::min<uint64_t>(1ull << (l - 1), mm);
-    }
-    d.col_src0 = (uint32_t)ptrs.size();
-    for (auto& c : its[k].cols) ptrs.push_back(c.ptr);
-    const OpenBound b = open_bound(m.max_log, ncols_of_log, nq, its[k].pairs);
-    d.ent_cap = (uint32_t)b.entries;
-    d.job_cap = (uint32_t)job_cap;
-    total_entries += b.entries;
-    total_jobs += job_cap;
-    total_words += b.words;
-    max_cap = std::max(max_cap, b.entries);
-    max_job_cap = std::max(max_job_cap, job_cap);
+    if (!append_open_item(m.max_log, m.layers.data(), ncols_of_log, its[k].cols, &m.cuts, nq, its[k].pairs ? OPEN_FRI_PAIRS : 0u,
+                          ptrs, cuts, descs[k], tot))
+      return;   // (more cuts than a launch takes: the host plans)
   }
   // What the plan takes beside the proof's own buffers: tables, headers and both entry tables in the arena, the tables'
   // staging, the headers' copy and the lists in page-locked memory.  Where either does not have it, the host plans.
   const size_t head_bytes = sizeof(OpenHeader) + n_items * sizeof(OpenItemHeader);
   const size_t ptr_bytes = ptrs.size() * sizeof(void*), desc_bytes = n_items * sizeof(OpenItemDesc);
   const size_t table_bytes = ptr_bytes + desc_bytes + (cuts.size() + 1) * sizeof(MerkleRecompute);
-  const size_t ent_bytes = (total_entries + 1) * sizeof(OpenEntry), job_bytes = (total_jobs + 1) * sizeof(OpenEntry);
+  const size_t ent_bytes = (tot.entries + 1) * sizeof(OpenEntry), job_bytes = (tot.jobs + 1) * sizeof(OpenEntry);
   // (room is left for what the proof still stages behind this point: the FRI results' download, and - should the grind
   // fall back - the host plan's own entry table and result block, which the same bound covers)
   const size_t slack = 1u << 20;
   const size_t arena_need = table_bytes + head_bytes + ent_bytes + job_bytes + slack;
-  const size_t pin_need = table_bytes + head_bytes + 2 * (total_words * 4) + total_entries * sizeof(GatherEntry) + r.fri.out_bytes + slack;
-  if (total_words > 0xffffffffull || total_entries > 0xffffffffull || arena_need > arena_.capacity() - arena_.used() ||
+  const size_t pin_need = table_bytes + head_bytes + 2 * (tot.words * 4) + tot.entries * sizeof(GatherEntry) + r.fri.out_bytes + slack;
+  if (tot.words > 0xffffffffull || tot.entries > 0xffffffffull || arena_need > arena_.capacity() - arena_.used() ||
       pin_need > pin_cap_ - pin_off_)
     return;
   char* h_tab = (char*)pin_alloc(table_bytes);
@@ -312,20 +264,20 @@ void Context::enqueue_device_decommit(ProofRun& r) {
   char* d_head = (char*)arena_.alloc_bytes(head_bytes);
   OpenHeader* head = (OpenHeader*)d_head;
   OpenItemHeader* heads = (OpenItemHeader*)(d_head + sizeof(OpenHeader));
-  char* block = (char*)result_block(head_bytes + total_words * 4);
+  char* block = (char*)result_block(head_bytes + tot.words * 4);
   uint32_t* out = (uint32_t*)(block + head_bytes);
   const FriCloseHeader* fh = reinterpret_cast<const FriCloseHeader*>(fc.h_block);
   launch_open_plan(&fh->n_positions, fc.h_block + sizeof(FriCloseHeader) / 4, &fh->found, fc.log_query_domain, d_items, n_items,
                    heads, d_ent, d_job, stream_);
-  launch_open_offsets(&fh->n_positions, head, heads, n_items, (uint32_t)total_words, stream_);
-  launch_open_fetch(d_ptrs, (uint32_t)ptrs.size(), d_items, n_items, (uint32_t)max_cap, head, heads, d_ent, out, stream_);
-  launch_open_recompute(d_cuts, (uint32_t)cuts.size(), d_items, n_items, (uint32_t)max_job_cap, head, heads, d_job, out, stream_);
+  launch_open_offsets(&fh->n_positions, head, heads, n_items, (uint32_t)tot.words, stream_);
+  launch_open_fetch(d_ptrs, (uint32_t)ptrs.size(), d_items, n_items, (uint32_t)tot.max_cap, head, heads, d_ent, out, stream_);
+  launch_open_recompute(d_cuts, (uint32_t)cuts.size(), d_items, n_items, (uint32_t)tot.max_job_cap, head, heads, d_job, out, stream_);
   lmn_d2h(block, d_head, head_bytes, stream_);
   r.open.on = true;
   r.open.n_items = n_items;
   r.open.h_block = block;
   r.open.head_bytes = head_bytes;
-  r.open.cap_words = total_words;
+  r.open.cap_words = tot.words;
   ++dev_open_counters_[0];
 }
 

@@ -181,8 +181,6 @@ struct ProofRun {
 std::vector<QM31> interpolate_last_layer(const std::vector<QM31>& last_vals, int last_log);
 // the words one nonce is hashed with: the channel's digest, or its prefixed digest in the prefixed form
 PowWords pow_words_of(const Channel& ch, uint32_t pow_bits, bool& kat);
-// Queries::generate: n_queries positions, 8 per draw_random_words, masked to log_domain bits; ascending and distinct
-std::vector<uint32_t> draw_query_positions(Channel& channel, uint32_t n_queries, uint32_t log_domain);
 
 // the four coordinate columns of a secure column as tree columns
 inline void secure_columns(const uint32_t* vals, int lg, bool s, int g, std::vector<ColRef>& out) {

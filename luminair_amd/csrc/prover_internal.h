@@ -11,6 +11,7 @@
 #include <mutex>
 #include <set>
 
+#include "openings.h"
 #include "prover.h"
 
 namespace lmn {
@@ -104,16 +105,29 @@ struct HostScratch {
   }
 };
 
-// upper bounds of one item of a device plan (kernels.h k_open_plan), from the number of positions alone (level2.cpp)
-struct OpenBound {
-  uint64_t entries = 0, words = 0;
+// which MerkleCut holds a layer that its launch never stored (null: none does)
+inline const MerkleCut* cut_holding(const std::vector<MerkleCut>& cuts, int layer) {
+  for (auto& c : cuts)
+    if (layer <= c.start_log && layer > c.start_log - c.depth) return &c;
+  return nullptr;
+}
+
+// One tree as the device planner's launches see it (kernels.h k_open_plan; level2.cpp).  Appends the tree's layer
+// pointers, then its columns' (tree order), to `ptrs` and fills `d`: ncols, cut_of_layer, the bounds and the offsets,
+// which `tot` - what a launch's items add up to - carries from item to item.  `cuts`: the MerkleCuts of the tree's
+// launches, null for a tree that keeps every layer; a layer one of them holds adds its recipe to `recompute`.  False
+// where that table is full (nothing else refuses here).
+struct OpenTotals {
+  uint64_t entries = 0, jobs = 0, words = 0, max_cap = 0, max_job_cap = 0;
 };
-OpenBound open_bound(int max_log, const std::vector<uint32_t>& ncols_of_log, uint32_t n_positions, bool pairs);
+bool append_open_item(int max_log, uint32_t* const* layers, const std::vector<uint32_t>& ncols_of_log,
+                      const std::vector<ColRef>& cols_sorted, const std::vector<MerkleCut>* cuts, uint32_t n_positions,
+                      uint32_t flags, std::vector<const uint32_t*>& ptrs, std::vector<MerkleRecompute>& recompute,
+                      OpenItemDesc& d, OpenTotals& tot);
 void release_host_scratch(void* p);
 void plan_merkle_decommit(const DevMerkle& m, const std::vector<ColRef>& cols_sorted, int g,
                           const std::map<int, std::vector<uint32_t>>& queries, std::vector<Ref>& queried,
                           std::vector<Ref>& hash_wit, std::vector<Ref>& col_wit, std::vector<MerkleRecompute>& jobs);
-std::vector<uint32_t> fold_positions(const std::vector<uint32_t>& p, int n);
 void plan_fri_witness(const ColRef (&cols)[4], int g, const std::vector<uint32_t>& qpos,
                              std::vector<uint32_t>& dec_pos, std::vector<Ref>& wit);
 

@@ -6,6 +6,7 @@
 #include <set>
 
 #include "capi_internal.h"
+#include "openings.h"
 
 namespace lmn {
 
@@ -137,102 +138,69 @@ Proof parse_proof(const uint8_t* data, size_t n, int n_slots) {
   return p;
 }
 
-// ---- MerkleVerifier::verify
-bool merkle_verify(const Hash32& root, std::vector<int> col_logs, const std::map<int, std::vector<uint32_t>>& queries,
+// ---- MerkleVerifier::verify (openings.h walk_openings): every opened node's hash from its children's and its column
+// values, pulled from the proof's lists in the walk's order; a list that runs out stops the walk
+struct MerkleReplay {
+  const std::vector<uint32_t>& queried;
+  const Decommitment& d;
+  size_t qi = 0, hi = 0, ci = 0;
+  std::vector<Hash32> nodes;   // the opened nodes' hashes in the walk's order; a layer opens ALL nodes of the layer below as
+  size_t taken = 0;            // children, in that order: nodes[taken] is the next opened child
+  std::vector<uint32_t> words;
+  bool child(int, uint32_t, bool opened) {
+    if (!opened && hi >= d.hash_witness.size()) return false;
+    const Hash32& h = opened ? nodes[taken++] : d.hash_witness[hi++];
+    words.insert(words.end(), h.w, h.w + 8);
+    return true;
+  }
+  bool column(uint32_t, uint32_t, bool is_query) {
+    const std::vector<uint32_t>& from = is_query ? queried : d.column_witness;
+    size_t& at = is_query ? qi : ci;
+    if (at >= from.size()) return false;
+    words.push_back(from[at++]);
+    return true;
+  }
+  bool node(int, uint32_t) {
+    nodes.push_back(b2_hash_words(words.data(), words.size()));
+    words.clear();
+    return true;
+  }
+};
+bool merkle_verify(const Hash32& root, const std::vector<int>& col_logs, const std::map<int, std::vector<uint32_t>>& queries,
                    const std::vector<uint32_t>& queried, const Decommitment& d) {
-  std::sort(col_logs.begin(), col_logs.end(), std::greater<int>());
   if (col_logs.empty()) {
     Hash32 e = b2_hash_words(nullptr, 0);
     return memcmp(e.w, root.w, 32) == 0 && queried.empty() && d.hash_witness.empty() && d.column_witness.empty();
   }
-  const int max_log = col_logs[0];
-  std::map<int, int> ncols;
-  for (int l : col_logs) ncols[l]++;
-  size_t qi = 0, hi = 0, ci = 0;
-  std::vector<std::pair<uint32_t, Hash32>> last;
-  static const std::vector<uint32_t> none;
-  for (int log = max_log; log >= 0; --log) {
-    int nc = ncols.count(log) ? ncols[log] : 0;
-    auto it = queries.find(log);
-    const std::vector<uint32_t>& cq = it != queries.end() ? it->second : none;
-    size_t pi = 0, cqi = 0;
-    std::vector<std::pair<uint32_t, Hash32>> total;
-    while (pi < last.size() || cqi < cq.size()) {
-      uint32_t node;
-      if (pi < last.size() && cqi < cq.size())
-        node = std::min(last[pi].first / 2, cq[cqi]);
-      else if (pi < last.size())
-        node = last[pi].first / 2;
-      else
-        node = cq[cqi];
-      std::vector<uint32_t> words;
-      if (log < max_log) {
-        Hash32 l, r;
-        if (pi < last.size() && last[pi].first == 2 * node)
-          l = last[pi++].second;
-        else if (hi < d.hash_witness.size())
-          l = d.hash_witness[hi++];
-        else
-          return false;
-        if (pi < last.size() && last[pi].first == 2 * node + 1)
-          r = last[pi++].second;
-        else if (hi < d.hash_witness.size())
-          r = d.hash_witness[hi++];
-        else
-          return false;
-        words.insert(words.end(), l.w, l.w + 8);
-        words.insert(words.end(), r.w, r.w + 8);
-      }
-      bool is_q = cqi < cq.size() && cq[cqi] == node;
-      if (is_q) ++cqi;
-      for (int k = 0; k < nc; ++k) {
-        if (is_q) {
-          if (qi >= queried.size()) return false;
-          words.push_back(queried[qi++]);
-        } else {
-          if (ci >= d.column_witness.size()) return false;
-          words.push_back(d.column_witness[ci++]);
-        }
-      }
-      total.push_back({node, b2_hash_words(words.data(), words.size())});
-    }
-    last.swap(total);
-  }
-  if (qi != queried.size() || hi != d.hash_witness.size() || ci != d.column_witness.size()) return false;
-  return last.size() == 1 && memcmp(last[0].second.w, root.w, 32) == 0;
-}
-
-std::vector<uint32_t> fold_pos(const std::vector<uint32_t>& p, int n) {
-  std::vector<uint32_t> out;
-  for (auto v : p) {
-    uint32_t q = v >> n;
-    if (out.empty() || out.back() != q) out.push_back(q);
-  }
-  return out;
+  const int max_log = *std::max_element(col_logs.begin(), col_logs.end());
+  std::vector<uint32_t> ncols_of_log(max_log + 1, 0u);
+  for (int l : col_logs) ncols_of_log[l]++;
+  std::vector<Positions> queries_of_log(max_log + 1);
+  for (auto& q : queries)
+    if (q.first >= 0 && q.first <= max_log) queries_of_log[q.first] = {q.second.data(), q.second.size()};
+  MerkleReplay v{queried, d};
+  if (!walk_openings(max_log, ncols_of_log.data(), queries_of_log.data(), v)) return false;
+  if (v.qi != queried.size() || v.hi != d.hash_witness.size() || v.ci != d.column_witness.size()) return false;
+  // (all but the root were taken as children: exactly one node is left, and only where the walk opened any)
+  return v.taken + 1 == v.nodes.size() && memcmp(v.nodes.back().w, root.w, 32) == 0;
 }
 
 // sibling pairs of a sparse evaluation: queried values come from `known`, the rest from the witness
 bool rebuild_pairs(const std::vector<uint32_t>& qpos, const std::map<uint32_t, QM31>& known,
                    const std::vector<QM31>& witness, size_t& wi, std::vector<uint32_t>& dec_pos,
                    std::map<uint32_t, QM31>& vals) {
-  size_t i = 0;
-  while (i < qpos.size()) {
-    uint32_t start = (qpos[i] >> 1) << 1;
-    std::set<uint32_t> subset;
-    while (i < qpos.size() && ((qpos[i] >> 1) << 1) == start) subset.insert(qpos[i++]);
-    for (uint32_t pos = start; pos < start + 2; ++pos) {
-      dec_pos.push_back(pos);
-      if (subset.count(pos)) {
-        auto it = known.find(pos);
-        if (it == known.end()) return false;
-        vals[pos] = it->second;
-      } else {
-        if (wi >= witness.size()) return false;
-        vals[pos] = witness[wi++];
-      }
+  return for_each_pair_member(qpos, [&](uint32_t pos, bool is_query) {
+    dec_pos.push_back(pos);
+    if (is_query) {
+      auto it = known.find(pos);
+      if (it == known.end()) return false;
+      vals[pos] = it->second;
+    } else {
+      if (wi >= witness.size()) return false;
+      vals[pos] = witness[wi++];
     }
-  }
-  return true;
+    return true;
+  });
 }
 
 // Where the verdicts of one pass over a proof go.
@@ -484,17 +452,8 @@ VerifyFront verify_front(const uint8_t* data, size_t len, const lmn_config& expe
   ch.mix_u64(p.proof_of_work);
   step(LMN_STEP_POW_NONCE, 0, ch);
   std::vector<uint32_t>& queries = f.queries;
-  {
-    std::set<uint32_t> qs;
-    uint64_t cnt = 0;
-    const uint32_t mask = (1u << top) - 1u;
-    while (cnt < p.n_queries) {
-      Hash32 r = ch.draw_random_words();
-      for (int i = 0; i < 8 && cnt < p.n_queries; ++i, ++cnt) qs.insert(r.w[i] & mask);
-    }
-    queries.assign(qs.begin(), qs.end());
-  }
-  for (int ls : sizes) f.pos_by_log[ls] = fold_pos(queries, top - ls);
+  queries = draw_query_positions(ch, p.n_queries, (uint32_t)top);
+  for (int ls : sizes) f.pos_by_log[ls] = fold_positions(queries, top - ls);
   return f;
 }
 // ---- FRI answers: which sampled columns make up the quotient of each LDE size (shared by the host's back half and by
@@ -657,7 +616,7 @@ void verify_back(const VerifyFront& f, const Checks& ck) {
   int layer_log = top - 1;
   std::map<uint32_t, QM31> cur = fold_circle(first_vals[top], top, alphas[0]);
   std::vector<int> left(sizes.begin() + 1, sizes.end());
-  std::vector<uint32_t> lq = fold_pos(queries, 1);
+  std::vector<uint32_t> lq = fold_positions(queries, 1);
   for (size_t li = 0; li < p.inner_layers.size(); ++li) {
     const FriLayerProof& l = p.inner_layers[li];
     std::vector<uint32_t> dpos;
@@ -683,7 +642,7 @@ void verify_back(const VerifyFront& f, const Checks& ck) {
       nxt[pos >> 1] = q_add(q_add(a, b), q_mul(alpha, q_mul_m(q_sub(a, b), m_inv(x))));
     }
     layer_log -= 1;
-    lq = fold_pos(lq, 1);
+    lq = fold_positions(lq, 1);
     for (auto it = left.begin(); it != left.end();) {
       if (*it - 1 == layer_log) {
         auto fc = fold_circle(first_vals[*it], *it, alpha);
@@ -777,11 +736,11 @@ bool build_layout(const VerifyFront& f, const QuotPlan& plan, std::vector<uint32
 // words of scratch the FRI trees' leaf lists take: 8 per sibling pair, as the positions imply
 void leaf_words(const VerifyFront& f, std::vector<uint32_t>& per_tree) {
   uint32_t first = 0;
-  for (int ls : f.sizes) first += 8u * (uint32_t)fold_pos(f.pos_by_log.at(ls), 1).size();
+  for (int ls : f.sizes) first += 8u * (uint32_t)fold_positions(f.pos_by_log.at(ls), 1).size();
   per_tree.assign(1, first);
-  std::vector<uint32_t> lq = fold_pos(f.queries, 1);
+  std::vector<uint32_t> lq = fold_positions(f.queries, 1);
   for (size_t li = 0; li < f.p.inner_layers.size(); ++li) {
-    lq = fold_pos(lq, 1);
+    lq = fold_positions(lq, 1);
     per_tree.push_back(8u * (uint32_t)lq.size());
   }
 }
@@ -839,16 +798,8 @@ int proof_guard(std::string& text, F&& body) {
   try {
     body();
     return LMN_OK;
-  } catch (const LmnError& e) {
-    text = e.what();
-    const int c = e.code;
-    return (c == -100 || (c <= -1 && c >= -10)) ? c : LMN_ERR_INTERNAL;
-  } catch (const std::bad_alloc&) {
-    text = "host allocation failed";
-    return LMN_ERR_OUT_OF_MEMORY;
-  } catch (const std::exception& e) {
-    text = e.what();
-    return LMN_ERR_INTERNAL;
+  } catch (...) {
+    return current_exception_code(text);
   }
 }
 

@@ -61,6 +61,8 @@ SHAPES = [
     ("log size 0", [(2, 0)]),
     ("log size 1", [(1, 1)]),
     ("log sizes 1 and 0", [(1, 0), (2, 1)]),
+    ("log sizes 5, 3 and 0", [(1, 3), (2, 5), (1, 0)]),
+    ("a root layer without columns of its own", [(2, 3), (1, 2)]),
 ]
 
 
@@ -75,6 +77,8 @@ def query_sets(t, n_queries, seed):
     if top >= 1:
         k = (last // 2) & ~1
         qs.append(("both children of one node", {top: [k, k + 1]}))
+    if top >= 2:
+        qs.append(("neighbours that are no siblings", {top: [1, 2]}))
     absent = [lg for lg in range(top, -1, -1) if lg not in sizes]
     if absent:
         qs.append(("a log size without columns", {absent[0]: [(1 << absent[0]) - 1], top: [1]}))
@@ -95,6 +99,8 @@ def assert_opening_equals_oracle(t, ref, queries, what):
     # - empty - opening as well, so there is nothing to verify then)
     if any(len(q) for q in queries.values()):
         assert verify_decommitment(t.tree.root(), t.log_sizes, queries, vals.tolist(), hw, cw.tolist()), what
+        if hw:      # (every leaf opened: no hash to take away) - one hash short, the walk runs out of witness
+            assert not verify_decommitment(t.tree.root(), t.log_sizes, queries, vals.tolist(), hw[:-1], cw.tolist()), what
     return vals, hw, cw
 
 
