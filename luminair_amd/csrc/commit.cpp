@@ -257,7 +257,8 @@ bool Context::shard_rows_front(int log_size) const {
 }
 
 Context::CommitOut Context::interpolate_for_commit(uint32_t* coeffs, const uint32_t* evals, int ncols, int log_size,
-                                                   int halo_first, bool evals_row_blocks) {
+                                                   int halo_first, bool evals_row_blocks, const ColSkip* skip,
+                                                   const uint32_t* skip_lde) {
   const uint64_t n = 1ull << log_size;
   CommitOut out;
   StageTimer t(this, g_log(this), stream_, C_FFT);
@@ -265,8 +266,9 @@ Context::CommitOut Context::interpolate_for_commit(uint32_t* coeffs, const uint3
     timings.fft_bytes += (uint64_t)ncols * 8ull * n;
     timings.fft_butterflies += (uint64_t)ncols * (n / 2) * (uint64_t)log_size;
     uint32_t* lde = arena_.alloc_words((size_t)ncols * 2 * n);
+    out.skipped = skip && skip->changed && lde == skip_lde;
     timings.fft_launches += launch_interp_extend(coeffs, n, evals, n, lde, 2 * n, ncols, log_size, itw(log_size),
-                                                 tw(log_size + 1), stream_);
+                                                 tw(log_size + 1), stream_, out.skipped ? *skip : ColSkip{});
     timings.fft_bytes += (uint64_t)ncols * 12ull * n;                       // the extension: 4n read + 8n written
     timings.fft_butterflies += (uint64_t)ncols * n * (uint64_t)log_size;  // 2^(k+1)/2 * k (the top layer is the identity)
     out.lde = lde;

@@ -60,6 +60,21 @@ inline constexpr ComponentSpec kSpecs[N_KINDS] = {
     {LMN_KIND_INPUTS, 7, 2, 1, {6}, {5}, {0}, 3, {0}, {0}, {0}, 0, {0, 0}, 0, {0}, {0}},
     {LMN_KIND_CONTIGUOUS, 11, 3, 2, {9, 10}, {7, 8}, {1, 0}, 4, {0}, {0}, {0}, 0, {0, 0}, 0, {0}, {0}},    // contiguous/component.rs
 };
+// The columns of a spec that are functions of the graph alone - ids, idx, is_last, their next_* columns, and the
+// multiplicities of the relations on main-trace columns - as a bit mask: the candidates of the trace reuse
+// (phase_trace.cpp run_main_trace).  Everything else carries values of the input and is never a candidate; components
+// without local constraints (the lookups: is_last_col < 0) have none.
+constexpr uint32_t graph_only_columns(const ComponentSpec& sp) {
+  if (sp.is_last_col < 0) return 0u;
+  uint32_t mask = (1u << (2 * sp.is_last_col + 1)) - 1u;
+  for (int j = 0; j < sp.n_rel; ++j)
+    if (sp.rel_pre[j] == 0) mask |= 1u << sp.rel_mult[j];
+  return mask;
+}
+static_assert(graph_only_columns(kSpecs[LMN_KIND_ADD]) == 0x71ffu && graph_only_columns(kSpecs[LMN_KIND_MUL]) == 0xe1ffu &&
+                  graph_only_columns(kSpecs[LMN_KIND_INPUTS]) == 0x5fu && graph_only_columns(kSpecs[LMN_KIND_SIN_LOOKUP]) == 0u,
+              "Add: 12 of 15, Mul: 12 of 16, Inputs: 6 of 7");
+
 // k_composition is instantiated once per shape: Exp2 / Log2 run Sin's code, their lookups SinLookup's (the element set
 // they differ in is a launch argument)
 constexpr int composition_shape(int kind) {

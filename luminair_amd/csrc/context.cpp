@@ -21,6 +21,7 @@ void Arena::reserve(size_t bytes) {
   }
   cap_ = bytes;
   off_ = 0;
+  ++generation_;   // another slab: nothing of what it held is left
 }
 void* Arena::alloc_bytes(size_t bytes) {
   size_t a = (off_ + 255) & ~(size_t)255;
@@ -76,9 +77,11 @@ Context::Context(int device, const lmn_config& c, size_t pin_bytes) : cfg(c), de
   pin_cap_ = pin_bytes;
   pin_base_ = (char*)lmn_host_alloc_pinned(pin_cap_);
   {
-    const uint32_t zero[2] = {0u, 0u};
-    bad_flag_ = (uint32_t*)lmn_dev_malloc(8);   // [0]: prove's non-canonical-word verdict, [1]: trace_lut's range verdict
-    lmn_h2d(bad_flag_, zero, 8, stream_);
+    // [0]: prove's non-canonical-word verdict, [1]: trace_lut's range verdict, then the comparing transposes' changed[] words
+    // (trace reuse; a proof's mark is at least 2, so zero never counts as "changed in this proof")
+    const std::vector<uint32_t> zero(2 + CHANGED_WORDS, 0u);
+    bad_flag_ = (uint32_t*)lmn_dev_malloc(zero.size() * 4);
+    lmn_h2d(bad_flag_, zero.data(), zero.size() * 4, stream_);
     lmn_sync(stream_);
   }
 }

@@ -337,7 +337,7 @@ static TwD doubled(const TwPtrs& tw) {
 template <bool INV, int RBITS, int CB, bool LO0, bool ZX = false>
 LMN_KERNEL LMN_BOUNDS((FxShape<RBITS, CB, LO0>::NT))
 k_fft_fx(uint32_t* data, uint64_t col_stride, const uint32_t* src, uint64_t src_stride, int lo_arg, TwD tw, uint32_t scale_log,
-         int ncols, int cpb, uint32_t h_off, int xcd_swizzle) {
+         int ncols, int cpb, uint32_t h_off, int xcd_swizzle, ColSkip skip) {
   using S = FxShape<RBITS, CB, LO0>;
   LMN_DYN_SMEM(uint32_t, sm);
   const int lo = LO0 ? 0 : lo_arg;
@@ -351,6 +351,7 @@ k_fft_fx(uint32_t* data, uint64_t col_stride, const uint32_t* src, uint64_t src_
   for (int cc = 0; cc < cpb; ++cc) {
     const int c = (int)blockIdx.y * cpb + cc;
     if (c >= ncols) break;
+    if (col_skipped(skip, c)) continue;   // before the column's first load and first barrier
     uint32_t* col = data + (uint64_t)c * col_stride + base;
     const uint32_t* scol = src + (uint64_t)c * src_stride + base;
     fx_steps<S, INV, 0, true, true, false, ZX>(sm, sm, col, scol, lo, H, tw.l, scale_log, nullptr, threadIdx.x);
@@ -364,7 +365,8 @@ k_fft_fx(uint32_t* data, uint64_t col_stride, const uint32_t* src, uint64_t src_
 // being copies); the inverse layers then use the first half of each table of the 2^(n+1)-point domain.
 template <int RBITS, int NH>
 LMN_D void fx_interp_extend_tile(uint32_t* sm, uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, uint64_t lde_stride,
-                                 const TwD& itw, const TwD& tw, uint32_t scale_log) {
+                                 const TwD& itw, const TwD& tw, uint32_t scale_log, const ColSkip& skip) {
+  if (col_skipped(skip, (int)blockIdx.y)) return;   // before the first load and the first barrier
   using S = FxShape<RBITS, 4, false>;
   constexpr int LO = 12;
   uint32_t* A = sm;                       // the coefficient tile, kept for every block
@@ -384,9 +386,9 @@ LMN_D void fx_interp_extend_tile(uint32_t* sm, uint32_t* coeffs, uint64_t coeff_
 template <int RBITS>
 LMN_KERNEL LMN_BOUNDS((FxShape<RBITS, 4, false>::NT))
 k_fft_interp_extend_fx(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, uint64_t lde_stride, TwD itw, TwD tw,
-                       uint32_t scale_log) {
+                       uint32_t scale_log, ColSkip skip) {
   LMN_DYN_SMEM(uint32_t, sm);
-  fx_interp_extend_tile<RBITS, 2>(sm, coeffs, coeff_stride, lde, lde_stride, itw, tw, scale_log);
+  fx_interp_extend_tile<RBITS, 2>(sm, coeffs, coeff_stride, lde, lde_stride, itw, tw, scale_log, skip);
 }
 
 template <int RBITS>
@@ -394,7 +396,7 @@ LMN_KERNEL LMN_BOUNDS((FxShape<RBITS, 4, false>::NT))
 k_fft_interp_quarters_fx(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, uint64_t lde_stride, TwD itw, TwD tw,
                          uint32_t scale_log) {
   LMN_DYN_SMEM(uint32_t, sm);
-  fx_interp_extend_tile<RBITS, 4>(sm, coeffs, coeff_stride, lde, lde_stride, itw, tw, scale_log);
+  fx_interp_extend_tile<RBITS, 4>(sm, coeffs, coeff_stride, lde, lde_stride, itw, tw, scale_log, ColSkip{});
 }
 
 // =============================================================================================
@@ -495,7 +497,8 @@ bool launch_fft_rows_fixed(uint32_t* coeffs, uint64_t col_stride, const uint32_t
 
 template <bool INV, int RBITS, int CB, bool LO0, bool ZX = false>
 static void launch_fx(uint32_t* data, uint64_t col_stride, const uint32_t* src, uint64_t src_stride, int lo, int log_n,
-                      const TwPtrs& tw, uint32_t scale_log, int ncols, int cpb, uint32_t h_off, int xcd, lmn_stream_t s) {
+                      const TwPtrs& tw, uint32_t scale_log, int ncols, int cpb, uint32_t h_off, int xcd, lmn_stream_t s,
+                      const ColSkip& skip) {
   using S = FxShape<RBITS, CB, LO0>;
   const unsigned tiles = 1u << (log_n - S::TB);
   const size_t smem = (size_t)4 * S::LDS_WORDS;
@@ -503,23 +506,23 @@ static void launch_fx(uint32_t* data, uint64_t col_stride, const uint32_t* src, 
   if (smem > 64 * 1024) allow_big_lds((const void*)k_fft_fx<INV, RBITS, CB, LO0, ZX>, 160 * 1024);
 #endif
   LMN_LAUNCH((k_fft_fx<INV, RBITS, CB, LO0, ZX>), dim3(tiles, (unsigned)((ncols + cpb - 1) / cpb)), dim3(S::NT), smem, s, data,
-             col_stride, src, src_stride, lo, doubled(tw), scale_log, ncols, cpb, h_off, xcd);
+             col_stride, src, src_stride, lo, doubled(tw), scale_log, ncols, cpb, h_off, xcd, skip);
 }
 
 template <bool INV>
 static bool dispatch_fx(uint32_t* data, uint64_t col_stride, const uint32_t* src, uint64_t src_stride, int lo, int rbits, int cb,
                         int log_n, const TwPtrs& tw, uint32_t scale_log, int ncols, int cpb, uint32_t h_off, int xcd,
-                        bool zext, lmn_stream_t s) {
+                        bool zext, lmn_stream_t s, const ColSkip& skip) {
 #define LMN_FX_CASE(RB, CBV, L0V)                                                                                            \
   if constexpr (!INV && !L0V) {                                                                                              \
     if (zext) {                                                                                                              \
       launch_fx<INV, RB, CBV, L0V, true>(data, col_stride, src, src_stride, lo, log_n, tw, scale_log, ncols, cpb, h_off, xcd, \
-                                         s);                                                                                 \
+                                         s, skip);                                                                           \
       return true;                                                                                                           \
     }                                                                                                                        \
   }                                                                                                                          \
   if (zext) return false;                                                                                                    \
-  launch_fx<INV, RB, CBV, L0V>(data, col_stride, src, src_stride, lo, log_n, tw, scale_log, ncols, cpb, h_off, xcd, s);      \
+  launch_fx<INV, RB, CBV, L0V>(data, col_stride, src, src_stride, lo, log_n, tw, scale_log, ncols, cpb, h_off, xcd, s, skip); \
   return true
   if (lo == 0 && cb == 0) {
     if (rbits == 12) { LMN_FX_CASE(12, 0, true); }
@@ -549,19 +552,19 @@ static bool dispatch_fx(uint32_t* data, uint64_t col_stride, const uint32_t* src
 
 bool launch_fft_fixed_pass(bool inverse, uint32_t* data, uint64_t col_stride, const uint32_t* src, uint64_t src_stride, int lo,
                            int rbits, int cb, int log_n, const TwPtrs& tw, uint32_t scale_log, int ncols, int cpb,
-                           uint32_t h_off, int xcd_swizzle, bool zero_extended_top, lmn_stream_t s) {
+                           uint32_t h_off, int xcd_swizzle, bool zero_extended_top, lmn_stream_t s, const ColSkip& skip) {
   static const bool off = env_set("LMN_NO_FFT_FIXED");
   if (off || !tw.d[0]) return false;
   if (zero_extended_top && (inverse || lo + rbits != log_n)) return false;
   return inverse ? dispatch_fx<true>(data, col_stride, src, src_stride, lo, rbits, cb, log_n, tw, scale_log, ncols, cpb, h_off,
-                                     xcd_swizzle, false, s)
+                                     xcd_swizzle, false, s, skip)
                  : dispatch_fx<false>(data, col_stride, src, src_stride, lo, rbits, cb, log_n, tw, scale_log, ncols, cpb, h_off,
-                                      xcd_swizzle, zero_extended_top, s);
+                                      xcd_swizzle, zero_extended_top, s, skip);
 }
 
 template <int RBITS, int NH>
 static void launch_ie(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, uint64_t lde_stride, const TwPtrs& itw,
-                      const TwPtrs& tw_ext, uint32_t scale_log, int ncols, lmn_stream_t s) {
+                      const TwPtrs& tw_ext, uint32_t scale_log, int ncols, lmn_stream_t s, const ColSkip& skip) {
   using S = FxShape<RBITS, 4, false>;
   const size_t smem = (size_t)8 * S::LDS_WORDS;
   if constexpr (NH == 2) {
@@ -569,7 +572,7 @@ static void launch_ie(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, ui
     if (smem > 64 * 1024) allow_big_lds((const void*)k_fft_interp_extend_fx<RBITS>, 160 * 1024);
 #endif
     LMN_LAUNCH((k_fft_interp_extend_fx<RBITS>), dim3(1u << (12 - 4), (unsigned)ncols), dim3(S::NT), smem, s, coeffs,
-               coeff_stride, lde, lde_stride, doubled(itw), doubled(tw_ext), scale_log);
+               coeff_stride, lde, lde_stride, doubled(itw), doubled(tw_ext), scale_log, skip);
   } else {
 #if !defined(LMN_EMU) && !defined(LMN_BATCH)
     if (smem > 64 * 1024) allow_big_lds((const void*)k_fft_interp_quarters_fx<RBITS>, 160 * 1024);
@@ -580,14 +583,15 @@ static void launch_ie(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, ui
 }
 
 bool launch_interp_extend_fixed(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, uint64_t lde_stride, int log_n,
-                                const TwPtrs& itw, const TwPtrs& tw_ext, int ncols, int n_ext, lmn_stream_t s) {
+                                const TwPtrs& itw, const TwPtrs& tw_ext, int ncols, int n_ext, lmn_stream_t s,
+                                const ColSkip& skip) {
   static const bool off = env_set("LMN_NO_FFT_FIXED");
   if (off || !itw.d[0] || !tw_ext.d[0] || (n_ext != 2 && n_ext != 4)) return false;
   const uint32_t scale_log = (uint32_t)((31 - (log_n % 31)) % 31);   // 2^-log_n = 2^(31 - log_n mod 31)
 #define LMN_IE_CASE(RB)                                                                                        \
   case RB:                                                                                                     \
-    if (n_ext == 2) launch_ie<RB, 2>(coeffs, coeff_stride, lde, lde_stride, itw, tw_ext, scale_log, ncols, s); \
-    else launch_ie<RB, 4>(coeffs, coeff_stride, lde, lde_stride, itw, tw_ext, scale_log, ncols, s);            \
+    if (n_ext == 2) launch_ie<RB, 2>(coeffs, coeff_stride, lde, lde_stride, itw, tw_ext, scale_log, ncols, s, skip); \
+    else launch_ie<RB, 4>(coeffs, coeff_stride, lde, lde_stride, itw, tw_ext, scale_log, ncols, s, skip);      \
     return true
   switch (log_n - 12) {
     LMN_IE_CASE(6);

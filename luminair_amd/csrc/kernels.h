@@ -20,6 +20,21 @@ struct TwPtrs {
 struct PadRow {
   uint32_t v[32];  // the component's padding row (e.g. add/table.rs:40-58)
 };
+// Trace reuse (phase_trace.cpp run_main_trace): which columns of a launch may keep what the previous proof left in their
+// blocks.  Column c is skipped when it is a candidate (bit c of candidate_mask) and changed[c] != epoch; the comparing
+// transpose stores `epoch` into changed[c] when a word of a candidate column differs from the word it is about to
+// overwrite.  changed == nullptr: every column is worked on.
+struct ColSkip {
+  const uint32_t* changed = nullptr;
+  uint32_t epoch = 0;
+  uint32_t candidate_mask = 0;
+};
+// In a kernel: column c keeps what the previous proof left in its blocks.  c is workgroup-uniform (it comes from blockIdx),
+// so the mark arrives through a uniform load and every lane of the workgroup takes the same branch.
+LMN_HD bool col_skipped(const ColSkip& k, int c) {
+  return k.changed != nullptr && ((k.candidate_mask >> c) & 1u) != 0u && k.changed[c] != k.epoch;
+}
+constexpr int CHANGED_WORDS = 128;   // a proof's changed[] words, all tables together (tables beyond them are not compared)
 void launch_transpose_pad(const uint32_t* rows, uint64_t n_rows, int ncols, int log_size, uint32_t* cols,
                           const PadRow& pad, uint32_t* bad_flag /* device word, set when a value >= P */, lmn_stream_t s);
 // only rows [blk_row0, blk_row0 + blk_rows) of the padded table (blk_row0 a multiple of 64); columns out_stride apart
@@ -27,6 +42,12 @@ void launch_transpose_pad_rows(const uint32_t* rows, uint64_t n_rows, int ncols,
                                uint64_t out_stride, uint64_t blk_row0, uint64_t blk_rows, const PadRow& pad, uint32_t* bad_flag,
                                lmn_stream_t s,
                                uint32_t bad_value = 1u /* what a non-canonical word writes to *bad_flag */);
+// The comparing form, whole tables only (`cols` hold the previous proof's columns): a word of a column of `cmp_mask` is
+// read before it is stored and stored only if it differs; a wave that saw a difference writes `epoch` to changed[column].
+// Columns outside the mask are stored as launch_transpose_pad stores them.
+void launch_transpose_pad_compare(const uint32_t* rows, uint64_t n_rows, int ncols, int log_size, uint32_t* cols,
+                                  const PadRow& pad, uint32_t* bad_flag, uint32_t bad_value, uint32_t cmp_mask,
+                                  uint32_t* changed, uint32_t epoch, lmn_stream_t s);
 // Row sinks (lmn_rows_*): one CHUNK of rows - its row 0 is table row r0, any r0, any length n >= 1 - transposed into
 // columns `stride` words apart.  `chunk` may be page-locked HOST memory in its device view (read over the link, once).
 // chunk == nullptr: rows [r0, r0 + n) receive the padding row instead.  A non-canonical word sets *bad_word to 1.
@@ -57,8 +78,10 @@ int launch_fft(uint32_t* dst, uint64_t dst_stride, const uint32_t* src, uint64_t
 // interpolate + extend by one bit in three launches (the strided passes of both transforms fused): evals (2^log_n) ->
 // coeffs (2^log_n, kept) and lde (2^(log_n+1)).  itw: inverse twiddles of domain log_n; tw_ext: twiddles of log_n + 1.
 bool fft_interp_extend_supported(int log_n);
+// skip.changed != nullptr: the workgroups of a skipped column (ColSkip) leave all three launches before their first load.
 int launch_interp_extend(uint32_t* coeffs, uint64_t coeff_stride, const uint32_t* evals, uint64_t evals_stride, uint32_t* lde,
-                         uint64_t lde_stride, int ncols, int log_n, const TwPtrs& itw, const TwPtrs& tw_ext, lmn_stream_t s);
+                         uint64_t lde_stride, int ncols, int log_n, const TwPtrs& itw, const TwPtrs& tw_ext, lmn_stream_t s,
+                         const ColSkip& skip = ColSkip{});
 // The same for a polynomial of 2^log_half coefficients given by its evaluations on storage rows [0, 2^log_half) of the
 // 2^(log_half + 1)-point domain (itw_full: that domain's inverse tables), extended onto the 2^(log_half + 2)-point domain
 // (tw_ext): the inverse low pass and the strided pass that writes four quarters (2 launches); launch_interp_extend_half_finish
@@ -140,6 +163,9 @@ struct DevReport {
   uint32_t roots[3][8];                      // main, interaction, composition tree
   uint32_t bad;                              // copy of the transposes' non-canonical-word verdict
   uint32_t pad[3];
+  // trace reuse: copy of the first ChanStep::changed_words words behind the verdict's two.  The words beyond them are never
+  // written and never read: they hold whatever the arena held (the last step copies the whole report, 0.5 KB of it this)
+  uint32_t changed[CHANGED_WORDS];
 };
 struct ChanElemSets {
   int n;
@@ -162,7 +188,7 @@ struct ChanOodsPlan {
 // One transcript step of the commitment phases, made by the launch that produces the tree's root (launch_merkle_small)
 // or by a launch of its own (launch_chan_step):
 //  kind 1  the channel starts at `start` (a launch argument instead of an upload); mix_root(root 1); one draw_felts(2) per
-//          entry of `sets` -> rep->elems; rep->bad = *bad_word
+//          entry of `sets` -> rep->elems; rep->bad = *bad_word; rep->changed[k] = bad_word[2 + k] for k < changed_words
 //  kind 2  mix_felts([claimed_i]) per component, mix_root(root 2), draw_felt() = the composition randomness alpha; then the
 //          coefficient of every kernel constraint slot of every component: sign * alpha^(n_total - 1 - (k0 + proto_index)),
 //          0 for a slot the protocol lacks (Context's constraint_layout) - 16 per component at coeff_out + 16 * i
@@ -185,7 +211,8 @@ struct ChanStep {
   // kind 3 also copies `copy_words` words from page-locked memory to device memory (the evaluation kernels' job table)
   const uint32_t* copy_src;
   uint32_t* copy_dst;
-  uint32_t copy_words, pad_;
+  uint32_t copy_words;
+  uint32_t changed_words;   // kind 1
 };
 // The kernels take the step as a device-visible pointer (+ its kind by value) and fetch it into LDS with one load per lane:
 // page-locked host memory serves (one round trip, behind the launch's first loads).  check_chan_step validates a plan.

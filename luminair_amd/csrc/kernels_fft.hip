@@ -240,7 +240,7 @@ LMN_D void fft_stage_dispatch(int R, const uint32_t* sm_in, uint32_t* sm_out, ui
 template <bool INV>
 LMN_KERNEL k_fft_staged(uint32_t* data, uint64_t col_stride, const uint32_t* src, uint64_t src_stride,
                         uint64_t src_len, FftStagePlan pl, TwPtrs tw, uint32_t scale, int ncols, int cpb,
-                        uint32_t h_off) {
+                        uint32_t h_off, ColSkip skip) {
   LMN_DYN_SMEM(uint32_t, sm);
   // XCD-aware tile order: consecutive workgroups are dealt round-robin to the 8 XCDs (observed, used
   // for speed only), so give each XCD a contiguous run of tiles: neighbouring strided tiles share
@@ -256,6 +256,7 @@ LMN_KERNEL k_fft_staged(uint32_t* data, uint64_t col_stride, const uint32_t* src
   for (int cc = 0; cc < cpb; ++cc) {
     const int c = blockIdx.y * cpb + cc;
     if (c >= ncols) break;
+    if (col_skipped(skip, c)) continue;   // before the column's first load and first barrier
     uint32_t* col = data + (uint64_t)c * col_stride;
     const uint32_t* scol = src + (uint64_t)c * src_stride;
     for (int k = 0; k < pl.nst; ++k) {
@@ -279,7 +280,7 @@ LMN_KERNEL k_fft_staged(uint32_t* data, uint64_t col_stride, const uint32_t* src
 // ---------------------------------------------------------------------------------------------
 LMN_KERNEL k_fft_interp_extend(uint32_t* coeffs, uint64_t coeff_stride, const uint32_t* src, uint64_t src_stride,
                                uint32_t* lde, uint64_t lde_stride, FftStagePlan pl, TwPtrs itw, TwPtrs tw, uint32_t scale,
-                               int ncols, int cpb, uint32_t n_ext) {
+                               int ncols, int cpb, uint32_t n_ext, ColSkip skip) {
   LMN_DYN_SMEM(uint32_t, sm);
   const uint32_t tile_elems = 1u << (pl.hi - pl.lo + pl.cb);
   uint32_t* A = sm;                                   // the coefficient tile (kept for the second half)
@@ -291,6 +292,7 @@ LMN_KERNEL k_fft_interp_extend(uint32_t* coeffs, uint64_t coeff_stride, const ui
   for (int cc = 0; cc < cpb; ++cc) {
     const int c = blockIdx.y * cpb + cc;
     if (c >= ncols) break;
+    if (col_skipped(skip, c)) continue;   // before the column's first load and first barrier
     uint32_t* ccol = coeffs + (uint64_t)c * coeff_stride;
     const uint32_t* scol = src + (uint64_t)c * src_stride;
     uint32_t* lcol = lde + (uint64_t)c * lde_stride;
@@ -363,7 +365,7 @@ static void split_stages(FftStagePlan& pl) {
 template <bool INV>
 static void launch_staged_pass(uint32_t* data, uint64_t col_stride, const uint32_t* psrc, uint64_t pstride, uint64_t plen,
                                const FftPass& p, int log_n, const TwPtrs& tw, uint32_t scale, int ncols, lmn_stream_t s,
-                               uint32_t block_index = 0) {
+                               uint32_t block_index = 0, const ColSkip& skip = ColSkip{}) {
   const int rbits = p.hi - p.lo;
   const unsigned tiles = 1u << (log_n - rbits - p.cb);
   FftStagePlan pl{};
@@ -383,13 +385,13 @@ static void launch_staged_pass(uint32_t* data, uint64_t col_stride, const uint32
   if (full || half_top) {
     const uint32_t scale_log = scale == 1u ? 0u : (uint32_t)__builtin_ctz(scale);
     if (launch_fft_fixed_pass(INV, data, col_stride, psrc, pstride, p.lo, rbits, p.cb, log_n, tw, scale_log, ncols, cpb,
-                              block_index << (log_n - p.hi), pl.xcd_swizzle, !full, s))
+                              block_index << (log_n - p.hi), pl.xcd_swizzle, !full, s, skip))
       return;
   }
   unsigned gy = (unsigned)((ncols + cpb - 1) / cpb);
   const int threads = (int)std::min<uint32_t>(TPB, std::max<uint32_t>(64u, tile_elems >> 4));
   LMN_LAUNCH(k_fft_staged<INV>, dim3(tiles, gy), dim3(threads), smem, s, data, col_stride, psrc, pstride, plen, pl, tw,
-             scale, ncols, cpb, block_index << (log_n - p.hi));
+             scale, ncols, cpb, block_index << (log_n - p.hi), skip);
 }
 
 template <bool INV>
@@ -419,7 +421,8 @@ bool fft_interp_extend_supported(int log_n) {
 }
 // the fused strided pass on coefficients that have been through the inverse low pass: n_ext blocks of 2^log_n evaluations
 static void interp_extend_strided(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, uint64_t lde_stride, int ncols,
-                                  int log_n, const TwPtrs& itw, const TwPtrs& tw_ext, uint32_t n_ext, lmn_stream_t s) {
+                                  int log_n, const TwPtrs& itw, const TwPtrs& tw_ext, uint32_t n_ext, lmn_stream_t s,
+                                  const ColSkip& skip = ColSkip{}) {
   FftStagePlan pl{};
   pl.lo = FFT_LOW_BITS;
   pl.hi = log_n;
@@ -434,24 +437,25 @@ static void interp_extend_strided(uint32_t* coeffs, uint64_t coeff_stride, uint3
 #if !defined(LMN_EMU) && !defined(LMN_BATCH)
   if (smem > 64 * 1024) allow_big_lds((const void*)k_fft_interp_extend, 160 * 1024);
 #endif
-  if (!launch_interp_extend_fixed(coeffs, coeff_stride, lde, lde_stride, log_n, itw, tw_ext, ncols, (int)n_ext, s))
+  if (!launch_interp_extend_fixed(coeffs, coeff_stride, lde, lde_stride, log_n, itw, tw_ext, ncols, (int)n_ext, s, skip))
     LMN_LAUNCH(k_fft_interp_extend, dim3(tiles, (unsigned)((ncols + cpb - 1) / cpb)), dim3(threads), smem, s, coeffs,
-               coeff_stride, coeffs, coeff_stride, lde, lde_stride, pl, itw, tw_ext, inv_pow2(log_n), ncols, cpb, n_ext);
+               coeff_stride, coeffs, coeff_stride, lde, lde_stride, pl, itw, tw_ext, inv_pow2(log_n), ncols, cpb, n_ext, skip);
 }
 // ... then the forward low pass
 static void interp_extend_tail(uint32_t* coeffs, uint64_t coeff_stride, uint32_t* lde, uint64_t lde_stride, int ncols, int log_n,
-                               const TwPtrs& itw, const TwPtrs& tw_ext, lmn_stream_t s) {
+                               const TwPtrs& itw, const TwPtrs& tw_ext, lmn_stream_t s, const ColSkip& skip = ColSkip{}) {
   const FftPass low{0, FFT_LOW_BITS, 0};
-  interp_extend_strided(coeffs, coeff_stride, lde, lde_stride, ncols, log_n, itw, tw_ext, 2u, s);
-  launch_staged_pass<false>(lde, lde_stride, lde, lde_stride, 2ull << log_n, low, log_n + 1, tw_ext, 1u, ncols, s);
+  interp_extend_strided(coeffs, coeff_stride, lde, lde_stride, ncols, log_n, itw, tw_ext, 2u, s, skip);
+  launch_staged_pass<false>(lde, lde_stride, lde, lde_stride, 2ull << log_n, low, log_n + 1, tw_ext, 1u, ncols, s, 0, skip);
 }
 
 int launch_interp_extend(uint32_t* coeffs, uint64_t coeff_stride, const uint32_t* evals, uint64_t evals_stride, uint32_t* lde,
-                         uint64_t lde_stride, int ncols, int log_n, const TwPtrs& itw, const TwPtrs& tw_ext, lmn_stream_t s) {
+                         uint64_t lde_stride, int ncols, int log_n, const TwPtrs& itw, const TwPtrs& tw_ext, lmn_stream_t s,
+                         const ColSkip& skip) {
   if (!fft_interp_extend_supported(log_n)) throw LmnError(-100, "interp_extend: unsupported size");
   const FftPass low{0, FFT_LOW_BITS, 0};
-  launch_staged_pass<true>(coeffs, coeff_stride, evals, evals_stride, 1ull << log_n, low, log_n, itw, 1u, ncols, s);
-  interp_extend_tail(coeffs, coeff_stride, lde, lde_stride, ncols, log_n, itw, tw_ext, s);
+  launch_staged_pass<true>(coeffs, coeff_stride, evals, evals_stride, 1ull << log_n, low, log_n, itw, 1u, ncols, s, 0, skip);
+  interp_extend_tail(coeffs, coeff_stride, lde, lde_stride, ncols, log_n, itw, tw_ext, s, skip);
   return 3;
 }
 

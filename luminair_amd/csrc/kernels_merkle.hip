@@ -735,6 +735,8 @@ LMN_D void chan_step_root_elems(uint32_t* scr, DevChannel* ch, uint32_t root_wor
     rep->roots[0][tid] = root_word;
   }
   if (tid == 0u) rep->bad = *st.bad_word;
+  // trace reuse: the comparing transposes' marks travel with the verdict (they lie behind its two words)
+  for (uint32_t k = tid; k < st.changed_words; k += blockDim.x) rep->changed[k] = st.bad_word[2u + k];
   qchan_mix(msg, 8u);
   uint32_t n_sent = 0u;
   const uint32_t t_draw = st.start.variant == 0u ? 64u : 37u;
@@ -1005,6 +1007,7 @@ LMN_KERNEL k_chan_step(DevChannel* ch, const ChanStep* __restrict__ step, int st
 void check_chan_step(const ChanStep& st) {
   if (st.kind < 1 || st.kind > 3) throw LmnError(-100, "chan_step: bad kind");
   if (st.kind == 1 && (st.sets.n < 1 || st.sets.n > CHAN_N_ELEMS)) throw LmnError(-100, "chan_step: bad draw count");
+  if (st.changed_words > (uint32_t)CHANGED_WORDS) throw LmnError(-100, "chan_step: more changed words than the report holds");
   if (st.kind == 2 && (st.coeff.n_inst < 1 || st.coeff.n_inst > CHAN_MAX_INST)) throw LmnError(-100, "chan_step: bad component count");
   if (st.kind == 3 && (st.oods.n_points < 1 || st.oods.n_points > CHAN_MAX_POINTS || st.oods.n_maps < 2))
     throw LmnError(-100, "chan_step: bad sample plan");

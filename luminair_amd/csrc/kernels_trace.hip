@@ -13,10 +13,16 @@ namespace lmn {
 // sharded proof); row r of column c lands at cols[c * out_stride + (r - blk_row0)].
 // ROWS rows per workgroup: 256 (a lane has `ncols` independent loads in flight and every column gets a 1 KB run) wherever
 // the row block allows, 64 for smaller blocks.
-template <int ROWS>
+// CMP, the comparing form (trace reuse, phase_trace.cpp run_main_trace): `cols` still hold the previous proof's columns.  A
+// lane reads the word of a column of `cmp_mask` that it is about to overwrite and stores only if the two differ (an unchanged
+// column costs its 4 bytes per cell of reads instead of writes); a wave that saw a difference - its 64 words belong to one
+// column - has one lane store `epoch` into changed[column].  Every word is compared: a column counts as unchanged only if
+// it is identical.  Columns outside the mask and the canonical-word check are as in the plain form.
+template <int ROWS, bool CMP = false>
 LMN_KERNEL k_transpose_pad(const uint32_t* __restrict__ rows, uint64_t n_rows, int ncols, uint64_t size,
                            uint32_t* __restrict__ cols, PadRow pad, uint32_t* __restrict__ bad_flag, uint32_t magic,
-                           uint64_t out_stride, uint64_t blk_row0, uint32_t bad_value) {
+                           uint64_t out_stride, uint64_t blk_row0, uint32_t bad_value, uint32_t cmp_mask,
+                           uint32_t* __restrict__ changed, uint32_t epoch) {
   LMN_DYN_SMEM(uint32_t, tile);  // ROWS x stride
   // odd row stride: the column-major read below walks rows at that stride, and an even one (16 words for the 15 columns of
   // Add) maps the rows of a column onto 2 of the 32 LDS banks
@@ -46,9 +52,28 @@ LMN_KERNEL k_transpose_pad(const uint32_t* __restrict__ rows, uint64_t n_rows, i
     }
   }
   __syncthreads();
-  for (int k = threadIdx.x; k < total; k += TPB) {
-    const int c = k / ROWS, r = k - c * ROWS;
-    if (row0 + r < size) cols[(uint64_t)c * out_stride + (row0 - blk_row0) + r] = tile[r * stride + c];
+  if constexpr (CMP) {
+    static_assert(ROWS % 64 == 0, "a wave's 64 words lie in one column");
+    // (every lane makes every trip: the vote below is taken by whole waves)
+    for (int k0 = 0; k0 < total; k0 += TPB) {
+      const int k = k0 + (int)threadIdx.x;
+      const bool on = k < total;
+      const int c = on ? k / ROWS : 0, r = k - c * ROWS;
+      bool differs = false;
+      if (on && row0 + r < size) {
+        uint32_t* dst = cols + (uint64_t)c * out_stride + (row0 - blk_row0) + r;
+        const uint32_t v = tile[r * stride + c];
+        differs = ((cmp_mask >> c) & 1u) == 0u || *dst != v;
+        if (differs) *dst = v;
+        differs = differs && ((cmp_mask >> c) & 1u) != 0u;
+      }
+      if (lmn_ballot(differs) != 0ull && (threadIdx.x & 63u) == 0u) changed[c] = epoch;
+    }
+  } else {
+    for (int k = threadIdx.x; k < total; k += TPB) {
+      const int c = k / ROWS, r = k - c * ROWS;
+      if (row0 + r < size) cols[(uint64_t)c * out_stride + (row0 - blk_row0) + r] = tile[r * stride + c];
+    }
   }
 }
 
@@ -63,13 +88,25 @@ void launch_transpose_pad_rows(const uint32_t* rows, uint64_t n_rows, int ncols,
   size_t smem = (size_t)tr_rows * (ncols + 1) * 4;
   if (ncols > 32 || ncols < 1) throw LmnError(-100, "transpose: bad column count");
   const uint32_t magic = ncols == 1 ? 0u : (uint32_t)((0x100000000ull + (uint64_t)ncols - 1) / (uint64_t)ncols);  // ceil(2^32 / ncols)
+  uint32_t* const no_changed = nullptr;   // (the plain form compares nothing)
   // rows beyond the block are cut off by treating its end as the table's size
   if (big)
     LMN_LAUNCH(k_transpose_pad<256>, dim3(grid), dim3(TPB), smem, s, rows, n_rows, ncols, blk_row0 + blk_rows, cols, pad, bad_flag,
-               magic, out_stride, blk_row0, bad_value);
+               magic, out_stride, blk_row0, bad_value, 0u, no_changed, 0u);
   else
     LMN_LAUNCH(k_transpose_pad<64>, dim3(grid), dim3(TPB), smem, s, rows, n_rows, ncols, blk_row0 + blk_rows, cols, pad, bad_flag,
-               magic, out_stride, blk_row0, bad_value);
+               magic, out_stride, blk_row0, bad_value, 0u, no_changed, 0u);
+}
+void launch_transpose_pad_compare(const uint32_t* rows, uint64_t n_rows, int ncols, int log_size, uint32_t* cols,
+                                  const PadRow& pad, uint32_t* bad_flag, uint32_t bad_value, uint32_t cmp_mask,
+                                  uint32_t* changed, uint32_t epoch, lmn_stream_t s) {
+  const uint64_t size = 1ull << log_size;
+  if (ncols > 32 || ncols < 1) throw LmnError(-100, "transpose: bad column count");
+  if (size % 256 || !changed || (ncols < 32 && (cmp_mask >> ncols) != 0u)) throw LmnError(-100, "comparing transpose: bad arguments");
+  const size_t smem = (size_t)256 * (ncols + 1) * 4;
+  const uint32_t magic = ncols == 1 ? 0u : (uint32_t)((0x100000000ull + (uint64_t)ncols - 1) / (uint64_t)ncols);  // ceil(2^32 / ncols)
+  LMN_LAUNCH((k_transpose_pad<256, true>), dim3(cdiv(size, 256)), dim3(TPB), smem, s, rows, n_rows, ncols, size, cols, pad, bad_flag,
+             magic, size, (uint64_t)0, bad_value, cmp_mask, changed, epoch);
 }
 void launch_transpose_pad(const uint32_t* rows, uint64_t n_rows, int ncols, int log_size, uint32_t* cols,
                           const PadRow& pad, uint32_t* bad_flag, lmn_stream_t s) {

@@ -10,6 +10,7 @@ namespace lmn {
 void Context::replay_device_transcript(ProofRun& r, const std::function<void(QM31)>& set_points) {
   LMN_RUN_ALIASES(r);
   const DevReport& rep = *r.h_report;
+  account_trace_reuse(r, rep.changed);
   if (rep.bad == r.bad_mark)
     throw LmnError(LMN_ERR_INVALID_ARGUMENT, "trace table holds a word that is not a canonical M31 (>= 2^31-1)");
   auto diverged = [](const char* what) {

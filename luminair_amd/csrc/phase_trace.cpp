@@ -182,6 +182,34 @@ void Context::build_prepared(Prepared& out, const lmn_settings* settings, uint32
   }
 }
 
+// Trace reuse, the accounting: `changed_words` = the comparing transposes' words as they came back with the verdict.  A
+// candidate column whose word is not this proof's mark was skipped by all three of its transform launches; the counters and
+// the timings' bytes and butterflies then say what ran (bench.py's roofline divides them by the measured time).  Both
+// counters, the correction and the back-off's count move here, together: a proof that throws in front of its report has
+// moved none of them.
+// Under LMN_COMP_FULL_DOMAIN=1 the timings are left as interpolate_for_commit counted them: that switch exists for A/B runs
+// of the composition, which compare fft_butterflies of two proofs of one context (tests/comp_half_checks.py) - the columns
+// reuse skipped would otherwise be the larger part of the difference.
+void Context::account_trace_reuse(ProofRun& r, const uint32_t* changed_words) {
+  const bool correct_timings = env_int("LMN_COMP_FULL_DOMAIN", 0) == 0;
+  for (const ProofRun::ReuseTable& t : r.reuse_tables) {
+    uint64_t skipped = 0;
+    for (int c = 0; c < 32; ++c)
+      if (((t.candidate_mask >> c) & 1u) && changed_words[t.first_word + c] != r.bad_mark) ++skipped;
+    reuse_counters_[0] += (uint64_t)__builtin_popcount(t.candidate_mask);
+    reuse_counters_[1] += skipped;
+    if (t.table < reuse_.tables.size()) {   // the back-off's count (TraceReuse::Table::misses)
+      int& misses = reuse_.tables[t.table].misses;
+      misses = skipped == 0 ? misses + 1 : 0;
+    }
+    if (!correct_timings) continue;
+    const uint64_t n = 1ull << t.log_size;
+    timings.fft_bytes -= skipped * 20ull * n;                                   // as interpolate_for_commit counted them
+    timings.fft_butterflies -= skipped * (n / 2 + n) * (uint64_t)t.log_size;
+  }
+  r.reuse_tables.clear();
+}
+
 void Context::run_main_trace(ProofRun& r) {
   LMN_RUN_ALIASES(r);
   // ---- PHASE 1: main trace (prover.rs:70-179)
@@ -195,6 +223,28 @@ void Context::run_main_trace(ProofRun& r) {
   const uint32_t bad_mark = shard_.active ? 1u : bad_epoch_;
   const uint32_t* h_bad = nullptr;
   bool any_rows_front = false;
+  // ---- Trace reuse (LMN_TRACE_REUSE, on by default; docs/SWITCHES.md).  One model is proved on many inputs: the id, index,
+  // successor and multiplicity columns of a table are functions of the graph alone (constraints.h graph_only_columns) and
+  // bit-identical from one proof of a context to the next, and the arena still holds the previous proof's evaluation,
+  // coefficient and LDE blocks at the addresses this proof gets (Context::TraceReuse).  The transpose compares those
+  // columns with what it is about to overwrite, word for word, and the three transform launches skip the ones that did not
+  // change.  Off for sharded proofs, the lock-step batch library, row sinks read in place, LMN_ROWS_FUSION, log_blowup != 1
+  // and sizes without the three-launch form.
+#ifdef LMN_BATCH
+  const bool reuse_cfg = false;
+#else
+  const bool reuse_cfg = env_int("LMN_TRACE_REUSE", 1) != 0 && !shard_.active && lb == 1 && env_int("LMN_ROWS_FUSION", 0) == 0;
+#endif
+  const bool reuse_live = reuse_.live && reuse_cfg;   // (validity was cleared when run_setup formed `live`)
+  reuse_.live = false;
+  std::vector<TraceReuse::Table> now(infos.size(), TraceReuse::Table{-1, 0, 0, 0, nullptr, nullptr, nullptr, 0});
+  struct Compared {
+    bool on = false;
+    uint32_t first_word = 0, mask = 0;
+  };
+  std::vector<Compared> compared(infos.size());
+  uint32_t* const d_changed = bad_flag_ + 2;
+  uint32_t changed_words = 0;
   {
     StageTimer st(this, log, stream_, C_TRANSPOSE);
     for (size_t t = 0; t < infos.size(); ++t) {
@@ -236,7 +286,31 @@ void Context::run_main_trace(ProofRun& r) {
         inst[t].trace_evals = nullptr;
       } else {
         uint32_t* evals = arena_.alloc_words((size_t)ti.spec->n_cols * nb);
-        launch_transpose_pad_rows(d_rows, ti.n_rows, ti.spec->n_cols, ti.log_size, evals, nb, blk0, nb, pad, d_bad, stream_, bad_mark);
+        // Only the graph's columns are compared.  A value column (lhs, rhs, out, ...) is transformed in every proof, even
+        // where it repeats - a benchmark proves the same buffers again and again, a service never sees the same input twice -
+        // so what reuse gains in a benchmark is what it gains in real use.
+        const uint32_t mask = graph_only_columns(*ti.spec);
+        const bool table_ok = reuse_cfg && mask != 0u && !rows_front && fft_interp_extend_supported(ti.log_size);
+        if (table_ok) now[t] = {ti.spec->kind, ti.log_size, ti.spec->n_cols, ti.n_rows, evals, nullptr, nullptr, 0};
+        const TraceReuse::Table* prev = reuse_live && t < reuse_.tables.size() ? &reuse_.tables[t] : nullptr;
+        const bool same_table = table_ok && prev && prev->kind == ti.spec->kind && prev->log_size == ti.log_size &&
+                                prev->n_cols == ti.spec->n_cols && prev->n_rows == ti.n_rows && prev->evals == evals;
+        // back-off (TraceReuse::Table::misses): a backed-off table counts its proofs on and is compared again every
+        // REUSE_RETRY-th of them - a context that has settled on one graph after several finds its way back
+        const bool backed_off = same_table && prev->misses >= TraceReuse::REUSE_BACKOFF && prev->misses % TraceReuse::REUSE_RETRY != 0;
+        if (same_table) now[t].misses = !backed_off ? prev->misses
+                                        : prev->misses < 2 * TraceReuse::REUSE_RETRY ? prev->misses + 1
+                                                                                     : prev->misses + 1 - TraceReuse::REUSE_RETRY;
+        if (same_table && !backed_off && changed_words + (uint32_t)ti.spec->n_cols <= (uint32_t)CHANGED_WORDS) {
+          compared[t].on = true;
+          compared[t].first_word = changed_words;
+          compared[t].mask = mask;
+          changed_words += (uint32_t)ti.spec->n_cols;
+          launch_transpose_pad_compare(d_rows, ti.n_rows, ti.spec->n_cols, ti.log_size, evals, pad, d_bad, bad_mark, mask,
+                                       d_changed + compared[t].first_word, bad_mark, stream_);
+        } else {
+          launch_transpose_pad_rows(d_rows, ti.n_rows, ti.spec->n_cols, ti.log_size, evals, nb, blk0, nb, pad, d_bad, stream_, bad_mark);
+        }
         inst[t].trace_evals = evals;
       }
       inst[t].rows_sharded = rows_front;
@@ -247,7 +321,8 @@ void Context::run_main_trace(ProofRun& r) {
   {
     StageTimer st(this, log, stream_, C_MAIN_COMMIT);
     int off = 0;
-    for (auto& ci : inst) {
+    for (size_t t = 0; t < inst.size(); ++t) {
+      Instance& ci = inst[t];
       uint64_t n = 1ull << ci.log_size;
       int nc = ci.spec->n_cols;
       uint32_t* coeffs = arena_.alloc_words((size_t)nc * n);
@@ -270,13 +345,33 @@ void Context::run_main_trace(ProofRun& r) {
           throw LmnError(LMN_ERR_INTERNAL, "main trace: no row pass for a size run_main_trace had chosen it for");
         }
       }
-      if (!fused) co = interpolate_for_commit(coeffs, ci.trace_evals, nc, ci.log_size, -1, ci.rows_sharded);
+      if (!fused) {
+        // the skip argument only where all three blocks lie where the previous proof left them; anything else: every column
+        ColSkip skip{};
+        const uint32_t* prev_lde = nullptr;
+        if (compared[t].on && reuse_.tables[t].coeffs == coeffs) {
+          skip = ColSkip{d_changed + compared[t].first_word, bad_mark, compared[t].mask};
+          prev_lde = reuse_.tables[t].lde;
+        }
+        co = interpolate_for_commit(coeffs, ci.trace_evals, nc, ci.log_size, -1, ci.rows_sharded, skip.changed ? &skip : nullptr, prev_lde);
+        if (co.skipped) {
+          r.reuse_tables.push_back({compared[t].first_word, compared[t].mask, ci.log_size, t});
+        }
+        if (now[t].kind >= 0) {
+          now[t].coeffs = coeffs;
+          now[t].lde = co.lde;
+        }
+      }
       ci.main_start = off;
       off += nc;
       for (int c = 0; c < nc; ++c)
         tree1.cols.push_back({ci.log_size, coeffs + (uint64_t)c * n, co.lde ? co.lde + (uint64_t)c * co.stride : nullptr,
                               co.sharded, co.owner_of(c)});
     }
+    // the last trace launch is enqueued: the record stands for the next proof (a proof that throws later leaves consistent
+    // blocks - the stream still runs what was queued; one that threw above has left the record invalid)
+    reuse_.tables = std::move(now);
+    reuse_.valid = reuse_cfg;
     for (int k = 0; k < n_slots; ++k)  // LuminairClaim::mix_into (crates/air/src/lib.rs:52-104)
       if (proof.claim[k] >= 0) channel.mix_u64((uint64_t)proof.claim[k]);
     r.bad_mark = bad_mark;
@@ -291,6 +386,7 @@ void Context::run_main_trace(ProofRun& r) {
       step.start.n_sent = 0;
       step.start.variant = (cfg.protocol_variant & LMN_PV_DRAW_CTR_U32) ? 1u : 0u;
       step.bad_word = d_bad;
+      step.changed_words = changed_words;   // the comparing transposes' marks come back with the verdict: no wait of their own
       int sets[CHAN_N_ELEMS];
       const int n_draws = relation_draw_sets(cfg.protocol_variant, sets);
       if (n_draws < 1 || n_draws > CHAN_N_ELEMS) throw LmnError(LMN_ERR_INTERNAL, "relation draws: bad count");
@@ -312,9 +408,10 @@ void Context::run_main_trace(ProofRun& r) {
       gather_columns(flags, 0, 1, 1);
       h_bad = (const uint32_t*)stage_download(flags, 4 * n_flags);
     } else {
-      h_bad = (const uint32_t*)stage_download(d_bad, 4);
+      h_bad = (const uint32_t*)stage_download(d_bad, 4 * (2 + (size_t)changed_words));
     }
     lmn_sync(stream_);
+    if (!any_rows_front) account_trace_reuse(r, h_bad + 2);
     bool bad_any = false;
     for (uint32_t k = 0; k < n_flags; ++k) bad_any = bad_any || h_bad[k] == bad_mark;
     if (bad_any) {

@@ -235,8 +235,14 @@ void Context::run_setup(ProofRun& r) {
   if (shard_.active) words += 64ull << std::min(max_lde, std::max(shard_.fri_min_log, 12) + 2);  // replicated small FRI layers + their trees
   words += (16u << 20);                                        // slack: tables, partials, gather buffers
   ensure_twiddles(max_lde);
+  // trace reuse: the previous proof's blocks are where it left them only if nothing but this reset has started over in
+  // the arena since that proof's own; the record is spent here and stands again once this proof has enqueued its main trace
+  const uint64_t gen_before = arena_.generation();
   arena_.reserve(words * 4);
   arena_.reset();
+  reuse_.live = reuse_.valid && reuse_.generation == gen_before && arena_.generation() == gen_before + 1;
+  reuse_.valid = false;
+  reuse_.generation = arena_.generation();
   pin_off_ = 0;
 
   proof.claim.assign(n_slots, -1);

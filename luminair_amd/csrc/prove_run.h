@@ -123,6 +123,14 @@ struct ProofRun {
   std::vector<EvalJob> eval_jobs;        // one per (column, sample point), sampled_values order (plan_eval_jobs)
   EvalJob* d_eval_jobs = nullptr;        // device copy made by the OODS step's workgroup (device-resident transcript)
   uint32_t bad_mark = 0;                 // this proof's mark of the non-canonical-word verdict
+  // trace reuse: the tables whose transforms got a skip argument - their changed[] words, candidate columns and size; the
+  // words come back with the verdict and say what was skipped (Context::account_trace_reuse)
+  struct ReuseTable {
+    uint32_t first_word, candidate_mask;
+    int log_size;
+    size_t table;   // its place in the context's record
+  };
+  std::vector<ReuseTable> reuse_tables;
   // Unsharded proofs go on without the sampled values as well (round 6): k_quot_prepare mixes them, draws the quotient
   // randomness and writes the quotient kernels' tables on the device; the host's first wait is the one for the FRI results,
   // where it replays everything from root 1 on (finish_oods_on_host).  LMN_HOST_QUOT=1 keeps the wait in run_oods.

@@ -98,7 +98,12 @@ class Arena {
  public:
   ~Arena();
   void reserve(size_t bytes);
-  void reset() { off_ = 0; }
+  void reset() {
+    off_ = 0;
+    ++generation_;
+  }
+  // counts the resets and the growths: two equal readings mean that nobody has started over in the arena in between
+  uint64_t generation() const { return generation_; }
   void* alloc_bytes(size_t bytes);
   uint32_t* alloc_words(size_t words) { return (uint32_t*)alloc_bytes(words * 4); }
   uint64_t word_offset(const void* p) const { return (uint64_t)((const char*)p - base_) / 4; }
@@ -109,6 +114,7 @@ class Arena {
  private:
   char* base_ = nullptr;
   size_t cap_ = 0, off_ = 0;
+  uint64_t generation_ = 0;
 };
 
 struct DevColumn {
@@ -460,11 +466,13 @@ class Context {
   // the device, 10: those among them that fell back to the host's grind rounds; 0 for any other number
   // 11, 12: proofs opened by the device plan, fallbacks among them; 13, 14, 15 (diagnostic): plan launches, fetch launches
   // and host waits of open_queries; 16 .. 19: verify_many's proofs judged by the device stage, stage-2 proofs, launches, waits
+  // 20, 21 (trace reuse): candidate columns compared with the previous proof's, columns among them whose transforms were skipped
   uint64_t counter(int which) const {
     return which >= 7 && which <= 10    ? counters_[which - 7]
            : which >= 11 && which <= 12 ? dev_open_counters_[which - 11]
            : which >= 13 && which <= 15 ? open_counters_[which - 13]
            : which >= 16 && which <= 19 ? verify_counters_[which - 16]
+           : which >= 20 && which <= 21 ? reuse_counters_[which - 20]
                                         : 0;
   }
   lmn_config cfg;
@@ -520,6 +528,7 @@ class Context {
     bool owned = false;           // column c's coefficients live on rank `owner_of(c)` only
     int first[9] = {0};           // columns [first[r], first[r + 1]) belong to rank r
     uint32_t* halo = nullptr;     // 4 columns x 2^(log + 1) words, the two neighbour blocks filled in
+    bool skipped = false;         // the transforms ran with the caller's ColSkip
     int owner_of(int c) const {
       if (!owned) return -1;
       int r = 0;
@@ -529,8 +538,11 @@ class Context {
   };
   // evals_row_blocks: `evals` holds this rank's row block of every column (row-parallel transposes / logup); the blocks
   // travel to the columns' owners through one more all-to-all before stage A
+  // skip (trace reuse, the three-launch form only): applied if the LDE block comes to lie at skip_lde, where the columns
+  // it lets through unworked still hold their values; CommitOut::skipped says whether it was
   CommitOut interpolate_for_commit(uint32_t* coeffs, const uint32_t* evals, int ncols, int log_size, int halo_first = -1,
-                                   bool evals_row_blocks = false);
+                                   bool evals_row_blocks = false, const ColSkip* skip = nullptr,
+                                   const uint32_t* skip_lde = nullptr);
   bool shard_all_to_all() const;
   bool shard_a2a_columns(int log_size) const;   // stage A / B for columns of this size
   bool shard_rows_front(int log_size) const;    // row-parallel transposes and logup fractions for tables of this size
@@ -591,8 +603,33 @@ class Context {
   }
   void fetch_root_async(DevMerkle& m);   // m.root_pinned valid after the next sync
   void eval_begin(int32_t* minmax);   // selects the device; the range words start at (INT32_MAX, INT32_MIN), on the stream
-  uint32_t* bad_flag_ = nullptr;  // two device words: [0] marked when a trace table holds a non-canonical M31 word, [1] trace_lut's
+  uint32_t* bad_flag_ = nullptr;  // two device words: [0] marked when a trace table holds a non-canonical M31 word, [1] trace_lut's;
+                                  // behind them the CHANGED_WORDS words of the comparing transposes (trace reuse)
   uint32_t bad_epoch_ = 1;        // the mark of the current unsharded proof (see Context::prove)
+  // Trace reuse (phase_trace.cpp run_main_trace): where the previous proof left the evaluation, coefficient and LDE blocks
+  // of its main trace.  The arena is not cleared between proofs and a pie of the same shape gets the same addresses, so a
+  // column that is bit-identical to the previous proof's needs no transform.  The record may be trusted only while `valid`
+  // (that proof enqueued its whole main-trace phase) and nobody but the next proof's own reset has started over in the
+  // arena since (`generation`); `live` is that verdict, formed by run_setup and consumed by run_main_trace.
+  struct TraceReuse {
+    struct Table {
+      int kind, log_size, n_cols;
+      uint64_t n_rows;   // (where the padding begins: another count is another table, compared with nothing)
+      const uint32_t *evals, *coeffs, *lde;
+      // back-off: consecutive compared proofs of this table in which not one candidate column was unchanged.  From
+      // REUSE_BACKOFF on the table is not compared - a context that proves another graph every time would pay for the
+      // comparison (1.1 % proofs/s at 2^20 rows, profiles/trace_reuse_ab.json) and gain nothing - and the count goes on with
+      // every proof; each time it reaches a multiple of REUSE_RETRY the table is compared once more, and a single unchanged
+      // column ends the back-off.  Another signature (kind, sizes, addresses) starts from zero.
+      int misses;
+    };
+    static constexpr int REUSE_BACKOFF = 2, REUSE_RETRY = 64;
+    std::vector<Table> tables;
+    bool valid = false, live = false;
+    uint64_t generation = 0;
+  } reuse_;
+  uint64_t reuse_counters_[2] = {0, 0};   // counter() 20, 21
+  void account_trace_reuse(struct ProofRun& r, const uint32_t* changed_words);   // phase_trace.cpp
   char* pin_base_ = nullptr;
   size_t pin_cap_ = 0, pin_off_ = 0;
   char *grp_pin_ = nullptr, *grp_dev_ = nullptr;   // open upload group (stage_group_begin)

@@ -145,6 +145,7 @@ void Context::set_shard(uint32_t rank, uint32_t world, uint32_t fri_min_log, con
   lmn_sync(stream_);
   void* keep = shard_.rccl;
   shard_ = Shard{};
+  reuse_.valid = false;   // (trace reuse: a shard being set or cleared ends the record)
   shard_.rccl = keep;
   shard_.active = true;
   shard_.rank = rank;
@@ -158,6 +159,7 @@ void Context::clear_shard() {
   lmn_sync(stream_);
   if (shard_.rccl) rccl_release(shard_.rccl);
   shard_ = Shard{};
+  reuse_.valid = false;
 }
 
 }  // namespace lmn

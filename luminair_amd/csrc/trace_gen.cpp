@@ -452,6 +452,9 @@ void Context::trace_check(const lmn_table* tables, size_t n_tables, const lmn_se
   LMN_HIP_CHECK(hipSetDevice(device_));
 #endif
   if (!tables || n_tables == 0) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "no trace tables");
+  // trace reuse trusts the previous proof's blocks only from one proof straight to the next: any other work of the context in
+  // between ends the record (the scratch below is this call's own, not the arena - the rule is kept simple on purpose)
+  reuse_.valid = false;
   // ---- lmn_prove's input rules (prove_run.h): the same calls in the same order, so the same rule is named with the
   // same code; the text names the table
   const Refusal refuse{tables};
