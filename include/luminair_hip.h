@@ -681,6 +681,47 @@ int lmn_rows_append_lut_ranges(lmn_ctx* ctx, lmn_rows* rows, uint32_t kind, cons
                                uint64_t n, const lmn_node_info* info, const uint32_t* lut_col1_dev, const lmn_range* ranges,
                                uint32_t n_ranges, uint32_t* mult_dev, int32_t* out_dev, uint32_t* refused_dev);
 
+/* ---- Float tensors in and out: `CopyToStwo` / `CopyFromStwo` on the device (crates/graph/src/op/prim.rs:52-101).  The
+ * reference's user-facing tensor is `Vec<f32>`: a graph input becomes Fixed<12> through `StwoData::from_f32`
+ * (`Fixed::from_f64(d as f64)` per element, crates/graph/src/data.rs:17-31) and an output leaves as `d.to_f64() as f32`.
+ * These calls state both rules once, in integers, for float tensors that already lie in HBM.
+ *
+ * Float -> Fixed<12> (dtype LMN_F32 / LMN_F16 / LMN_BF16; the source holds raw IEEE bits, 4 or 2 bytes per element):
+ *  - the exact real value x 4096, rounded to the nearest integer, ties away from zero (`f64::round`; numerair is un-vendored,
+ *    so its rounding is unpinned - DESIGN.md section 2 - as for lmn_lut_from_ranges).  Widening f16 / bf16 is exact, so this
+ *    is what the reference's `d as f64` route gives for the widened value.  +-0 and every denormal give 0.
+ *  - Refused: a NaN of any payload or sign, +-Inf, and a rounded value outside [-(2^30-1), 2^30-1].  A refused element is
+ *    handled as the producers' contract (lmn_trace_elementwise) says: the word P in the Inputs row's val, 0 in the output
+ *    tensor, counted where the form has a counter, and no lane does value-dependent work for it.
+ * Fixed<12> -> float: the exact value v / 4096 rounded once to the format, round-to-nearest-even (bf16 is NOT rounded
+ * through f32); an f16 magnitude above 65504 becomes +-Inf as IEEE says.  A source word outside [-(2^30-1), 2^30-1] cannot
+ * occur in a tensor a producer wrote: its result is unspecified, the call stays memory-safe.
+ *
+ * The four input forms are lmn_trace_elementwise(LMN_KIND_INPUTS, ...), lmn_trace_many_elementwise_v, lmn_rows_append_elementwise_v
+ * and lmn_eval_elementwise_v with the conversion in front, in the SAME launch: rows, output tensor, marks, counters, strides
+ * (0 = shared, with the shared-output rule), stream order, locks and "no call waits" are exactly what those forms document,
+ * and rows and out_dev are word for word what the integer form writes for the converted integers.  src_dev is contiguous;
+ * src_member_stride is in elements of dtype.  Refused before any launch, the argument named by lmn_last_error: an unknown
+ * dtype, a null src_dev, n = 0 (LMN_ERR_EMPTY_TRACE for the three trace forms, LMN_ERR_INVALID_ARGUMENT for the eval form,
+ * as their siblings), a src_dev that is not aligned to the element size, and every error of the sibling form.
+ * libluminair_hip_batch.so exports all five; the sink form refuses there as every lmn_rows_append_* does.
+ *
+ * lmn_tensor_to_float converts n contiguous values and returns when dst_dev is complete, as lmn_download does: a reader on
+ * another stream may use dst_dev at once.  dst_dev is aligned to the element size. */
+#define LMN_F32 0u
+#define LMN_F16 1u
+#define LMN_BF16 2u
+int lmn_trace_inputs_float(lmn_ctx* ctx, uint32_t dtype, const void* src_dev, uint64_t n, const lmn_node_info* info,
+                           uint32_t* rows_dev, uint64_t row_offset, int32_t* out_dev);
+int lmn_trace_many_inputs_float(lmn_ctx* ctx, uint32_t dtype, const void* src_dev, uint64_t src_member_stride, uint64_t n,
+                                const lmn_node_info* info, uint32_t n_members, uint32_t* rows_dev, uint64_t row_offset,
+                                uint64_t rows_member_stride, int32_t* out_dev, uint64_t out_member_stride, uint32_t* refused_dev);
+int lmn_rows_append_inputs_float(lmn_ctx* ctx, lmn_rows* rows, uint32_t dtype, const void* src_dev, uint64_t n,
+                                 const lmn_node_info* info, int32_t* out_dev, uint32_t* refused_dev);
+int lmn_eval_inputs_float(lmn_ctx* ctx, uint32_t dtype, const void* src_dev, uint64_t n, int32_t* out_dev, int32_t* minmax_dev,
+                          uint32_t* refused_dev);
+int lmn_tensor_to_float(lmn_ctx* ctx, uint32_t dtype, const int32_t* src_dev, uint64_t n, void* dst_dev);
+
 /* ---- lmn_trace_check: which rows and which logup tuples break a trace.  lmn_prove answers a bad trace once, at the end of
  * a whole proof, with LMN_ERR_CONSTRAINTS - no table, no row, no constraint - and a trace whose logup relations do not
  * balance is proved all the same (only lmn_verify says LMN_ERR_INVALID_LOGUP).  This call is the prover-side counterpart of

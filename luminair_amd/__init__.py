@@ -7,9 +7,9 @@ gfx950 behind the C ABI of `include/luminair_hip.h`; there is no CPU fallback.
 """
 from .pie import (CircuitSettings, ExecutionResources, Lookup, LookupLayout, LuminairError, LuminairPie, LuminairProof,
                   Metadata, RangeCheckLookup, TraceTable, TraceTableKind)
-from .backend import RowSink, TraceReport
+from .backend import RowSink, TraceReport, from_fixed, to_fixed
 from .graph import DeviceGraph
 from .prover import Prover, ProverPool, check_trace, prove, verify, verify_many
 
 __all__ = ["Lookup", "LookupLayout", "RangeCheckLookup", "CircuitSettings", "ExecutionResources", "LuminairError", "LuminairPie", "LuminairProof", "Metadata",
-           "TraceTable", "TraceTableKind", "Prover", "ProverPool", "prove", "verify", "verify_many", "DeviceGraph", "RowSink", "TraceReport", "check_trace"]
+           "TraceTable", "TraceTableKind", "Prover", "ProverPool", "prove", "verify", "verify_many", "DeviceGraph", "RowSink", "TraceReport", "check_trace", "to_fixed", "from_fixed"]

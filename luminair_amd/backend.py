@@ -311,8 +311,103 @@ EXPORTS = ["lmn_abi_version", "lmn_kind_padding_row", "lmn_strerror", "lmn_last_
            "lmn_settings_prepare", "lmn_prepared_root", "lmn_prepared_lookups", "lmn_prepared_destroy", "lmn_prove_prepared",
            "lmn_prove_submit_prepared", "lmn_batch_prove_prepared",
            "lmn_positions_from_cpu", "lmn_positions_to_cpu", "lmn_positions_log_domain", "lmn_positions_free",
-           "lmn_col_fri_close_keep", "lmn_open_queries", "lmn_verify_many"]
+           "lmn_col_fri_close_keep", "lmn_open_queries", "lmn_verify_many",
+           "lmn_trace_inputs_float", "lmn_trace_many_inputs_float", "lmn_rows_append_inputs_float", "lmn_eval_inputs_float",
+           "lmn_tensor_to_float"]
 TRACE_MANY_MAX = 1024   # LMN_TRACE_MANY_MAX
+F32, F16, BF16 = 0, 1, 2   # LMN_F32 / LMN_F16 / LMN_BF16: the dtype of a float source or destination
+FLOAT_BYTES = {F32: 4, F16: 2, BF16: 2}
+FIXED_MAX = (1 << 30) - 1   # the producers' value range (include/luminair_hip.h, lmn_trace_elementwise)
+
+
+def float_dtype_code(dtype) -> int:
+    """LMN_F32 / LMN_F16 / LMN_BF16 for a numpy or torch float dtype, the string "bfloat16" (numpy has no bf16), or the code
+    itself."""
+    if isinstance(dtype, int) and not isinstance(dtype, bool) and dtype in FLOAT_BYTES:
+        return dtype
+    name = str(dtype).replace("torch.", "")
+    if name in ("bfloat16", "bf16"):
+        return BF16
+    try:
+        name = np.dtype(dtype).name
+    except TypeError:
+        pass
+    if name == "float32":
+        return F32
+    if name == "float16":
+        return F16
+    raise ValueError("float tensors are float32, float16 or bfloat16, not %r" % (dtype,))
+
+
+def _float_bits(x, code: Optional[int] = None):
+    """(raw IEEE bits as int64, exponent bits, mantissa bits) of a float32 / float16 array; code=BF16: `x` holds bf16 bit
+    patterns (uint16) already."""
+    if code == BF16:
+        return np.ascontiguousarray(x).view(np.uint16).astype(np.int64), 8, 7
+    x = np.ascontiguousarray(x)
+    if x.dtype == np.float32:
+        return x.view(np.uint32).astype(np.int64), 8, 23
+    if x.dtype == np.float16:
+        return x.view(np.uint16).astype(np.int64), 5, 10
+    raise ValueError("to_fixed takes float32 or float16 arrays (bfloat16 as uint16 bit patterns with dtype=BF16), not %s" % x.dtype)
+
+
+def to_fixed(x, dtype: Optional[int] = None, refused: Optional[list] = None) -> np.ndarray:
+    """Float -> Fixed<12>, the host mirror of the device rule (`CopyToStwo`: `Fixed::from_f64(d as f64)`, taken as
+    round-to-nearest, ties away from zero - numerair is un-vendored, its rounding unpinned): the exact value x 4096 rounded
+    to the nearest integer, computed from the bit pattern in integers.  +-0 and denormals give 0.  `x`: a float32 or
+    float16 array, or uint16 bf16 bit patterns with dtype=BF16.  Raises ValueError for what the device refuses - NaN, +-Inf, a
+    result outside [-(2^30-1), 2^30-1] - unless `refused` is a list: then the refused elements' flat indices are appended
+    to it and those elements are 0, as in a device tensor.  Returns int32 of x's shape."""
+    bits, eb, mb = _float_bits(x, dtype)
+    shape = np.shape(x)
+    bits = bits.reshape(-1)
+    bias = (1 << (eb - 1)) - 1
+    e = (bits >> mb) & ((1 << eb) - 1)
+    sig = (bits & ((1 << mb) - 1)) | (1 << mb)
+    sh = e - bias - mb + 12                                   # value * 4096 = sig * 2^sh
+    up = sig << np.clip(sh, 0, 31)
+    r = np.clip(-sh, 1, mb + 3)
+    down = np.where(-sh > mb + 2, 0, (sig + (np.int64(1) << (r - 1))) >> r)
+    mag = np.where(sh >= 0, up, down)
+    bad = (e == (1 << eb) - 1) | (mag > FIXED_MAX)
+    mag = np.where((e == 0) | bad, 0, mag)
+    out = np.where((bits >> (eb + mb)) & 1 == 1, -mag, mag).astype(np.int32)
+    if bad.any():
+        if refused is None:
+            raise ValueError("to_fixed: %d elements are NaN, infinite or outside [-(2^30-1), 2^30-1] after scaling "
+                             "(first at flat index %d)" % (int(bad.sum()), int(np.flatnonzero(bad)[0])))
+        refused.extend(int(i) for i in np.flatnonzero(bad))
+    return out.reshape(shape)
+
+
+def from_fixed(v, dtype=np.float32) -> np.ndarray:
+    """Fixed<12> -> float, the host mirror of `lmn_tensor_to_float` (`CopyFromStwo`: `d.to_f64() as f32`): the exact value
+    v / 4096 rounded once to the format, round-to-nearest-even, in integers.  dtype: np.float32, np.float16, or BF16 /
+    "bfloat16" - then the result is the uint16 bf16 bit patterns (numpy has no bfloat16)."""
+    code = float_dtype_code(dtype)
+    eb, mb = {F32: (8, 23), F16: (5, 10), BF16: (8, 7)}[code]
+    v = np.asarray(v).astype(np.int64)
+    shape = v.shape
+    v = v.reshape(-1)
+    bias = (1 << (eb - 1)) - 1
+    mag = np.abs(v)
+    p = np.zeros_like(mag)                                    # the leading bit of mag
+    for k in (16, 8, 4, 2, 1):
+        big = (mag >> (p + k)) != 0
+        p = np.where(big, p + k, p)
+    r = np.clip(p - mb, 1, 32)
+    rem, half, q_dn = mag & ((np.int64(1) << r) - 1), np.int64(1) << (r - 1), mag >> r
+    q_dn = q_dn + ((rem > half) | ((rem == half) & (q_dn & 1 == 1)))
+    q = np.where(p <= mb, mag << np.clip(mb - p, 0, 32), q_dn)
+    bits = ((p - 12 + bias - 1) << mb) + q
+    inf = ((1 << eb) - 1) << mb
+    bits = np.where(bits >= inf, inf, bits)
+    bits = np.where(mag == 0, 0, bits | np.where(v < 0, 1 << (eb + mb), 0))
+    if code == F32:
+        return bits.astype(np.uint32).view(np.float32).reshape(shape)
+    out = bits.astype(np.uint16)
+    return (out.view(np.float16) if code == F16 else out).reshape(shape)
 
 
 class LuminairBackendError(RuntimeError):
@@ -529,6 +624,11 @@ class Library:
                                               U64, VP]
         lib.lmn_trace_many_lut_ranges.argtypes = [VP, U32, VP, C.POINTER(LmnView), U64, U64, C.POINTER(LmnNodeInfo), VP,
                                                   C.POINTER(LmnRange), U32, U32, VP, U64, VP, U64, U64, VP, U64, VP]
+        lib.lmn_trace_inputs_float.argtypes = [VP, U32, VP, U64, C.POINTER(LmnNodeInfo), VP, U64, VP]
+        lib.lmn_trace_many_inputs_float.argtypes = [VP, U32, VP, U64, U64, C.POINTER(LmnNodeInfo), U32, VP, U64, U64, VP, U64, VP]
+        lib.lmn_rows_append_inputs_float.argtypes = [VP, VP, U32, VP, U64, C.POINTER(LmnNodeInfo), VP, VP]
+        lib.lmn_eval_inputs_float.argtypes = [VP, U32, VP, U64, VP, VP, VP]
+        lib.lmn_tensor_to_float.argtypes = [VP, U32, VP, U64, VP]
 
     def eval_reduce_split(self, dim: int, back: int) -> int:
         """How `lmn_eval_reduce` maps (dim, back) onto lanes: 0 = one lane per output element, 1 = one wave per group."""
@@ -1608,6 +1708,57 @@ class Context:
         minmax = minmax or self.alloc(8)
         self._check(self.lib.lib.lmn_tensor_range(self.handle, buf.ptr if buf is not None else None, n, minmax.ptr))
         return minmax
+
+    # ---- float tensors in and out (`CopyToStwo` / `CopyFromStwo`): the Inputs producers reading raw float bits of `dtype`
+    # (F32 / F16 / BF16), converted in the launch that writes the rows, and the way back.  `src` is a DeviceBuffer or a
+    # device address (an int: memory of another owner, a torch tensor's data_ptr()); nothing but tensor_to_float waits.
+    @staticmethod
+    def _addr(b):
+        return b.ptr if isinstance(b, DeviceBuffer) else b
+
+    def trace_inputs_float(self, dtype: int, src, n: int, node_id: int, num_consumers: int, is_final_output: bool = False,
+                           rows: Optional[DeviceBuffer] = None, row_offset: int = 0, out: Optional[DeviceBuffer] = None,
+                           sink: Optional["RowSink"] = None, refused: Optional[DeviceBuffer] = None):
+        """`lmn_trace_inputs_float`, or with sink= `lmn_rows_append_inputs_float`: `trace_elementwise(Inputs)` on a float
+        source.  Returns (rows DeviceBuffer or the sink, out DeviceBuffer)."""
+        if rows is None and sink is None:
+            rows = self.alloc((row_offset + n) * 7 * 4)
+        out = out or self.alloc(max(n, 1) * 4)
+        info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(0, 0), num_consumers, 1 if is_final_output else 0, (C.c_int32 * 2)(0, 0))
+        if sink is not None:
+            self._check(self.lib.lib.lmn_rows_append_inputs_float(self.handle, sink.handle, dtype, self._addr(src), n, C.byref(info),
+                                                                  out.ptr, self._addr(refused)))
+            return sink, out
+        self._check(self.lib.lib.lmn_trace_inputs_float(self.handle, dtype, self._addr(src), n, C.byref(info), rows.ptr, row_offset,
+                                                        out.ptr))
+        return rows, out
+
+    def trace_many_inputs_float(self, dtype: int, src, n: int, n_members: int, node_id: int, num_consumers: int,
+                                rows: DeviceBuffer, rows_stride: int, out: Optional[DeviceBuffer], out_stride: int,
+                                src_stride: int = 0, is_final_output: bool = False, row_offset: int = 0,
+                                refused: Optional[DeviceBuffer] = None):
+        """`lmn_trace_many_inputs_float`: `trace_many_elementwise(Inputs)` on a float source; `src_stride` in elements of
+        `dtype` (0: one source shared by all members)."""
+        info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(0, 0), num_consumers, 1 if is_final_output else 0, (C.c_int32 * 2)(0, 0))
+        self._check(self.lib.lib.lmn_trace_many_inputs_float(
+            self.handle, dtype, self._addr(src), src_stride, n, C.byref(info), n_members, self._addr(rows), row_offset, rows_stride,
+            self._addr(out), out_stride, self._addr(refused)))
+        return rows, out
+
+    def eval_inputs_float(self, dtype: int, src, n: int, out: Optional[DeviceBuffer] = None,
+                          minmax: Optional[DeviceBuffer] = None, refused: Optional[DeviceBuffer] = None) -> DeviceBuffer:
+        """`lmn_eval_inputs_float`: `eval_elementwise(Inputs)` on a float source."""
+        out = out or self.alloc(max(n, 1) * 4)
+        self._check(self.lib.lib.lmn_eval_inputs_float(self.handle, dtype, self._addr(src), n, out.ptr, self._addr(minmax),
+                                                       self._addr(refused)))
+        return out
+
+    def tensor_to_float(self, dtype: int, src, n: int, dst=None):
+        """`lmn_tensor_to_float`: n Fixed<12> values -> floats of `dtype` in `dst` (a DeviceBuffer, a device address, or
+        None: a new DeviceBuffer).  Returns `dst` when the result is complete."""
+        dst = dst if dst is not None else self.alloc(max(n, 1) * FLOAT_BYTES.get(dtype, 4))
+        self._check(self.lib.lib.lmn_tensor_to_float(self.handle, dtype, self._addr(src), n, self._addr(dst)))
+        return dst
 
     def _marshal_tables(self, tables, luts):
         """-> (LmnTable array, n, LmnSettings, objects that must stay alive while the library reads them)"""

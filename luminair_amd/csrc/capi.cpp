@@ -463,6 +463,14 @@ int lmn_rows_append_lut_ranges(lmn_ctx* ctx, lmn_rows* rows, uint32_t kind, cons
                      });
 }
 
+// (a null src_dev is named by Context::rows_append_inputs_float, behind an unknown dtype)
+int lmn_rows_append_inputs_float(lmn_ctx* ctx, lmn_rows* rows, uint32_t dtype, const void* src_dev, uint64_t n,
+                                 const lmn_node_info* info, int32_t* out_dev, uint32_t* refused_dev) {
+  return rows_append(ctx, rows, "lmn_rows_append_inputs_float", !info ? "info" : nullptr, [&](lmn::RowSink& sink) {
+    ctx->impl->rows_append_inputs_float(sink, dtype, src_dev, n, *info, out_dev, refused_dev);
+  });
+}
+
 int lmn_upload(lmn_ctx* ctx, const void* host, size_t bytes, void** device_out) {
   if (!ctx || !host || !device_out) return LMN_ERR_INVALID_ARGUMENT;
   return guard(ctx, [&] { *device_out = ctx->impl->upload(host, bytes); });
@@ -739,6 +747,42 @@ int lmn_tensor_range(lmn_ctx* ctx, const int32_t* buf_dev, uint64_t n, int32_t* 
   if (!buf_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_tensor_range: null buf_dev");
   if (!minmax_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_tensor_range: null minmax_dev");
   return guard(ctx, [&] { ctx->impl->tensor_range(buf_dev, n, minmax_dev); });
+}
+
+// ---- float tensors in and out (trace_gen.cpp): every refusal names its argument; dtype, src_dev and n are checked by the
+// context, in that order, in front of the sibling form's own rules
+int lmn_trace_inputs_float(lmn_ctx* ctx, uint32_t dtype, const void* src_dev, uint64_t n, const lmn_node_info* info,
+                           uint32_t* rows_dev, uint64_t row_offset, int32_t* out_dev) {
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  if (!info) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_inputs_float: null info");
+  if (!rows_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_inputs_float: null rows_dev");
+  return guard(ctx, [&] { ctx->impl->trace_inputs_float(dtype, src_dev, n, *info, rows_dev, row_offset, out_dev); });
+}
+
+int lmn_trace_many_inputs_float(lmn_ctx* ctx, uint32_t dtype, const void* src_dev, uint64_t src_member_stride, uint64_t n,
+                                const lmn_node_info* info, uint32_t n_members, uint32_t* rows_dev, uint64_t row_offset,
+                                uint64_t rows_member_stride, int32_t* out_dev, uint64_t out_member_stride, uint32_t* refused_dev) {
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  if (n_members == 0) return LMN_OK;
+  if (!info) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_inputs_float: null info");
+  if (!rows_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_inputs_float: null rows_dev");
+  return guard(ctx, [&] {
+    ctx->impl->trace_many_inputs_float(dtype, src_dev, src_member_stride, n, *info, n_members, rows_dev, row_offset,
+                                       rows_member_stride, out_dev, out_member_stride, refused_dev);
+  });
+}
+
+int lmn_eval_inputs_float(lmn_ctx* ctx, uint32_t dtype, const void* src_dev, uint64_t n, int32_t* out_dev, int32_t* minmax_dev,
+                          uint32_t* refused_dev) {
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  if (!out_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_eval_inputs_float: null out_dev");
+  return guard(ctx, [&] { ctx->impl->eval_inputs_float(dtype, src_dev, n, out_dev, minmax_dev, refused_dev); });
+}
+
+int lmn_tensor_to_float(lmn_ctx* ctx, uint32_t dtype, const int32_t* src_dev, uint64_t n, void* dst_dev) {
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  if (!src_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_tensor_to_float: null src_dev");
+  return guard(ctx, [&] { ctx->impl->tensor_to_float(dtype, src_dev, n, dst_dev); });
 }
 
 int lmn_trace_check(lmn_ctx* ctx, const lmn_table* tables, size_t n_tables, const lmn_settings* settings,

@@ -606,6 +606,19 @@ bool eval_reduce_by_wave(uint64_t dim, uint64_t back);
 void launch_eval_reduce(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back, int32_t* out,
                         int32_t* minmax, uint32_t* refused, lmn_stream_t s);
 void launch_tensor_range(const int32_t* buf, uint64_t n, int32_t* minmax, lmn_stream_t s);
+// Float tensors in and out (kernels_trace.hip float_bits_to_fixed / fixed_to_float_bits): the Inputs producers reading raw
+// float bits of dtype LMN_F32 / LMN_F16 / LMN_BF16 - row, column, many-member and eval form, the conversion inside the launch
+// that writes the rows - and the way back.  src_ms in elements of the dtype.
+void launch_trace_inputs_float(uint32_t dtype, const void* src, uint64_t n, const TraceNode& nd, uint32_t* rows, int32_t* out,
+                               lmn_stream_t s);
+void launch_trace_inputs_float_cols(uint32_t dtype, const void* src, uint64_t n, const TraceNode& nd, uint32_t* cols,
+                                    uint64_t col_stride, int32_t* out, uint32_t* bad_word, uint32_t* refused, lmn_stream_t s);
+void launch_trace_many_inputs_float(uint32_t dtype, const void* src, uint64_t src_ms, uint64_t n, const TraceNode& nd,
+                                    uint32_t n_members, uint32_t* rows, uint64_t rows_ms, int32_t* out, uint64_t out_ms,
+                                    uint32_t* refused, lmn_stream_t s);
+void launch_eval_inputs_float(uint32_t dtype, const void* src, uint64_t n, int32_t* out, int32_t* minmax, uint32_t* refused,
+                              lmn_stream_t s);
+void launch_tensor_to_float(uint32_t dtype, const int32_t* src, uint64_t n, void* dst, lmn_stream_t s);
 
 // ---- lmn_trace_check (trace_gen.cpp): which rows break a local constraint, which logup tuples do not balance.
 // One open-addressing table per relation element set: entry i = {keys[i] = val | id << 31 (TC_EMPTY: free), sums[i] = the

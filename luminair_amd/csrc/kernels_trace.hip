@@ -188,6 +188,74 @@ LMN_HD uint32_t fixed_to_m31(int64_t v) {
   return v < 0 && w ? P31 - w : w;
 }
 
+// ---- Float tensors in and out (`CopyToStwo` / `CopyFromStwo`, crates/graph/src/op/prim.rs:52-101: `StwoData::from_f32` is
+// `Fixed::from_f64(d as f64)` per element, crates/graph/src/data.rs:17-31, and the way back is `d.to_f64() as f32`).  Both
+// rules are integer decodes of the IEEE bit pattern - EB exponent bits, MB mantissa bits: f32 <8, 23>, f16 <5, 10>,
+// bf16 <8, 7> - so the library still does no floating point and the result cannot depend on a wave's denormal or rounding
+// mode.
+// Float -> Fixed<12>: the exact value x 4096 rounded to the nearest integer, ties away from zero (`f64::round`; numerair is
+// un-vendored, its rounding unpinned).  +-0 and every denormal give 0 (the largest f16 denormal x 4096 is below 1/4).  A NaN,
+// an infinity and a rounded value outside fixed_ok are refused: FLOAT_REFUSED, which no range check accepts, so the element
+// takes the producers' ordinary refusal (P in the row, 0 in the tensor, counted).  Straight-line code: a refused element does
+// the same work as any other.
+constexpr int64_t FLOAT_REFUSED = INT64_MIN;
+template <int EB, int MB>
+LMN_HD int64_t float_bits_to_fixed(uint32_t bits) {
+  constexpr int BIAS = (1 << (EB - 1)) - 1;
+  const uint32_t e = (bits >> MB) & ((1u << EB) - 1u);
+  const uint64_t sig = (uint64_t)((bits & ((1u << MB) - 1u)) | (1u << MB));   // 1.m as an integer: value = sig * 2^(e - BIAS - MB)
+  const int sh = (int)e - BIAS - MB + 12;                                     // value * 4096 = sig * 2^sh
+  uint64_t mag;
+  if (sh >= 0) mag = sig << (sh < 31 ? sh : 31);                              // >= 2^31 from sh = 31 - MB on: refused below
+  else if (-sh > MB + 2) mag = 0;                                             // below 1/4
+  else mag = (sig + (1ull << (-sh - 1))) >> -sh;                              // floor(x + 1/2): ties away from zero
+  const bool refused = e == (1u << EB) - 1u || mag > (uint64_t)FIXED_MAX;     // Inf / NaN, or outside the value range
+  if (e == 0u) mag = 0;                                                       // zero and the denormals
+  return refused ? FLOAT_REFUSED : (bits >> (EB + MB)) & 1u ? -(int64_t)mag : (int64_t)mag;
+}
+// Fixed<12> -> float: the exact value v / 4096 rounded ONCE to the format, round-to-nearest-even (for f32 what
+// `d.to_f64() as f32` gives: v / 4096 is exact in f64).  Every |v| >= 1 is 2^-12 or more, a normal number in all three
+// formats; a magnitude above the format's largest finite value becomes +-Inf (f16 only).  Defined for every 32-bit word
+// - a word outside fixed_ok cannot occur in a tensor a producer wrote; its result is unspecified.
+template <int EB, int MB>
+LMN_HD uint32_t fixed_to_float_bits(int32_t v) {
+  constexpr int BIAS = (1 << (EB - 1)) - 1;
+  const uint32_t sign = v < 0 ? 1u << (EB + MB) : 0u;
+  const uint32_t mag = v < 0 ? 0u - (uint32_t)v : (uint32_t)v;
+  if (mag == 0u) return 0u;
+  int p = 31;   // the leading bit: mag = 1.xxx * 2^p, the value 1.xxx * 2^(p - 12)
+  while (!(mag >> p)) --p;
+  uint32_t q;   // 1.m as an integer of MB + 1 bits (MB + 2 when the rounding carries)
+  if (p <= MB) {
+    q = mag << (MB - p);
+  } else {
+    const int r = p - MB;
+    const uint32_t rem = mag & ((1u << r) - 1u), half = 1u << (r - 1);
+    q = mag >> r;
+    q += rem > half || (rem == half && (q & 1u)) ? 1u : 0u;
+  }
+  uint32_t bits = ((uint32_t)(p - 12 + BIAS - 1) << MB) + q;   // the leading 1 of q - or its carry - counts the exponent up
+  if ((bits >> MB) >= (1u << EB) - 1u) bits = ((1u << EB) - 1u) << MB;
+  return sign | bits;
+}
+// Where a producer's operand comes from: an int32 Fixed<12> tensor, or raw float bits of dtype LMN_F32 / LMN_F16 / LMN_BF16
+// (SRC = the dtype) converted as they are read.  The float forms hand their source's address through the operand's
+// `const int32_t*` parameter; src_at and src_value give it its element size back.
+constexpr int SRC_FIXED = -1;
+template <int SRC>
+LMN_HD const int32_t* src_at(const int32_t* base, uint64_t elems) {
+  constexpr uint64_t BYTES = SRC == SRC_FIXED || SRC == 0 ? 4 : 2;
+  return (const int32_t*)((const char*)base + elems * BYTES);
+}
+template <int SRC>
+LMN_HD int64_t src_value(const int32_t* __restrict__ base, uint64_t i) {
+  static_assert(SRC >= SRC_FIXED && SRC <= 2, "LMN_F32, LMN_F16 or LMN_BF16");
+  if (SRC == 0) return float_bits_to_fixed<8, 23>(((const uint32_t*)base)[i]);
+  if (SRC == 1) return float_bits_to_fixed<5, 10>(((const uint16_t*)base)[i]);
+  if (SRC == 2) return float_bits_to_fixed<8, 7>(((const uint16_t*)base)[i]);
+  return base[i];
+}
+
 LMN_D uint64_t view_offset(const TraceView& v, uint64_t r) {
   if (v.ndim == 0) return r;
   int64_t off = v.offset;
@@ -310,12 +378,15 @@ struct RowOut<NC, true, ST> {   // the column form
 // The row rule of the elementwise kinds, stated once for k_trace_elementwise (one tensor per launch) and
 // k_trace_many_elementwise (blockIdx.y = the member): the pointers are the launch's own or the member's bases, blockIdx.x is
 // the tile of TPB rows in both.  MANY or COLS: the refused elements are counted in *refused (may be null).  COLS: the
-// column form of the single launch (k_sink_elementwise), see TraceDst.
-template <int KIND, bool MANY, bool COLS = false>
+// column form of the single launch (k_sink_elementwise), see TraceDst.  SRC: what `lhs` holds (src_value; a float source is
+// Inputs' alone - k_trace_inputs_float and its siblings: the conversion happens where the row is built, the converted
+// tensor is never read back).
+template <int KIND, bool MANY, bool COLS = false, int SRC = SRC_FIXED>
 LMN_D void trace_elementwise_rows(const int32_t* __restrict__ lhs, const TraceView& lv, const int32_t* __restrict__ rhs,
                                   const TraceView& rv, uint64_t n, const TraceNode& nd, const TraceDst& dst,
                                   int32_t* __restrict__ out, uint32_t* __restrict__ aux, uint32_t* __restrict__ refused) {
   static_assert(!(MANY && COLS), "the many-member forms keep rows only");
+  static_assert(SRC == SRC_FIXED || KIND == 15, "float sources feed graph inputs only");
   constexpr int NC = trace_ncols(KIND);
   RowOut<NC, COLS> ro;
   const uint64_t row0 = (uint64_t)blockIdx.x * TPB;
@@ -324,7 +395,7 @@ LMN_D void trace_elementwise_rows(const int32_t* __restrict__ lhs, const TraceVi
   if (r < n) {
     uint32_t* t = ro.t;
     const bool ref_contig = KIND == 16 && nd.phys_n != 0;
-    const int64_t a = lhs[view_offset(lv, ref_contig ? r % nd.out_n : r)];
+    const int64_t a = src_value<SRC>(lhs, view_offset(lv, ref_contig ? r % nd.out_n : r));
     const uint32_t idx = (uint32_t)r, last = r + 1 == (ref_contig ? nd.phys_n : n) ? 1u : 0u;
     if (ref_contig) {
       // LuminairContiguous::process_trace as the reference writes it (prim.rs:253-296): row idx pairs the idx-th
@@ -638,6 +709,65 @@ void launch_trace_many_elementwise(int kind, const int32_t* lhs, const TraceView
 #undef LMN_MANY_CASE
 }
 
+// The float forms of the Inputs producers (lmn_trace_inputs_float and its many and sink siblings): k_trace_elementwise<15>,
+// k_sink_elementwise<15> and k_trace_many_elementwise<15> with a float source - the same row rule, RowOut and TraceDst, the
+// conversion where the row is built.  A member's source is src_ms elements of the dtype behind the previous member's.
+template <int SRC>
+LMN_KERNEL k_trace_inputs_float(const int32_t* __restrict__ src, uint64_t n, TraceNode nd, uint32_t* __restrict__ rows,
+                                int32_t* __restrict__ out) {
+  trace_elementwise_rows<15, false, false, SRC>(src, TraceView{}, nullptr, TraceView{}, n, nd, TraceDst{rows, 0, nullptr}, out,
+                                                nullptr, nullptr);
+}
+template <int SRC>
+LMN_KERNEL k_sink_inputs_float(const int32_t* __restrict__ src, uint64_t n, TraceNode nd, uint32_t* __restrict__ cols,
+                               uint64_t col_stride, int32_t* __restrict__ out, uint32_t* __restrict__ bad_word,
+                               uint32_t* __restrict__ refused) {
+  trace_elementwise_rows<15, false, true, SRC>(src, TraceView{}, nullptr, TraceView{}, n, nd, TraceDst{cols, col_stride, bad_word},
+                                               out, nullptr, refused);
+}
+template <int SRC>
+LMN_KERNEL k_trace_many_inputs_float(const int32_t* __restrict__ src, uint64_t src_ms, uint64_t n, TraceNode nd,
+                                     uint32_t* __restrict__ rows, uint64_t rows_ms, int32_t* __restrict__ out, uint64_t out_ms,
+                                     uint32_t* __restrict__ refused) {
+  const uint64_t m = blockIdx.y;
+  trace_elementwise_rows<15, true, false, SRC>(src_at<SRC>(src, m * src_ms), TraceView{}, nullptr, TraceView{}, n, nd,
+                                               TraceDst{rows + m * rows_ms, 0, nullptr}, many_out_base(out, out_ms, m), nullptr,
+                                               refused ? refused + m : nullptr);
+}
+// X(SRC) launches one instantiation
+#define LMN_FLOAT_DTYPES(what, X)                     \
+  switch (dtype) {                                    \
+    case 0: X(0); break;                              \
+    case 1: X(1); break;                              \
+    case 2: X(2); break;                              \
+    default: throw LmnError(-100, what ": unsupported dtype"); \
+  }
+void launch_trace_inputs_float(uint32_t dtype, const void* src, uint64_t n, const TraceNode& nd, uint32_t* rows, int32_t* out,
+                               lmn_stream_t s) {
+  const dim3 g(cdiv(n, TPB)), b(TPB);
+  const int32_t* lhs = (const int32_t*)src;
+#define LMN_X(S) LMN_LAUNCH(k_trace_inputs_float<S>, g, b, 0, s, lhs, n, nd, rows, out)
+  LMN_FLOAT_DTYPES("trace_inputs_float", LMN_X)
+#undef LMN_X
+}
+void launch_trace_inputs_float_cols(uint32_t dtype, const void* src, uint64_t n, const TraceNode& nd, uint32_t* cols,
+                                    uint64_t col_stride, int32_t* out, uint32_t* bad_word, uint32_t* refused, lmn_stream_t s) {
+  const dim3 g(cdiv(n, TPB)), b(TPB);
+  const int32_t* lhs = (const int32_t*)src;
+#define LMN_X(S) LMN_LAUNCH(k_sink_inputs_float<S>, g, b, 0, s, lhs, n, nd, cols, col_stride, out, bad_word, refused)
+  LMN_FLOAT_DTYPES("trace_inputs_float_cols", LMN_X)
+#undef LMN_X
+}
+void launch_trace_many_inputs_float(uint32_t dtype, const void* src, uint64_t src_ms, uint64_t n, const TraceNode& nd,
+                                    uint32_t n_members, uint32_t* rows, uint64_t rows_ms, int32_t* out, uint64_t out_ms,
+                                    uint32_t* refused, lmn_stream_t s) {
+  const dim3 g(cdiv(n, TPB), n_members), b(TPB);
+  const int32_t* lhs = (const int32_t*)src;
+#define LMN_X(S) LMN_LAUNCH(k_trace_many_inputs_float<S>, g, b, 0, s, lhs, src_ms, n, nd, rows, rows_ms, out, out_ms, refused)
+  LMN_FLOAT_DTYPES("trace_many_inputs_float", LMN_X)
+#undef LMN_X
+}
+
 // LookupLayout::find_index: the LUT row of the range that holds `a`, -1 when no range does (few ranges: a linear scan of
 // block-uniform bounds)
 LMN_D int64_t lut_find_index(const LutRanges& rg, int64_t a) {
@@ -791,17 +921,18 @@ void launch_eval_init(int32_t* minmax, lmn_stream_t s) { LMN_LAUNCH(k_eval_init,
 
 // One lane per element, operands through their views, coalesced int32 stores; no LDS tile, and LessThan touches no
 // multiplicity table.
-template <int KIND>
-LMN_KERNEL k_eval_elementwise(const int32_t* __restrict__ lhs, TraceView lv, const int32_t* __restrict__ rhs, TraceView rv,
-                              uint64_t n, int32_t* __restrict__ out, int32_t* __restrict__ minmax,
-                              uint32_t* __restrict__ refused) {
+// (the body once, for k_eval_elementwise and k_eval_inputs_float: SRC as in trace_elementwise_rows)
+template <int KIND, int SRC = SRC_FIXED>
+LMN_D void eval_elementwise_values(const int32_t* __restrict__ lhs, const TraceView& lv, const int32_t* __restrict__ rhs,
+                                   const TraceView& rv, uint64_t n, int32_t* __restrict__ out, int32_t* __restrict__ minmax,
+                                   uint32_t* __restrict__ refused) {
   constexpr bool BINARY = KIND == 0 || KIND == 1 || KIND == 8 || KIND == 13;
   const uint64_t r = (uint64_t)blockIdx.x * TPB + threadIdx.x;
   const bool on = r < n;
   int32_t o = 0;
   bool bad = false;
   if (on) {
-    const int64_t a = lhs[view_offset(lv, r)];
+    const int64_t a = src_value<SRC>(lhs, view_offset(lv, r));
     const int64_t b = BINARY ? (int64_t)rhs[view_offset(rv, r)] : 0;
     const ElemValue e = elem_value<KIND>(a, b);
     o = (int32_t)e.out;
@@ -809,6 +940,17 @@ LMN_KERNEL k_eval_elementwise(const int32_t* __restrict__ lhs, TraceView lv, con
     out[r] = o;
   }
   eval_finish(on ? o : INT32_MAX, on ? o : INT32_MIN, wave_count(bad), minmax, refused);
+}
+template <int KIND>
+LMN_KERNEL k_eval_elementwise(const int32_t* __restrict__ lhs, TraceView lv, const int32_t* __restrict__ rhs, TraceView rv,
+                              uint64_t n, int32_t* __restrict__ out, int32_t* __restrict__ minmax,
+                              uint32_t* __restrict__ refused) {
+  eval_elementwise_values<KIND>(lhs, lv, rhs, rv, n, out, minmax, refused);
+}
+template <int SRC>
+LMN_KERNEL k_eval_inputs_float(const int32_t* __restrict__ src, uint64_t n, int32_t* __restrict__ out, int32_t* __restrict__ minmax,
+                               uint32_t* __restrict__ refused) {
+  eval_elementwise_values<15, SRC>(src, TraceView{}, nullptr, TraceView{}, n, out, minmax, refused);
 }
 
 void launch_eval_elementwise(int kind, const int32_t* lhs, const TraceView& lv, const int32_t* rhs, const TraceView& rv,
@@ -826,6 +968,33 @@ void launch_eval_elementwise(int kind, const int32_t* lhs, const TraceView& lv, 
     default: throw LmnError(-100, "eval_elementwise: unsupported kind");
   }
 }
+
+void launch_eval_inputs_float(uint32_t dtype, const void* src, uint64_t n, int32_t* out, int32_t* minmax, uint32_t* refused,
+                              lmn_stream_t s) {
+  const dim3 g(cdiv(n, TPB)), b(TPB);
+  const int32_t* lhs = (const int32_t*)src;
+#define LMN_X(S) LMN_LAUNCH(k_eval_inputs_float<S>, g, b, 0, s, lhs, n, out, minmax, refused)
+  LMN_FLOAT_DTYPES("eval_inputs_float", LMN_X)
+#undef LMN_X
+}
+
+// lmn_tensor_to_float (`CopyFromStwo`): one lane per element, fixed_to_float_bits, coalesced 4- or 2-byte stores
+template <int DT>
+LMN_KERNEL k_tensor_to_float(const int32_t* __restrict__ src, uint64_t n, void* __restrict__ dst) {
+  const uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= n) return;
+  const int32_t v = src[i];
+  if (DT == 0) ((uint32_t*)dst)[i] = fixed_to_float_bits<8, 23>(v);
+  else if (DT == 1) ((uint16_t*)dst)[i] = (uint16_t)fixed_to_float_bits<5, 10>(v);
+  else ((uint16_t*)dst)[i] = (uint16_t)fixed_to_float_bits<8, 7>(v);
+}
+void launch_tensor_to_float(uint32_t dtype, const int32_t* src, uint64_t n, void* dst, lmn_stream_t s) {
+  const dim3 g(cdiv(n, TPB)), b(TPB);
+#define LMN_X(S) LMN_LAUNCH(k_tensor_to_float<S>, g, b, 0, s, src, n, dst)
+  LMN_FLOAT_DTYPES("tensor_to_float", LMN_X)
+#undef LMN_X
+}
+#undef LMN_FLOAT_DTYPES
 
 // out = lut_col1[find_index(input)]; an input outside every range is a refused element (the trace form fails the call
 // instead: a dry run must not wait per node).  No multiplicity increments.

@@ -457,6 +457,16 @@ class Context {
   void eval_lut(uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t n, const uint32_t* lut_col1,
                 const lmn_range* ranges, uint32_t n_ranges, int32_t* out, int32_t* minmax, uint32_t* refused);
   void tensor_range(const int32_t* buf, uint64_t n, int32_t* minmax);
+  // lmn_*_inputs_float / lmn_tensor_to_float (trace_gen.cpp): graph inputs from raw float bits, outputs back to floats
+  void trace_inputs_float(uint32_t dtype, const void* src, uint64_t n, const lmn_node_info& info, uint32_t* rows,
+                          uint64_t row_offset, int32_t* out);
+  void trace_many_inputs_float(uint32_t dtype, const void* src, uint64_t src_ms, uint64_t n, const lmn_node_info& info,
+                               uint32_t n_members, uint32_t* rows, uint64_t row_offset, uint64_t rows_ms, int32_t* out,
+                               uint64_t out_ms, uint32_t* refused);
+  void rows_append_inputs_float(RowSink& sink, uint32_t dtype, const void* src, uint64_t n, const lmn_node_info& info, int32_t* out,
+                                uint32_t* refused);
+  void eval_inputs_float(uint32_t dtype, const void* src, uint64_t n, int32_t* out, int32_t* minmax, uint32_t* refused);
+  void tensor_to_float(uint32_t dtype, const int32_t* src, uint64_t n, void* dst);
   void device_free(void* p);
   // lmn_trace_check (trace_gen.cpp): the rows that break a local constraint and the logup tuples that do not balance
   void trace_check(const lmn_table* tables, size_t n_tables, const lmn_settings* settings, lmn_trace_report& report);

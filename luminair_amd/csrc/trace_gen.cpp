@@ -409,6 +409,84 @@ void Context::rows_append_lut(RowSink& sink, uint32_t kind, const int32_t* input
   ap.done();
 }
 
+// ------------------------------------------------------------------------------------ float tensors in and out
+// `CopyToStwo` on raw float bits (prim.rs:52-101): the four Inputs producers - row, many-member, sink and eval form - with
+// the float -> Fixed<12> rule (kernels_trace.hip float_bits_to_fixed) inside the launch that writes the rows, and
+// `CopyFromStwo` back.  The float arguments are checked first, then the sibling form's own rules apply, with its codes.
+namespace {
+void check_float_ptr(const char* call, uint32_t dtype, const void* p, const char* name) {
+  if (dtype != LMN_F32 && dtype != LMN_F16 && dtype != LMN_BF16)
+    many_bad(call, "dtype " + std::to_string(dtype) + " is not LMN_F32, LMN_F16 or LMN_BF16");
+  if (!p) many_bad(call, std::string("null ") + name);
+  if ((uintptr_t)p % (dtype == LMN_F32 ? 4u : 2u)) many_bad(call, std::string(name) + " is not aligned to the dtype's element size");
+}
+// n = 0 with the code of the integer trace forms (check_elementwise), the argument named
+void check_float_rows(const char* call, uint64_t n) {
+  if (n == 0) throw LmnError(LMN_ERR_EMPTY_TRACE, std::string(call) + ": n is 0 (TraceError::EmptyTrace)");
+  many_rules(call, [&] { return check_elementwise(LMN_KIND_INPUTS, nullptr, nullptr, n); });
+}
+}  // namespace
+
+void Context::trace_inputs_float(uint32_t dtype, const void* src, uint64_t n, const lmn_node_info& info, uint32_t* rows,
+                                 uint64_t row_offset, int32_t* out) {
+  const char* call = "lmn_trace_inputs_float";
+#ifndef LMN_EMU
+  LMN_HIP_CHECK(hipSetDevice(device_));
+#endif
+  check_float_ptr(call, dtype, src, "src_dev");
+  check_float_rows(call, n);
+  launch_trace_inputs_float(dtype, src, n, trace_node(info), rows + row_offset * 7ull, out, stream_);
+}
+
+void Context::trace_many_inputs_float(uint32_t dtype, const void* src, uint64_t src_ms, uint64_t n, const lmn_node_info& info,
+                                      uint32_t n_members, uint32_t* rows, uint64_t row_offset, uint64_t rows_ms, int32_t* out,
+                                      uint64_t out_ms, uint32_t* refused) {
+  const char* call = "lmn_trace_many_inputs_float";
+#ifndef LMN_EMU
+  LMN_HIP_CHECK(hipSetDevice(device_));
+#endif
+  check_float_ptr(call, dtype, src, "src_dev");
+  check_float_rows(call, n);
+  many_strides(call, n_members, rows_ms, row_offset, n, out, out_ms, n, src_ms == 0);
+  launch_trace_many_inputs_float(dtype, src, src_ms, n, trace_node(info), n_members, rows + row_offset * 7ull, rows_ms * 7ull, out,
+                                 out_ms, refused, stream_);
+}
+
+void Context::rows_append_inputs_float(RowSink& sink, uint32_t dtype, const void* src, uint64_t n, const lmn_node_info& info,
+                                       int32_t* out, uint32_t* refused) {
+  const char* call = "lmn_rows_append_inputs_float";
+#ifndef LMN_EMU
+  LMN_HIP_CHECK(hipSetDevice(device_));
+#endif
+  check_float_ptr(call, dtype, src, "src_dev");
+  check_float_rows(call, n);
+  RowSink::Append ap(sink, call, device_, stream_, LMN_KIND_INPUTS, n);
+  launch_trace_inputs_float_cols(dtype, src, n, trace_node(info), ap.cols(), ap.stride(), out, ap.bad(), refused, stream_);
+  ap.done();
+}
+
+void Context::eval_inputs_float(uint32_t dtype, const void* src, uint64_t n, int32_t* out, int32_t* minmax, uint32_t* refused) {
+  const char* call = "lmn_eval_inputs_float";
+  check_float_ptr(call, dtype, src, "src_dev");
+  if (n == 0) eval_bad(call, "n is 0");
+  if (n >= (1ull << 31)) eval_bad(call, "n: tensor too large");
+  eval_begin(minmax);
+  launch_eval_inputs_float(dtype, src, n, out, minmax, refused, stream_);
+}
+
+// `CopyFromStwo`: returns when dst is complete, as download does - a reader on another stream may use it at once
+void Context::tensor_to_float(uint32_t dtype, const int32_t* src, uint64_t n, void* dst) {
+  const char* call = "lmn_tensor_to_float";
+#ifndef LMN_EMU
+  LMN_HIP_CHECK(hipSetDevice(device_));
+#endif
+  check_float_ptr(call, dtype, dst, "dst_dev");
+  if (n == 0) eval_bad(call, "n is 0");
+  if (n >= (1ull << 31)) eval_bad(call, "n: tensor too large");
+  launch_tensor_to_float(dtype, src, n, dst, stream_);
+  lmn_sync(stream_);
+}
+
 // ------------------------------------------------------------------------------------ lmn_trace_check
 // lmn_prove answers a bad trace with ProverError(ConstraintsNotSatisfied) after the FRI loop (phase_oods.cpp) and proves an
 // unbalanced one all the same.  This pass names the rows and the tuples instead: one launch per table over the rows where

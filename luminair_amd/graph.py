@@ -12,8 +12,10 @@ with multiplicity -1 and yields its output `num_consumers` times (0 for a final 
 is yielded `num_consumers` times by its Inputs rows — so the logup sums of a complete graph cancel.
 `num_consumers` is expansion-adjusted as in `graph.rs:215-243`: a consumer that reads the tensor through a
 view with expanded dimensions counts once per repetition of each element.
-The graph front-end itself (luminal's compiler passes, shape tracking, f32 -> fixed conversion rules)
-is outside the hot-path scope; this is the execution + table-fill step only."""
+Float tensors enter through `input_float` and leave through `read_float`: the f32 -> fixed conversion of `CopyToStwo` and
+its inverse run on the device (`lmn_trace_inputs_float`, `lmn_tensor_to_float`).
+The graph front-end itself (luminal's compiler passes, shape tracking) is outside the hot-path scope; this is the
+execution + table-fill step only."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -126,6 +128,59 @@ def _padded_lut_range(name: str, buf_min: int, buf_max: int) -> Tuple[int, int]:
     return lo, hi
 
 
+def _is_torch(x) -> bool:
+    return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
+
+
+def _words(arr: np.ndarray) -> np.ndarray:
+    """an array's bytes as uint32 words, zero-padded to a whole word (2-byte elements of odd count)"""
+    b = np.ascontiguousarray(arr).reshape(-1).view(np.uint8)
+    if b.nbytes % 4:
+        b = np.concatenate([b, np.zeros(4 - b.nbytes % 4, dtype=np.uint8)])
+    return b.view(np.uint32)
+
+
+class _FloatSource:
+    """The float tensor behind an `input_float` node or a float feed: raw float bits, either on the host (`host`: float32 /
+    float16, or uint16 bf16 patterns) or in a torch tensor on the context's device (`tensor`, kept alive here and read
+    where it lies)."""
+
+    def __init__(self, ctx, values, what: str):
+        self.host, self.tensor = None, None
+        if _is_torch(values):
+            import torch
+            self.code = backend.float_dtype_code(values.dtype)
+            t = values.detach().contiguous()
+            self.shape = tuple(int(d) for d in t.shape)
+            if t.is_cuda:
+                if t.device.index != ctx.device:
+                    raise ValueError("%s: the tensor lives on %s, the context on device %d" % (what, t.device, ctx.device))
+                self.tensor = t
+            else:
+                self.host = t.view(torch.int16).numpy().view(np.uint16) if self.code == backend.BF16 else t.numpy()
+        else:
+            v = np.asarray(values)
+            self.code = backend.float_dtype_code(v.dtype)
+            self.host = np.ascontiguousarray(v)
+            self.shape = tuple(int(d) for d in v.shape)
+
+    @property
+    def size(self) -> int:
+        return int(np.prod(self.shape))
+
+    def on_host(self) -> np.ndarray:
+        """the raw bits on the host (a device tensor comes down: one copy per call)"""
+        if self.tensor is None:
+            return self.host
+        import torch
+        t = self.tensor.cpu()
+        return t.view(torch.int16).numpy().view(np.uint16) if self.code == backend.BF16 else t.numpy()
+
+    def fixed(self) -> np.ndarray:
+        """the Fixed<12> integers (`backend.to_fixed`: ValueError for what the device refuses)"""
+        return backend.to_fixed(self.on_host(), backend.BF16 if self.code == backend.BF16 else None)
+
+
 @dataclass
 class _Node:
     kind: int
@@ -134,6 +189,7 @@ class _Node:
     host: Optional[np.ndarray] = None      # graph inputs
     axis: int = 0                          # SumReduce
     per_member: bool = False               # graph inputs: one tensor per member of gen_trace_many (fed through `feeds`)
+    fsrc: Optional[_FloatSource] = None    # graph inputs made by input_float (`host` is None then)
 
 
 class DeviceGraph:
@@ -157,6 +213,29 @@ class DeviceGraph:
         t = self._tensor(v.shape)
         self.nodes.append(_Node(int(TraceTableKind.Inputs), t, [], host=v, per_member=per_member))
         return t
+
+    def input_float(self, values, per_member: bool = False) -> GraphTensor:
+        """A graph input given as floats (`CopyToStwo` with `StwoData::from_f32`, prim.rs:52-101): the conversion to
+        Fixed<12> - round to nearest, ties away from zero; NaN, +-Inf and values outside [-(2^30-1), 2^30-1] / 4096 are
+        refused elements - happens on the device, in the launch that writes the Inputs rows (`lmn_trace_inputs_float`).
+        `values`: a numpy float32 / float16 array, or a torch tensor of float32 / float16 / bfloat16 on the CPU or on the
+        context's device.  A device tensor is read where it lies - no staging, no copy (a non-contiguous one is made
+        contiguous first) - and the node keeps a reference to it, so its memory outlives the asynchronous launches; it
+        must not be written while a `gen_trace` / `gen_trace_many` / `dry_run_device` that reads it is in flight.  The
+        context works on a stream of its own: before the first launch of a call that reads torch device memory, torch's
+        current stream on that device is synchronised, so what torch has enqueued there so far is visible.  Host
+        arrays go up as raw float bits in the call's one staging upload.  per_member: as `input`; the `feeds` of
+        `gen_trace_many` are then (n_members, *shape) arrays or tensors of this input's dtype."""
+        src = _FloatSource(self.ctx, values, "input_float")
+        t = self._tensor(src.shape)
+        self.nodes.append(_Node(int(TraceTableKind.Inputs), t, [], per_member=per_member, fsrc=src))
+        return t
+
+    def _sync_torch(self, sources) -> None:
+        """torch's current stream on the context's device, once, if any of `sources` is torch device memory"""
+        if any(s is not None and s.tensor is not None for s in sources):
+            import torch
+            torch.cuda.current_stream(self.ctx.device).synchronize()
 
     def constant(self, value: int) -> GraphTensor:
         """`LuminairConstant` (prim.rs:151-200): a one-element tensor, expanded by its consumers."""
@@ -383,6 +462,8 @@ class DeviceGraph:
                                  % _LUT_OF[n.kind][0])
             if n.host is not None:
                 stage(("in", n.out.node_id), n.host.astype(np.int32, copy=False))
+            elif n.fsrc is not None and n.fsrc.tensor is None:
+                stage(("in", n.out.node_id), _words(n.fsrc.host))
         luts_out = {}
         for kind in sorted(total):
             if kind in _LUT_OF:
@@ -436,6 +517,7 @@ class DeviceGraph:
         if int(K.LessThan) in total:
             rc_mult = dev_of(("rc",))
             lut_tables[int(K.RangeCheckLookup)] = (rc_mult, 256)
+        self._sync_torch(n.fsrc for n in self.nodes)
         for n in self.nodes:
             t = n.out
             t.member_stride = 0
@@ -444,7 +526,11 @@ class DeviceGraph:
                 common.update(sink=tables[n.kind], refused=refused)
             else:
                 common.update(rows=tables[n.kind], row_offset=offset[n.kind])
-            if n.kind == int(K.Inputs):
+            if n.fsrc is not None:
+                f = n.fsrc
+                src = f.tensor.data_ptr() if f.tensor is not None else dev_of(("in", t.node_id))
+                _, t.buf = ctx.trace_inputs_float(f.code, src, t.size, node_id=t.node_id, **common)
+            elif n.kind == int(K.Inputs):
                 src = dev_of(("in", t.node_id))
                 _, t.buf = ctx.trace_elementwise(n.kind, src, None, t.size, node_id=t.node_id, input_ids=(),
                                                  input_mults=(), **common)
@@ -524,8 +610,14 @@ class DeviceGraph:
             raise ValueError("gen_trace_many: 1..%d members" % backend.TRACE_MANY_MAX)
         self.release_dry_run()
         fed = {}
+        float_nodes = {n.out.node_id: n for n in self.nodes if n.fsrc is not None}
         for t, arr in (feeds.items() if hasattr(feeds, "items") else feeds):
-            fed[t.node_id] = np.ascontiguousarray(arr, dtype=np.int32)
+            if t.node_id in float_nodes:
+                fed[t.node_id] = f = _FloatSource(ctx, arr, "gen_trace_many: feeds")
+                if f.code != float_nodes[t.node_id].fsrc.code:
+                    raise ValueError("gen_trace_many: the feed of input %d has another dtype than the input" % t.node_id)
+            else:
+                fed[t.node_id] = np.ascontiguousarray(arr, dtype=np.int32)
         reduces = (int(K.SumReduce), int(K.MaxReduce))
         ref_contig = lambda n: n.kind == int(K.Contiguous) and n.inputs[0].expansion == 1
 
@@ -568,6 +660,10 @@ class DeviceGraph:
         for n in self.nodes:
             if n.host is not None:
                 stage(("in", n.out.node_id), fed[n.out.node_id] if n.per_member else n.host.astype(np.int32, copy=False))
+            elif n.fsrc is not None:
+                f = fed[n.out.node_id] if n.per_member else n.fsrc
+                if f.tensor is None:
+                    stage(("in", n.out.node_id), _words(f.host))
         luts_out, lut_len, lut_rg = {}, {}, {}
         for kind in sorted(total):
             if kind in _LUT_OF:
@@ -598,6 +694,7 @@ class DeviceGraph:
         tables = {k: carve(n_members * total[k] * _NCOLS[k] * 4) for k in total}
         offset = {k: 0 for k in total}
         stride_of = lambda t: t.member_stride          # of a tensor that has been produced
+        self._sync_torch((fed[n.out.node_id] if n.per_member else n.fsrc) for n in float_nodes.values())
         for n in self.nodes:
             t = n.out
             t.member_stride = t.size if t.node_id in varying else 0
@@ -605,7 +702,11 @@ class DeviceGraph:
             common = dict(n_members=n_members, node_id=t.node_id, num_consumers=t.consumers, is_final_output=t.is_output,
                           rows=tables[n.kind], rows_stride=total[n.kind], row_offset=offset[n.kind], out=t.buf,
                           out_stride=t.member_stride, refused=refused)
-            if n.kind == int(K.Inputs):
+            if n.fsrc is not None:
+                f = fed[t.node_id] if n.per_member else n.fsrc
+                src = f.tensor.data_ptr() if f.tensor is not None else dev_of(("in", t.node_id))
+                ctx.trace_many_inputs_float(f.code, src, t.size, src_stride=t.member_stride, **common)
+            elif n.kind == int(K.Inputs):
                 ctx.trace_many_elementwise(n.kind, dev_of(("in", t.node_id)), None, t.size, input_ids=(), input_mults=(),
                                            lhs_stride=t.member_stride, **common)
             elif n.kind in reduces:
@@ -660,6 +761,34 @@ class DeviceGraph:
             buf = buf.view(int(member) * t.member_stride * 4, t.size * 4)
         return self.ctx.download(buf, np.int32).reshape(t.shape)
 
+    def read_float(self, t: GraphTensor, member: Optional[int] = None, dtype=np.float32, device: bool = False):
+        """The tensor's values as floats (`CopyFromStwo`, prim.rs:90-101: `d.to_f64() as f32`): v / 4096 rounded once to
+        `dtype`, to nearest even, by `lmn_tensor_to_float` on the device.  dtype: float32, float16 or bfloat16 (numpy or
+        torch dtype, or "bfloat16").  Returns a numpy array - for bfloat16, which numpy lacks, its uint16 bit patterns - or,
+        with device=True, a torch tensor on the context's device, filled with no host trip and complete when the call
+        returns.  `member` as in `read`."""
+        code = backend.float_dtype_code(dtype)
+        buf = t.buf
+        if t.member_stride:
+            if member is None:
+                raise ValueError("read_float: tensor %d differs between members: pass member=" % t.node_id)
+            buf = buf.view(int(member) * t.member_stride * 4, t.size * 4)
+        if device:
+            import torch
+            tdt = {backend.F32: torch.float32, backend.F16: torch.float16, backend.BF16: torch.bfloat16}[code]
+            out = torch.empty(t.shape, dtype=tdt, device="cuda:%d" % self.ctx.device)
+            # (the allocator may hand out memory that work on torch's stream still uses; the context writes on its own)
+            torch.cuda.current_stream(self.ctx.device).synchronize()
+            self.ctx.tensor_to_float(code, buf, t.size, dst=out.data_ptr())
+            return out
+        dst = self.ctx.tensor_to_float(code, buf, t.size)
+        try:
+            bits = self.ctx.download(dst, np.uint32 if code == backend.F32 else np.uint16)[:t.size]
+        finally:
+            dst.free()
+        return (bits.view(np.float32) if code == backend.F32 else bits.view(np.float16) if code == backend.F16
+                else bits).reshape(t.shape)
+
     # ---- gen_circuit_settings (crates/graph/src/graph.rs:61-159): a HOST dry run, as in the reference
     def _dry_run(self) -> Dict[int, np.ndarray]:
         """Every node's values as Fixed<12> integers, computed on the host with the same integer rules as the device
@@ -680,7 +809,9 @@ class DeviceGraph:
 
         for n in self.nodes:
             k = n.kind
-            if k == int(K.Inputs):
+            if n.fsrc is not None:
+                out = n.fsrc.fixed().astype(np.int64).reshape(-1)     # (a device-resident input comes down once)
+            elif k == int(K.Inputs):
                 out = n.host.astype(np.int64).reshape(-1)
             elif k in (int(K.Add), int(K.Mul), int(K.Rem), int(K.LessThan)):
                 a, b = view(n.inputs[0]), view(n.inputs[1])
@@ -733,8 +864,9 @@ class DeviceGraph:
         parts, off, cur = [np.zeros(64 + 2 * n_nodes, dtype=np.uint32)], {}, al((64 + 2 * n_nodes) * 4)
         parts.append(np.zeros((cur - parts[0].nbytes) // 4, dtype=np.uint32))
         for n in self.nodes:
-            if n.host is not None:
-                a = np.ascontiguousarray(n.host.astype(np.int32, copy=False)).reshape(-1).view(np.uint32)
+            if n.host is not None or (n.fsrc is not None and n.fsrc.tensor is None):
+                a = np.ascontiguousarray(n.host.astype(np.int32, copy=False)).reshape(-1).view(np.uint32) \
+                    if n.host is not None else _words(n.fsrc.host)
                 off[n.out.node_id] = (cur, a.nbytes)
                 parts += [a, np.zeros((al(a.nbytes) - a.nbytes) // 4, dtype=np.uint32)]
                 cur += al(a.nbytes)
@@ -745,12 +877,17 @@ class DeviceGraph:
             ctx.upload_to(slab.view(0, cur), np.concatenate(parts))
             refused = slab.view(0, 4)
             slot = {n.out.node_id: slab.view(256 + 8 * i, 8) for i, n in enumerate(self.nodes)}
+            self._sync_torch(n.fsrc for n in self.nodes)
             for n in self.nodes:
                 t = n.out
                 t.buf = slab.view(cur, t.size * 4)
                 cur += al(t.size * 4)
                 common = dict(out=t.buf, minmax=slot[t.node_id], refused=refused)
-                if n.kind == int(K.Inputs):
+                if n.fsrc is not None:
+                    f = n.fsrc
+                    ctx.eval_inputs_float(f.code, f.tensor.data_ptr() if f.tensor is not None else slab.view(*off[t.node_id]),
+                                          t.size, **common)
+                elif n.kind == int(K.Inputs):
                     ctx.eval_elementwise(n.kind, slab.view(*off[t.node_id]), None, t.size, **common)
                 elif n.kind in (int(K.SumReduce), int(K.MaxReduce)):
                     a = n.inputs[0].base
