@@ -93,6 +93,28 @@ class LmnRange(C.Structure):
     _fields_ = [("lo", C.c_int64), ("hi", C.c_int64)]
 
 
+# ---- what every producer wrapper marshals (Context.trace_* / trace_many_* / eval_*)
+def _node_info(node_id: int, input_ids=(), num_consumers: int = 0, is_final_output: bool = False, input_mults=()) -> LmnNodeInfo:
+    """ids and mults padded to two"""
+    ids = list(input_ids) + [0] * (2 - len(input_ids))
+    mults = list(input_mults) + [0] * (2 - len(input_mults))
+    return LmnNodeInfo(node_id, (C.c_uint32 * 2)(*ids), num_consumers, 1 if is_final_output else 0, (C.c_int32 * 2)(*mults))
+
+
+def _addr(b):
+    """a DeviceBuffer's address, a device address as it is (an int: memory of another owner), None"""
+    return b.ptr if isinstance(b, DeviceBuffer) else b
+
+
+def _ref(v):
+    """an optional struct argument"""
+    return C.byref(v) if v is not None else None
+
+
+def _range_array(ranges):
+    return (LmnRange * max(len(ranges), 1))(*[LmnRange(int(a), int(b)) for a, b in ranges])
+
+
 ALL_GATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 
@@ -1476,28 +1498,21 @@ class Context:
         sink= (every `trace_*` method takes it): the node's rows are appended to that `RowSink`'s columns at its current
         row count instead (`lmn_rows_append_*`; `rows` / `row_offset` are not used, and the sink is returned in place of the
         rows buffer); `refused` is then a uint32 counter on the device that grows by the refused elements.  Nothing waits."""
-        ncols = self.lib.kind_columns(kind)
+        L = self.lib.lib
         if rows is None and sink is None:
-            rows = self.alloc((row_offset + n) * ncols * 4)
+            rows = self.alloc((row_offset + n) * self.lib.kind_columns(kind) * 4)
         out = out or self.alloc(n * 4)
-        ids = list(input_ids) + [0] * (2 - len(input_ids))
-        mults = list(input_mults) + [0] * (2 - len(input_mults))
-        info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(*ids), num_consumers, 1 if is_final_output else 0,
-                           (C.c_int32 * 2)(*mults))
+        info = _node_info(node_id, input_ids, num_consumers, is_final_output, input_mults)
         if sink is not None:
-            self._check(self.lib.lib.lmn_rows_append_elementwise_v(
-                self.handle, sink.handle, kind, lhs.ptr, C.byref(lhs_view) if lhs_view is not None else None,
-                rhs.ptr if rhs is not None else None, C.byref(rhs_view) if rhs_view is not None else None, n,
-                C.byref(info), None, out.ptr, refused.ptr if refused is not None else None))
+            self._check(L.lmn_rows_append_elementwise_v(self.handle, sink.handle, kind, lhs.ptr, _ref(lhs_view), _addr(rhs),
+                                                        _ref(rhs_view), n, C.byref(info), None, out.ptr, _addr(refused)))
             return sink, out
         if lhs_view is None and rhs_view is None:
-            self._check(self.lib.lib.lmn_trace_elementwise(self.handle, kind, lhs.ptr, rhs.ptr if rhs is not None else None,
-                                                           n, C.byref(info), rows.ptr, row_offset, out.ptr))
+            self._check(L.lmn_trace_elementwise(self.handle, kind, lhs.ptr, _addr(rhs), n, C.byref(info), rows.ptr, row_offset,
+                                                out.ptr))
         else:
-            self._check(self.lib.lib.lmn_trace_elementwise_v(
-                self.handle, kind, lhs.ptr, C.byref(lhs_view) if lhs_view is not None else None,
-                rhs.ptr if rhs is not None else None, C.byref(rhs_view) if rhs_view is not None else None, n,
-                C.byref(info), rows.ptr, row_offset, out.ptr))
+            self._check(L.lmn_trace_elementwise_v(self.handle, kind, lhs.ptr, _ref(lhs_view), _addr(rhs), _ref(rhs_view), n,
+                                                  C.byref(info), rows.ptr, row_offset, out.ptr))
         return rows, out
 
     def trace_contiguous(self, inp: DeviceBuffer, in_size: int, out_size: int, node_id: int, input_id: int,
@@ -1506,19 +1521,17 @@ class Context:
                          out: Optional[DeviceBuffer] = None, sink: Optional["RowSink"] = None,
                          refused: Optional[DeviceBuffer] = None):
         """`LuminairContiguous::process_trace` in the reference's row rule: max(in_size, out_size) rows."""
-        n_rows = max(in_size, out_size)
+        L = self.lib.lib
         if rows is None and sink is None:
-            rows = self.alloc((row_offset + n_rows) * 11 * 4)
+            rows = self.alloc((row_offset + max(in_size, out_size)) * 11 * 4)
         out = out or self.alloc(out_size * 4)
-        info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(input_id, 0), num_consumers, 1 if is_final_output else 0,
-                           (C.c_int32 * 2)(input_mult, 0))
+        info = _node_info(node_id, (input_id,), num_consumers, is_final_output, (input_mult,))
         if sink is not None:
-            self._check(self.lib.lib.lmn_rows_append_contiguous(
-                self.handle, sink.handle, inp.ptr, in_size, C.byref(view) if view is not None else None, out_size,
-                C.byref(info), out.ptr, refused.ptr if refused is not None else None))
+            self._check(L.lmn_rows_append_contiguous(self.handle, sink.handle, inp.ptr, in_size, _ref(view), out_size,
+                                                     C.byref(info), out.ptr, _addr(refused)))
             return sink, out
-        self._check(self.lib.lib.lmn_trace_contiguous(self.handle, inp.ptr, in_size, C.byref(view) if view is not None else None,
-                                                      out_size, C.byref(info), rows.ptr, row_offset, out.ptr))
+        self._check(L.lmn_trace_contiguous(self.handle, inp.ptr, in_size, _ref(view), out_size, C.byref(info), rows.ptr,
+                                           row_offset, out.ptr))
         return rows, out
 
     def trace_lut(self, kind: int, inp: DeviceBuffer, n: int, node_id: int, input_id: int, num_consumers: int,
@@ -1530,26 +1543,22 @@ class Context:
         """`process_trace` of a Sin / Exp2 / Log2 node; `mult` (the lookup component's table) is updated in place.
         The LUT enumerates either the single range lo .. lo + lut_len - 1 or `ranges` (ascending, disjoint).
         With sink= an input outside every range is a refused element (marked, counted), not an error of the call."""
+        L = self.lib.lib
         if rows is None and sink is None:
             rows = self.alloc((row_offset + n) * 12 * 4)
         out = out or self.alloc(n * 4)
-        info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(input_id, 0), num_consumers, 1 if is_final_output else 0,
-                           (C.c_int32 * 2)(input_mult, 0))
-        vp = C.byref(view) if view is not None else None
+        info = _node_info(node_id, (input_id,), num_consumers, is_final_output, (input_mult,))
         if sink is not None:
             rg = ranges if ranges is not None else [(lo, lo + lut_len - 1)]
-            arr = (LmnRange * max(len(rg), 1))(*[LmnRange(int(a), int(b)) for a, b in rg])
-            self._check(self.lib.lib.lmn_rows_append_lut_ranges(
-                self.handle, sink.handle, kind, inp.ptr, vp, n, C.byref(info), lut_col1.ptr, arr, len(rg), mult.ptr, out.ptr,
-                refused.ptr if refused is not None else None))
+            self._check(L.lmn_rows_append_lut_ranges(self.handle, sink.handle, kind, inp.ptr, _ref(view), n, C.byref(info),
+                                                     lut_col1.ptr, _range_array(rg), len(rg), mult.ptr, out.ptr, _addr(refused)))
             return sink, out
         if ranges is None:
-            self._check(self.lib.lib.lmn_trace_lut(self.handle, kind, inp.ptr, vp, n, C.byref(info), lut_col1.ptr, lo,
-                                                   lut_len, mult.ptr, rows.ptr, row_offset, out.ptr))
+            self._check(L.lmn_trace_lut(self.handle, kind, inp.ptr, _ref(view), n, C.byref(info), lut_col1.ptr, lo, lut_len,
+                                        mult.ptr, rows.ptr, row_offset, out.ptr))
         else:
-            arr = (LmnRange * len(ranges))(*[LmnRange(int(a), int(b)) for a, b in ranges])
-            self._check(self.lib.lib.lmn_trace_lut_ranges(self.handle, kind, inp.ptr, vp, n, C.byref(info), lut_col1.ptr,
-                                                          arr, len(ranges), mult.ptr, rows.ptr, row_offset, out.ptr))
+            self._check(L.lmn_trace_lut_ranges(self.handle, kind, inp.ptr, _ref(view), n, C.byref(info), lut_col1.ptr,
+                                               _range_array(ranges), len(ranges), mult.ptr, rows.ptr, row_offset, out.ptr))
         return rows, out
 
     def trace_sum_reduce(self, inp: DeviceBuffer, front: int, dim: int, back: int, node_id: int, input_id: int,
@@ -1559,18 +1568,16 @@ class Context:
                          refused: Optional[DeviceBuffer] = None):
         """`LuminairSumReduce::process_trace` (or MaxReduce with maximum=True) on a contiguous
         (front, dim, back) int32 device tensor."""
-        n_rows, n_out = front * dim * back, front * back
+        L = self.lib.lib
         if rows is None and sink is None:
-            rows = self.alloc((row_offset + n_rows) * (15 if maximum else 14) * 4)
-        out = out or self.alloc(n_out * 4)
-        info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(input_id, 0), num_consumers, 1 if is_final_output else 0,
-                           (C.c_int32 * 2)(input_mult, 0))
+            rows = self.alloc((row_offset + front * dim * back) * (15 if maximum else 14) * 4)
+        out = out or self.alloc(front * back * 4)
+        info = _node_info(node_id, (input_id,), num_consumers, is_final_output, (input_mult,))
         if sink is not None:
-            self._check(self.lib.lib.lmn_rows_append_reduce(
-                self.handle, sink.handle, 1 if maximum else 0, inp.ptr, front, dim, back, C.byref(info), out.ptr,
-                refused.ptr if refused is not None else None))
+            self._check(L.lmn_rows_append_reduce(self.handle, sink.handle, 1 if maximum else 0, inp.ptr, front, dim, back,
+                                                 C.byref(info), out.ptr, _addr(refused)))
             return sink, out
-        fn = self.lib.lib.lmn_trace_max_reduce if maximum else self.lib.lib.lmn_trace_sum_reduce
+        fn = L.lmn_trace_max_reduce if maximum else L.lmn_trace_sum_reduce
         self._check(fn(self.handle, inp.ptr, front, dim, back, C.byref(info), rows.ptr, row_offset, out.ptr))
         return rows, out
 
@@ -1581,21 +1588,18 @@ class Context:
                         out: Optional[DeviceBuffer] = None, sink: Optional["RowSink"] = None,
                         refused: Optional[DeviceBuffer] = None):
         """`LuminairLessThan::process_trace`; `range_check_mult` (256 words) is the RangeCheckLookup table."""
+        L = self.lib.lib
         if rows is None and sink is None:
             rows = self.alloc((row_offset + n) * 22 * 4)
         out = out or self.alloc(n * 4)
-        info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(*input_ids), num_consumers, 1 if is_final_output else 0,
-                           (C.c_int32 * 2)(*input_mults))
+        info = _node_info(node_id, input_ids, num_consumers, is_final_output, input_mults)
         if sink is not None:
-            self._check(self.lib.lib.lmn_rows_append_elementwise_v(
-                self.handle, sink.handle, 13, lhs.ptr, C.byref(lhs_view) if lhs_view is not None else None,
-                rhs.ptr, C.byref(rhs_view) if rhs_view is not None else None, n, C.byref(info), range_check_mult.ptr,
-                out.ptr, refused.ptr if refused is not None else None))
+            self._check(L.lmn_rows_append_elementwise_v(self.handle, sink.handle, 13, lhs.ptr, _ref(lhs_view), rhs.ptr,
+                                                        _ref(rhs_view), n, C.byref(info), range_check_mult.ptr, out.ptr,
+                                                        _addr(refused)))
             return sink, out
-        self._check(self.lib.lib.lmn_trace_less_than(
-            self.handle, lhs.ptr, C.byref(lhs_view) if lhs_view is not None else None, rhs.ptr,
-            C.byref(rhs_view) if rhs_view is not None else None, n, C.byref(info), range_check_mult.ptr, rows.ptr,
-            row_offset, out.ptr))
+        self._check(L.lmn_trace_less_than(self.handle, lhs.ptr, _ref(lhs_view), rhs.ptr, _ref(rhs_view), n, C.byref(info),
+                                          range_check_mult.ptr, rows.ptr, row_offset, out.ptr))
         return rows, out
 
     # ---- lmn_trace_many_*: one call (one launch) fills a node's rows for `n_members` pies of one shape.  Member m works on
@@ -1610,15 +1614,11 @@ class Context:
                                range_check_mult: Optional[DeviceBuffer] = None, range_check_mult_stride: int = 0,
                                refused: Optional[DeviceBuffer] = None):
         """`lmn_trace_many_elementwise_v`: every kind of `trace_elementwise`, and LessThan with `range_check_mult`."""
-        ids = list(input_ids) + [0] * (2 - len(input_ids))
-        mults = list(input_mults) + [0] * (2 - len(input_mults))
-        info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(*ids), num_consumers, 1 if is_final_output else 0,
-                           (C.c_int32 * 2)(*mults))
-        ptr = lambda b: b.ptr if b is not None else None
+        info = _node_info(node_id, input_ids, num_consumers, is_final_output, input_mults)
         self._check(self.lib.lib.lmn_trace_many_elementwise_v(
-            self.handle, kind, ptr(lhs), C.byref(lhs_view) if lhs_view is not None else None, lhs_stride, ptr(rhs),
-            C.byref(rhs_view) if rhs_view is not None else None, rhs_stride, n, C.byref(info), n_members, ptr(rows),
-            row_offset, rows_stride, ptr(out), out_stride, ptr(range_check_mult), range_check_mult_stride, ptr(refused)))
+            self.handle, kind, _addr(lhs), _ref(lhs_view), lhs_stride, _addr(rhs), _ref(rhs_view), rhs_stride, n, C.byref(info),
+            n_members, _addr(rows), row_offset, rows_stride, _addr(out), out_stride, _addr(range_check_mult),
+            range_check_mult_stride, _addr(refused)))
         return rows, out
 
     def trace_many_contiguous(self, inp: DeviceBuffer, in_size: int, out_size: int, n_members: int, node_id: int,
@@ -1627,12 +1627,10 @@ class Context:
                               is_final_output: bool = False, input_mult: int = -1, view: Optional[LmnView] = None,
                               row_offset: int = 0, refused: Optional[DeviceBuffer] = None):
         """`lmn_trace_many_contiguous`: the reference's buffer rule, max(in_size, out_size) rows per member."""
-        info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(input_id, 0), num_consumers, 1 if is_final_output else 0,
-                           (C.c_int32 * 2)(input_mult, 0))
-        ptr = lambda b: b.ptr if b is not None else None
+        info = _node_info(node_id, (input_id,), num_consumers, is_final_output, (input_mult,))
         self._check(self.lib.lib.lmn_trace_many_contiguous(
-            self.handle, ptr(inp), inp_stride, in_size, C.byref(view) if view is not None else None, out_size, C.byref(info),
-            n_members, ptr(rows), row_offset, rows_stride, ptr(out), out_stride, ptr(refused)))
+            self.handle, _addr(inp), inp_stride, in_size, _ref(view), out_size, C.byref(info), n_members, _addr(rows), row_offset,
+            rows_stride, _addr(out), out_stride, _addr(refused)))
         return rows, out
 
     def trace_many_reduce(self, inp: DeviceBuffer, front: int, dim: int, back: int, n_members: int, node_id: int,
@@ -1641,12 +1639,10 @@ class Context:
                           is_final_output: bool = False, input_mult: int = -1, row_offset: int = 0,
                           refused: Optional[DeviceBuffer] = None):
         """`lmn_trace_many_reduce`: SumReduce, or MaxReduce with maximum=True, of a (front, dim, back) tensor per member."""
-        info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(input_id, 0), num_consumers, 1 if is_final_output else 0,
-                           (C.c_int32 * 2)(input_mult, 0))
-        ptr = lambda b: b.ptr if b is not None else None
+        info = _node_info(node_id, (input_id,), num_consumers, is_final_output, (input_mult,))
         self._check(self.lib.lib.lmn_trace_many_reduce(
-            self.handle, 1 if maximum else 0, ptr(inp), inp_stride, front, dim, back, C.byref(info), n_members, ptr(rows),
-            row_offset, rows_stride, ptr(out), out_stride, ptr(refused)))
+            self.handle, 1 if maximum else 0, _addr(inp), inp_stride, front, dim, back, C.byref(info), n_members, _addr(rows),
+            row_offset, rows_stride, _addr(out), out_stride, _addr(refused)))
         return rows, out
 
     def trace_many_lut(self, kind: int, inp: DeviceBuffer, n: int, n_members: int, node_id: int, input_id: int,
@@ -1657,14 +1653,11 @@ class Context:
         """`lmn_trace_many_lut_ranges`: Sin / Exp2 / Log2 over `ranges` (one (lo, hi) pair for a single-range LUT);
         `lut_col1` is shared, `mult` holds one multiplicity table per member.  An input outside every range is a refused
         element (marked, counted), not an error."""
-        info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(input_id, 0), num_consumers, 1 if is_final_output else 0,
-                           (C.c_int32 * 2)(input_mult, 0))
-        ptr = lambda b: b.ptr if b is not None else None
-        arr = (LmnRange * max(len(ranges), 1))(*[LmnRange(int(a), int(b)) for a, b in ranges])
+        info = _node_info(node_id, (input_id,), num_consumers, is_final_output, (input_mult,))
         self._check(self.lib.lib.lmn_trace_many_lut_ranges(
-            self.handle, kind, ptr(inp), C.byref(view) if view is not None else None, inp_stride, n, C.byref(info),
-            ptr(lut_col1), arr, len(ranges), n_members, ptr(mult), mult_stride, ptr(rows), row_offset, rows_stride, ptr(out),
-            out_stride, ptr(refused)))
+            self.handle, kind, _addr(inp), _ref(view), inp_stride, n, C.byref(info), _addr(lut_col1), _range_array(ranges),
+            len(ranges), n_members, _addr(mult), mult_stride, _addr(rows), row_offset, rows_stride, _addr(out), out_stride,
+            _addr(refused)))
         return rows, out
 
     # ---- lmn_eval_*: the producers' forward pass (values, their range, the refused elements; no rows, no waiting).
@@ -1676,10 +1669,8 @@ class Context:
                          refused: Optional[DeviceBuffer] = None) -> DeviceBuffer:
         """`Operator::process` of an elementwise node (LessThan included) on int32 Fixed<12> device tensors."""
         out = out or self.alloc(max(n, 1) * 4)
-        ptr = lambda b: b.ptr if b is not None else None
-        self._check(self.lib.lib.lmn_eval_elementwise_v(
-            self.handle, kind, ptr(lhs), C.byref(lhs_view) if lhs_view is not None else None, ptr(rhs),
-            C.byref(rhs_view) if rhs_view is not None else None, n, out.ptr, ptr(minmax), ptr(refused)))
+        self._check(self.lib.lib.lmn_eval_elementwise_v(self.handle, kind, _addr(lhs), _ref(lhs_view), _addr(rhs), _ref(rhs_view),
+                                                        n, out.ptr, _addr(minmax), _addr(refused)))
         return out
 
     def eval_reduce(self, inp: DeviceBuffer, front: int, dim: int, back: int, maximum: bool = False,
@@ -1687,9 +1678,8 @@ class Context:
                     refused: Optional[DeviceBuffer] = None) -> DeviceBuffer:
         """SumReduce / MaxReduce of `dim` on a contiguous (front, dim, back) int32 device tensor."""
         out = out or self.alloc(max(front * back, 1) * 4)
-        ptr = lambda b: b.ptr if b is not None else None
-        self._check(self.lib.lib.lmn_eval_reduce(self.handle, 1 if maximum else 0, ptr(inp), front, dim, back, out.ptr,
-                                                 ptr(minmax), ptr(refused)))
+        self._check(self.lib.lib.lmn_eval_reduce(self.handle, 1 if maximum else 0, _addr(inp), front, dim, back, out.ptr,
+                                                 _addr(minmax), _addr(refused)))
         return out
 
     def eval_lut(self, kind: int, inp: DeviceBuffer, n: int, lut_col1: DeviceBuffer, ranges: Sequence[Tuple[int, int]],
@@ -1697,25 +1687,19 @@ class Context:
                  minmax: Optional[DeviceBuffer] = None, refused: Optional[DeviceBuffer] = None) -> DeviceBuffer:
         """Sin / Exp2 / Log2: out = lut_col1[find_index(input)] over `ranges`; an input outside them is refused."""
         out = out or self.alloc(max(n, 1) * 4)
-        ptr = lambda b: b.ptr if b is not None else None
-        arr = (LmnRange * max(len(ranges), 1))(*[LmnRange(int(a), int(b)) for a, b in ranges])
-        self._check(self.lib.lib.lmn_eval_lut_ranges(self.handle, kind, ptr(inp), C.byref(view) if view is not None else None,
-                                                     n, ptr(lut_col1), arr, len(ranges), out.ptr, ptr(minmax), ptr(refused)))
+        self._check(self.lib.lib.lmn_eval_lut_ranges(self.handle, kind, _addr(inp), _ref(view), n, _addr(lut_col1),
+                                                     _range_array(ranges), len(ranges), out.ptr, _addr(minmax), _addr(refused)))
         return out
 
     def tensor_range(self, buf: DeviceBuffer, n: int, minmax: Optional[DeviceBuffer] = None) -> DeviceBuffer:
         """The (min, max) of an int32 device buffer that no eval call produced, left in `minmax` (two int32 words)."""
         minmax = minmax or self.alloc(8)
-        self._check(self.lib.lib.lmn_tensor_range(self.handle, buf.ptr if buf is not None else None, n, minmax.ptr))
+        self._check(self.lib.lib.lmn_tensor_range(self.handle, _addr(buf), n, minmax.ptr))
         return minmax
 
     # ---- float tensors in and out (`CopyToStwo` / `CopyFromStwo`): the Inputs producers reading raw float bits of `dtype`
     # (F32 / F16 / BF16), converted in the launch that writes the rows, and the way back.  `src` is a DeviceBuffer or a
     # device address (an int: memory of another owner, a torch tensor's data_ptr()); nothing but tensor_to_float waits.
-    @staticmethod
-    def _addr(b):
-        return b.ptr if isinstance(b, DeviceBuffer) else b
-
     def trace_inputs_float(self, dtype: int, src, n: int, node_id: int, num_consumers: int, is_final_output: bool = False,
                            rows: Optional[DeviceBuffer] = None, row_offset: int = 0, out: Optional[DeviceBuffer] = None,
                            sink: Optional["RowSink"] = None, refused: Optional[DeviceBuffer] = None):
@@ -1724,12 +1708,12 @@ class Context:
         if rows is None and sink is None:
             rows = self.alloc((row_offset + n) * 7 * 4)
         out = out or self.alloc(max(n, 1) * 4)
-        info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(0, 0), num_consumers, 1 if is_final_output else 0, (C.c_int32 * 2)(0, 0))
+        info = _node_info(node_id, (), num_consumers, is_final_output)
         if sink is not None:
-            self._check(self.lib.lib.lmn_rows_append_inputs_float(self.handle, sink.handle, dtype, self._addr(src), n, C.byref(info),
-                                                                  out.ptr, self._addr(refused)))
+            self._check(self.lib.lib.lmn_rows_append_inputs_float(self.handle, sink.handle, dtype, _addr(src), n, C.byref(info),
+                                                                  out.ptr, _addr(refused)))
             return sink, out
-        self._check(self.lib.lib.lmn_trace_inputs_float(self.handle, dtype, self._addr(src), n, C.byref(info), rows.ptr, row_offset,
+        self._check(self.lib.lib.lmn_trace_inputs_float(self.handle, dtype, _addr(src), n, C.byref(info), rows.ptr, row_offset,
                                                         out.ptr))
         return rows, out
 
@@ -1739,25 +1723,24 @@ class Context:
                                 refused: Optional[DeviceBuffer] = None):
         """`lmn_trace_many_inputs_float`: `trace_many_elementwise(Inputs)` on a float source; `src_stride` in elements of
         `dtype` (0: one source shared by all members)."""
-        info = LmnNodeInfo(node_id, (C.c_uint32 * 2)(0, 0), num_consumers, 1 if is_final_output else 0, (C.c_int32 * 2)(0, 0))
+        info = _node_info(node_id, (), num_consumers, is_final_output)
         self._check(self.lib.lib.lmn_trace_many_inputs_float(
-            self.handle, dtype, self._addr(src), src_stride, n, C.byref(info), n_members, self._addr(rows), row_offset, rows_stride,
-            self._addr(out), out_stride, self._addr(refused)))
+            self.handle, dtype, _addr(src), src_stride, n, C.byref(info), n_members, _addr(rows), row_offset, rows_stride,
+            _addr(out), out_stride, _addr(refused)))
         return rows, out
 
     def eval_inputs_float(self, dtype: int, src, n: int, out: Optional[DeviceBuffer] = None,
                           minmax: Optional[DeviceBuffer] = None, refused: Optional[DeviceBuffer] = None) -> DeviceBuffer:
         """`lmn_eval_inputs_float`: `eval_elementwise(Inputs)` on a float source."""
         out = out or self.alloc(max(n, 1) * 4)
-        self._check(self.lib.lib.lmn_eval_inputs_float(self.handle, dtype, self._addr(src), n, out.ptr, self._addr(minmax),
-                                                       self._addr(refused)))
+        self._check(self.lib.lib.lmn_eval_inputs_float(self.handle, dtype, _addr(src), n, out.ptr, _addr(minmax), _addr(refused)))
         return out
 
     def tensor_to_float(self, dtype: int, src, n: int, dst=None):
         """`lmn_tensor_to_float`: n Fixed<12> values -> floats of `dtype` in `dst` (a DeviceBuffer, a device address, or
         None: a new DeviceBuffer).  Returns `dst` when the result is complete."""
         dst = dst if dst is not None else self.alloc(max(n, 1) * FLOAT_BYTES.get(dtype, 4))
-        self._check(self.lib.lib.lmn_tensor_to_float(self.handle, dtype, self._addr(src), n, self._addr(dst)))
+        self._check(self.lib.lib.lmn_tensor_to_float(self.handle, dtype, _addr(src), n, _addr(dst)))
         return dst
 
     def _marshal_tables(self, tables, luts):

@@ -8,6 +8,7 @@
 #include <cmath>
 
 using lmn::Context;
+using lmn::TraceTarget;
 
 namespace {
 // for the entry points that need no context
@@ -412,7 +413,7 @@ int lmn_rows_reset(lmn_rows* rows) {
 }
 void lmn_rows_close(lmn_rows* rows) { delete rows; }
 
-// ---- device producers that fill a sink (trace_gen.cpp Context::rows_append_*).  These do take the context's lock - the
+// ---- device producers that fill a sink (trace_gen.cpp: the Context producers with TraceTarget::into).  These do take the context's lock - the
 // launch runs on its stream, as every lmn_trace_* launch does - and the sink's behind it.  Null pointers are refused where
 // the single forms refuse them, with the argument's name in lmn_last_error(ctx).
 }  // extern "C"
@@ -435,39 +436,44 @@ extern "C" {
 int lmn_rows_append_elementwise_v(lmn_ctx* ctx, lmn_rows* rows, uint32_t kind, const int32_t* lhs_dev, const lmn_view* lhs_view,
                                   const int32_t* rhs_dev, const lmn_view* rhs_view, uint64_t n, const lmn_node_info* info,
                                   uint32_t* range_check_mult_dev, int32_t* out_dev, uint32_t* refused_dev) {
-  return rows_append(ctx, rows, "lmn_rows_append_elementwise_v", !lhs_dev ? "lhs_dev" : !info ? "info" : nullptr, [&](lmn::RowSink& sink) {
-    ctx->impl->rows_append_elementwise(sink, kind, lhs_dev, lhs_view, rhs_dev, rhs_view, n, *info, range_check_mult_dev, out_dev,
-                                       refused_dev);
+  const char* call = "lmn_rows_append_elementwise_v";
+  return rows_append(ctx, rows, call, !lhs_dev ? "lhs_dev" : !info ? "info" : nullptr, [&](lmn::RowSink& sink) {
+    ctx->impl->elementwise(TraceTarget::into(call, sink, out_dev, refused_dev), kind, {lhs_dev, lhs_view}, {rhs_dev, rhs_view}, n,
+                           *info, range_check_mult_dev);
   });
 }
 int lmn_rows_append_contiguous(lmn_ctx* ctx, lmn_rows* rows, const int32_t* input_dev, uint64_t in_size, const lmn_view* view,
                                uint64_t out_size, const lmn_node_info* info, int32_t* out_dev, uint32_t* refused_dev) {
-  return rows_append(ctx, rows, "lmn_rows_append_contiguous", !input_dev ? "input_dev" : !info ? "info" : nullptr, [&](lmn::RowSink& sink) {
-    ctx->impl->rows_append_contiguous(sink, input_dev, in_size, view, out_size, *info, out_dev, refused_dev);
+  const char* call = "lmn_rows_append_contiguous";
+  return rows_append(ctx, rows, call, !input_dev ? "input_dev" : !info ? "info" : nullptr, [&](lmn::RowSink& sink) {
+    ctx->impl->contiguous(TraceTarget::into(call, sink, out_dev, refused_dev), {input_dev, view}, in_size, out_size, *info);
   });
 }
 int lmn_rows_append_reduce(lmn_ctx* ctx, lmn_rows* rows, uint32_t is_max, const int32_t* input_dev, uint64_t front, uint64_t dim,
                            uint64_t back, const lmn_node_info* info, int32_t* out_dev, uint32_t* refused_dev) {
-  return rows_append(ctx, rows, "lmn_rows_append_reduce", !input_dev ? "input_dev" : !info ? "info" : nullptr, [&](lmn::RowSink& sink) {
-    ctx->impl->rows_append_reduce(sink, is_max != 0, input_dev, front, dim, back, *info, out_dev, refused_dev);
+  const char* call = "lmn_rows_append_reduce";
+  return rows_append(ctx, rows, call, !input_dev ? "input_dev" : !info ? "info" : nullptr, [&](lmn::RowSink& sink) {
+    ctx->impl->reduce(TraceTarget::into(call, sink, out_dev, refused_dev), is_max != 0, {input_dev}, front, dim, back, *info);
   });
 }
 int lmn_rows_append_lut_ranges(lmn_ctx* ctx, lmn_rows* rows, uint32_t kind, const int32_t* input_dev, const lmn_view* view,
                                uint64_t n, const lmn_node_info* info, const uint32_t* lut_col1_dev, const lmn_range* ranges,
                                uint32_t n_ranges, uint32_t* mult_dev, int32_t* out_dev, uint32_t* refused_dev) {
-  return rows_append(ctx, rows, "lmn_rows_append_lut_ranges",
+  const char* call = "lmn_rows_append_lut_ranges";
+  return rows_append(ctx, rows, call,
                      !input_dev ? "input_dev" : !info ? "info" : !lut_col1_dev ? "lut_col1_dev" : !mult_dev ? "mult_dev" : nullptr,
                      [&](lmn::RowSink& sink) {
-                       ctx->impl->rows_append_lut(sink, kind, input_dev, view, n, *info, lut_col1_dev, ranges, n_ranges, mult_dev,
-                                                  out_dev, refused_dev);
+                       ctx->impl->lut(TraceTarget::into(call, sink, out_dev, refused_dev), kind, {input_dev, view}, n, *info,
+                                      lut_col1_dev, ranges, n_ranges, mult_dev);
                      });
 }
 
-// (a null src_dev is named by Context::rows_append_inputs_float, behind an unknown dtype)
+// (a null src_dev is named by Context::inputs_float, behind an unknown dtype)
 int lmn_rows_append_inputs_float(lmn_ctx* ctx, lmn_rows* rows, uint32_t dtype, const void* src_dev, uint64_t n,
                                  const lmn_node_info* info, int32_t* out_dev, uint32_t* refused_dev) {
-  return rows_append(ctx, rows, "lmn_rows_append_inputs_float", !info ? "info" : nullptr, [&](lmn::RowSink& sink) {
-    ctx->impl->rows_append_inputs_float(sink, dtype, src_dev, n, *info, out_dev, refused_dev);
+  const char* call = "lmn_rows_append_inputs_float";
+  return rows_append(ctx, rows, call, !info ? "info" : nullptr, [&](lmn::RowSink& sink) {
+    ctx->impl->inputs_float(TraceTarget::into(call, sink, out_dev, refused_dev), dtype, {src_dev}, n, *info);
   });
 }
 
@@ -581,14 +587,15 @@ int lmn_download(lmn_ctx* ctx, const void* device, void* host, size_t bytes) {
 
 int lmn_trace_elementwise(lmn_ctx* ctx, uint32_t kind, const int32_t* lhs_dev, const int32_t* rhs_dev, uint64_t n,
                           const lmn_node_info* info, uint32_t* rows_dev, uint64_t row_offset, int32_t* out_dev) {
-  if (!ctx || !lhs_dev || !info || !rows_dev || kind == LMN_KIND_LESS_THAN) return LMN_ERR_INVALID_ARGUMENT;
-  return guard(ctx, [&] { ctx->impl->trace_elementwise(kind, lhs_dev, nullptr, rhs_dev, nullptr, n, *info, rows_dev, row_offset, out_dev); });
+  return lmn_trace_elementwise_v(ctx, kind, lhs_dev, nullptr, rhs_dev, nullptr, n, info, rows_dev, row_offset, out_dev);
 }
 
 int lmn_trace_sum_reduce(lmn_ctx* ctx, const int32_t* input_dev, uint64_t front, uint64_t dim, uint64_t back,
                          const lmn_node_info* info, uint32_t* rows_dev, uint64_t row_offset, int32_t* out_dev) {
   if (!ctx || !input_dev || !info || !rows_dev) return LMN_ERR_INVALID_ARGUMENT;
-  return guard(ctx, [&] { ctx->impl->trace_reduce(false, input_dev, front, dim, back, *info, rows_dev, row_offset, out_dev); });
+  return guard(ctx, [&] {
+    ctx->impl->reduce(TraceTarget::table(rows_dev, row_offset, out_dev), false, {input_dev}, front, dim, back, *info);
+  });
 }
 
 int lmn_trace_elementwise_v(lmn_ctx* ctx, uint32_t kind, const int32_t* lhs_dev, const lmn_view* lhs_view,
@@ -596,24 +603,25 @@ int lmn_trace_elementwise_v(lmn_ctx* ctx, uint32_t kind, const int32_t* lhs_dev,
                             uint32_t* rows_dev, uint64_t row_offset, int32_t* out_dev) {
   if (!ctx || !lhs_dev || !info || !rows_dev || kind == LMN_KIND_LESS_THAN) return LMN_ERR_INVALID_ARGUMENT;
   return guard(ctx, [&] {
-    ctx->impl->trace_elementwise(kind, lhs_dev, lhs_view, rhs_dev, rhs_view, n, *info, rows_dev, row_offset, out_dev);
+    ctx->impl->elementwise(TraceTarget::table(rows_dev, row_offset, out_dev), kind, {lhs_dev, lhs_view}, {rhs_dev, rhs_view}, n,
+                           *info);
   });
 }
 
 int lmn_trace_contiguous(lmn_ctx* ctx, const int32_t* input_dev, uint64_t in_size, const lmn_view* view, uint64_t out_size,
                          const lmn_node_info* info, uint32_t* rows_dev, uint64_t row_offset, int32_t* out_dev) {
   if (!ctx || !input_dev || !info || !rows_dev) return LMN_ERR_INVALID_ARGUMENT;
-  return guard(ctx, [&] { ctx->impl->trace_contiguous(input_dev, in_size, view, out_size, *info, rows_dev, row_offset, out_dev); });
+  return guard(ctx, [&] {
+    ctx->impl->contiguous(TraceTarget::table(rows_dev, row_offset, out_dev), {input_dev, view}, in_size, out_size, *info);
+  });
 }
 
 int lmn_trace_lut(lmn_ctx* ctx, uint32_t kind, const int32_t* input_dev, const lmn_view* view, uint64_t n,
                   const lmn_node_info* info, const uint32_t* lut_col1_dev, int32_t lo, uint32_t lut_len,
                   uint32_t* mult_dev, uint32_t* rows_dev, uint64_t row_offset, int32_t* out_dev) {
-  if (!ctx || !input_dev || !info || !lut_col1_dev || !mult_dev || !rows_dev || lut_len == 0) return LMN_ERR_INVALID_ARGUMENT;
+  if (lut_len == 0) return LMN_ERR_INVALID_ARGUMENT;
   const lmn_range one{(int64_t)lo, (int64_t)lo + (int64_t)lut_len - 1};
-  return guard(ctx, [&] {
-    ctx->impl->trace_lut(kind, input_dev, view, n, *info, lut_col1_dev, &one, 1, mult_dev, rows_dev, row_offset, out_dev);
-  });
+  return lmn_trace_lut_ranges(ctx, kind, input_dev, view, n, info, lut_col1_dev, &one, 1, mult_dev, rows_dev, row_offset, out_dev);
 }
 
 int lmn_trace_lut_ranges(lmn_ctx* ctx, uint32_t kind, const int32_t* input_dev, const lmn_view* view, uint64_t n,
@@ -621,7 +629,8 @@ int lmn_trace_lut_ranges(lmn_ctx* ctx, uint32_t kind, const int32_t* input_dev, 
                          uint32_t* mult_dev, uint32_t* rows_dev, uint64_t row_offset, int32_t* out_dev) {
   if (!ctx || !input_dev || !info || !lut_col1_dev || !mult_dev || !rows_dev) return LMN_ERR_INVALID_ARGUMENT;
   return guard(ctx, [&] {
-    ctx->impl->trace_lut(kind, input_dev, view, n, *info, lut_col1_dev, ranges, n_ranges, mult_dev, rows_dev, row_offset, out_dev);
+    ctx->impl->lut(TraceTarget::table(rows_dev, row_offset, out_dev), kind, {input_dev, view}, n, *info, lut_col1_dev, ranges,
+                   n_ranges, mult_dev);
   });
 }
 
@@ -630,34 +639,42 @@ int lmn_trace_less_than(lmn_ctx* ctx, const int32_t* lhs_dev, const lmn_view* lh
                         uint32_t* rows_dev, uint64_t row_offset, int32_t* out_dev) {
   if (!ctx || !lhs_dev || !rhs_dev || !info || !range_check_mult_dev || !rows_dev) return LMN_ERR_INVALID_ARGUMENT;
   return guard(ctx, [&] {
-    ctx->impl->trace_elementwise(LMN_KIND_LESS_THAN, lhs_dev, lhs_view, rhs_dev, rhs_view, n, *info, rows_dev, row_offset,
-                                 out_dev, range_check_mult_dev);
+    ctx->impl->elementwise(TraceTarget::table(rows_dev, row_offset, out_dev), LMN_KIND_LESS_THAN, {lhs_dev, lhs_view},
+                           {rhs_dev, rhs_view}, n, *info, range_check_mult_dev);
   });
 }
 
 int lmn_trace_max_reduce(lmn_ctx* ctx, const int32_t* input_dev, uint64_t front, uint64_t dim, uint64_t back,
                          const lmn_node_info* info, uint32_t* rows_dev, uint64_t row_offset, int32_t* out_dev) {
   if (!ctx || !input_dev || !info || !rows_dev) return LMN_ERR_INVALID_ARGUMENT;
-  return guard(ctx, [&] { ctx->impl->trace_reduce(true, input_dev, front, dim, back, *info, rows_dev, row_offset, out_dev); });
+  return guard(ctx, [&] {
+    ctx->impl->reduce(TraceTarget::table(rows_dev, row_offset, out_dev), true, {input_dev}, front, dim, back, *info);
+  });
 }
 
 // ---- the many-member producers: n_members == 0 is LMN_OK and touches nothing (as lmn_ctx_grind_many); null pointers are
 // refused where the single forms refuse them, with the argument's name in lmn_last_error
+namespace {
+template <class F>
+int producer_call(lmn_ctx* ctx, uint32_t n_members, const char* call, const char* null_arg /* the first null argument, if any */, F&& f) {
+  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
+  if (n_members == 0) return LMN_OK;
+  if (null_arg) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, (std::string(call) + ": null " + null_arg).c_str());
+  return guard(ctx, f);
+}
+}  // namespace
 int lmn_trace_many_elementwise_v(lmn_ctx* ctx, uint32_t kind, const int32_t* lhs_dev, const lmn_view* lhs_view,
                                  uint64_t lhs_member_stride, const int32_t* rhs_dev, const lmn_view* rhs_view,
                                  uint64_t rhs_member_stride, uint64_t n, const lmn_node_info* info, uint32_t n_members,
                                  uint32_t* rows_dev, uint64_t row_offset, uint64_t rows_member_stride, int32_t* out_dev,
                                  uint64_t out_member_stride, uint32_t* range_check_mult_dev,
                                  uint64_t range_check_mult_member_stride, uint32_t* refused_dev) {
-  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
-  if (n_members == 0) return LMN_OK;
-  if (!lhs_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_elementwise_v: null lhs_dev");
-  if (!info) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_elementwise_v: null info");
-  if (!rows_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_elementwise_v: null rows_dev");
-  return guard(ctx, [&] {
-    ctx->impl->trace_many_elementwise(kind, lhs_dev, lhs_view, lhs_member_stride, rhs_dev, rhs_view, rhs_member_stride, n, *info,
-                                      n_members, rows_dev, row_offset, rows_member_stride, out_dev, out_member_stride,
-                                      range_check_mult_dev, range_check_mult_member_stride, refused_dev);
+  const char* call = "lmn_trace_many_elementwise_v";
+  return producer_call(ctx, n_members, call, !lhs_dev ? "lhs_dev" : !info ? "info" : !rows_dev ? "rows_dev" : nullptr, [&] {
+    ctx->impl->elementwise(
+        TraceTarget::many(call, n_members, rows_dev, row_offset, rows_member_stride, out_dev, out_member_stride, refused_dev), kind,
+        {lhs_dev, lhs_view, lhs_member_stride}, {rhs_dev, rhs_view, rhs_member_stride}, n, *info, range_check_mult_dev,
+        range_check_mult_member_stride);
   });
 }
 
@@ -665,14 +682,11 @@ int lmn_trace_many_contiguous(lmn_ctx* ctx, const int32_t* input_dev, uint64_t i
                               const lmn_view* view, uint64_t out_size, const lmn_node_info* info, uint32_t n_members,
                               uint32_t* rows_dev, uint64_t row_offset, uint64_t rows_member_stride, int32_t* out_dev,
                               uint64_t out_member_stride, uint32_t* refused_dev) {
-  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
-  if (n_members == 0) return LMN_OK;
-  if (!input_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_contiguous: null input_dev");
-  if (!info) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_contiguous: null info");
-  if (!rows_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_contiguous: null rows_dev");
-  return guard(ctx, [&] {
-    ctx->impl->trace_many_contiguous(input_dev, input_member_stride, in_size, view, out_size, *info, n_members, rows_dev,
-                                     row_offset, rows_member_stride, out_dev, out_member_stride, refused_dev);
+  const char* call = "lmn_trace_many_contiguous";
+  return producer_call(ctx, n_members, call, !input_dev ? "input_dev" : !info ? "info" : !rows_dev ? "rows_dev" : nullptr, [&] {
+    ctx->impl->contiguous(
+        TraceTarget::many(call, n_members, rows_dev, row_offset, rows_member_stride, out_dev, out_member_stride, refused_dev),
+        {input_dev, view, input_member_stride}, in_size, out_size, *info);
   });
 }
 
@@ -680,14 +694,11 @@ int lmn_trace_many_reduce(lmn_ctx* ctx, uint32_t is_max, const int32_t* input_de
                           uint64_t dim, uint64_t back, const lmn_node_info* info, uint32_t n_members, uint32_t* rows_dev,
                           uint64_t row_offset, uint64_t rows_member_stride, int32_t* out_dev, uint64_t out_member_stride,
                           uint32_t* refused_dev) {
-  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
-  if (n_members == 0) return LMN_OK;
-  if (!input_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_reduce: null input_dev");
-  if (!info) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_reduce: null info");
-  if (!rows_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_reduce: null rows_dev");
-  return guard(ctx, [&] {
-    ctx->impl->trace_many_reduce(is_max != 0, input_dev, input_member_stride, front, dim, back, *info, n_members, rows_dev,
-                                 row_offset, rows_member_stride, out_dev, out_member_stride, refused_dev);
+  const char* call = "lmn_trace_many_reduce";
+  return producer_call(ctx, n_members, call, !input_dev ? "input_dev" : !info ? "info" : !rows_dev ? "rows_dev" : nullptr, [&] {
+    ctx->impl->reduce(
+        TraceTarget::many(call, n_members, rows_dev, row_offset, rows_member_stride, out_dev, out_member_stride, refused_dev),
+        is_max != 0, {input_dev, nullptr, input_member_stride}, front, dim, back, *info);
   });
 }
 
@@ -696,17 +707,13 @@ int lmn_trace_many_lut_ranges(lmn_ctx* ctx, uint32_t kind, const int32_t* input_
                               const lmn_range* ranges, uint32_t n_ranges, uint32_t n_members, uint32_t* mult_dev,
                               uint64_t mult_member_stride, uint32_t* rows_dev, uint64_t row_offset, uint64_t rows_member_stride,
                               int32_t* out_dev, uint64_t out_member_stride, uint32_t* refused_dev) {
-  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
-  if (n_members == 0) return LMN_OK;
-  if (!input_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_lut_ranges: null input_dev");
-  if (!info) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_lut_ranges: null info");
-  if (!lut_col1_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_lut_ranges: null lut_col1_dev");
-  if (!mult_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_lut_ranges: null mult_dev");
-  if (!rows_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_lut_ranges: null rows_dev");
-  return guard(ctx, [&] {
-    ctx->impl->trace_many_lut(kind, input_dev, view, input_member_stride, n, *info, lut_col1_dev, ranges, n_ranges, n_members,
-                              mult_dev, mult_member_stride, rows_dev, row_offset, rows_member_stride, out_dev,
-                              out_member_stride, refused_dev);
+  const char* call = "lmn_trace_many_lut_ranges";
+  const char* null_arg = !input_dev ? "input_dev" : !info ? "info" : !lut_col1_dev ? "lut_col1_dev" : !mult_dev ? "mult_dev"
+                         : !rows_dev ? "rows_dev" : nullptr;
+  return producer_call(ctx, n_members, call, null_arg, [&] {
+    ctx->impl->lut(TraceTarget::many(call, n_members, rows_dev, row_offset, rows_member_stride, out_dev, out_member_stride, refused_dev),
+                   kind, {input_dev, view, input_member_stride}, n, *info, lut_col1_dev, ranges, n_ranges, mult_dev,
+                   mult_member_stride);
   });
 }
 
@@ -753,22 +760,20 @@ int lmn_tensor_range(lmn_ctx* ctx, const int32_t* buf_dev, uint64_t n, int32_t* 
 // context, in that order, in front of the sibling form's own rules
 int lmn_trace_inputs_float(lmn_ctx* ctx, uint32_t dtype, const void* src_dev, uint64_t n, const lmn_node_info* info,
                            uint32_t* rows_dev, uint64_t row_offset, int32_t* out_dev) {
-  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
-  if (!info) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_inputs_float: null info");
-  if (!rows_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_inputs_float: null rows_dev");
-  return guard(ctx, [&] { ctx->impl->trace_inputs_float(dtype, src_dev, n, *info, rows_dev, row_offset, out_dev); });
+  const char* call = "lmn_trace_inputs_float";
+  return producer_call(ctx, 1, call, !info ? "info" : !rows_dev ? "rows_dev" : nullptr, [&] {
+    ctx->impl->inputs_float(TraceTarget::table(rows_dev, row_offset, out_dev, call), dtype, {src_dev}, n, *info);
+  });
 }
 
 int lmn_trace_many_inputs_float(lmn_ctx* ctx, uint32_t dtype, const void* src_dev, uint64_t src_member_stride, uint64_t n,
                                 const lmn_node_info* info, uint32_t n_members, uint32_t* rows_dev, uint64_t row_offset,
                                 uint64_t rows_member_stride, int32_t* out_dev, uint64_t out_member_stride, uint32_t* refused_dev) {
-  if (!ctx) return LMN_ERR_INVALID_ARGUMENT;
-  if (n_members == 0) return LMN_OK;
-  if (!info) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_inputs_float: null info");
-  if (!rows_dev) return set_error(ctx, LMN_ERR_INVALID_ARGUMENT, "lmn_trace_many_inputs_float: null rows_dev");
-  return guard(ctx, [&] {
-    ctx->impl->trace_many_inputs_float(dtype, src_dev, src_member_stride, n, *info, n_members, rows_dev, row_offset,
-                                       rows_member_stride, out_dev, out_member_stride, refused_dev);
+  const char* call = "lmn_trace_many_inputs_float";
+  return producer_call(ctx, n_members, call, !info ? "info" : !rows_dev ? "rows_dev" : nullptr, [&] {
+    ctx->impl->inputs_float(
+        TraceTarget::many(call, n_members, rows_dev, row_offset, rows_member_stride, out_dev, out_member_stride, refused_dev), dtype,
+        {src_dev, nullptr, src_member_stride}, n, *info);
   });
 }
 

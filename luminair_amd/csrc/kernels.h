@@ -543,9 +543,43 @@ struct TraceView {  // strided view; ndim == 0: contiguous
   int64_t strides[4];
   int64_t offset;
 };
-void launch_trace_elementwise(int kind, const int32_t* lhs, const TraceView& lv, const int32_t* rhs, const TraceView& rv,
-                              uint64_t n, const TraceNode& nd, uint32_t* rows, int32_t* out, uint32_t* aux,
-                              lmn_stream_t s);
+// An operand of a producer: member m of a many-member launch reads p + m * ms elements (ms == 0 shares it; a float source:
+// elements of its dtype); the reduce producers read it contiguous and take no view
+struct TraceOperand {
+  const int32_t* p;
+  TraceView view;
+  uint64_t ms;
+};
+// Where a producer's rows and values go, as the launchers take it (the host side of the kernels' TraceDst).
+//   ROWS: `rows` is the node's first row in an array-of-structs table (lmn_trace_*).
+//   COLS: the column form (lmn_rows_append_*) - word c of the node's row r goes to cols[c * col_stride + r], so `cols` is
+//         column 0 at the node's FIRST TABLE ROW (the sink's row count, any value: no alignment is asked of it).  One dword
+//         per lane per column, no LDS tile (the reduce kernels keep the LDS of their scan).  A refused element is marked as
+//         in the row forms, sets *bad_word (the sink's verdict word) to 1 and is added to *refused (may be null).
+//   MANY: one launch fills the node's rows for n_members pies (lmn_trace_many_*), grid.y = the member: member m works on
+//         base + m * stride (operands and `out` in elements, rows / aux / mult in WORDS here - the host side converts row
+//         strides); out_ms == 0 stores the shared output from member 0 only.  refused (n_members counters, may be null)
+//         grows by each member's refused elements.
+// A LUT input outside every range is a refused element in COLS and MANY; ROWS sets *err_flag (a device word) instead.
+struct TraceOut {
+  enum Form { ROWS, COLS, MANY } form = ROWS;
+  uint32_t* rows = nullptr;       // ROWS, MANY
+  uint64_t rows_ms = 0;           // MANY
+  uint32_t* cols = nullptr;       // COLS
+  uint64_t col_stride = 0;
+  uint32_t* bad_word = nullptr;
+  uint32_t n_members = 1;
+  int32_t* out = nullptr;         // the node's output tensor (may be null)
+  uint64_t out_ms = 0;
+  uint32_t* refused = nullptr;    // COLS, MANY
+  uint32_t* err_flag = nullptr;   // ROWS of the LUT producer
+};
+constexpr int SRC_FIXED = -1;     // src_dtype of an int32 Fixed<12> source; LMN_F32 / LMN_F16 / LMN_BF16: raw float bits
+// One launcher per family, the kernel picked by o.form.  src_dtype != SRC_FIXED: the Inputs kind reading raw float bits of
+// that dtype (kernels_trace.hip float_bits_to_fixed), the conversion inside the launch that writes the rows.
+// aux: LessThan's range-check multiplicities (256 words per member, aux_ms apart).
+void launch_trace_elementwise(int kind, int src_dtype, const TraceOperand& lhs, const TraceOperand& rhs, uint64_t n,
+                              const TraceNode& nd, uint32_t* aux, uint64_t aux_ms, const TraceOut& o, lmn_stream_t s);
 // The value ranges a LUT enumerates, ascending and disjoint (`LookupLayout::ranges` after `coalesce_ranges`,
 // crates/graph/src/graph.rs:665-691): LUT row of value v in range r = base[r] + (v - lo[r])
 // (`LookupLayout::find_index`, crates/air/src/preprocessed.rs:60-77).
@@ -555,44 +589,12 @@ struct LutRanges {
   int32_t lo[LUT_MAX_RANGES], hi[LUT_MAX_RANGES];
   uint32_t base[LUT_MAX_RANGES];
 };
-// LUT op rows + LUT multiplicities; *err_flag (device word) is set when an input falls outside every range
-void launch_trace_lut(const int32_t* input, const TraceView& view, uint64_t n, const TraceNode& nd,
-                      const uint32_t* lut_col1, const LutRanges& ranges, uint32_t* mult, uint32_t* rows,
-                      int32_t* out, uint32_t* err_flag, lmn_stream_t s);
-
-void launch_trace_reduce(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back,
-                         const TraceNode& nd, uint32_t* rows, int32_t* out, lmn_stream_t s);
-
-// ---- the column forms (lmn_rows_append_*): the same row rules with the rows stored into a row sink's columns - word c of
-// the node's row r goes to cols[c * col_stride + r], so `cols` is column 0 at the node's FIRST TABLE ROW (the sink's row
-// count, any value: no alignment is asked of it).  One dword per lane per column, no LDS tile (the reduce kernels keep the
-// LDS of their scan).  A refused element is marked as in the row forms, sets *bad_word (the sink's verdict word) to 1 and is
-// added to *refused (may be null); a LUT input outside every range is a refused element, as in the many-member forms.
-void launch_trace_elementwise_cols(int kind, const int32_t* lhs, const TraceView& lv, const int32_t* rhs, const TraceView& rv,
-                                   uint64_t n, const TraceNode& nd, uint32_t* cols, uint64_t col_stride, int32_t* out,
-                                   uint32_t* aux, uint32_t* bad_word, uint32_t* refused, lmn_stream_t s);
-void launch_trace_reduce_cols(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back,
-                              const TraceNode& nd, uint32_t* cols, uint64_t col_stride, int32_t* out, uint32_t* bad_word,
-                              uint32_t* refused, lmn_stream_t s);
-void launch_trace_lut_cols(const int32_t* input, const TraceView& view, uint64_t n, const TraceNode& nd,
-                           const uint32_t* lut_col1, const LutRanges& ranges, uint32_t* mult, uint32_t* cols,
-                           uint64_t col_stride, int32_t* out, uint32_t* bad_word, uint32_t* refused, lmn_stream_t s);
-
-// ---- the many-member forms (lmn_trace_many_*): one launch fills a node's rows for n_members pies, grid.y = the member.
-// Member m works on base + m * stride (`*_ms`: operands and outputs in elements, rows / aux / mult in WORDS here - the host
-// side converts row strides); an operand stride of 0 shares the operand, out_ms == 0 stores the shared output from member 0
-// only.  refused (n_members counters, may be null) grows by each member's refused elements; a LUT input outside every range
-// is one of them.
-void launch_trace_many_elementwise(int kind, const int32_t* lhs, const TraceView& lv, uint64_t lhs_ms, const int32_t* rhs,
-                                   const TraceView& rv, uint64_t rhs_ms, uint64_t n, const TraceNode& nd, uint32_t n_members,
-                                   uint32_t* rows, uint64_t rows_ms, int32_t* out, uint64_t out_ms, uint32_t* aux, uint64_t aux_ms,
-                                   uint32_t* refused, lmn_stream_t s);
-void launch_trace_many_reduce(bool is_max, const int32_t* input, uint64_t in_ms, uint64_t front, uint64_t dim, uint64_t back,
-                              const TraceNode& nd, uint32_t n_members, uint32_t* rows, uint64_t rows_ms, int32_t* out,
-                              uint64_t out_ms, uint32_t* refused, lmn_stream_t s);
-void launch_trace_many_lut(const int32_t* input, const TraceView& view, uint64_t in_ms, uint64_t n, const TraceNode& nd,
-                           const uint32_t* lut_col1, const LutRanges& ranges, uint32_t n_members, uint32_t* mult, uint64_t mult_ms,
-                           uint32_t* rows, uint64_t rows_ms, int32_t* out, uint64_t out_ms, uint32_t* refused, lmn_stream_t s);
+// LUT op rows + LUT multiplicities (lut_col1 is shared by all members, the multiplicity atomics go to the member's own
+// table, mult_ms words apart)
+void launch_trace_lut(const TraceOperand& input, uint64_t n, const TraceNode& nd, const uint32_t* lut_col1,
+                      const LutRanges& ranges, uint32_t* mult, uint64_t mult_ms, const TraceOut& o, lmn_stream_t s);
+void launch_trace_reduce(bool is_max, const TraceOperand& input, uint64_t front, uint64_t dim, uint64_t back,
+                         const TraceNode& nd, const TraceOut& o, lmn_stream_t s);
 
 // ---- the eval forms of the producers (lmn_eval_*): values only, plus the range of what was written in minmax[0 .. 1]
 // (atomicMin / atomicMax: initialise with launch_eval_init) and the refused elements added to *refused; both may be null
@@ -606,16 +608,8 @@ bool eval_reduce_by_wave(uint64_t dim, uint64_t back);
 void launch_eval_reduce(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back, int32_t* out,
                         int32_t* minmax, uint32_t* refused, lmn_stream_t s);
 void launch_tensor_range(const int32_t* buf, uint64_t n, int32_t* minmax, lmn_stream_t s);
-// Float tensors in and out (kernels_trace.hip float_bits_to_fixed / fixed_to_float_bits): the Inputs producers reading raw
-// float bits of dtype LMN_F32 / LMN_F16 / LMN_BF16 - row, column, many-member and eval form, the conversion inside the launch
-// that writes the rows - and the way back.  src_ms in elements of the dtype.
-void launch_trace_inputs_float(uint32_t dtype, const void* src, uint64_t n, const TraceNode& nd, uint32_t* rows, int32_t* out,
-                               lmn_stream_t s);
-void launch_trace_inputs_float_cols(uint32_t dtype, const void* src, uint64_t n, const TraceNode& nd, uint32_t* cols,
-                                    uint64_t col_stride, int32_t* out, uint32_t* bad_word, uint32_t* refused, lmn_stream_t s);
-void launch_trace_many_inputs_float(uint32_t dtype, const void* src, uint64_t src_ms, uint64_t n, const TraceNode& nd,
-                                    uint32_t n_members, uint32_t* rows, uint64_t rows_ms, int32_t* out, uint64_t out_ms,
-                                    uint32_t* refused, lmn_stream_t s);
+// Float tensors in and out (kernels_trace.hip float_bits_to_fixed / fixed_to_float_bits): the eval form of the float
+// Inputs producer, and the way back
 void launch_eval_inputs_float(uint32_t dtype, const void* src, uint64_t n, int32_t* out, int32_t* minmax, uint32_t* refused,
                               lmn_stream_t s);
 void launch_tensor_to_float(uint32_t dtype, const int32_t* src, uint64_t n, void* dst, lmn_stream_t s);

@@ -240,8 +240,7 @@ LMN_HD uint32_t fixed_to_float_bits(int32_t v) {
 }
 // Where a producer's operand comes from: an int32 Fixed<12> tensor, or raw float bits of dtype LMN_F32 / LMN_F16 / LMN_BF16
 // (SRC = the dtype) converted as they are read.  The float forms hand their source's address through the operand's
-// `const int32_t*` parameter; src_at and src_value give it its element size back.
-constexpr int SRC_FIXED = -1;
+// `const int32_t*` parameter; src_at and src_value give it its element size back.  (SRC_FIXED: kernels.h)
 template <int SRC>
 LMN_HD const int32_t* src_at(const int32_t* base, uint64_t elems) {
   constexpr uint64_t BYTES = SRC == SRC_FIXED || SRC == 0 ? 4 : 2;
@@ -627,86 +626,33 @@ LMN_KERNEL k_trace_many_reduce(const int32_t* __restrict__ input, uint64_t in_ms
                                many_out_base(out, out_ms, m), refused ? refused + m : nullptr);
 }
 
-void launch_trace_reduce(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back,
-                         const TraceNode& nd, uint32_t* rows, int32_t* out, lmn_stream_t s) {
+// One launcher per family: the destination's form (TraceOut, kernels.h) picks the kernel in front of the same row rule
+void launch_trace_reduce(bool is_max, const TraceOperand& input, uint64_t front, uint64_t dim, uint64_t back,
+                         const TraceNode& nd, const TraceOut& o, lmn_stream_t s) {
   const uint64_t n_out = front * back, n_rows = n_out * dim;
-  if (is_max)
-    LMN_LAUNCH(k_trace_reduce<true>, dim3(cdiv(n_rows, TPB)), dim3(TPB), 0, s, input, dim, back, n_rows, n_out, nd, rows, out);
-  else
-    LMN_LAUNCH(k_trace_reduce<false>, dim3(cdiv(n_rows, TPB)), dim3(TPB), 0, s, input, dim, back, n_rows, n_out, nd, rows, out);
-}
-
-void launch_trace_reduce_cols(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back,
-                              const TraceNode& nd, uint32_t* cols, uint64_t col_stride, int32_t* out, uint32_t* bad_word,
-                              uint32_t* refused, lmn_stream_t s) {
-  const uint64_t n_out = front * back, n_rows = n_out * dim;
-  const dim3 g(cdiv(n_rows, TPB)), b(TPB);
-  if (is_max)
-    LMN_LAUNCH(k_sink_reduce<true>, g, b, 0, s, input, dim, back, n_rows, n_out, nd, cols, col_stride, out, bad_word, refused);
-  else
-    LMN_LAUNCH(k_sink_reduce<false>, g, b, 0, s, input, dim, back, n_rows, n_out, nd, cols, col_stride, out, bad_word, refused);
-}
-
-void launch_trace_many_reduce(bool is_max, const int32_t* input, uint64_t in_ms, uint64_t front, uint64_t dim, uint64_t back,
-                              const TraceNode& nd, uint32_t n_members, uint32_t* rows, uint64_t rows_ms, int32_t* out,
-                              uint64_t out_ms, uint32_t* refused, lmn_stream_t s) {
-  const uint64_t n_out = front * back, n_rows = n_out * dim;
-  const dim3 g(cdiv(n_rows, TPB), n_members), b(TPB);
-  if (is_max)
-    LMN_LAUNCH(k_trace_many_reduce<true>, g, b, 0, s, input, in_ms, dim, back, n_rows, n_out, nd, rows, rows_ms, out, out_ms, refused);
-  else
-    LMN_LAUNCH(k_trace_many_reduce<false>, g, b, 0, s, input, in_ms, dim, back, n_rows, n_out, nd, rows, rows_ms, out, out_ms, refused);
-}
-
-void launch_trace_elementwise(int kind, const int32_t* lhs, const TraceView& lv, const int32_t* rhs, const TraceView& rv,
-                              uint64_t n, const TraceNode& nd, uint32_t* rows, int32_t* out, uint32_t* aux,
-                              lmn_stream_t s) {
-  dim3 g(cdiv(n, TPB)), b(TPB);
-  switch (kind) {
-    case 0: LMN_LAUNCH(k_trace_elementwise<0>, g, b, 0, s, lhs, lv, rhs, rv, n, nd, rows, out, aux); break;
-    case 1: LMN_LAUNCH(k_trace_elementwise<1>, g, b, 0, s, lhs, lv, rhs, rv, n, nd, rows, out, aux); break;
-    case 2: LMN_LAUNCH(k_trace_elementwise<2>, g, b, 0, s, lhs, lv, rhs, rv, n, nd, rows, out, aux); break;
-    case 7: LMN_LAUNCH(k_trace_elementwise<7>, g, b, 0, s, lhs, lv, rhs, rv, n, nd, rows, out, aux); break;
-    case 8: LMN_LAUNCH(k_trace_elementwise<8>, g, b, 0, s, lhs, lv, rhs, rv, n, nd, rows, out, aux); break;
-    case 13: LMN_LAUNCH(k_trace_elementwise<13>, g, b, 0, s, lhs, lv, rhs, rv, n, nd, rows, out, aux); break;
-    case 15: LMN_LAUNCH(k_trace_elementwise<15>, g, b, 0, s, lhs, lv, rhs, rv, n, nd, rows, out, aux); break;
-    case 16: LMN_LAUNCH(k_trace_elementwise<16>, g, b, 0, s, lhs, lv, rhs, rv, n, nd, rows, out, aux); break;
-    default: throw LmnError(-100, "trace_elementwise: unsupported kind");
+  const dim3 g(cdiv(n_rows, TPB), o.form == TraceOut::MANY ? o.n_members : 1), b(TPB);
+  switch (o.form) {
+    case TraceOut::ROWS:
+      if (is_max) LMN_LAUNCH(k_trace_reduce<true>, g, b, 0, s, input.p, dim, back, n_rows, n_out, nd, o.rows, o.out);
+      else LMN_LAUNCH(k_trace_reduce<false>, g, b, 0, s, input.p, dim, back, n_rows, n_out, nd, o.rows, o.out);
+      break;
+    case TraceOut::COLS:
+      if (is_max)
+        LMN_LAUNCH(k_sink_reduce<true>, g, b, 0, s, input.p, dim, back, n_rows, n_out, nd, o.cols, o.col_stride, o.out, o.bad_word,
+                   o.refused);
+      else
+        LMN_LAUNCH(k_sink_reduce<false>, g, b, 0, s, input.p, dim, back, n_rows, n_out, nd, o.cols, o.col_stride, o.out, o.bad_word,
+                   o.refused);
+      break;
+    case TraceOut::MANY:
+      if (is_max)
+        LMN_LAUNCH(k_trace_many_reduce<true>, g, b, 0, s, input.p, input.ms, dim, back, n_rows, n_out, nd, o.rows, o.rows_ms, o.out,
+                   o.out_ms, o.refused);
+      else
+        LMN_LAUNCH(k_trace_many_reduce<false>, g, b, 0, s, input.p, input.ms, dim, back, n_rows, n_out, nd, o.rows, o.rows_ms, o.out,
+                   o.out_ms, o.refused);
+      break;
   }
-}
-
-void launch_trace_elementwise_cols(int kind, const int32_t* lhs, const TraceView& lv, const int32_t* rhs, const TraceView& rv,
-                                   uint64_t n, const TraceNode& nd, uint32_t* cols, uint64_t col_stride, int32_t* out,
-                                   uint32_t* aux, uint32_t* bad_word, uint32_t* refused, lmn_stream_t s) {
-  const dim3 g(cdiv(n, TPB)), b(TPB);
-#define LMN_COLS_CASE(K)                                                                                                       \
-  case K:                                                                                                                      \
-    LMN_LAUNCH(k_sink_elementwise<K>, g, b, 0, s, lhs, lv, rhs, rv, n, nd, cols, col_stride, out, aux, bad_word, refused); \
-    break;
-  switch (kind) {
-    LMN_COLS_CASE(0) LMN_COLS_CASE(1) LMN_COLS_CASE(2) LMN_COLS_CASE(7) LMN_COLS_CASE(8) LMN_COLS_CASE(13) LMN_COLS_CASE(15)
-    LMN_COLS_CASE(16)
-    default: throw LmnError(-100, "trace_elementwise_cols: unsupported kind");
-  }
-#undef LMN_COLS_CASE
-}
-
-void launch_trace_many_elementwise(int kind, const int32_t* lhs, const TraceView& lv, uint64_t lhs_ms, const int32_t* rhs,
-                                   const TraceView& rv, uint64_t rhs_ms, uint64_t n, const TraceNode& nd, uint32_t n_members,
-                                   uint32_t* rows, uint64_t rows_ms, int32_t* out, uint64_t out_ms, uint32_t* aux, uint64_t aux_ms,
-                                   uint32_t* refused, lmn_stream_t s) {
-  const dim3 g(cdiv(n, TPB), n_members), b(TPB);
-#define LMN_MANY_CASE(K)                                                                                                       \
-  case K:                                                                                                                      \
-    LMN_LAUNCH(k_trace_many_elementwise<K>, g, b, 0, s, lhs, lv, lhs_ms, rhs, rv, rhs_ms, n, nd, rows, rows_ms, out, out_ms, aux, \
-               aux_ms, refused);                                                                                               \
-    break;
-  switch (kind) {
-    LMN_MANY_CASE(0) LMN_MANY_CASE(1) LMN_MANY_CASE(2) LMN_MANY_CASE(7) LMN_MANY_CASE(8) LMN_MANY_CASE(13) LMN_MANY_CASE(15)
-    LMN_MANY_CASE(16)
-    default: throw LmnError(-100, "trace_many_elementwise: unsupported kind");
-  }
-#undef LMN_MANY_CASE
 }
 
 // The float forms of the Inputs producers (lmn_trace_inputs_float and its many and sink siblings): k_trace_elementwise<15>,
@@ -734,38 +680,69 @@ LMN_KERNEL k_trace_many_inputs_float(const int32_t* __restrict__ src, uint64_t s
                                                TraceDst{rows + m * rows_ms, 0, nullptr}, many_out_base(out, out_ms, m), nullptr,
                                                refused ? refused + m : nullptr);
 }
-// X(SRC) launches one instantiation
-#define LMN_FLOAT_DTYPES(what, X)                     \
-  switch (dtype) {                                    \
-    case 0: X(0); break;                              \
-    case 1: X(1); break;                              \
-    case 2: X(2); break;                              \
+// The elementwise kinds and the float dtypes, each stated once for every launcher that picks an instantiation by them:
+// X(K) launches one
+#define LMN_ELEMENTWISE_KINDS(kind, what, X)                  \
+  switch (kind) {                                             \
+    case 0: X(0); break;                                      \
+    case 1: X(1); break;                                      \
+    case 2: X(2); break;                                      \
+    case 7: X(7); break;                                      \
+    case 8: X(8); break;                                      \
+    case 13: X(13); break;                                    \
+    case 15: X(15); break;                                    \
+    case 16: X(16); break;                                    \
+    default: throw LmnError(-100, what ": unsupported kind"); \
+  }
+#define LMN_FLOAT_DTYPES(dtype, what, X)                       \
+  switch (dtype) {                                             \
+    case 0: X(0); break;                                       \
+    case 1: X(1); break;                                       \
+    case 2: X(2); break;                                       \
     default: throw LmnError(-100, what ": unsupported dtype"); \
   }
-void launch_trace_inputs_float(uint32_t dtype, const void* src, uint64_t n, const TraceNode& nd, uint32_t* rows, int32_t* out,
-                               lmn_stream_t s) {
-  const dim3 g(cdiv(n, TPB)), b(TPB);
-  const int32_t* lhs = (const int32_t*)src;
-#define LMN_X(S) LMN_LAUNCH(k_trace_inputs_float<S>, g, b, 0, s, lhs, n, nd, rows, out)
-  LMN_FLOAT_DTYPES("trace_inputs_float", LMN_X)
+void launch_trace_elementwise(int kind, int src_dtype, const TraceOperand& lhs, const TraceOperand& rhs, uint64_t n,
+                              const TraceNode& nd, uint32_t* aux, uint64_t aux_ms, const TraceOut& o, lmn_stream_t s) {
+  const dim3 g(cdiv(n, TPB), o.form == TraceOut::MANY ? o.n_members : 1), b(TPB);
+  if (src_dtype == SRC_FIXED) switch (o.form) {
+      case TraceOut::ROWS:
+#define LMN_X(K) LMN_LAUNCH(k_trace_elementwise<K>, g, b, 0, s, lhs.p, lhs.view, rhs.p, rhs.view, n, nd, o.rows, o.out, aux)
+        LMN_ELEMENTWISE_KINDS(kind, "trace_elementwise", LMN_X)
 #undef LMN_X
-}
-void launch_trace_inputs_float_cols(uint32_t dtype, const void* src, uint64_t n, const TraceNode& nd, uint32_t* cols,
-                                    uint64_t col_stride, int32_t* out, uint32_t* bad_word, uint32_t* refused, lmn_stream_t s) {
-  const dim3 g(cdiv(n, TPB)), b(TPB);
-  const int32_t* lhs = (const int32_t*)src;
-#define LMN_X(S) LMN_LAUNCH(k_sink_inputs_float<S>, g, b, 0, s, lhs, n, nd, cols, col_stride, out, bad_word, refused)
-  LMN_FLOAT_DTYPES("trace_inputs_float_cols", LMN_X)
+        break;
+      case TraceOut::COLS:
+#define LMN_X(K)                                                                                                          \
+  LMN_LAUNCH(k_sink_elementwise<K>, g, b, 0, s, lhs.p, lhs.view, rhs.p, rhs.view, n, nd, o.cols, o.col_stride, o.out, aux, \
+             o.bad_word, o.refused)
+        LMN_ELEMENTWISE_KINDS(kind, "trace_elementwise_cols", LMN_X)
 #undef LMN_X
-}
-void launch_trace_many_inputs_float(uint32_t dtype, const void* src, uint64_t src_ms, uint64_t n, const TraceNode& nd,
-                                    uint32_t n_members, uint32_t* rows, uint64_t rows_ms, int32_t* out, uint64_t out_ms,
-                                    uint32_t* refused, lmn_stream_t s) {
-  const dim3 g(cdiv(n, TPB), n_members), b(TPB);
-  const int32_t* lhs = (const int32_t*)src;
-#define LMN_X(S) LMN_LAUNCH(k_trace_many_inputs_float<S>, g, b, 0, s, lhs, src_ms, n, nd, rows, rows_ms, out, out_ms, refused)
-  LMN_FLOAT_DTYPES("trace_many_inputs_float", LMN_X)
+        break;
+      case TraceOut::MANY:
+#define LMN_X(K)                                                                                                             \
+  LMN_LAUNCH(k_trace_many_elementwise<K>, g, b, 0, s, lhs.p, lhs.view, lhs.ms, rhs.p, rhs.view, rhs.ms, n, nd, o.rows, o.rows_ms, \
+             o.out, o.out_ms, aux, aux_ms, o.refused)
+        LMN_ELEMENTWISE_KINDS(kind, "trace_many_elementwise", LMN_X)
 #undef LMN_X
+        break;
+    }
+  else switch (o.form) {   // the float source is Inputs' alone
+      case TraceOut::ROWS:
+#define LMN_X(S) LMN_LAUNCH(k_trace_inputs_float<S>, g, b, 0, s, lhs.p, n, nd, o.rows, o.out)
+        LMN_FLOAT_DTYPES(src_dtype, "trace_inputs_float", LMN_X)
+#undef LMN_X
+        break;
+      case TraceOut::COLS:
+#define LMN_X(S) LMN_LAUNCH(k_sink_inputs_float<S>, g, b, 0, s, lhs.p, n, nd, o.cols, o.col_stride, o.out, o.bad_word, o.refused)
+        LMN_FLOAT_DTYPES(src_dtype, "trace_inputs_float_cols", LMN_X)
+#undef LMN_X
+        break;
+      case TraceOut::MANY:
+#define LMN_X(S) \
+  LMN_LAUNCH(k_trace_many_inputs_float<S>, g, b, 0, s, lhs.p, lhs.ms, n, nd, o.rows, o.rows_ms, o.out, o.out_ms, o.refused)
+        LMN_FLOAT_DTYPES(src_dtype, "trace_many_inputs_float", LMN_X)
+#undef LMN_X
+        break;
+    }
 }
 
 // LookupLayout::find_index: the LUT row of the range that holds `a`, -1 when no range does (few ranges: a linear scan of
@@ -836,25 +813,22 @@ LMN_KERNEL k_trace_many_lut(const int32_t* __restrict__ input, TraceView view, u
                        many_out_base(out, out_ms, m), nullptr, refused ? refused + m : nullptr);
 }
 
-void launch_trace_lut(const int32_t* input, const TraceView& view, uint64_t n, const TraceNode& nd,
-                      const uint32_t* lut_col1, const LutRanges& ranges, uint32_t* mult, uint32_t* rows,
-                      int32_t* out, uint32_t* err_flag, lmn_stream_t s) {
-  LMN_LAUNCH(k_trace_lut, dim3(cdiv(n, TPB)), dim3(TPB), 0, s, input, view, n, nd, lut_col1, ranges, mult, rows, out,
-             err_flag);
-}
-
-void launch_trace_lut_cols(const int32_t* input, const TraceView& view, uint64_t n, const TraceNode& nd,
-                           const uint32_t* lut_col1, const LutRanges& ranges, uint32_t* mult, uint32_t* cols,
-                           uint64_t col_stride, int32_t* out, uint32_t* bad_word, uint32_t* refused, lmn_stream_t s) {
-  LMN_LAUNCH(k_sink_lut, dim3(cdiv(n, TPB)), dim3(TPB), 0, s, input, view, n, nd, lut_col1, ranges, mult, cols, col_stride,
-             out, bad_word, refused);
-}
-
-void launch_trace_many_lut(const int32_t* input, const TraceView& view, uint64_t in_ms, uint64_t n, const TraceNode& nd,
-                           const uint32_t* lut_col1, const LutRanges& ranges, uint32_t n_members, uint32_t* mult, uint64_t mult_ms,
-                           uint32_t* rows, uint64_t rows_ms, int32_t* out, uint64_t out_ms, uint32_t* refused, lmn_stream_t s) {
-  LMN_LAUNCH(k_trace_many_lut, dim3(cdiv(n, TPB), n_members), dim3(TPB), 0, s, input, view, in_ms, n, nd, lut_col1, ranges, mult,
-             mult_ms, rows, rows_ms, out, out_ms, refused);
+void launch_trace_lut(const TraceOperand& input, uint64_t n, const TraceNode& nd, const uint32_t* lut_col1,
+                      const LutRanges& ranges, uint32_t* mult, uint64_t mult_ms, const TraceOut& o, lmn_stream_t s) {
+  const dim3 g(cdiv(n, TPB), o.form == TraceOut::MANY ? o.n_members : 1), b(TPB);
+  switch (o.form) {
+    case TraceOut::ROWS:
+      LMN_LAUNCH(k_trace_lut, g, b, 0, s, input.p, input.view, n, nd, lut_col1, ranges, mult, o.rows, o.out, o.err_flag);
+      break;
+    case TraceOut::COLS:
+      LMN_LAUNCH(k_sink_lut, g, b, 0, s, input.p, input.view, n, nd, lut_col1, ranges, mult, o.cols, o.col_stride, o.out,
+                 o.bad_word, o.refused);
+      break;
+    case TraceOut::MANY:
+      LMN_LAUNCH(k_trace_many_lut, g, b, 0, s, input.p, input.view, input.ms, n, nd, lut_col1, ranges, mult, mult_ms, o.rows,
+                 o.rows_ms, o.out, o.out_ms, o.refused);
+      break;
+  }
 }
 
 // =============================================================================================
@@ -956,17 +930,9 @@ LMN_KERNEL k_eval_inputs_float(const int32_t* __restrict__ src, uint64_t n, int3
 void launch_eval_elementwise(int kind, const int32_t* lhs, const TraceView& lv, const int32_t* rhs, const TraceView& rv,
                              uint64_t n, int32_t* out, int32_t* minmax, uint32_t* refused, lmn_stream_t s) {
   dim3 g(cdiv(n, TPB)), b(TPB);
-  switch (kind) {
-    case 0: LMN_LAUNCH(k_eval_elementwise<0>, g, b, 0, s, lhs, lv, rhs, rv, n, out, minmax, refused); break;
-    case 1: LMN_LAUNCH(k_eval_elementwise<1>, g, b, 0, s, lhs, lv, rhs, rv, n, out, minmax, refused); break;
-    case 2: LMN_LAUNCH(k_eval_elementwise<2>, g, b, 0, s, lhs, lv, rhs, rv, n, out, minmax, refused); break;
-    case 7: LMN_LAUNCH(k_eval_elementwise<7>, g, b, 0, s, lhs, lv, rhs, rv, n, out, minmax, refused); break;
-    case 8: LMN_LAUNCH(k_eval_elementwise<8>, g, b, 0, s, lhs, lv, rhs, rv, n, out, minmax, refused); break;
-    case 13: LMN_LAUNCH(k_eval_elementwise<13>, g, b, 0, s, lhs, lv, rhs, rv, n, out, minmax, refused); break;
-    case 15: LMN_LAUNCH(k_eval_elementwise<15>, g, b, 0, s, lhs, lv, rhs, rv, n, out, minmax, refused); break;
-    case 16: LMN_LAUNCH(k_eval_elementwise<16>, g, b, 0, s, lhs, lv, rhs, rv, n, out, minmax, refused); break;
-    default: throw LmnError(-100, "eval_elementwise: unsupported kind");
-  }
+#define LMN_X(K) LMN_LAUNCH(k_eval_elementwise<K>, g, b, 0, s, lhs, lv, rhs, rv, n, out, minmax, refused)
+  LMN_ELEMENTWISE_KINDS(kind, "eval_elementwise", LMN_X)
+#undef LMN_X
 }
 
 void launch_eval_inputs_float(uint32_t dtype, const void* src, uint64_t n, int32_t* out, int32_t* minmax, uint32_t* refused,
@@ -974,7 +940,7 @@ void launch_eval_inputs_float(uint32_t dtype, const void* src, uint64_t n, int32
   const dim3 g(cdiv(n, TPB)), b(TPB);
   const int32_t* lhs = (const int32_t*)src;
 #define LMN_X(S) LMN_LAUNCH(k_eval_inputs_float<S>, g, b, 0, s, lhs, n, out, minmax, refused)
-  LMN_FLOAT_DTYPES("eval_inputs_float", LMN_X)
+  LMN_FLOAT_DTYPES(dtype, "eval_inputs_float", LMN_X)
 #undef LMN_X
 }
 
@@ -991,10 +957,11 @@ LMN_KERNEL k_tensor_to_float(const int32_t* __restrict__ src, uint64_t n, void* 
 void launch_tensor_to_float(uint32_t dtype, const int32_t* src, uint64_t n, void* dst, lmn_stream_t s) {
   const dim3 g(cdiv(n, TPB)), b(TPB);
 #define LMN_X(S) LMN_LAUNCH(k_tensor_to_float<S>, g, b, 0, s, src, n, dst)
-  LMN_FLOAT_DTYPES("tensor_to_float", LMN_X)
+  LMN_FLOAT_DTYPES(dtype, "tensor_to_float", LMN_X)
 #undef LMN_X
 }
 #undef LMN_FLOAT_DTYPES
+#undef LMN_ELEMENTWISE_KINDS
 
 // out = lut_col1[find_index(input)]; an input outside every range is a refused element (the trace form fails the call
 // instead: a dry run must not wait per node).  No multiplicity increments.

@@ -208,7 +208,7 @@ QuotientSamples parse_quotient_samples(uint32_t ncols, const uint32_t* sample_co
 // rows and one wait.  The columns come from lmn_dev_malloc, outside every context's per-proof arena; all device work runs
 // on the sink's own stream, so a proof on the context it was opened on overlaps with its filling.  Calls on one sink are
 // serialised by its own lock and never take the context's.
-// A DEVICE producer may fill it too (lmn_rows_append_*, Context::rows_append_*): the producer's column-form launch runs on
+// A DEVICE producer may fill it too (lmn_rows_append_*, a Context producer with TraceTarget::into): the producer's column-form launch runs on
 // the context's stream and writes the node's rows straight into the columns at the sink's current row count.  Such a call
 // holds the context's lock and takes the sink's behind it - always in that order.  The two streams are tied by two events:
 // `appended_` (recorded on the producer's stream behind every append; sync, finish, reset and the destructor make the sink's
@@ -278,6 +278,40 @@ class RowSink {
 // prove(): a LMN_TABLE_COLS_ON_DEVICE table must be the finished columns of a sink on this device (LMN_ERR_INVALID_ARGUMENT
 // otherwise); the proof stream is made to wait for the sink's finish event - the host does not wait
 void rows_sink_attach(const lmn_table& tb, int device, lmn_stream_t proof_stream);
+
+// An operand of a trace producer as the C API hands it over: a device pointer, an optional strided view, and the member
+// stride of the many-member forms
+struct TraceIn {
+  const void* p = nullptr;
+  const lmn_view* view = nullptr;
+  uint64_t ms = 0;
+};
+// Where a trace producer's rows and outputs go (Context::elementwise and its siblings): a table at row_offset
+// (lmn_trace_*), n_members tables with their strides and counters (lmn_trace_many_*: `*_ms` of operands / outputs in
+// elements, rows in rows of the kind, tables in words), or a row sink's columns at its current count (lmn_rows_append_*).
+// `call`: the entry point's name, put in front of every rule's text; the integer table forms carry none.
+// Refused elements are counted in *refused (may be null; the table form has none) - and fail a sink's finish.
+struct TraceTarget {
+  enum Form { TABLE, MANY, SINK } form;
+  const char* call;
+  uint32_t* rows;
+  uint64_t row_offset, rows_ms;
+  uint32_t n_members;
+  RowSink* sink;
+  int32_t* out;
+  uint64_t out_ms;
+  uint32_t* refused;
+  static TraceTarget table(uint32_t* rows, uint64_t row_offset, int32_t* out, const char* call = nullptr) {
+    return {TABLE, call, rows, row_offset, 0, 1, nullptr, out, 0, nullptr};
+  }
+  static TraceTarget many(const char* call, uint32_t n_members, uint32_t* rows, uint64_t row_offset, uint64_t rows_ms, int32_t* out,
+                          uint64_t out_ms, uint32_t* refused) {
+    return {MANY, call, rows, row_offset, rows_ms, n_members, nullptr, out, out_ms, refused};
+  }
+  static TraceTarget into(const char* call, RowSink& sink, int32_t* out, uint32_t* refused) {
+    return {SINK, call, nullptr, 0, 0, 1, &sink, out, 0, refused};
+  }
+};
 
 // Settings prepared once (lmn_settings_prepare): everything about tree 0 that does not depend on the pie - the LUT and
 // range-check columns on their trace domain, their coefficients, their LDE, every Merkle layer and the root - in device
@@ -411,44 +445,18 @@ class Context {
   void upload_to(const void* host, size_t bytes, void* dst);
   void device_copy(void* dst, const void* src, size_t bytes);
   void download(const void* device, void* host, size_t bytes);
-  void trace_reduce(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back,
-                    const lmn_node_info& info, uint32_t* rows, uint64_t row_offset, int32_t* out);
-  void trace_elementwise(uint32_t kind, const int32_t* lhs, const lmn_view* lv, const int32_t* rhs, const lmn_view* rv,
-                         uint64_t n, const lmn_node_info& info, uint32_t* rows, uint64_t row_offset, int32_t* out,
-                         uint32_t* aux = nullptr);
-  void trace_contiguous(const int32_t* input, uint64_t in_size, const lmn_view* view, uint64_t out_size,
-                        const lmn_node_info& info, uint32_t* rows, uint64_t row_offset, int32_t* out);
-  void trace_lut(uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t n, const lmn_node_info& info,
-                 const uint32_t* lut_col1, const lmn_range* ranges, uint32_t n_ranges, uint32_t* mult, uint32_t* rows,
-                 uint64_t row_offset, int32_t* out);
-  // lmn_rows_append_* (trace_gen.cpp): the same four producers in their column form, appending the node's rows to a row
-  // sink at its current count; refused elements are counted in *refused (may be null) and fail the sink's finish.  No wait.
-  void rows_append_elementwise(RowSink& sink, uint32_t kind, const int32_t* lhs, const lmn_view* lv, const int32_t* rhs,
-                               const lmn_view* rv, uint64_t n, const lmn_node_info& info, uint32_t* rc_mult, int32_t* out,
-                               uint32_t* refused);
-  void rows_append_contiguous(RowSink& sink, const int32_t* input, uint64_t in_size, const lmn_view* view, uint64_t out_size,
-                              const lmn_node_info& info, int32_t* out, uint32_t* refused);
-  void rows_append_reduce(RowSink& sink, bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back,
-                          const lmn_node_info& info, int32_t* out, uint32_t* refused);
-  void rows_append_lut(RowSink& sink, uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t n,
-                       const lmn_node_info& info, const uint32_t* lut_col1, const lmn_range* ranges, uint32_t n_ranges,
-                       uint32_t* mult, int32_t* out, uint32_t* refused);
-  // lmn_trace_many_* (trace_gen.cpp): the same producers for n_members pies of one shape, one launch per node; member m
-  // works on base + m * member stride (`*_ms`: operands / outputs in elements, rows in rows of the kind, tables in words)
-  void trace_many_elementwise(uint32_t kind, const int32_t* lhs, const lmn_view* lv, uint64_t lhs_ms, const int32_t* rhs,
-                              const lmn_view* rv, uint64_t rhs_ms, uint64_t n, const lmn_node_info& info, uint32_t n_members,
-                              uint32_t* rows, uint64_t row_offset, uint64_t rows_ms, int32_t* out, uint64_t out_ms,
-                              uint32_t* rc_mult, uint64_t rc_ms, uint32_t* refused);
-  void trace_many_contiguous(const int32_t* input, uint64_t in_ms, uint64_t in_size, const lmn_view* view, uint64_t out_size,
-                             const lmn_node_info& info, uint32_t n_members, uint32_t* rows, uint64_t row_offset, uint64_t rows_ms,
-                             int32_t* out, uint64_t out_ms, uint32_t* refused);
-  void trace_many_reduce(bool is_max, const int32_t* input, uint64_t in_ms, uint64_t front, uint64_t dim, uint64_t back,
-                         const lmn_node_info& info, uint32_t n_members, uint32_t* rows, uint64_t row_offset, uint64_t rows_ms,
-                         int32_t* out, uint64_t out_ms, uint32_t* refused);
-  void trace_many_lut(uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t in_ms, uint64_t n,
-                      const lmn_node_info& info, const uint32_t* lut_col1, const lmn_range* ranges, uint32_t n_ranges,
-                      uint32_t n_members, uint32_t* mult, uint64_t mult_ms, uint32_t* rows, uint64_t row_offset, uint64_t rows_ms,
-                      int32_t* out, uint64_t out_ms, uint32_t* refused);
+  // The trace producers (trace_gen.cpp): `process_trace` of a node on device tensors, one method per producer.  What it
+  // computes is the method's; where the rows and outputs go is the TraceTarget's (the three forms of the C API).
+  // Operands: member m of a many-member target reads p + m * ms elements (ms == 0 shares the operand).
+  void elementwise(const TraceTarget& tg, uint32_t kind, const TraceIn& lhs, const TraceIn& rhs, uint64_t n,
+                   const lmn_node_info& info, uint32_t* rc_mult = nullptr, uint64_t rc_ms = 0, int src_dtype = SRC_FIXED);
+  void contiguous(const TraceTarget& tg, const TraceIn& input, uint64_t in_size, uint64_t out_size, const lmn_node_info& info);
+  void reduce(const TraceTarget& tg, bool is_max, const TraceIn& input, uint64_t front, uint64_t dim, uint64_t back,
+              const lmn_node_info& info);
+  void lut(const TraceTarget& tg, uint32_t kind, const TraceIn& input, uint64_t n, const lmn_node_info& info,
+           const uint32_t* lut_col1, const lmn_range* ranges, uint32_t n_ranges, uint32_t* mult, uint64_t mult_ms = 0);
+  // graph inputs from raw float bits of `dtype` (src.ms in elements of the dtype)
+  void inputs_float(const TraceTarget& tg, uint32_t dtype, const TraceIn& src, uint64_t n, const lmn_node_info& info);
   // lmn_eval_* (trace_gen.cpp): the producers' forward pass - values, their range, the refused elements; no rows
   void eval_elementwise(uint32_t kind, const int32_t* lhs, const lmn_view* lv, const int32_t* rhs, const lmn_view* rv, uint64_t n,
                         int32_t* out, int32_t* minmax, uint32_t* refused);
@@ -457,14 +465,7 @@ class Context {
   void eval_lut(uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t n, const uint32_t* lut_col1,
                 const lmn_range* ranges, uint32_t n_ranges, int32_t* out, int32_t* minmax, uint32_t* refused);
   void tensor_range(const int32_t* buf, uint64_t n, int32_t* minmax);
-  // lmn_*_inputs_float / lmn_tensor_to_float (trace_gen.cpp): graph inputs from raw float bits, outputs back to floats
-  void trace_inputs_float(uint32_t dtype, const void* src, uint64_t n, const lmn_node_info& info, uint32_t* rows,
-                          uint64_t row_offset, int32_t* out);
-  void trace_many_inputs_float(uint32_t dtype, const void* src, uint64_t src_ms, uint64_t n, const lmn_node_info& info,
-                               uint32_t n_members, uint32_t* rows, uint64_t row_offset, uint64_t rows_ms, int32_t* out,
-                               uint64_t out_ms, uint32_t* refused);
-  void rows_append_inputs_float(RowSink& sink, uint32_t dtype, const void* src, uint64_t n, const lmn_node_info& info, int32_t* out,
-                                uint32_t* refused);
+  // lmn_eval_inputs_float / lmn_tensor_to_float (trace_gen.cpp): the float source's forward pass, outputs back to floats
   void eval_inputs_float(uint32_t dtype, const void* src, uint64_t n, int32_t* out, int32_t* minmax, uint32_t* refused);
   void tensor_to_float(uint32_t dtype, const int32_t* src, uint64_t n, void* dst);
   void device_free(void* p);

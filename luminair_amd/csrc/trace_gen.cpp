@@ -1,8 +1,11 @@
 // The step before the path: `process_trace` of the reference's operators on device-resident tensors
-// (crates/graph/src/op/prim.rs), filling trace-table rows in HBM.  Host side of the lmn_trace_* entry points.
+// (crates/graph/src/op/prim.rs), filling trace-table rows in HBM.  Host side of the lmn_trace_*, lmn_trace_many_*,
+// lmn_rows_append_* and lmn_eval_* entry points: a producer (Context::elementwise, contiguous, reduce, lut, inputs_float)
+// states what is computed and its argument rules once; a TraceTarget states where the rows and outputs go.
 #include "prove_run.h"
 
 #include <algorithm>
+#include <optional>
 
 namespace lmn {
 
@@ -18,25 +21,30 @@ static TraceNode trace_node(const lmn_node_info& info) {
   return nd;
 }
 
-// the shape rules of the reduce producers (single and many-member form)
-static void check_reduce_shape(uint64_t front, uint64_t dim, uint64_t back) {
-  if (front == 0 || dim == 0 || back == 0) throw LmnError(LMN_ERR_EMPTY_TRACE, "TraceError::EmptyTrace");
-  if (front * back * dim >= (1ull << 31)) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "tensor too large");
+// ------------------------------------------------------------------------------------ the producers' argument rules
+// Each rule is stated once.  The trace forms answer a broken rule with the reference's own codes and texts (trace_fail); the
+// eval forms name the argument instead, so a rule set takes the caller's way to fail: fail(rule) does not return.
+namespace {
+struct RuleText {
+  int code;
+  const char* text;
+};
+[[noreturn]] void trace_fail(const RuleText& t) { throw LmnError(t.code, t.text); }
+[[noreturn]] void bad_argument(const char* call, const std::string& why) {
+  throw LmnError(LMN_ERR_INVALID_ARGUMENT, std::string(call) + ": " + why);
+}
+// the rules of `f`, with the entry point's name in front of the text (no name: the text as it is)
+template <class F>
+auto named_rules(const char* call, F&& f) {
+  if (!call) return f();
+  try {
+    return f();
+  } catch (const LmnError& e) {
+    throw LmnError(e.code, std::string(call) + ": " + e.what());
+  }
 }
 
-// `LuminairSumReduce::process_trace` (prim.rs:1450-1565) on a contiguous (front, dim, back) device tensor
-void Context::trace_reduce(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back,
-                           const lmn_node_info& info, uint32_t* rows, uint64_t row_offset, int32_t* out) {
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
-  check_reduce_shape(front, dim, back);
-  launch_trace_reduce(is_max, input, front, dim, back, trace_node(info), rows + row_offset * (is_max ? 15ull : 14ull), out,
-                      stream_);  // stream-ordered with every later call on this context (lmn_prove, lmn_download)
-}
-
-// `process_trace` of one Add / Mul / Recip node on device tensors (prim.rs:967-1013, :1090-1139, :388-431)
-static TraceView trace_view(const lmn_view* v, uint64_t n) {
+TraceView trace_view(const lmn_view* v, uint64_t n) {
   TraceView t{};
   if (!v) return t;
   if (v->ndim < 1 || v->ndim > 4) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "view: ndim must be 1..4");
@@ -54,14 +62,29 @@ static TraceView trace_view(const lmn_view* v, uint64_t n) {
   return t;
 }
 
-// the argument rules of the LUT producers (single and many-member form); lut_rows = the LUT rows the ranges enumerate
-static LutRanges trace_lut_ranges(uint32_t kind, uint64_t n, const lmn_range* ranges, uint32_t n_ranges, uint64_t& lut_rows) {
-  if (kind != LMN_KIND_SIN && kind != LMN_KIND_EXP2 && kind != LMN_KIND_LOG2)
-    throw LmnError(LMN_ERR_INVALID_ARGUMENT, "trace_lut: kind must be Sin, Exp2 or Log2");
-  if (n == 0) throw LmnError(LMN_ERR_EMPTY_TRACE, "TraceError::EmptyTrace");
-  if (n >= (1ull << 31)) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "bad sizes");
-  if (!ranges || n_ranges == 0 || n_ranges > (uint32_t)LUT_MAX_RANGES)
-    throw LmnError(LMN_ERR_INVALID_ARGUMENT, "trace_lut: 1..16 value ranges");
+// the shape rules of the reduce producers
+void check_reduce_shape(uint64_t front, uint64_t dim, uint64_t back) {
+  if (front == 0 || dim == 0 || back == 0) throw LmnError(LMN_ERR_EMPTY_TRACE, "TraceError::EmptyTrace");
+  if (front * back * dim >= (1ull << 31)) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "tensor too large");
+}
+
+// the argument rules of the LUT producers; lut_rows = the LUT rows the ranges enumerate
+enum LutRule { LUT_KIND, LUT_EMPTY, LUT_TOO_LARGE, LUT_NO_RANGES, LUT_N_RANGES, LUT_ORDER, LUT_ROWS };
+const RuleText kTraceLutRules[] = {
+    {LMN_ERR_INVALID_ARGUMENT, "trace_lut: kind must be Sin, Exp2 or Log2"},
+    {LMN_ERR_EMPTY_TRACE, "TraceError::EmptyTrace"},
+    {LMN_ERR_INVALID_ARGUMENT, "bad sizes"},
+    {LMN_ERR_INVALID_ARGUMENT, "trace_lut: 1..16 value ranges"},
+    {LMN_ERR_INVALID_ARGUMENT, "trace_lut: 1..16 value ranges"},
+    {LMN_ERR_INVALID_ARGUMENT, "trace_lut: ranges must be ascending, disjoint and inside (-2^30, 2^30)"},
+    {LMN_ERR_INVALID_ARGUMENT, "trace_lut: LUT larger than 2^26 rows"}};
+template <class Fail>
+LutRanges lut_ranges(uint32_t kind, uint64_t n, const lmn_range* ranges, uint32_t n_ranges, uint64_t& lut_rows, Fail&& fail) {
+  if (kind != LMN_KIND_SIN && kind != LMN_KIND_EXP2 && kind != LMN_KIND_LOG2) fail(LUT_KIND);
+  if (n == 0) fail(LUT_EMPTY);
+  if (n >= (1ull << 31)) fail(LUT_TOO_LARGE);
+  if (!ranges) fail(LUT_NO_RANGES);
+  if (n_ranges == 0 || n_ranges > (uint32_t)LUT_MAX_RANGES) fail(LUT_N_RANGES);
   LutRanges rg{};
   rg.n = (int)n_ranges;
   uint64_t base = 0;
@@ -69,156 +92,44 @@ static LutRanges trace_lut_ranges(uint32_t kind, uint64_t n, const lmn_range* ra
     // ascending, disjoint, inside the Fixed<12> range the LUT generator accepts (coalesce_ranges' output)
     if (ranges[k].hi < ranges[k].lo || ranges[k].lo <= -(1ll << 30) || ranges[k].hi >= (1ll << 30) ||
         (k > 0 && ranges[k].lo <= ranges[k - 1].hi))
-      throw LmnError(LMN_ERR_INVALID_ARGUMENT, "trace_lut: ranges must be ascending, disjoint and inside (-2^30, 2^30)");
+      fail(LUT_ORDER);
     rg.lo[k] = (int32_t)ranges[k].lo;
     rg.hi[k] = (int32_t)ranges[k].hi;
     rg.base[k] = (uint32_t)base;
     base += (uint64_t)(ranges[k].hi - ranges[k].lo + 1);
-    if (base > (1ull << 26)) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "trace_lut: LUT larger than 2^26 rows");
+    if (base > (1ull << 26)) fail(LUT_ROWS);
   }
   lut_rows = base;
   return rg;
 }
 
-// `process_trace` of a Sin / Exp2 / Log2 node on a device tensor; fills the LUT multiplicity column too
-void Context::trace_lut(uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t n, const lmn_node_info& info,
-                        const uint32_t* lut_col1, const lmn_range* ranges, uint32_t n_ranges, uint32_t* mult, uint32_t* rows,
-                        uint64_t row_offset, int32_t* out) {
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
-  uint64_t lut_rows = 0;
-  const LutRanges rg = trace_lut_ranges(kind, n, ranges, n_ranges, lut_rows);
-  const TraceView tv = trace_view(view, n);
-  // bad_flag_[1] is zero between calls; the kernel sets it when an input misses every range
-  launch_trace_lut(input, tv, n, trace_node(info), lut_col1, rg, mult, rows + row_offset * 12ull, out, bad_flag_ + 1, stream_);
-  uint32_t err = 0;
-  lmn_d2h(&err, bad_flag_ + 1, 4, stream_);
-  lmn_sync(stream_);
-  if (err) {
-    const uint32_t zero = 0u;
-    lmn_h2d(bad_flag_ + 1, &zero, 4, stream_);
-    lmn_sync(stream_);
-    throw LmnError(LMN_ERR_INVALID_ARGUMENT, "trace_lut: an input value lies outside the LUT's range");
-  }
-}
-
-// the argument rules of the elementwise producers (single and many-member form)
-static bool elementwise_binary(uint32_t kind) {
+// the argument rules of the elementwise producers
+bool elementwise_binary(uint32_t kind) {
   return kind == LMN_KIND_ADD || kind == LMN_KIND_MUL || kind == LMN_KIND_REM || kind == LMN_KIND_LESS_THAN;
 }
-static const ComponentSpec* check_elementwise(uint32_t kind, const int32_t* rhs, const uint32_t* aux, uint64_t n) {
-  const ComponentSpec* sp = component_spec((int)kind);
+bool elementwise_unary(uint32_t kind) {
+  return kind == LMN_KIND_RECIP || kind == LMN_KIND_SQRT || kind == LMN_KIND_CONTIGUOUS || kind == LMN_KIND_INPUTS;
+}
+enum ElemRule { ELEM_KIND, ELEM_RHS, ELEM_AUX, ELEM_EMPTY, ELEM_TOO_LARGE };
+const RuleText kTraceElemRules[] = {
+    {LMN_ERR_INVALID_ARGUMENT, "trace_elementwise: not an elementwise kind"},
+    {LMN_ERR_INVALID_ARGUMENT, "trace_elementwise: missing right operand"},
+    {LMN_ERR_INVALID_ARGUMENT, "trace_elementwise: LessThan needs the range-check multiplicity table"},
+    {LMN_ERR_EMPTY_TRACE, "TraceError::EmptyTrace"},
+    {LMN_ERR_INVALID_ARGUMENT, "tensor too large"}};
+// aux_missing: the kind is LessThan and the form takes its multiplicity table, but got none
+template <class Fail>
+void check_elementwise(uint32_t kind, const void* rhs, bool aux_missing, uint64_t n, Fail&& fail) {
   const bool binary = elementwise_binary(kind);
-  const bool unary = kind == LMN_KIND_RECIP || kind == LMN_KIND_SQRT || kind == LMN_KIND_CONTIGUOUS || kind == LMN_KIND_INPUTS;
-  if (!sp || !(binary || unary))
-    throw LmnError(LMN_ERR_INVALID_ARGUMENT, "trace_elementwise: not an elementwise kind");
-  if (binary && !rhs) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "trace_elementwise: missing right operand");
-  if (kind == LMN_KIND_LESS_THAN && !aux)
-    throw LmnError(LMN_ERR_INVALID_ARGUMENT, "trace_elementwise: LessThan needs the range-check multiplicity table");
-  if (n == 0) throw LmnError(LMN_ERR_EMPTY_TRACE, "TraceError::EmptyTrace");
-  if (n >= (1ull << 31)) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "tensor too large");
-  return sp;
+  if (!component_spec((int)kind) || !(binary || elementwise_unary(kind))) fail(ELEM_KIND);
+  if (binary && !rhs) fail(ELEM_RHS);
+  if (aux_missing) fail(ELEM_AUX);
+  if (n == 0) fail(ELEM_EMPTY);
+  if (n >= (1ull << 31)) fail(ELEM_TOO_LARGE);
 }
 
-void Context::trace_elementwise(uint32_t kind, const int32_t* lhs, const lmn_view* lv, const int32_t* rhs,
-                                const lmn_view* rv, uint64_t n, const lmn_node_info& info, uint32_t* rows,
-                                uint64_t row_offset, int32_t* out, uint32_t* aux) {
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
-  const ComponentSpec* sp = check_elementwise(kind, rhs, aux, n);
-  const TraceNode nd = trace_node(info);
-  const TraceView tlv = trace_view(lv, n), trv = trace_view(rv, n);
-  launch_trace_elementwise((int)kind, lhs, tlv, rhs, trv, n, nd, rows + row_offset * (uint64_t)sp->n_cols, out, aux,
-                           stream_);  // stream-ordered with every later call on this context
-}
-
-// ------------------------------------------------------------------------------------ lmn_eval_*
-// `Operator::process` of the same operators: the forward pass in front of gen_trace (gen_circuit_settings' dry run,
-// crates/graph/src/graph.rs:61-159).  Values only; every call also leaves the range of what it wrote and adds its refused
-// elements to a counter, and none waits for the device.
-namespace {
-void eval_bad(const char* call, const std::string& why) { throw LmnError(LMN_ERR_INVALID_ARGUMENT, std::string(call) + ": " + why); }
-TraceView eval_view(const char* call, const char* name, const lmn_view* v, uint64_t n) {
-  try {
-    return trace_view(v, n);
-  } catch (const LmnError& e) {
-    throw LmnError(e.code, std::string(call) + ": " + name + ": " + e.what());
-  }
-}
-}  // namespace
-
-void Context::eval_begin(int32_t* minmax) {
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
-  if (minmax) launch_eval_init(minmax, stream_);
-}
-
-void Context::eval_elementwise(uint32_t kind, const int32_t* lhs, const lmn_view* lv, const int32_t* rhs, const lmn_view* rv,
-                               uint64_t n, int32_t* out, int32_t* minmax, uint32_t* refused) {
-  const char* call = "lmn_eval_elementwise_v";
-  const bool binary = kind == LMN_KIND_ADD || kind == LMN_KIND_MUL || kind == LMN_KIND_REM || kind == LMN_KIND_LESS_THAN;
-  const bool unary = kind == LMN_KIND_RECIP || kind == LMN_KIND_SQRT || kind == LMN_KIND_CONTIGUOUS || kind == LMN_KIND_INPUTS;
-  if (!(binary || unary)) eval_bad(call, "kind " + std::to_string(kind) + " is not an elementwise kind");
-  if (binary && !rhs) eval_bad(call, "null rhs_dev for a binary kind");
-  if (n == 0) eval_bad(call, "n is 0");
-  if (n >= (1ull << 31)) eval_bad(call, "n: tensor too large");
-  const TraceView tlv = eval_view(call, "lhs_view", lv, n);
-  const TraceView trv = binary ? eval_view(call, "rhs_view", rv, n) : TraceView{};
-  eval_begin(minmax);
-  launch_eval_elementwise((int)kind, lhs, tlv, rhs, trv, n, out, minmax, refused, stream_);
-}
-
-void Context::eval_reduce(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back, int32_t* out,
-                          int32_t* minmax, uint32_t* refused) {
-  const char* call = "lmn_eval_reduce";
-  if (front == 0) eval_bad(call, "front is 0");
-  if (dim == 0) eval_bad(call, "dim is 0");
-  if (back == 0) eval_bad(call, "back is 0");
-  if (front >= (1ull << 31) || dim >= (1ull << 31) || back >= (1ull << 31) || front * back >= (1ull << 31) ||
-      front * back * dim >= (1ull << 31))
-    eval_bad(call, "front * dim * back: tensor too large");
-  eval_begin(minmax);
-  launch_eval_reduce(is_max, input, front, dim, back, out, minmax, refused, stream_);
-}
-
-void Context::eval_lut(uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t n, const uint32_t* lut_col1,
-                       const lmn_range* ranges, uint32_t n_ranges, int32_t* out, int32_t* minmax, uint32_t* refused) {
-  const char* call = "lmn_eval_lut_ranges";
-  if (kind != LMN_KIND_SIN && kind != LMN_KIND_EXP2 && kind != LMN_KIND_LOG2) eval_bad(call, "kind must be Sin, Exp2 or Log2");
-  if (n == 0) eval_bad(call, "n is 0");
-  if (n >= (1ull << 31)) eval_bad(call, "n: tensor too large");
-  if (!ranges) eval_bad(call, "null ranges");
-  if (n_ranges == 0 || n_ranges > (uint32_t)LUT_MAX_RANGES) eval_bad(call, "n_ranges must be 1..16");
-  LutRanges rg{};
-  rg.n = (int)n_ranges;
-  uint64_t base = 0;
-  for (uint32_t k = 0; k < n_ranges; ++k) {   // the rules of lmn_trace_lut_ranges
-    if (ranges[k].hi < ranges[k].lo || ranges[k].lo <= -(1ll << 30) || ranges[k].hi >= (1ll << 30) ||
-        (k > 0 && ranges[k].lo <= ranges[k - 1].hi))
-      eval_bad(call, "ranges must be ascending, disjoint and inside (-2^30, 2^30)");
-    rg.lo[k] = (int32_t)ranges[k].lo;
-    rg.hi[k] = (int32_t)ranges[k].hi;
-    rg.base[k] = (uint32_t)base;
-    base += (uint64_t)(ranges[k].hi - ranges[k].lo + 1);
-    if (base > (1ull << 26)) eval_bad(call, "ranges: LUT larger than 2^26 rows");
-  }
-  const TraceView tv = eval_view(call, "view", view, n);
-  eval_begin(minmax);
-  launch_eval_lut(input, tv, n, lut_col1, rg, out, minmax, refused, stream_);
-}
-
-void Context::tensor_range(const int32_t* buf, uint64_t n, int32_t* minmax) {
-  if (n == 0) eval_bad("lmn_tensor_range", "n is 0");
-  if (n >= (1ull << 31)) eval_bad("lmn_tensor_range", "n: tensor too large");
-  eval_begin(minmax);
-  launch_tensor_range(buf, n, minmax, stream_);
-}
-
-// the argument rules of the buffer-rule Contiguous producers (single and many-member form); fills nd.phys_n / nd.out_n
-static TraceView check_contiguous(uint64_t in_size, const lmn_view* view, uint64_t out_size, TraceNode& nd) {
+// the argument rules of the buffer-rule Contiguous producer; fills nd.phys_n / nd.out_n
+TraceView check_contiguous(uint64_t in_size, const lmn_view* view, uint64_t out_size, TraceNode& nd) {
   if (in_size == 0 || out_size == 0) throw LmnError(LMN_ERR_EMPTY_TRACE, "TraceError::EmptyTrace");
   if (in_size >= (1ull << 31) || out_size >= (1ull << 31)) throw LmnError(LMN_ERR_INVALID_ARGUMENT, "tensor too large");
   nd.phys_n = in_size;
@@ -236,240 +147,219 @@ static TraceView check_contiguous(uint64_t in_size, const lmn_view* view, uint64
   return tv;
 }
 
-// `LuminairContiguous::process_trace` in the reference's own row rule (prim.rs:229-301): max(in_size, out_size) rows
-void Context::trace_contiguous(const int32_t* input, uint64_t in_size, const lmn_view* view, uint64_t out_size,
-                               const lmn_node_info& info, uint32_t* rows, uint64_t row_offset, int32_t* out) {
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
-  TraceNode nd = trace_node(info);
-  const TraceView tv = check_contiguous(in_size, view, out_size, nd);
-  const uint64_t n = std::max(in_size, out_size);
-  launch_trace_elementwise(LMN_KIND_CONTIGUOUS, input, tv, nullptr, TraceView{}, n, nd, rows + row_offset * 11ull, out, nullptr,
-                           stream_);
-}
-
-// ------------------------------------------------------------------------------------ lmn_trace_many_*
-// One launch per graph node for n_members pies of one shape (the producers in front of lmn_batch_prove): member m works on
-// base + m * member stride.  Everything is refused here, before any launch, and the text names the argument; no call waits.
-namespace {
-void many_bad(const char* call, const std::string& why) { throw LmnError(LMN_ERR_INVALID_ARGUMENT, std::string(call) + ": " + why); }
-// the single form's own argument rules, with the many form's name in front of the text
-template <class F>
-auto many_rules(const char* call, F&& f) {
-  try {
-    return f();
-  } catch (const LmnError& e) {
-    throw LmnError(e.code, std::string(call) + ": " + e.what());
-  }
-}
-// rows_ms in rows of the kind; out_n = elements of one member's output; shared_in = every operand the kind reads has stride 0
-void many_strides(const char* call, uint32_t n_members, uint64_t rows_ms, uint64_t row_offset, uint64_t n_rows, const int32_t* out,
-                  uint64_t out_ms, uint64_t out_n, bool shared_in) {
-  if (n_members > LMN_TRACE_MANY_MAX) many_bad(call, "n_members exceeds LMN_TRACE_MANY_MAX");
-  if (row_offset >= (1ull << 31) || rows_ms >= (1ull << 40)) many_bad(call, "row_offset / rows_member_stride: table too large");
-  if (rows_ms < row_offset + n_rows)
-    many_bad(call, "rows_member_stride is smaller than row_offset + the node's " + std::to_string(n_rows) + " rows");
-  if (out && out_ms == 0 && !shared_in)
-    many_bad(call, "out_member_stride 0 (a shared output tensor) needs every operand stride to be 0");
-  if (out && out_ms != 0 && out_ms < out_n)
-    many_bad(call, "out_member_stride is smaller than the output's " + std::to_string(out_n) + " elements");
-}
-}  // namespace
-
-void Context::trace_many_elementwise(uint32_t kind, const int32_t* lhs, const lmn_view* lv, uint64_t lhs_ms, const int32_t* rhs,
-                                     const lmn_view* rv, uint64_t rhs_ms, uint64_t n, const lmn_node_info& info, uint32_t n_members,
-                                     uint32_t* rows, uint64_t row_offset, uint64_t rows_ms, int32_t* out, uint64_t out_ms,
-                                     uint32_t* rc_mult, uint64_t rc_ms, uint32_t* refused) {
-  const char* call = "lmn_trace_many_elementwise_v";
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
-  const ComponentSpec* sp = many_rules(call, [&] { return check_elementwise(kind, rhs, rc_mult, n); });
-  const bool binary = elementwise_binary(kind);
-  const TraceView tlv = many_rules(call, [&] { return trace_view(lv, n); });
-  const TraceView trv = binary ? many_rules(call, [&] { return trace_view(rv, n); }) : TraceView{};
-  many_strides(call, n_members, rows_ms, row_offset, n, out, out_ms, n, lhs_ms == 0 && (!binary || rhs_ms == 0));
-  const bool lt = kind == LMN_KIND_LESS_THAN;
-  if (lt && rc_ms < 256) many_bad(call, "range_check_mult_member_stride is smaller than the table's 256 words");
-  launch_trace_many_elementwise((int)kind, lhs, tlv, lhs_ms, binary ? rhs : nullptr, trv, rhs_ms, n, trace_node(info), n_members,
-                                rows + row_offset * (uint64_t)sp->n_cols, rows_ms * (uint64_t)sp->n_cols, out, out_ms,
-                                lt ? rc_mult : nullptr, rc_ms, refused, stream_);
-}
-
-void Context::trace_many_contiguous(const int32_t* input, uint64_t in_ms, uint64_t in_size, const lmn_view* view, uint64_t out_size,
-                                    const lmn_node_info& info, uint32_t n_members, uint32_t* rows, uint64_t row_offset,
-                                    uint64_t rows_ms, int32_t* out, uint64_t out_ms, uint32_t* refused) {
-  const char* call = "lmn_trace_many_contiguous";
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
-  TraceNode nd = trace_node(info);
-  const TraceView tv = many_rules(call, [&] { return check_contiguous(in_size, view, out_size, nd); });
-  const uint64_t n = std::max(in_size, out_size);
-  many_strides(call, n_members, rows_ms, row_offset, n, out, out_ms, out_size, in_ms == 0);
-  launch_trace_many_elementwise(LMN_KIND_CONTIGUOUS, input, tv, in_ms, nullptr, TraceView{}, 0, n, nd, n_members,
-                                rows + row_offset * 11ull, rows_ms * 11ull, out, out_ms, nullptr, 0, refused, stream_);
-}
-
-void Context::trace_many_reduce(bool is_max, const int32_t* input, uint64_t in_ms, uint64_t front, uint64_t dim, uint64_t back,
-                                const lmn_node_info& info, uint32_t n_members, uint32_t* rows, uint64_t row_offset,
-                                uint64_t rows_ms, int32_t* out, uint64_t out_ms, uint32_t* refused) {
-  const char* call = "lmn_trace_many_reduce";
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
-  many_rules(call, [&] { check_reduce_shape(front, dim, back); return 0; });
-  many_strides(call, n_members, rows_ms, row_offset, front * dim * back, out, out_ms, front * back, in_ms == 0);
-  const uint64_t nc = is_max ? 15ull : 14ull;
-  launch_trace_many_reduce(is_max, input, in_ms, front, dim, back, trace_node(info), n_members, rows + row_offset * nc,
-                           rows_ms * nc, out, out_ms, refused, stream_);
-}
-
-void Context::trace_many_lut(uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t in_ms, uint64_t n,
-                             const lmn_node_info& info, const uint32_t* lut_col1, const lmn_range* ranges, uint32_t n_ranges,
-                             uint32_t n_members, uint32_t* mult, uint64_t mult_ms, uint32_t* rows, uint64_t row_offset,
-                             uint64_t rows_ms, int32_t* out, uint64_t out_ms, uint32_t* refused) {
-  const char* call = "lmn_trace_many_lut_ranges";
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
-  uint64_t lut_rows = 0;
-  const LutRanges rg = many_rules(call, [&] { return trace_lut_ranges(kind, n, ranges, n_ranges, lut_rows); });
-  const TraceView tv = many_rules(call, [&] { return trace_view(view, n); });
-  many_strides(call, n_members, rows_ms, row_offset, n, out, out_ms, n, in_ms == 0);
-  if (mult_ms < lut_rows)
-    many_bad(call, "mult_member_stride is smaller than the " + std::to_string(lut_rows) + " LUT rows the ranges enumerate");
-  launch_trace_many_lut(input, tv, in_ms, n, trace_node(info), lut_col1, rg, n_members, mult, mult_ms, rows + row_offset * 12ull,
-                        rows_ms * 12ull, out, out_ms, refused, stream_);
-}
-
-// ------------------------------------------------------------------------------------ lmn_rows_append_*
-// The four single producers in their column form: the node's rows go straight into a row sink's columns at its current row
-// count (no array-of-structs table, no transpose in front of the proof).  The single form's own argument rules come first,
-// then the sink's (RowSink::Append); nothing is launched before both hold, and no call waits.
-void Context::rows_append_elementwise(RowSink& sink, uint32_t kind, const int32_t* lhs, const lmn_view* lv, const int32_t* rhs,
-                                      const lmn_view* rv, uint64_t n, const lmn_node_info& info, uint32_t* rc_mult, int32_t* out,
-                                      uint32_t* refused) {
-  const char* call = "lmn_rows_append_elementwise_v";
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
-  many_rules(call, [&] { return check_elementwise(kind, rhs, rc_mult, n); });
-  const bool binary = elementwise_binary(kind);
-  const TraceView tlv = many_rules(call, [&] { return trace_view(lv, n); });
-  const TraceView trv = binary ? many_rules(call, [&] { return trace_view(rv, n); }) : TraceView{};
-  RowSink::Append ap(sink, call, device_, stream_, kind, n);
-  launch_trace_elementwise_cols((int)kind, lhs, tlv, binary ? rhs : nullptr, trv, n, trace_node(info), ap.cols(), ap.stride(), out,
-                                kind == LMN_KIND_LESS_THAN ? rc_mult : nullptr, ap.bad(), refused, stream_);
-  ap.done();
-}
-
-void Context::rows_append_contiguous(RowSink& sink, const int32_t* input, uint64_t in_size, const lmn_view* view,
-                                     uint64_t out_size, const lmn_node_info& info, int32_t* out, uint32_t* refused) {
-  const char* call = "lmn_rows_append_contiguous";
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
-  TraceNode nd = trace_node(info);
-  const TraceView tv = many_rules(call, [&] { return check_contiguous(in_size, view, out_size, nd); });
-  const uint64_t n = std::max(in_size, out_size);
-  RowSink::Append ap(sink, call, device_, stream_, LMN_KIND_CONTIGUOUS, n);
-  launch_trace_elementwise_cols(LMN_KIND_CONTIGUOUS, input, tv, nullptr, TraceView{}, n, nd, ap.cols(), ap.stride(), out, nullptr,
-                                ap.bad(), refused, stream_);
-  ap.done();
-}
-
-void Context::rows_append_reduce(RowSink& sink, bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back,
-                                 const lmn_node_info& info, int32_t* out, uint32_t* refused) {
-  const char* call = "lmn_rows_append_reduce";
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
-  many_rules(call, [&] { check_reduce_shape(front, dim, back); return 0; });
-  RowSink::Append ap(sink, call, device_, stream_, is_max ? LMN_KIND_MAX_REDUCE : LMN_KIND_SUM_REDUCE, front * dim * back);
-  launch_trace_reduce_cols(is_max, input, front, dim, back, trace_node(info), ap.cols(), ap.stride(), out, ap.bad(), refused,
-                           stream_);
-  ap.done();
-}
-
-void Context::rows_append_lut(RowSink& sink, uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t n,
-                              const lmn_node_info& info, const uint32_t* lut_col1, const lmn_range* ranges, uint32_t n_ranges,
-                              uint32_t* mult, int32_t* out, uint32_t* refused) {
-  const char* call = "lmn_rows_append_lut_ranges";
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
-  uint64_t lut_rows = 0;
-  const LutRanges rg = many_rules(call, [&] { return trace_lut_ranges(kind, n, ranges, n_ranges, lut_rows); });
-  const TraceView tv = many_rules(call, [&] { return trace_view(view, n); });
-  RowSink::Append ap(sink, call, device_, stream_, kind, n);
-  launch_trace_lut_cols(input, tv, n, trace_node(info), lut_col1, rg, mult, ap.cols(), ap.stride(), out, ap.bad(), refused,
-                        stream_);
-  ap.done();
-}
-
-// ------------------------------------------------------------------------------------ float tensors in and out
-// `CopyToStwo` on raw float bits (prim.rs:52-101): the four Inputs producers - row, many-member, sink and eval form - with
-// the float -> Fixed<12> rule (kernels_trace.hip float_bits_to_fixed) inside the launch that writes the rows, and
-// `CopyFromStwo` back.  The float arguments are checked first, then the sibling form's own rules apply, with its codes.
-namespace {
+// the float source of the Inputs producers and the destination of lmn_tensor_to_float
 void check_float_ptr(const char* call, uint32_t dtype, const void* p, const char* name) {
   if (dtype != LMN_F32 && dtype != LMN_F16 && dtype != LMN_BF16)
-    many_bad(call, "dtype " + std::to_string(dtype) + " is not LMN_F32, LMN_F16 or LMN_BF16");
-  if (!p) many_bad(call, std::string("null ") + name);
-  if ((uintptr_t)p % (dtype == LMN_F32 ? 4u : 2u)) many_bad(call, std::string(name) + " is not aligned to the dtype's element size");
+    bad_argument(call, "dtype " + std::to_string(dtype) + " is not LMN_F32, LMN_F16 or LMN_BF16");
+  if (!p) bad_argument(call, std::string("null ") + name);
+  if ((uintptr_t)p % (dtype == LMN_F32 ? 4u : 2u)) bad_argument(call, std::string(name) + " is not aligned to the dtype's element size");
 }
-// n = 0 with the code of the integer trace forms (check_elementwise), the argument named
-void check_float_rows(const char* call, uint64_t n) {
-  if (n == 0) throw LmnError(LMN_ERR_EMPTY_TRACE, std::string(call) + ": n is 0 (TraceError::EmptyTrace)");
-  many_rules(call, [&] { return check_elementwise(LMN_KIND_INPUTS, nullptr, nullptr, n); });
+
+// ------------------------------------------------------------------------------------ the destinations
+// One producer call's place in its target, between the producer's own argument rules and its launch.  The constructor
+// applies the form's rules - everything is refused here, before any launch, and the text names the argument - and gives
+// the launcher its TraceOut; done() follows the launch.  No form waits.
+//   a table (lmn_trace_*):        the node's rows start at row_offset.
+//   many (lmn_trace_many_*):      member m works on base + m * member stride; the strides must hold the node.
+//   a sink (lmn_rows_append_*):   the rows go straight into a row sink's columns at its current row count (no
+//                                 array-of-structs table, no transpose in front of the proof), inside RowSink::Append.
+// n_rows = the node's rows, out_n = elements of one member's output, shared_in = every operand the kind reads has stride 0
+struct Placed {
+  TraceOut o;
+  std::optional<RowSink::Append> append;
+  Placed(const TraceTarget& tg, int device, lmn_stream_t stream, uint32_t kind, uint64_t n_rows, uint64_t out_n, bool shared_in) {
+    const uint64_t nc = (uint64_t)component_spec((int)kind)->n_cols;
+    o.out = tg.out;
+    o.refused = tg.refused;
+    switch (tg.form) {
+      case TraceTarget::TABLE:
+        o.form = TraceOut::ROWS;
+        o.rows = tg.rows + tg.row_offset * nc;
+        break;
+      case TraceTarget::MANY:
+        if (tg.n_members > LMN_TRACE_MANY_MAX) bad_argument(tg.call, "n_members exceeds LMN_TRACE_MANY_MAX");
+        if (tg.row_offset >= (1ull << 31) || tg.rows_ms >= (1ull << 40))
+          bad_argument(tg.call, "row_offset / rows_member_stride: table too large");
+        if (tg.rows_ms < tg.row_offset + n_rows)
+          bad_argument(tg.call, "rows_member_stride is smaller than row_offset + the node's " + std::to_string(n_rows) + " rows");
+        if (tg.out && tg.out_ms == 0 && !shared_in)
+          bad_argument(tg.call, "out_member_stride 0 (a shared output tensor) needs every operand stride to be 0");
+        if (tg.out && tg.out_ms != 0 && tg.out_ms < out_n)
+          bad_argument(tg.call, "out_member_stride is smaller than the output's " + std::to_string(out_n) + " elements");
+        o.form = TraceOut::MANY;
+        o.rows = tg.rows + tg.row_offset * nc;
+        o.rows_ms = tg.rows_ms * nc;
+        o.n_members = tg.n_members;
+        o.out_ms = tg.out_ms;
+        break;
+      case TraceTarget::SINK:
+        append.emplace(*tg.sink, tg.call, device, stream, kind, n_rows);
+        o.form = TraceOut::COLS;
+        o.cols = append->cols();
+        o.col_stride = append->stride();
+        o.bad_word = append->bad();
+        break;
+    }
+  }
+  void done() {
+    if (append) append->done();
+  }
+};
+}  // namespace
+
+// ------------------------------------------------------------------------------------ the producers
+// Every producer: select the device, the producer's own rules, the target's, then one launch - stream-ordered with every
+// later call on this context (lmn_prove, lmn_download).  Nothing is launched before all rules hold.
+
+// `process_trace` of an Add / Mul / Recip / Sqrt / Rem / LessThan / Inputs node on device tensors (prim.rs:967-1013,
+// :1090-1139, :388-431); rc_mult: LessThan's RangeCheckLookup multiplicities.  src_dtype: inputs_float's source.
+void Context::elementwise(const TraceTarget& tg, uint32_t kind, const TraceIn& lhs, const TraceIn& rhs, uint64_t n,
+                          const lmn_node_info& info, uint32_t* rc_mult, uint64_t rc_ms, int src_dtype) {
+  lmn_set_device(device_);
+  const bool binary = elementwise_binary(kind), lt = kind == LMN_KIND_LESS_THAN;
+  named_rules(tg.call, [&] { check_elementwise(kind, rhs.p, lt && !rc_mult, n, [](ElemRule r) { trace_fail(kTraceElemRules[r]); }); });
+  const TraceOperand l{(const int32_t*)lhs.p, named_rules(tg.call, [&] { return trace_view(lhs.view, n); }), lhs.ms};
+  // (the table form has always held a unary kind's right view to the view rules as well)
+  const TraceOperand r{binary ? (const int32_t*)rhs.p : nullptr,
+                       binary || tg.form == TraceTarget::TABLE ? named_rules(tg.call, [&] { return trace_view(rhs.view, n); }) : TraceView{},
+                       rhs.ms};
+  Placed pl(tg, device_, stream_, kind, n, n, lhs.ms == 0 && (!binary || rhs.ms == 0));
+  if (tg.form == TraceTarget::MANY && lt && rc_ms < 256)
+    bad_argument(tg.call, "range_check_mult_member_stride is smaller than the table's 256 words");
+  launch_trace_elementwise((int)kind, src_dtype, l, r, n, trace_node(info), lt ? rc_mult : nullptr, rc_ms, pl.o, stream_);
+  pl.done();
+}
+
+// `LuminairContiguous::process_trace` in the reference's own row rule (prim.rs:229-301): max(in_size, out_size) rows
+void Context::contiguous(const TraceTarget& tg, const TraceIn& input, uint64_t in_size, uint64_t out_size, const lmn_node_info& info) {
+  lmn_set_device(device_);
+  TraceNode nd = trace_node(info);
+  const TraceOperand in{(const int32_t*)input.p, named_rules(tg.call, [&] { return check_contiguous(in_size, input.view, out_size, nd); }),
+                        input.ms};
+  const uint64_t n = std::max(in_size, out_size);
+  Placed pl(tg, device_, stream_, LMN_KIND_CONTIGUOUS, n, out_size, input.ms == 0);
+  launch_trace_elementwise(LMN_KIND_CONTIGUOUS, SRC_FIXED, in, TraceOperand{}, n, nd, nullptr, 0, pl.o, stream_);
+  pl.done();
+}
+
+// `LuminairSumReduce::process_trace` (prim.rs:1450-1565), or MaxReduce, on a contiguous (front, dim, back) device tensor
+void Context::reduce(const TraceTarget& tg, bool is_max, const TraceIn& input, uint64_t front, uint64_t dim, uint64_t back,
+                     const lmn_node_info& info) {
+  lmn_set_device(device_);
+  named_rules(tg.call, [&] { check_reduce_shape(front, dim, back); });
+  Placed pl(tg, device_, stream_, is_max ? LMN_KIND_MAX_REDUCE : LMN_KIND_SUM_REDUCE, front * dim * back, front * back, input.ms == 0);
+  launch_trace_reduce(is_max, TraceOperand{(const int32_t*)input.p, TraceView{}, input.ms}, front, dim, back, trace_node(info), pl.o,
+                      stream_);
+  pl.done();
+}
+
+// `process_trace` of a Sin / Exp2 / Log2 node on a device tensor; fills the LUT multiplicity column too.  An input outside
+// every range is a refused element of a many-member or sink target; the table form fails the call - the one wait here.
+void Context::lut(const TraceTarget& tg, uint32_t kind, const TraceIn& input, uint64_t n, const lmn_node_info& info,
+                  const uint32_t* lut_col1, const lmn_range* ranges, uint32_t n_ranges, uint32_t* mult, uint64_t mult_ms) {
+  lmn_set_device(device_);
+  uint64_t lut_rows = 0;
+  const LutRanges rg = named_rules(tg.call, [&] {
+    return lut_ranges(kind, n, ranges, n_ranges, lut_rows, [](LutRule r) { trace_fail(kTraceLutRules[r]); });
+  });
+  const TraceOperand in{(const int32_t*)input.p, named_rules(tg.call, [&] { return trace_view(input.view, n); }), input.ms};
+  Placed pl(tg, device_, stream_, kind, n, n, input.ms == 0);
+  if (tg.form == TraceTarget::MANY && mult_ms < lut_rows)
+    bad_argument(tg.call, "mult_member_stride is smaller than the " + std::to_string(lut_rows) + " LUT rows the ranges enumerate");
+  const bool table = tg.form == TraceTarget::TABLE;
+  if (table) pl.o.err_flag = bad_flag_ + 1;   // zero between calls; the kernel sets it when an input misses every range
+  launch_trace_lut(in, n, trace_node(info), lut_col1, rg, mult, mult_ms, pl.o, stream_);
+  pl.done();
+  if (!table) return;
+  uint32_t err = 0;
+  lmn_d2h(&err, bad_flag_ + 1, 4, stream_);
+  lmn_sync(stream_);
+  if (err) {
+    const uint32_t zero = 0u;
+    lmn_h2d(bad_flag_ + 1, &zero, 4, stream_);
+    lmn_sync(stream_);
+    throw LmnError(LMN_ERR_INVALID_ARGUMENT, "trace_lut: an input value lies outside the LUT's range");
+  }
+}
+
+// `CopyToStwo` on raw float bits (prim.rs:52-101): the Inputs producer with the float -> Fixed<12> rule (kernels_trace.hip
+// float_bits_to_fixed) inside the launch that writes the rows.  The float arguments are checked first, then Inputs' own
+// rules apply, with their codes; every form's text carries the entry point's name.
+void Context::inputs_float(const TraceTarget& tg, uint32_t dtype, const TraceIn& src, uint64_t n, const lmn_node_info& info) {
+  lmn_set_device(device_);
+  check_float_ptr(tg.call, dtype, src.p, "src_dev");
+  if (n == 0) throw LmnError(LMN_ERR_EMPTY_TRACE, std::string(tg.call) + ": n is 0 (TraceError::EmptyTrace)");
+  elementwise(tg, LMN_KIND_INPUTS, src, TraceIn{}, n, info, nullptr, 0, (int)dtype);
+}
+
+// ------------------------------------------------------------------------------------ lmn_eval_*
+// `Operator::process` of the same operators: the forward pass in front of gen_trace (gen_circuit_settings' dry run,
+// crates/graph/src/graph.rs:61-159).  Values only; every call also leaves the range of what it wrote and adds its refused
+// elements to a counter, and none waits for the device.  The producers' rules, failing with the argument's name.
+namespace {
+TraceView eval_view(const char* call, const char* name, const lmn_view* v, uint64_t n) {
+  return named_rules(call, [&] { return named_rules(name, [&] { return trace_view(v, n); }); });
 }
 }  // namespace
 
-void Context::trace_inputs_float(uint32_t dtype, const void* src, uint64_t n, const lmn_node_info& info, uint32_t* rows,
-                                 uint64_t row_offset, int32_t* out) {
-  const char* call = "lmn_trace_inputs_float";
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
-  check_float_ptr(call, dtype, src, "src_dev");
-  check_float_rows(call, n);
-  launch_trace_inputs_float(dtype, src, n, trace_node(info), rows + row_offset * 7ull, out, stream_);
+void Context::eval_begin(int32_t* minmax) {
+  lmn_set_device(device_);
+  if (minmax) launch_eval_init(minmax, stream_);
 }
 
-void Context::trace_many_inputs_float(uint32_t dtype, const void* src, uint64_t src_ms, uint64_t n, const lmn_node_info& info,
-                                      uint32_t n_members, uint32_t* rows, uint64_t row_offset, uint64_t rows_ms, int32_t* out,
-                                      uint64_t out_ms, uint32_t* refused) {
-  const char* call = "lmn_trace_many_inputs_float";
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
-  check_float_ptr(call, dtype, src, "src_dev");
-  check_float_rows(call, n);
-  many_strides(call, n_members, rows_ms, row_offset, n, out, out_ms, n, src_ms == 0);
-  launch_trace_many_inputs_float(dtype, src, src_ms, n, trace_node(info), n_members, rows + row_offset * 7ull, rows_ms * 7ull, out,
-                                 out_ms, refused, stream_);
+void Context::eval_elementwise(uint32_t kind, const int32_t* lhs, const lmn_view* lv, const int32_t* rhs, const lmn_view* rv,
+                               uint64_t n, int32_t* out, int32_t* minmax, uint32_t* refused) {
+  const char* call = "lmn_eval_elementwise_v";
+  check_elementwise(kind, rhs, false, n, [&](ElemRule r) {
+    bad_argument(call, r == ELEM_KIND    ? "kind " + std::to_string(kind) + " is not an elementwise kind"
+                       : r == ELEM_RHS   ? "null rhs_dev for a binary kind"
+                       : r == ELEM_EMPTY ? "n is 0"
+                                         : "n: tensor too large");
+  });
+  const TraceView tlv = eval_view(call, "lhs_view", lv, n);
+  const TraceView trv = elementwise_binary(kind) ? eval_view(call, "rhs_view", rv, n) : TraceView{};
+  eval_begin(minmax);
+  launch_eval_elementwise((int)kind, lhs, tlv, rhs, trv, n, out, minmax, refused, stream_);
 }
 
-void Context::rows_append_inputs_float(RowSink& sink, uint32_t dtype, const void* src, uint64_t n, const lmn_node_info& info,
-                                       int32_t* out, uint32_t* refused) {
-  const char* call = "lmn_rows_append_inputs_float";
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
-  check_float_ptr(call, dtype, src, "src_dev");
-  check_float_rows(call, n);
-  RowSink::Append ap(sink, call, device_, stream_, LMN_KIND_INPUTS, n);
-  launch_trace_inputs_float_cols(dtype, src, n, trace_node(info), ap.cols(), ap.stride(), out, ap.bad(), refused, stream_);
-  ap.done();
+void Context::eval_reduce(bool is_max, const int32_t* input, uint64_t front, uint64_t dim, uint64_t back, int32_t* out,
+                          int32_t* minmax, uint32_t* refused) {
+  const char* call = "lmn_eval_reduce";
+  if (front == 0) bad_argument(call, "front is 0");
+  if (dim == 0) bad_argument(call, "dim is 0");
+  if (back == 0) bad_argument(call, "back is 0");
+  if (front >= (1ull << 31) || dim >= (1ull << 31) || back >= (1ull << 31) || front * back >= (1ull << 31) ||
+      front * back * dim >= (1ull << 31))
+    bad_argument(call, "front * dim * back: tensor too large");
+  eval_begin(minmax);
+  launch_eval_reduce(is_max, input, front, dim, back, out, minmax, refused, stream_);
+}
+
+void Context::eval_lut(uint32_t kind, const int32_t* input, const lmn_view* view, uint64_t n, const uint32_t* lut_col1,
+                       const lmn_range* ranges, uint32_t n_ranges, int32_t* out, int32_t* minmax, uint32_t* refused) {
+  const char* call = "lmn_eval_lut_ranges";
+  static const char* const why[] = {"kind must be Sin, Exp2 or Log2", "n is 0", "n: tensor too large", "null ranges",
+                                    "n_ranges must be 1..16", "ranges must be ascending, disjoint and inside (-2^30, 2^30)",
+                                    "ranges: LUT larger than 2^26 rows"};
+  uint64_t lut_rows = 0;
+  const LutRanges rg = lut_ranges(kind, n, ranges, n_ranges, lut_rows, [&](LutRule r) { bad_argument(call, why[r]); });
+  const TraceView tv = eval_view(call, "view", view, n);
+  eval_begin(minmax);
+  launch_eval_lut(input, tv, n, lut_col1, rg, out, minmax, refused, stream_);
+}
+
+void Context::tensor_range(const int32_t* buf, uint64_t n, int32_t* minmax) {
+  if (n == 0) bad_argument("lmn_tensor_range", "n is 0");
+  if (n >= (1ull << 31)) bad_argument("lmn_tensor_range", "n: tensor too large");
+  eval_begin(minmax);
+  launch_tensor_range(buf, n, minmax, stream_);
 }
 
 void Context::eval_inputs_float(uint32_t dtype, const void* src, uint64_t n, int32_t* out, int32_t* minmax, uint32_t* refused) {
   const char* call = "lmn_eval_inputs_float";
   check_float_ptr(call, dtype, src, "src_dev");
-  if (n == 0) eval_bad(call, "n is 0");
-  if (n >= (1ull << 31)) eval_bad(call, "n: tensor too large");
+  if (n == 0) bad_argument(call, "n is 0");
+  if (n >= (1ull << 31)) bad_argument(call, "n: tensor too large");
   eval_begin(minmax);
   launch_eval_inputs_float(dtype, src, n, out, minmax, refused, stream_);
 }
@@ -477,12 +367,10 @@ void Context::eval_inputs_float(uint32_t dtype, const void* src, uint64_t n, int
 // `CopyFromStwo`: returns when dst is complete, as download does - a reader on another stream may use it at once
 void Context::tensor_to_float(uint32_t dtype, const int32_t* src, uint64_t n, void* dst) {
   const char* call = "lmn_tensor_to_float";
-#ifndef LMN_EMU
-  LMN_HIP_CHECK(hipSetDevice(device_));
-#endif
+  lmn_set_device(device_);
   check_float_ptr(call, dtype, dst, "dst_dev");
-  if (n == 0) eval_bad(call, "n is 0");
-  if (n >= (1ull << 31)) eval_bad(call, "n: tensor too large");
+  if (n == 0) bad_argument(call, "n is 0");
+  if (n >= (1ull << 31)) bad_argument(call, "n: tensor too large");
   launch_tensor_to_float(dtype, src, n, dst, stream_);
   lmn_sync(stream_);
 }

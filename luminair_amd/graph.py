@@ -66,6 +66,55 @@ def _lease_slab(ctx, need: int) -> _SlabLease:
     return _SlabLease(ctx, b.ptr, b.nbytes)
 
 
+_al = lambda nbytes: (nbytes + 255) & ~255
+
+
+class _Stager:
+    """The one slab of a walk over the graph (hipMalloc per node would dominate small graphs) and the host data that has to
+    reach it - graph inputs, LUT output columns, zeroed multiplicity tables and counters: packed into ONE staging array, each
+    part 256-byte aligned, and uploaded with one copy (one synchronisation instead of one per tensor).  The staged bytes are
+    the slab's first carve; tables and tensors are carved behind them."""
+
+    def __init__(self):
+        self.parts, self.off, self.nbytes, self.staged = [], {}, 0, None
+
+    def stage(self, key, arr):
+        a = np.ascontiguousarray(arr).reshape(-1).view(np.uint32)
+        self.off[key] = (self.nbytes, a.nbytes)
+        self.parts.append(a)
+        if _al(a.nbytes) > a.nbytes:
+            self.parts.append(np.zeros((_al(a.nbytes) - a.nbytes) // 4, dtype=np.uint32))
+        self.nbytes += _al(a.nbytes)
+
+    def stage_input(self, n: "_Node", host, fsrc):
+        """a graph input's values: int32 `host`, or the raw bits of a float source that does not lie on the device yet"""
+        if n.host is not None:
+            self.stage(("in", n.out.node_id), host.astype(np.int32, copy=False))
+        elif fsrc is not None and fsrc.tensor is None:
+            self.stage(("in", n.out.node_id), _words(fsrc.host))
+
+    def lease(self, ctx, carved_bytes: int) -> _SlabLease:
+        self.slab, self.cursor = _lease_slab(ctx, carved_bytes + self.nbytes), 0
+        return self.slab
+
+    def upload(self, ctx):
+        if self.nbytes:
+            self.staged = ctx.upload_to(self.carve(self.nbytes), np.concatenate(self.parts))
+
+    def dev_of(self, key) -> backend.DeviceBuffer:
+        return self.staged.view(*self.off[key])
+
+    def carve(self, nbytes: int) -> backend.DeviceBuffer:
+        v = self.slab.view(self.cursor, nbytes)
+        self.cursor += _al(nbytes)
+        return v
+
+
+def _refused_error(n_refused: int) -> ValueError:
+    return ValueError("dry run: %d elements refused (a value outside [-(2^30-1), 2^30-1], Recip of a value <= 0, Sqrt of a "
+                      "negative value, Rem outside lhs >= 0 and rhs > 0, or a LUT input outside its range)" % n_refused)
+
+
 @dataclass(eq=False)          # a tensor is itself (a key of gen_trace_many's `feeds`), not its fields
 class GraphTensor:
     node_id: int
@@ -190,6 +239,114 @@ class _Node:
     axis: int = 0                          # SumReduce
     per_member: bool = False               # graph inputs: one tensor per member of gen_trace_many (fed through `feeds`)
     fsrc: Optional[_FloatSource] = None    # graph inputs made by input_float (`host` is None then)
+
+
+_REDUCES = (int(TraceTableKind.SumReduce), int(TraceTableKind.MaxReduce))
+_LESS_THAN = int(TraceTableKind.LessThan)
+
+
+def _ref_contig(n: "_Node") -> bool:
+    """a Contiguous node in the reference's buffer rule (no expanded dimension)"""
+    return n.kind == int(TraceTableKind.Contiguous) and n.inputs[0].expansion == 1
+
+
+def _rows_of(n: "_Node") -> int:
+    if n.kind in _REDUCES:
+        return n.inputs[0].size
+    if _ref_contig(n):
+        return max(n.inputs[0].base.size, n.out.size)
+    return n.out.size
+
+
+class _Call:
+    """What one node's producer call computes, whatever its destination: the producer (`op`), the operand buffers with
+    their base tensors and views, and what only that producer reads - the reduce's (front, dim, back), the LUT's name,
+    the float source's dtype.  `staged`: the staged values of a graph input; `fsrc`: the float source to read, if any.
+    The emitters below turn it into a `trace_*` (table or sink), `trace_many_*` or `eval_*` call."""
+
+    def __init__(self, n: "_Node", staged, fsrc=None):
+        t = n.out
+        self.kind, self.node_id, self.n = n.kind, t.node_id, t.size
+        self.bases = [v.base for v in n.inputs]
+        self.bufs = [b.buf for b in self.bases]
+        self.views = [_lmn_view(v) for v in n.inputs]
+        if fsrc is not None:
+            self.op, self.code = "inputs_float", fsrc.code
+            self.bufs = [fsrc.tensor.data_ptr() if fsrc.tensor is not None else staged(t.node_id)]
+        elif n.kind == int(TraceTableKind.Inputs):
+            self.op, self.bufs = "elementwise", [staged(t.node_id)]
+        elif n.kind in _REDUCES:
+            a = self.bases[0]
+            front = int(np.prod(a.shape[:n.axis])) if n.axis else 1
+            back = int(np.prod(a.shape[n.axis + 1:])) if n.axis + 1 < len(a.shape) else 1
+            self.op, self.shape3, self.maximum = "reduce", (front, a.shape[n.axis], back), n.kind == _REDUCES[1]
+        elif _ref_contig(n):
+            self.op = "contiguous"
+        elif n.kind in _LUT_OF:
+            self.op, self.lut = "lut", _LUT_OF[n.kind][0]
+        else:
+            self.op = "elementwise"
+        self.ids = tuple(b.node_id for b in self.bases)
+
+    def pair(self, xs, fill=None):
+        """(lhs, rhs) of an elementwise call from the node's zero, one or two inputs"""
+        return tuple((list(xs) + [fill, fill])[:2])
+
+
+def _emit_trace(ctx, c: _Call, lut_dev, lut_ranges, rc_mult, dst):
+    """-> `lmn_trace_*` into a table at its row offset, or `lmn_rows_append_*` into a sink (`dst` says which); returns
+    the output buffer.  lut_dev: (output column, multiplicities, lo, hi) of the node's LUT."""
+    ids = dict(node_id=c.node_id, **dst)
+    if c.op == "inputs_float":
+        return ctx.trace_inputs_float(c.code, c.bufs[0], c.n, **ids)[1]
+    if c.op == "reduce":
+        return ctx.trace_sum_reduce(c.bufs[0], *c.shape3, input_id=c.ids[0], maximum=c.maximum, **ids)[1]
+    if c.op == "contiguous":
+        return ctx.trace_contiguous(c.bufs[0], c.bases[0].size, c.n, input_id=c.ids[0], view=c.views[0], **ids)[1]
+    if c.op == "lut":
+        col1, mult, lo, hi = lut_dev
+        return ctx.trace_lut(c.kind, c.bufs[0], c.n, input_id=c.ids[0], lut_col1=col1, lo=lo, lut_len=hi - lo + 1, mult=mult,
+                             view=c.views[0], ranges=lut_ranges, **ids)[1]
+    (lhs, rhs), (lv, rv) = c.pair(c.bufs), c.pair(c.views)
+    if c.kind == _LESS_THAN:
+        return ctx.trace_less_than(lhs, rhs, c.n, input_ids=c.ids, range_check_mult=rc_mult, lhs_view=lv, rhs_view=rv, **ids)[1]
+    return ctx.trace_elementwise(c.kind, lhs, rhs, c.n, input_ids=c.ids, input_mults=tuple(-1 for _ in c.ids), lhs_view=lv,
+                                 rhs_view=rv, **ids)[1]
+
+
+def _emit_trace_many(ctx, c: _Call, out_stride: int, lut_dev, lut_ranges, rc_mult, dst):
+    """-> `lmn_trace_many_*`; an operand's member stride is its tensor's (0: shared), a graph input's its own"""
+    strides = [b.member_stride for b in c.bases] or [out_stride]
+    ids = dict(node_id=c.node_id, out_stride=out_stride, **dst)
+    if c.op == "inputs_float":
+        ctx.trace_many_inputs_float(c.code, c.bufs[0], c.n, src_stride=strides[0], **ids)
+    elif c.op == "reduce":
+        ctx.trace_many_reduce(c.bufs[0], *c.shape3, input_id=c.ids[0], inp_stride=strides[0], maximum=c.maximum, **ids)
+    elif c.op == "contiguous":
+        ctx.trace_many_contiguous(c.bufs[0], c.bases[0].size, c.n, input_id=c.ids[0], inp_stride=strides[0], view=c.views[0], **ids)
+    elif c.op == "lut":
+        col1, mult, mult_stride = lut_dev
+        ctx.trace_many_lut(c.kind, c.bufs[0], c.n, input_id=c.ids[0], lut_col1=col1, ranges=lut_ranges, mult=mult,
+                           mult_stride=mult_stride, inp_stride=strides[0], view=c.views[0], **ids)
+    else:
+        (lhs, rhs), (lv, rv), (ls, rs) = c.pair(c.bufs), c.pair(c.views), c.pair(strides, 0)
+        lt = c.kind == _LESS_THAN
+        ctx.trace_many_elementwise(c.kind, lhs, rhs, c.n, input_ids=c.ids, input_mults=tuple(-1 for _ in c.ids), lhs_stride=ls,
+                                   rhs_stride=rs, lhs_view=lv, rhs_view=rv, range_check_mult=rc_mult if lt else None,
+                                   range_check_mult_stride=256 if lt else 0, **ids)
+
+
+def _emit_eval(ctx, c: _Call, lut_col1, lut_ranges, dst):
+    """-> `lmn_eval_*`: the values, their range, the refused elements"""
+    if c.op == "inputs_float":
+        ctx.eval_inputs_float(c.code, c.bufs[0], c.n, **dst)
+    elif c.op == "reduce":
+        ctx.eval_reduce(c.bufs[0], *c.shape3, maximum=c.maximum, **dst)
+    elif c.op == "lut":
+        ctx.eval_lut(c.kind, c.bufs[0], c.n, lut_col1, lut_ranges, view=c.views[0], **dst)
+    else:       # (the forward pass has one Contiguous: the view rule)
+        (lhs, rhs), (lv, rv) = c.pair(c.bufs), c.pair(c.views)
+        ctx.eval_elementwise(c.kind, lhs, rhs, c.n, lhs_view=lv, rhs_view=rv, **dst)
 
 
 class DeviceGraph:
@@ -427,69 +584,32 @@ class DeviceGraph:
         ctx = self.ctx
         K = TraceTableKind
         self.release_dry_run()     # (its slab goes back to the context's cache: the lease below may take it)
-        view_of = _lmn_view
-        reduces = (int(K.SumReduce), int(K.MaxReduce))
-        ref_contig = lambda n: n.kind == int(K.Contiguous) and n.inputs[0].expansion == 1
-
-        def rows_of(n):
-            if n.kind in reduces:
-                return n.inputs[0].size
-            if ref_contig(n):
-                return max(n.inputs[0].base.size, n.out.size)
-            return n.out.size
         total: Dict[int, int] = {}
         for n in self.nodes:
-            total[n.kind] = total.get(n.kind, 0) + rows_of(n)
-        # one allocation for all tables and tensors (hipMalloc per node would dominate small graphs); the trace
-        # calls are stream-ordered, so nothing waits until the tables are proved or a tensor is read back
-        al = lambda nbytes: (nbytes + 255) & ~255
-        # host data that has to reach the device: graph inputs, LUT output columns, zeroed multiplicity tables - packed
-        # into ONE staging array and uploaded with one copy (one synchronisation instead of one per tensor)
-        stage_parts, stage_off, cursor_h = [], {}, [0]
-
-        def stage(key, arr):
-            a = np.ascontiguousarray(arr).reshape(-1).view(np.uint32)
-            stage_off[key] = (cursor_h[0], a.nbytes)
-            pad = (al(a.nbytes) - a.nbytes) // 4
-            stage_parts.append(a)
-            if pad:
-                stage_parts.append(np.zeros(pad, dtype=np.uint32))
-            cursor_h[0] += al(a.nbytes)
-
+            total[n.kind] = total.get(n.kind, 0) + _rows_of(n)
+        # one allocation for all tables and tensors; the trace calls are stream-ordered, so nothing waits until the tables
+        # are proved or a tensor is read back
+        st = _Stager()
         for n in self.nodes:
             if n.kind in _LUT_OF and _LUT_OF[n.kind][0] not in self.luts:
                 raise ValueError("no LUT for %r: call gen_circuit_settings() (or set_lut / set_lut_ranges) before gen_trace"
                                  % _LUT_OF[n.kind][0])
-            if n.host is not None:
-                stage(("in", n.out.node_id), n.host.astype(np.int32, copy=False))
-            elif n.fsrc is not None and n.fsrc.tensor is None:
-                stage(("in", n.out.node_id), _words(n.fsrc.host))
+            st.stage_input(n, n.host, n.fsrc)
         luts_out = {}
         for kind in sorted(total):
             if kind in _LUT_OF:
                 name, _ = _LUT_OF[kind]
                 lo, hi, (c0, c1) = self.luts[name]
-                stage(("lut1", name), c1)
-                stage(("lutm", name), np.zeros(len(c0), dtype=np.uint32))
+                st.stage(("lut1", name), c1)
+                st.stage(("lutm", name), np.zeros(len(c0), dtype=np.uint32))
                 luts_out[name] = (c0, c1)
-        if int(K.LessThan) in total:
-            stage(("rc",), np.zeros(256, dtype=np.uint32))
+        if _LESS_THAN in total:
+            st.stage(("rc",), np.zeros(256, dtype=np.uint32))
         if columns:
-            stage(("refused",), np.zeros(1, dtype=np.uint32))
-        need = (0 if columns else sum(al(total[k] * _NCOLS[k] * 4) for k in total)) + \
-            sum(al(n.out.size * 4) for n in self.nodes) + cursor_h[0]
-        slab = _lease_slab(ctx, need)
-        cursor = [0]
-
-        def carve(nbytes):
-            v = slab.view(cursor[0], nbytes)
-            cursor[0] += al(nbytes)
-            return v
-
-        staged = carve(cursor_h[0]) if cursor_h[0] else None
-        if staged is not None:
-            ctx.upload_to(staged, np.concatenate(stage_parts))
-        dev_of = lambda key: staged.view(*stage_off[key])
+            st.stage(("refused",), np.zeros(1, dtype=np.uint32))
+        slab = st.lease(ctx, (0 if columns else sum(_al(total[k] * _NCOLS[k] * 4) for k in total)) +
+                        sum(_al(n.out.size * 4) for n in self.nodes))
+        st.upload(ctx)
         bufs = [slab]
         refused = None
         if columns:
@@ -503,66 +623,34 @@ class DeviceGraph:
                     sink.reset()
                 tables[k] = sink
                 bufs.append(_SinkLease(sink))
-            refused = dev_of(("refused",))
+            refused = st.dev_of(("refused",))
         else:
-            tables = {k: carve(total[k] * _NCOLS[k] * 4) for k in total}
+            tables = {k: st.carve(total[k] * _NCOLS[k] * 4) for k in total}
         offset = {k: 0 for k in total}
         lut_dev, lut_tables = {}, {}
         for kind in sorted(total):
             if kind in _LUT_OF:
                 name, lookup_kind = _LUT_OF[kind]
-                lut_dev[name] = (dev_of(("lut1", name)), dev_of(("lutm", name)))   # outputs, multiplicities
-                lut_tables[lookup_kind] = (lut_dev[name][1], len(self.luts[name][2][0]))
+                lo, hi, (c0, _) = self.luts[name]
+                lut_dev[name] = (st.dev_of(("lut1", name)), st.dev_of(("lutm", name)), lo, hi)   # outputs, multiplicities
+                lut_tables[lookup_kind] = (lut_dev[name][1], len(c0))
         rc_mult = None
-        if int(K.LessThan) in total:
-            rc_mult = dev_of(("rc",))
+        if _LESS_THAN in total:
+            rc_mult = st.dev_of(("rc",))
             lut_tables[int(K.RangeCheckLookup)] = (rc_mult, 256)
         self._sync_torch(n.fsrc for n in self.nodes)
         for n in self.nodes:
             t = n.out
             t.member_stride = 0
-            common = dict(num_consumers=t.consumers, is_final_output=t.is_output, out=carve(t.size * 4))
+            dst = dict(num_consumers=t.consumers, is_final_output=t.is_output, out=st.carve(t.size * 4))
             if columns:
-                common.update(sink=tables[n.kind], refused=refused)
+                dst.update(sink=tables[n.kind], refused=refused)
             else:
-                common.update(rows=tables[n.kind], row_offset=offset[n.kind])
-            if n.fsrc is not None:
-                f = n.fsrc
-                src = f.tensor.data_ptr() if f.tensor is not None else dev_of(("in", t.node_id))
-                _, t.buf = ctx.trace_inputs_float(f.code, src, t.size, node_id=t.node_id, **common)
-            elif n.kind == int(K.Inputs):
-                src = dev_of(("in", t.node_id))
-                _, t.buf = ctx.trace_elementwise(n.kind, src, None, t.size, node_id=t.node_id, input_ids=(),
-                                                 input_mults=(), **common)
-            elif n.kind in reduces:
-                a = n.inputs[0].base
-                front = int(np.prod(a.shape[:n.axis])) if n.axis else 1
-                back = int(np.prod(a.shape[n.axis + 1:])) if n.axis + 1 < len(a.shape) else 1
-                _, t.buf = ctx.trace_sum_reduce(a.buf, front, a.shape[n.axis], back, node_id=t.node_id,
-                                                input_id=a.node_id, maximum=n.kind == int(K.MaxReduce), **common)
-            elif n.kind == int(K.LessThan):
-                ins = n.inputs
-                _, t.buf = ctx.trace_less_than(ins[0].base.buf, ins[1].base.buf, t.size, node_id=t.node_id,
-                                               input_ids=tuple(i.base.node_id for i in ins), range_check_mult=rc_mult,
-                                               lhs_view=view_of(ins[0]), rhs_view=view_of(ins[1]), **common)
-            elif ref_contig(n):
-                v = n.inputs[0]
-                _, t.buf = ctx.trace_contiguous(v.base.buf, v.base.size, t.size, node_id=t.node_id,
-                                                input_id=v.base.node_id, view=view_of(v), **common)
-            elif n.kind in _LUT_OF:
-                name = _LUT_OF[n.kind][0]
-                lo, hi, (c0, _) = self.luts[name]
-                v = n.inputs[0]
-                _, t.buf = ctx.trace_lut(n.kind, v.base.buf, t.size, node_id=t.node_id, input_id=v.base.node_id,
-                                         lut_col1=lut_dev[name][0], lo=lo, lut_len=hi - lo + 1, mult=lut_dev[name][1],
-                                         view=view_of(v), ranges=self.lut_ranges.get(name), **common)
-            else:
-                ins = n.inputs
-                _, t.buf = ctx.trace_elementwise(
-                    n.kind, ins[0].base.buf, ins[1].base.buf if len(ins) > 1 else None, t.size, node_id=t.node_id,
-                    input_ids=tuple(i.base.node_id for i in ins), input_mults=tuple(-1 for _ in ins),
-                    lhs_view=view_of(ins[0]), rhs_view=view_of(ins[1]) if len(ins) > 1 else None, **common)
-            offset[n.kind] += rows_of(n)
+                dst.update(rows=tables[n.kind], row_offset=offset[n.kind])
+            c = _Call(n, lambda node_id: st.dev_of(("in", node_id)), n.fsrc)
+            name = getattr(c, "lut", None)
+            t.buf = _emit_trace(ctx, c, lut_dev.get(name), self.lut_ranges.get(name), rc_mult, dst)
+            offset[n.kind] += _rows_of(n)
         if columns:
             # every node is enqueued: the first finish waits for nearly all of the work, the others find it done.  A sink
             # fails its finish exactly when a producer refused one of its elements; only then the counter is read
@@ -579,9 +667,7 @@ class DeviceGraph:
                 for b in bufs:
                     if not (isinstance(b, _SinkLease) and sinks is not None and b.sink in sinks.values()):
                         b.free()           # (the caller's own sinks stay open: the next call resets them)
-                raise ValueError("dry run: %d elements refused (a value outside [-(2^30-1), 2^30-1], Recip of a value <= 0, "
-                                 "Sqrt of a negative value, Rem outside lhs >= 0 and rhs > 0, or a LUT input outside its range)"
-                                 % n_refused)
+                raise _refused_error(n_refused)
         out = [(k, tables[k], total[k]) for k in tables] + [(k, b, n) for k, (b, n) in lut_tables.items()]
         return sorted(out, key=lambda e: e[0]), luts_out, bufs
 
@@ -618,19 +704,10 @@ class DeviceGraph:
                     raise ValueError("gen_trace_many: the feed of input %d has another dtype than the input" % t.node_id)
             else:
                 fed[t.node_id] = np.ascontiguousarray(arr, dtype=np.int32)
-        reduces = (int(K.SumReduce), int(K.MaxReduce))
-        ref_contig = lambda n: n.kind == int(K.Contiguous) and n.inputs[0].expansion == 1
-
-        def rows_of(n):
-            if n.kind in reduces:
-                return n.inputs[0].size
-            if ref_contig(n):
-                return max(n.inputs[0].base.size, n.out.size)
-            return n.out.size
         total: Dict[int, int] = {}
         varying = set()            # tensors that differ between members: the per-member inputs and what depends on them
         for n in self.nodes:
-            total[n.kind] = total.get(n.kind, 0) + rows_of(n)
+            total[n.kind] = total.get(n.kind, 0) + _rows_of(n)
             if n.per_member or any(i.base.node_id in varying for i in n.inputs):
                 varying.add(n.out.node_id)
             if n.kind in _LUT_OF and _LUT_OF[n.kind][0] not in self.luts:
@@ -644,97 +721,47 @@ class DeviceGraph:
         extra = set(fed) - {n.out.node_id for n in self.nodes if n.per_member}
         if extra:
             raise ValueError("gen_trace_many: feeds name tensors that are no per_member inputs: %s" % sorted(extra))
-        al = lambda nbytes: (nbytes + 255) & ~255
-        stage_parts, stage_off, cursor_h = [], {}, [0]
-
-        def stage(key, arr):
-            a = np.ascontiguousarray(arr).reshape(-1).view(np.uint32)
-            stage_off[key] = (cursor_h[0], a.nbytes)
-            pad = (al(a.nbytes) - a.nbytes) // 4
-            stage_parts.append(a)
-            if pad:
-                stage_parts.append(np.zeros(pad, dtype=np.uint32))
-            cursor_h[0] += al(a.nbytes)
-
-        stage(("refused",), np.zeros(n_members, dtype=np.uint32))
+        # what an input node reads: its feed when it is per_member, the graph's own values otherwise
+        host_of = lambda n: fed[n.out.node_id] if n.per_member else n.host
+        fsrc_of = lambda n: n.fsrc if n.fsrc is None or not n.per_member else fed[n.out.node_id]
+        st = _Stager()
+        st.stage(("refused",), np.zeros(n_members, dtype=np.uint32))
         for n in self.nodes:
-            if n.host is not None:
-                stage(("in", n.out.node_id), fed[n.out.node_id] if n.per_member else n.host.astype(np.int32, copy=False))
-            elif n.fsrc is not None:
-                f = fed[n.out.node_id] if n.per_member else n.fsrc
-                if f.tensor is None:
-                    stage(("in", n.out.node_id), _words(f.host))
-        luts_out, lut_len, lut_rg = {}, {}, {}
+            st.stage_input(n, host_of(n), fsrc_of(n))
+        luts_out, lut_dev, lut_rg = {}, {}, {}
         for kind in sorted(total):
             if kind in _LUT_OF:
                 name, _ = _LUT_OF[kind]
                 lo, hi, (c0, c1) = self.luts[name]
-                lut_len[name] = len(c0)
                 lut_rg[name] = self.lut_ranges.get(name) or [(lo, hi)]
-                stage(("lut1", name), c1)
-                stage(("lutm", name), np.zeros(n_members * len(c0), dtype=np.uint32))
+                st.stage(("lut1", name), c1)
+                st.stage(("lutm", name), np.zeros(n_members * len(c0), dtype=np.uint32))
                 luts_out[name] = (c0, c1)
-        if int(K.LessThan) in total:
-            stage(("rc",), np.zeros(n_members * 256, dtype=np.uint32))
+        if _LESS_THAN in total:
+            st.stage(("rc",), np.zeros(n_members * 256, dtype=np.uint32))
         out_words = lambda n: n.out.size * (n_members if n.out.node_id in varying else 1)
-        need = sum(al(n_members * total[k] * _NCOLS[k] * 4) for k in total) + sum(al(out_words(n) * 4) for n in self.nodes) \
-            + cursor_h[0]
-        slab = _lease_slab(ctx, need)
-        cursor = [0]
-
-        def carve(nbytes):
-            v = slab.view(cursor[0], nbytes)
-            cursor[0] += al(nbytes)
-            return v
-
-        staged = carve(cursor_h[0])
-        ctx.upload_to(staged, np.concatenate(stage_parts))
-        dev_of = lambda key: staged.view(*stage_off[key])
-        refused = dev_of(("refused",))
-        tables = {k: carve(n_members * total[k] * _NCOLS[k] * 4) for k in total}
+        slab = st.lease(ctx, sum(_al(n_members * total[k] * _NCOLS[k] * 4) for k in total) +
+                        sum(_al(out_words(n) * 4) for n in self.nodes))
+        st.upload(ctx)
+        staged, stage_off = st.staged, st.off
+        refused = st.dev_of(("refused",))
+        tables = {k: st.carve(n_members * total[k] * _NCOLS[k] * 4) for k in total}
         offset = {k: 0 for k in total}
-        stride_of = lambda t: t.member_stride          # of a tensor that has been produced
-        self._sync_torch((fed[n.out.node_id] if n.per_member else n.fsrc) for n in float_nodes.values())
+        lut_len = {name: len(c0) for name, (c0, _) in luts_out.items()}
+        for name in luts_out:
+            lut_dev[name] = (st.dev_of(("lut1", name)), st.dev_of(("lutm", name)), lut_len[name])
+        rc_mult = st.dev_of(("rc",)) if _LESS_THAN in total else None
+        self._sync_torch(fsrc_of(n) for n in float_nodes.values())
         for n in self.nodes:
             t = n.out
             t.member_stride = t.size if t.node_id in varying else 0
-            t.buf = carve(out_words(n) * 4)
-            common = dict(n_members=n_members, node_id=t.node_id, num_consumers=t.consumers, is_final_output=t.is_output,
-                          rows=tables[n.kind], rows_stride=total[n.kind], row_offset=offset[n.kind], out=t.buf,
-                          out_stride=t.member_stride, refused=refused)
-            if n.fsrc is not None:
-                f = fed[t.node_id] if n.per_member else n.fsrc
-                src = f.tensor.data_ptr() if f.tensor is not None else dev_of(("in", t.node_id))
-                ctx.trace_many_inputs_float(f.code, src, t.size, src_stride=t.member_stride, **common)
-            elif n.kind == int(K.Inputs):
-                ctx.trace_many_elementwise(n.kind, dev_of(("in", t.node_id)), None, t.size, input_ids=(), input_mults=(),
-                                           lhs_stride=t.member_stride, **common)
-            elif n.kind in reduces:
-                a = n.inputs[0].base
-                front = int(np.prod(a.shape[:n.axis])) if n.axis else 1
-                back = int(np.prod(a.shape[n.axis + 1:])) if n.axis + 1 < len(a.shape) else 1
-                ctx.trace_many_reduce(a.buf, front, a.shape[n.axis], back, input_id=a.node_id, inp_stride=stride_of(a),
-                                      maximum=n.kind == int(K.MaxReduce), **common)
-            elif ref_contig(n):
-                v = n.inputs[0]
-                ctx.trace_many_contiguous(v.base.buf, v.base.size, t.size, input_id=v.base.node_id,
-                                          inp_stride=stride_of(v.base), view=_lmn_view(v), **common)
-            elif n.kind in _LUT_OF:
-                name = _LUT_OF[n.kind][0]
-                v = n.inputs[0]
-                ctx.trace_many_lut(n.kind, v.base.buf, t.size, input_id=v.base.node_id, lut_col1=dev_of(("lut1", name)),
-                                   ranges=lut_rg[name], mult=dev_of(("lutm", name)), mult_stride=lut_len[name],
-                                   inp_stride=stride_of(v.base), view=_lmn_view(v), **common)
-            else:
-                ins = n.inputs
-                lt = n.kind == int(K.LessThan)
-                ctx.trace_many_elementwise(
-                    n.kind, ins[0].base.buf, ins[1].base.buf if len(ins) > 1 else None, t.size,
-                    input_ids=tuple(i.base.node_id for i in ins), input_mults=tuple(-1 for _ in ins),
-                    lhs_stride=stride_of(ins[0].base), rhs_stride=stride_of(ins[1].base) if len(ins) > 1 else 0,
-                    lhs_view=_lmn_view(ins[0]), rhs_view=_lmn_view(ins[1]) if len(ins) > 1 else None,
-                    range_check_mult=dev_of(("rc",)) if lt else None, range_check_mult_stride=256 if lt else 0, **common)
-            offset[n.kind] += rows_of(n)
+            t.buf = st.carve(out_words(n) * 4)
+            dst = dict(n_members=n_members, num_consumers=t.consumers, is_final_output=t.is_output, rows=tables[n.kind],
+                       rows_stride=total[n.kind], row_offset=offset[n.kind], out=t.buf, refused=refused)
+            c = _Call(n, lambda node_id: st.dev_of(("in", node_id)), fsrc_of(n))
+            name = getattr(c, "lut", None)
+            _emit_trace_many(ctx, c, t.member_stride, lut_dev.get(name), lut_rg.get(name), rc_mult, dst)
+            offset[n.kind] += _rows_of(n)
         counts = [int(c) for c in ctx.download(refused)[:n_members]]      # the one wait
         pies = []
         for m in range(n_members):
@@ -856,67 +883,39 @@ class DeviceGraph:
         every tensor readable (`read`) until `gen_trace` or `release_dry_run`.  Raises ValueError when an element was
         refused (outside the producers' contract: the host dry run divides by zero or goes on with garbage there)."""
         ctx = self.ctx
-        K = TraceTableKind
         self.release_dry_run()
-        al = lambda nbytes: (nbytes + 255) & ~255
-        n_nodes = len(self.nodes)
-        # staged in one upload: the refused counter (zero), the range slots, the graph inputs
-        parts, off, cur = [np.zeros(64 + 2 * n_nodes, dtype=np.uint32)], {}, al((64 + 2 * n_nodes) * 4)
-        parts.append(np.zeros((cur - parts[0].nbytes) // 4, dtype=np.uint32))
+        # staged in one upload: the refused counter (zero) and the range slots, then the graph inputs
+        st = _Stager()
+        st.stage(("head",), np.zeros(64 + 2 * len(self.nodes), dtype=np.uint32))
         for n in self.nodes:
-            if n.host is not None or (n.fsrc is not None and n.fsrc.tensor is None):
-                a = np.ascontiguousarray(n.host.astype(np.int32, copy=False)).reshape(-1).view(np.uint32) \
-                    if n.host is not None else _words(n.fsrc.host)
-                off[n.out.node_id] = (cur, a.nbytes)
-                parts += [a, np.zeros((al(a.nbytes) - a.nbytes) // 4, dtype=np.uint32)]
-                cur += al(a.nbytes)
-        slab = _lease_slab(ctx, cur + sum(al(n.out.size * 4) for n in self.nodes))
-        self._dry_bufs = [slab]
+            st.stage_input(n, n.host, n.fsrc)
+        self._dry_bufs = [st.lease(ctx, sum(_al(n.out.size * 4) for n in self.nodes))]
         per_fn: Dict[str, list] = {"sin": [], "exp2": [], "log2": []}
         try:
-            ctx.upload_to(slab.view(0, cur), np.concatenate(parts))
-            refused = slab.view(0, 4)
-            slot = {n.out.node_id: slab.view(256 + 8 * i, 8) for i, n in enumerate(self.nodes)}
+            st.upload(ctx)
+            head = st.dev_of(("head",))
+            refused = head.view(0, 4)
+            slot = {n.out.node_id: head.view(256 + 8 * i, 8) for i, n in enumerate(self.nodes)}
             self._sync_torch(n.fsrc for n in self.nodes)
             for n in self.nodes:
                 t = n.out
-                t.buf = slab.view(cur, t.size * 4)
-                cur += al(t.size * 4)
-                common = dict(out=t.buf, minmax=slot[t.node_id], refused=refused)
-                if n.fsrc is not None:
-                    f = n.fsrc
-                    ctx.eval_inputs_float(f.code, f.tensor.data_ptr() if f.tensor is not None else slab.view(*off[t.node_id]),
-                                          t.size, **common)
-                elif n.kind == int(K.Inputs):
-                    ctx.eval_elementwise(n.kind, slab.view(*off[t.node_id]), None, t.size, **common)
-                elif n.kind in (int(K.SumReduce), int(K.MaxReduce)):
-                    a = n.inputs[0].base
-                    front = int(np.prod(a.shape[:n.axis])) if n.axis else 1
-                    back = int(np.prod(a.shape[n.axis + 1:])) if n.axis + 1 < len(a.shape) else 1
-                    ctx.eval_reduce(a.buf, front, a.shape[n.axis], back, maximum=n.kind == int(K.MaxReduce), **common)
-                elif n.kind in _LUT_OF:
-                    name = _LUT_OF[n.kind][0]
-                    v = n.inputs[0]
-                    lo, hi = (int(w) for w in ctx.download(slot[v.base.node_id], np.int32))   # of the BUFFER, not the view
-                    rg = _padded_lut_range(name, lo, hi)
-                    per_fn[name].append(rg)
-                    col1 = ctx.upload(ctx.lib.lut_from_ranges(name, [rg])[1])
+                t.buf = st.carve(t.size * 4)
+                c = _Call(n, lambda node_id: st.dev_of(("in", node_id)), n.fsrc)
+                col1 = rg = None
+                if c.op == "lut":
+                    lo, hi = (int(w) for w in ctx.download(slot[c.ids[0]], np.int32))   # of the BUFFER, not the view
+                    rg = [_padded_lut_range(c.lut, lo, hi)]
+                    per_fn[c.lut] += rg
+                    col1 = ctx.upload(ctx.lib.lut_from_ranges(c.lut, rg)[1])
                     self._dry_bufs.append(col1)
-                    ctx.eval_lut(n.kind, v.base.buf, t.size, col1, [rg], view=_lmn_view(v), **common)
-                else:
-                    ins = n.inputs
-                    ctx.eval_elementwise(n.kind, ins[0].base.buf, ins[1].base.buf if len(ins) > 1 else None, t.size,
-                                         lhs_view=_lmn_view(ins[0]), rhs_view=_lmn_view(ins[1]) if len(ins) > 1 else None,
-                                         **common)
+                _emit_eval(ctx, c, col1, rg, dict(out=t.buf, minmax=slot[t.node_id], refused=refused))
             n_refused = int(ctx.download(refused)[0])
         except Exception:
             self.release_dry_run()
             raise
         if n_refused:
             self.release_dry_run()
-            raise ValueError("dry run: %d elements refused (a value outside [-(2^30-1), 2^30-1], Recip of a value <= 0, Sqrt "
-                             "of a negative value, Rem outside lhs >= 0 and rhs > 0, or a LUT input outside its range)"
-                             % n_refused)
+            raise _refused_error(n_refused)
         return per_fn
 
     def gen_circuit_settings(self, device: bool = False):
