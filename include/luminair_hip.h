@@ -1079,8 +1079,10 @@ int lmn_open_queries(lmn_ctx* ctx, const lmn_positions* positions, const lmn_ope
  * (LMN_DEVICE_DECOMMIT=1 where 9 counts), 12: those among them that fell back to the host plan (no nonce in the queued
  * windows).  Diagnostic only, outside lmn_batch_counter's numbering and not part of what a binding needs - 13: k_open_plan
  * launches made for lmn_open_queries (counted where the launch is made), 14: its k_open_fetch launches, 15: its host
- * waits; 16 - 19: lmn_verify_many's proofs judged by the device stage, stage-2 proofs, launches and host waits.  Any
- * other number, or a null context: 0. */
+ * waits; 16 - 19: lmn_verify_many's proofs judged by the device stage, stage-2 proofs, launches and host waits;
+ * 22: proofs whose quotient tables were made on the device (k_quot_prepare), 23: unsharded proofs with the device
+ * transcript that kept the host's wait for the sampled values instead (LMN_HOST_QUOT=1, or more distinct LDE sizes or
+ * samples than the kernel plans for).  Any other number, or a null context: 0. */
 uint64_t lmn_ctx_counter(const lmn_ctx* ctx, int which);
 int lmn_col_accumulate(lmn_ctx* ctx, lmn_col* dst, const lmn_col* src);     /* AccumulationOps::accumulate: dst += src (same shape) */
 /* FieldOps<BaseField>::batch_inverse and FieldOps<SecureField>::batch_inverse on whole columns, on the device.

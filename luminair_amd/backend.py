@@ -308,6 +308,8 @@ COUNTER_DEVICE_OPENINGS, COUNTER_DEVICE_OPENING_FALLBACKS = 11, 12
 COUNTER_OPEN_PLAN_LAUNCHES, COUNTER_OPEN_FETCH_LAUNCHES, COUNTER_OPEN_WAITS = 13, 14, 15
 # lmn_verify_many: proofs judged by the device stage, stage-2 proofs, verify launches, host waits
 COUNTER_VERIFY_DEVICE, COUNTER_VERIFY_STAGE2, COUNTER_VERIFY_LAUNCHES, COUNTER_VERIFY_WAITS = 16, 17, 18, 19
+# diagnostic only: proofs whose quotient tables k_quot_prepare made; unsharded device-transcript proofs that kept the host's wait
+COUNTER_QUOT_DEVICE, COUNTER_QUOT_HOST_WAIT = 22, 23
 
 API_VERSION = 6   # LMN_API_VERSION of include/luminair_hip.h
 

@@ -802,7 +802,8 @@ void launch_quotients(const QuotientArgs& a, lmn_stream_t s);
 // writes what QuotientOps::accumulate_quotients' host side (quotients.cpp make_quotient_args) would have uploaded: per LDE
 // size the (column, alpha^k * c_k) entries and the batches' QuotDev.  The host enqueues the quotient kernels and the whole
 // FRI commit loop without waiting for the sampled values; it replays this step (and checks the composition identity) when
-// the FRI results arrive.
+// the FRI results arrive.  With one table per kind a proof has fewer samples than QUOT_PREP_MAX_SAMPLES (all 17 kinds
+// make about 424), so lmn_prove reaches the host's fallback through the size count or LMN_HOST_QUOT only.
 constexpr int QUOT_PREP_MAX_SIZES = 8;
 constexpr int QUOT_PREP_MAX_SAMPLES = 496;   // 8 + 4 x 496 message words = 125 Blake2s blocks
 struct QuotPrepEntry {

@@ -256,7 +256,6 @@ void Context::finish_oods_on_host(ProofRun& r) {
 void Context::run_oods(ProofRun& r) {
   LMN_RUN_ALIASES(r);
   plan_sample_points(r);
-  std::map<int, int>& prev_point_of_log = r.prev_point_of_log;
   const std::vector<Pt>& neg_step = r.neg_step;
   auto set_points = [&](QM31 tt) { set_sample_points(r, tt); };
   if (!r.dev_fs) set_points(channel.draw_felt());   // (device-resident transcript: run_composition's plan_oods_step)
@@ -291,9 +290,11 @@ void Context::run_oods(ProofRun& r) {
     }
     StageTimer st(this, log, stream_, C_QUOT);
     enqueue_quotient_tables(r, d_vals);
+    ++quot_counters_[0];
     hm.mark("oods + quotient tables enqueued (device transcript)");
     return;
   }
+  if (r.dev_fs && !shard_.active) ++quot_counters_[1];   // the host's wait, whatever kept the tables from the device
   {
     StageTimer st(this, log, stream_, C_OODS);
     std::vector<QM31> vals = eval_at_points(r.eval_jobs, points, comp_log, /*split=*/true, r.dev_fs ? r.d_maps : nullptr,

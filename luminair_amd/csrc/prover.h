@@ -478,12 +478,14 @@ class Context {
   // 11, 12: proofs opened by the device plan, fallbacks among them; 13, 14, 15 (diagnostic): plan launches, fetch launches
   // and host waits of open_queries; 16 .. 19: verify_many's proofs judged by the device stage, stage-2 proofs, launches, waits
   // 20, 21 (trace reuse): candidate columns compared with the previous proof's, columns among them whose transforms were skipped
+  // 22, 23 (diagnostic): proofs whose quotient tables k_quot_prepare made, unsharded device-transcript proofs that kept the host's wait
   uint64_t counter(int which) const {
     return which >= 7 && which <= 10    ? counters_[which - 7]
            : which >= 11 && which <= 12 ? dev_open_counters_[which - 11]
            : which >= 13 && which <= 15 ? open_counters_[which - 13]
            : which >= 16 && which <= 19 ? verify_counters_[which - 16]
            : which >= 20 && which <= 21 ? reuse_counters_[which - 20]
+           : which >= 22 && which <= 23 ? quot_counters_[which - 22]
                                         : 0;
   }
   lmn_config cfg;
@@ -640,6 +642,7 @@ class Context {
     uint64_t generation = 0;
   } reuse_;
   uint64_t reuse_counters_[2] = {0, 0};   // counter() 20, 21
+  uint64_t quot_counters_[2] = {0, 0};    // counter() 22, 23: run_oods's device path, and its host wait under the device transcript
   void account_trace_reuse(struct ProofRun& r, const uint32_t* changed_words);   // phase_trace.cpp
   char* pin_base_ = nullptr;
   size_t pin_cap_ = 0, pin_off_ = 0;
